@@ -19,8 +19,14 @@ The JSON line also carries
                  HIP events recorded on the kernel's own stream inside the library
   roofline_expand : same for the pair-expand kernel (the kernel the north star's
                  40 % target names)
-  cpu_baseline : the CPU oracle timed on a bounded sample of the same stream
+and, with --full only (each leg runs work of its own after the timed steps):
+  dropin_7kinds : the 7-kind drop-in build
   mf           : BPR-MF training throughput (second half of the metric), when built
+  candidates, next_rows : the callers either side of the path
+  cpu_baseline : the CPU oracle timed on a bounded sample of the same stream
+
+--dump-outputs DIR writes the top-k lists of the last timed step to DIR/*.npy (float64) for a fixed, seeded sample of
+aid_x rows, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -42,12 +48,16 @@ def parse():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--sessions', type=int, default=14_571_582, help='sessions per rank (full OTTO = 14,571,582)')
     ap.add_argument('--k', type=int, default=20)
-    ap.add_argument('--cpu-sessions', type=int, default=4_000_000, help='sample size of the cpu_baseline leg (0 = skip)')
+    ap.add_argument('--cpu-sessions', type=int, default=4_000_000, help='--full: sample size of the cpu_baseline leg (0 = skip)')
     ap.add_argument('--scaling', choices=('weak', 'strong'), default='weak',
                     help='N > 1: weak = --sessions per rank (default); strong = ONE --sessions stream split by session chunk '
                          '(BASELINE.json config 4: full OTTO across the GPUs)')
-    ap.add_argument('--no-mf', action='store_true')
-    ap.add_argument('--no-dropin', action='store_true', help='skip the 7-kind drop-in build leg')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run the drop-in, MF, candidates, next-rows and CPU baseline legs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the top-k lists of the last timed step (a seeded sample of aid_x rows) to DIR/*.npy')
+    ap.add_argument('--no-mf', action='store_true', help='--full: skip the MF, candidates and next-rows legs')
+    ap.add_argument('--no-dropin', action='store_true', help='--full: skip the 7-kind drop-in build leg')
     ap.add_argument('--mf-rows', type=int, default=200_000_000)
     ap.add_argument('--mf-factors', type=int, default=64)
     return ap.parse_args()
@@ -360,6 +370,45 @@ def mf_cpu_baseline(U, V, users, items, n_items, sample):
                       f'({dt:.2f} s; probe on {sample // 4} triplets, s by threads: ' + ', '.join(f'{k}: {v:.2f}' for k, v in sorted(probe.items()))
                       + f'; pure-Python counter RNG of the oracle excluded: {t_neg:.1f} s extrapolated)'}
 
+DUMP_BYTES = 48 << 20   # --dump-outputs budget for the sampled rows (float64)
+
+
+def dump_outputs(path, out, n_aids, k, dev, world=1, rank=0, bounds=None, red_dev=None):
+    """The top-k lists the last timed step left in ``out`` ((y int32, W int64, n int32) over [kinds, n_aids, k]) for a fixed,
+    seeded sample of aid_x rows, as float64 .npy files: <kind>_aid_y / <kind>_weight [rows, k] with -1 / 0 beyond the list
+    length (those entries are unspecified), <kind>_count [rows], and sample_aid_x [rows]. N > 1: every rank contributes the
+    rows it owns (collective; rank 0 writes)."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    y, w, n = out
+    nk = y.shape[0]
+    rows = min(n_aids, DUMP_BYTES // (8 * nk * (2 * k + 1)))
+    xs = np.sort(np.random.default_rng(0).choice(n_aids, size=rows, replace=False))
+    idx = torch.from_numpy(xs).to(dev)
+    ns = n[:, idx].to(torch.int64)
+    valid = torch.arange(k, device=dev)[None, None, :] < ns[:, :, None]
+    # shifted by one so that a sum over the ranks' (zeroed where not owned) rows gives the owner's row
+    ys = torch.where(valid, y[:, idx].to(torch.float64) + 1, 0.0)
+    ws = torch.where(valid, w[:, idx].to(torch.float64), 0.0)
+    ns = ns.to(torch.float64)
+    if world > 1:
+        own = ((idx >= bounds[rank]) & (idx < bounds[rank + 1])).to(torch.float64)
+        parts = [ys * own[None, :, None], ws * own[None, :, None], ns * own[None, :]]
+        for i, t_ in enumerate(parts):
+            t_ = t_.to(red_dev or dev)
+            dist.all_reduce(t_, op=dist.ReduceOp.SUM)
+            parts[i] = t_
+        ys, ws, ns = parts
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    ys, ws, ns = (ys - 1).cpu().numpy(), ws.cpu().numpy(), ns.cpu().numpy()
+    np.save(os.path.join(path, 'sample_aid_x.npy'), xs.astype(np.float64))
+    for i, kind in enumerate(BENCH_KINDS[:nk]):
+        np.save(os.path.join(path, f'{kind}_aid_y.npy'), ys[i])
+        np.save(os.path.join(path, f'{kind}_weight.npy'), ws[i])
+        np.save(os.path.join(path, f'{kind}_count.npy'), ns[i])
 
 
 def self_launch(n):
@@ -465,6 +514,9 @@ def main():
         sm = red.clone()
         dist.all_reduce(sm, op=dist.ReduceOp.SUM)
         dt, pairs = float(mx[0].item()), int(sm[1].item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out[_lib.GROUP_TYPE], n_aids, a.k, dev, world, rank,
+                     builder.bounds if world > 1 else None, 'cpu' if stage else None)
 
     result = None
     if rank == 0:
@@ -515,14 +567,15 @@ def main():
             'kernel_ms': {k_: round(v, 3) for k_, v in kernel_ms.items()},
             'stats': st,
         }
+    # ---- everything below runs work of its own after the headline: --full only ------------------------------------
     # ---- the real drop-in workload (covisitation/builder.py:build_matrices): all 7 reference kinds, k = 20, N = 1 ------
-    if rank == 0 and world == 1 and not a.no_dropin:
+    if a.full and rank == 0 and world == 1 and not a.no_dropin:
         try:
             result['dropin_7kinds'] = dropin_leg(data, dev, n_aids, ts_min, ts_max, a.k)
         except Exception as e:                                   # a reported extra, never a reason to lose the bench line
             result['dropin_7kinds'] = {'error': repr(e)}
     # ---- second half of the metric: BPR-MF triplets/s ----------------------------------------------
-    if not a.no_mf:
+    if a.full and not a.no_mf:
         import bench_mf
         if bench_mf is not None:
             del builder, eng, out
@@ -532,17 +585,17 @@ def main():
             if rank == 0:
                 result['mf'] = mf
     # ---- the callers either side of the path, N = 1 only: candidate lookup + recency ----
-    if rank == 0 and world == 1 and not a.no_mf:
+    if a.full and rank == 0 and world == 1 and not a.no_mf:
         try:
             result['candidates'] = candidates_leg(data, dev, n_aids)
         except Exception as e:                                   # a reported extra, never a reason to lose the bench line
             result['candidates'] = {'error': repr(e)}
-    if rank == 0 and world == 1 and not a.no_mf:
+    if a.full and rank == 0 and world == 1 and not a.no_mf:
         try:
             result['next_rows'] = next_rows_leg(data, dev, n_aids)
         except Exception as e:                                   # a reported extra, never a reason to lose the bench line
             result['next_rows'] = {'error': repr(e)}
-    if rank == 0 and world == 1 and a.cpu_sessions > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_sessions > 0:
         result['cpu_baseline'] = cpu_baseline(data, min(a.cpu_sessions, a.sessions), a.k)
     if rank == 0:
         print(json.dumps(result), flush=True)

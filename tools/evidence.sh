@@ -2,6 +2,7 @@
 # Run with gpurun (bash tools/evidence.sh); tools/collect_profiles.sh copies the summaries into profiles/round3.
 set -e
 cd /root/repo
+R=$PWD
 export TMPDIR=/tmp
 E=gpurun_out/ev3
 mkdir -p $E
@@ -25,5 +26,5 @@ timeout -k 10 300 python tools/perf_cand.py --reps 2 > $E/cand_perf.log 2>&1; gr
 : > $E/cand_phase_split.log
 for d in 0 1; do echo "OTTO_CAND_DEBUG=$d (1: no inserts -- the tables stay empty, so the selection is trivial too)" >> $E/cand_phase_split.log; OTTO_CAND_DEBUG=$d OTTO_AMD_LIB=$PWD/otto-multi-objective-recommender-system_amd/csrc/libotto_amd_prof.so timeout -k 10 300 python tools/perf_cand.py --reps 1 2>&1 | grep "phase-prof. k_cand" | head -n 2 >> $E/cand_phase_split.log; done
 echo "== next rows"; timeout -k 10 400 python tools/perf_next_rows.py > $E/next_rows_perf.log 2>&1; tail -5 $E/next_rows_perf.log
-echo "== bench under rocprof"; cd /tmp; timeout -k 10 700 rocprofv3 --kernel-trace --stats -d /root/repo/$E/prof -o r1 --output-format csv -- python /root/repo/bench.py > /root/repo/$E/bench_rocprof.log 2>&1; cd /root/repo; grep '"metric"' $E/bench_rocprof.log | cut -c1-300
-echo "== plain bench"; timeout -k 10 600 python bench.py > $E/bench_plain.log 2>&1; grep '"metric"' $E/bench_plain.log | cut -c1-300
+echo "== bench --full under rocprof"; cd "$TMPDIR"; timeout -k 10 700 rocprofv3 --kernel-trace --stats -d "$R/$E/prof" -o r1 --output-format csv -- python "$R/bench.py" --full > "$R/$E/bench_rocprof.log" 2>&1; cd "$R"; grep '"metric"' $E/bench_rocprof.log | cut -c1-300
+echo "== bench --full, no profiler"; timeout -k 10 600 python bench.py --full > $E/bench_plain.log 2>&1; grep '"metric"' $E/bench_plain.log | cut -c1-300
