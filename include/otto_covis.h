@@ -49,7 +49,7 @@ typedef struct otto_covis_params {
     int32_t max_gap;       /* |ts_x - ts_y| <= max_gap seconds (SPEC-COVIS 3)           */
     uint32_t n_aids;       /* aids are 0..n_aids-1, n_aids <= 2^26                      */
     int32_t ts_min;        /* t0 of the time weight (global over ALL chunks / ranks)    */
-    int32_t ts_max;        /* t1                                                        */
+    int32_t ts_max;        /* t1; a ts outside [t0, t1] is clamped to it (SPEC-COVIS 6) */
     int32_t want_time;     /* !=0: keep the time-weight channel (needed for GROUP_TIME) */
     int32_t n_filters;     /* 0..4 pair-filter kinds                                    */
     uint16_t filter_mask[OTTO_COVIS_MAX_FILTERS];              /* bit (type_x*3+type_y) */

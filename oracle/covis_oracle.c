@@ -63,7 +63,9 @@ static int64_t expand_window(const uint32_t* aid, const int32_t* ts, const uint8
                 r.x = aid[lo + ci];
                 r.y = aid[lo + cj];
                 r.ch = (uint32_t)type[lo + j] | (fb[ci][cj] << 2);
-                r.extra = t1 > t0 ? (uint32_t)((196608ll * ((int64_t)ts[lo + i] - t0)) / (t1 - t0)) : 0u;
+                int64_t t = ts[lo + i];                    /* clamped to [t0, t1] (SPEC-COVIS 6) */
+                t = t < t0 ? t0 : t > t1 ? t1 : t;
+                r.extra = t1 > t0 ? (uint32_t)((196608ll * (t - t0)) / (t1 - t0)) : 0u;
                 out[cnt] = r;
             }
             ++cnt;

@@ -32,8 +32,9 @@ SPEC-COVIS (normative):
  4. per kind a 3x3 type mask M[type_i][type_j].
  5. dedupe: per (session, aid_x, aid_y, kind) only the FIRST valid pair in
     (i, j) lexicographic order contributes.
- 6. weight (Q16 integer): time_weighted 65536 + (3*65536*(ts_i - t0)) // (t1 - t0)
-    (t0, t1 = global min/max ts; 0 extra if t1 == t0); type-weighted kinds
+ 6. weight (Q16 integer): time_weighted 65536 + (3*65536*(clamp(ts_i, t0, t1) - t0)) // (t1 - t0)
+    (t0, t1 = global min/max ts as given by the caller; ts_i outside [t0, t1] is clamped
+    to it, so the extra lies in [0, 3*65536]; 0 extra if t1 == t0); type-weighted kinds
     65536 * Wk[type_j]; filter kinds 65536.
  7. W[x, y] = sum over sessions (exact integer).
  8. top-k per aid_x by (W desc, aid_y asc).
@@ -86,7 +87,7 @@ def _t01(ts, spec):
 def _weight(kind, ts_x, type_y, t0, t1):
     """Q16 weight of one contribution (python ints)."""
     if kind == 'time_weighted':
-        extra = (3 * Q16 * (int(ts_x) - t0)) // (t1 - t0) if t1 > t0 else 0
+        extra = (3 * Q16 * (min(max(int(ts_x), t0), t1) - t0)) // (t1 - t0) if t1 > t0 else 0
         return Q16 + extra
     if kind in TYPE_WEIGHTS:
         return Q16 * TYPE_WEIGHTS[kind][int(type_y)]
@@ -170,7 +171,7 @@ def covis_pairs_numpy(aid, ts, typ, sess_off, spec=CovisSpec(), chunk_elems=8_00
                 i, j = np.divmod(rem, n)
                 x, y = A[mm, i], A[mm, j]
                 if k == 'time_weighted':
-                    extra = (3 * Q16 * (T[mm, i] - t0)) // (t1 - t0) if t1 > t0 else 0
+                    extra = (3 * Q16 * (np.clip(T[mm, i], t0, t1) - t0)) // (t1 - t0) if t1 > t0 else np.zeros(sel.shape, np.int64)
                     w = Q16 + extra
                 elif k in TYPE_WEIGHTS:
                     w = Q16 * np.array(TYPE_WEIGHTS[k], dtype=np.int64)[Y[mm, j]]
@@ -260,7 +261,7 @@ def expand_window_python(aid, ts, typ, lo, hi, spec, filter_kinds=(), t0=0, t1=0
                 continue
             key = (ai, aj)
             if key not in first:
-                extra = (3 * Q16 * (ti - t0)) // (t1 - t0) if t1 > t0 else 0
+                extra = (3 * Q16 * (min(max(ti, t0), t1) - t0)) // (t1 - t0) if t1 > t0 else 0
                 first[key] = (yj, extra)
             b = 0
             for f, M in enumerate(masks):

@@ -72,33 +72,41 @@ def exchange_runs(export_fn, import_fn, bounds, group=None, want_time=False, sta
     return int(sc[:, 0].sum()), int(sc[:, 1].sum()), int(rc[:, 0].sum()), int(rc[:, 1].sum())
 
 
-def exchange_runs_chunked(engine, owner, bounds, group=None, want_time=False, n_chunks=4):
+def exchange_runs_chunked(engine, owner, bounds, group=None, want_time=False, n_chunks=4, stage_device=None):
     """The same exchange cut into ``n_chunks`` ranges of run slots, so that the export of range c + 1 (a pass over its run
     descriptors + the record copies, ~6 ms for a full-size shard) runs on the compute stream while range c is on the links:
     the collectives are issued asynchronously right behind the fill they depend on (torch.distributed orders a collective
     after the work already queued on the current stream, nothing more). All counts are planned and exchanged first (one
     small all-to-all), the records of every range are received straight into the owner engine's arrays
-    (``import_reserve``), range after range, and registered with ONE ``import_runs`` at the end. Device tensors only (RCCL
-    or a world of one); the staged rehearsal path stays ``exchange_runs``.
+    (``import_reserve``), range after range, and registered with ONE ``import_runs`` at the end.
+
+    Every rank cuts its run slots into exactly ``n_chunks`` ranges (a small shard gets empty ones) and issues the same
+    collectives in the same order, whatever its shard holds: 1 count all-to-all, then per range hdr, rec (and tw).
+    ``stage_device`` (e.g. ``'cpu'`` with a gloo group): each range's filled send buffers are copied there before its
+    collectives, the records are received into staged buffers and handed to ``import_runs`` on the device at the end
+    (the multi-rank rehearsal on a single GPU). None: device tensors only (RCCL or a world of one), no extra copies.
     Returns (runs_sent, recs_sent, runs_received, recs_received)."""
     import torch
     import torch.distributed as dist
     W = dist.get_world_size(group)
     slots = engine.run_slots()
-    K = max(1, min(int(n_chunks), slots if slots else 1))
+    K = max(1, int(n_chunks))                               # never from the local slot count: every rank must agree
     cuts = [slots * c // K for c in range(K + 1)]
     plans = [engine.export_plan_range(bounds, cuts[c], cuts[c + 1]) for c in range(K)]
     dev = engine.device
+    cdev = dev if stage_device is None else torch.device(stage_device)     # where the collectives run
     # counts: [W dest][K][2] -> every source's [K][2] for me
-    send_counts = torch.tensor([[[plans[c][0][o], plans[c][1][o]] for c in range(K)] for o in range(W)], dtype=torch.int64, device=dev)
+    send_counts = torch.tensor([[[plans[c][0][o], plans[c][1][o]] for c in range(K)] for o in range(W)], dtype=torch.int64, device=cdev)
     recv_counts = torch.empty_like(send_counts)
     dist.all_to_all_single(recv_counts.view(-1), send_counts.view(-1), group=group)
     rc = recv_counts.cpu().numpy()                          # [W src][K][2]
     tot_runs_in, tot_recs_in = int(rc[:, :, 0].sum()), int(rc[:, :, 1].sum())
-    rec_in, tw_in = owner.import_reserve(tot_recs_in) if tot_recs_in else (None, None)
+    rec_in, tw_in = owner.import_reserve(tot_recs_in) if tot_recs_in and stage_device is None else (None, None)
     if rec_in is None:
-        rec_in = torch.empty(0, dtype=torch.int32, device=dev)
-    hdr_in = torch.empty((tot_runs_in, 2), dtype=torch.int32, device=dev)
+        rec_in = torch.empty(tot_recs_in, dtype=torch.int32, device=cdev)
+    if want_time and tw_in is None:                         # nothing reserved: the zero-size collectives still run
+        tw_in = torch.empty(tot_recs_in, dtype=torch.int32, device=cdev)
+    hdr_in = torch.empty((tot_runs_in, 2), dtype=torch.int32, device=cdev)
     handles, keep = [], []
     r0 = c0 = 0
     for c in range(K):
@@ -107,6 +115,9 @@ def exchange_runs_chunked(engine, owner, bounds, group=None, want_time=False, n_
         rec_s = torch.empty(sum(recs), dtype=torch.int32, device=dev)
         tw_s = torch.empty(sum(recs), dtype=torch.int32, device=dev) if want_time else None
         engine.export_fill_range(bounds, cuts[c], cuts[c + 1], runs, recs, hdr_s, rec_s, tw_s)
+        if stage_device is not None:
+            hdr_s, rec_s = hdr_s.to(cdev), rec_s.to(cdev)
+            tw_s = None if tw_s is None else tw_s.to(cdev)
         nr, nc = int(rc[:, c, 0].sum()), int(rc[:, c, 1].sum())
         jobs = [(hdr_in[r0:r0 + nr].view(-1), hdr_s.view(-1), [int(v) * 2 for v in rc[:, c, 0]], [int(v) * 2 for v in runs]),
                 (rec_in[c0:c0 + nc], rec_s, [int(v) for v in rc[:, c, 1]], [int(v) for v in recs])]
@@ -120,7 +131,8 @@ def exchange_runs_chunked(engine, owner, bounds, group=None, want_time=False, n_
     for h in handles:
         h.wait()
     if tot_runs_in:
-        owner.import_runs(hdr_in, rec_in[:tot_recs_in], tw_in[:tot_recs_in] if want_time else None)
+        hdr_in, rec_in = hdr_in.to(dev), rec_in[:tot_recs_in].to(dev)
+        owner.import_runs(hdr_in, rec_in, tw_in[:tot_recs_in].to(dev) if want_time else None)
     sent = (sum(sum(p_[0]) for p_ in plans), sum(sum(p_[1]) for p_ in plans))
     return sent[0], sent[1], tot_runs_in, tot_recs_in
 
@@ -141,12 +153,17 @@ class ShardedCovisBuilder:
     ``[bounds[r], bounds[r+1])`` and returns top-k rows for that range only."""
 
     def __init__(self, n_aids, kinds, ts_min, ts_max, device, group=None, window=30, max_gap=86400, stage_device=None,
-                 exchange_chunks=4):
+                 exchange_chunks=4, exchange='auto'):
         import torch.distributed as dist
         from .engine import CovisBuilder
+        if exchange not in ('auto', 'chunked', 'single'):
+            raise ValueError(f"exchange must be 'auto', 'chunked' or 'single', got {exchange!r}")
         self.group = group
         self.stage_device = stage_device
-        self.exchange_chunks = exchange_chunks    # device path: slot ranges in flight (export of c + 1 under the send of c); 0 = one piece
+        self.exchange_chunks = exchange_chunks    # chunked path: slot ranges in flight (export of c + 1 under the send of c)
+        # 'auto': chunked on the device path when exchange_chunks > 1, else the single-piece exchange_runs (staged runs
+        # take it too); 'chunked' / 'single' force one of the two, staged or not
+        self.exchange = exchange
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)
         self.bounds = owner_bounds(n_aids, self.world)
@@ -161,10 +178,15 @@ class ShardedCovisBuilder:
     def feed(self, aid, ts, typ, sess_off):
         self.local.feed(aid, ts, typ, sess_off)
 
+    def _chunked(self):
+        if self.exchange == 'auto':
+            return self.stage_device is None and bool(self.exchange_chunks) and self.exchange_chunks > 1
+        return self.exchange == 'chunked'
+
     def finalize(self, k=20, out=None):
-        if self.stage_device is None and self.exchange_chunks and self.exchange_chunks > 1:
+        if self._chunked():
             self.last_exchange = exchange_runs_chunked(self.local, self.owner, self.bounds, self.group, self.local.want_time,
-                                                       self.exchange_chunks)
+                                                       self.exchange_chunks, self.stage_device)
             return self.owner.finalize(k=k, out=out)
         self.last_exchange = exchange_runs(self.local.export_runs, self.owner.import_runs, self.bounds, self.group,
                                            self.local.want_time, self.stage_device, export_all_fn=self.local.export_all,

@@ -150,6 +150,14 @@ struct ExpandArgs {
     int debug;                   // timing diagnostics (wrong results): 1 no record stores, 2 no row loops
 };
 
+// SPEC-COVIS 6 time extra 3*65536*(t - t0) / (t1 - t0), t clamped to [t0, t1] so that extra <= 196608 even for an event
+// outside the caller's global range (unclamped, t < t0 wraps to ~2^32 and carries into the aid_y bits of the packed sums).
+__device__ __forceinline__ uint32_t time_extra(const ExpandArgs& a, int32_t t) {
+    if (a.tspan <= 0) return 0u;
+    const int64_t d = min(max((int64_t)t - a.t0, (int64_t)0), a.tspan);
+    return (uint32_t)((uint64_t)(196608ull * (uint64_t)d) / (uint64_t)a.tspan);
+}
+
 // (wave_lds_sync: common.h) -- no workgroup barrier anywhere in this kernel.
 
 // G lanes per window, 64/G windows per wave, 4 independent waves per workgroup.
@@ -206,7 +214,7 @@ __global__ __launch_bounds__(256) void k_expand(ExpandArgs a) {
             aid = a.aid[wstart + g];
             t = a.ts[wstart + g];
             ty = a.type[wstart + g];
-            if (TIME) extra = a.tspan > 0 ? (uint32_t)((uint64_t)(196608ull * (uint64_t)((int64_t)t - a.t0)) / (uint64_t)a.tspan) : 0u;
+            if (TIME) extra = time_extra(a, t);
         }
         ev[g] = make_uint4(aid, (uint32_t)t, ty, extra);
         wave_lds_sync();
@@ -326,7 +334,7 @@ __global__ __launch_bounds__(256) void k_expand_fast(ExpandArgs a) {
             ty = a.type[wstart + g];
             if (TIME) {
                 const int32_t t = a.ts[wstart + g];
-                extra = a.tspan > 0 ? (uint32_t)((uint64_t)(196608ull * (uint64_t)((int64_t)t - a.t0)) / (uint64_t)a.tspan) : 0u;
+                extra = time_extra(a, t);
             }
         }
         av[g] = aid;
@@ -438,7 +446,7 @@ __device__ __forceinline__ void expand_task_reg(const ExpandArgs& a, uint4* ev, 
     const uint32_t aid = tp.aid, ty = tp.ty;
     const int32_t t = tp.t;
     uint32_t extra = 0;
-    if (TIME && act) extra = a.tspan > 0 ? (uint32_t)((uint64_t)(196608ull * (uint64_t)((int64_t)t - a.t0)) / (uint64_t)a.tspan) : 0u;
+    if (TIME && act) extra = time_extra(a, t);
     ev[lane] = make_uint4(aid, (uint32_t)t, 0u, extra);
     wave_lds_sync();
     uint32_t same = 0;                                          // window-relative bits
@@ -655,7 +663,7 @@ __device__ __forceinline__ void expand_task_lists(const ExpandArgs& a, uint4* ev
     const uint32_t aid = tp.aid, ty = tp.ty;
     const int32_t t = tp.t;
     uint32_t extra = 0;
-    if (TIME && act) extra = a.tspan > 0 ? (uint32_t)((uint64_t)(196608ull * (uint64_t)((int64_t)t - a.t0)) / (uint64_t)a.tspan) : 0u;
+    if (TIME && act) extra = time_extra(a, t);
     ev[lane] = make_uint4(aid, (uint32_t)t, 0u, extra);
     wave_lds_sync();
     uint32_t same = 0;                                          // window-relative bits: events holding my aid

@@ -21,9 +21,11 @@ def _to_dev(ev, dev):
             torch.from_numpy(ev.type).to(dev), torch.from_numpy(ev.sess_off).to(dev))
 
 
-def _build(ev, dev, kinds=cs.ALL_KINDS, k=20, window=30, max_gap=86400, chunks=1, l_cap=None, options=None):
+def _build(ev, dev, kinds=cs.ALL_KINDS, k=20, window=30, max_gap=86400, chunks=1, l_cap=None, options=None, ts_range=None):
     from otto_amd.covisitation.engine import CovisBuilder, topk_to_rows
     ts_min, ts_max = (int(ev.ts.min()), int(ev.ts.max())) if ev.n_events else (0, 0)
+    if ts_range is not None:
+        ts_min, ts_max = ts_range
     b = CovisBuilder(ev.n_aids, kinds=kinds, window=window, max_gap=max_gap, ts_min=ts_min, ts_max=ts_max, device=dev)
     if l_cap is not None:
         b.set_option('l_cap', l_cap)
@@ -42,8 +44,10 @@ def _build(ev, dev, kinds=cs.ALL_KINDS, k=20, window=30, max_gap=86400, chunks=1
     return b, rows
 
 
-def _oracle_rows(ev, kinds, k=20, window=30, max_gap=86400, stats=None):
+def _oracle_rows(ev, kinds, k=20, window=30, max_gap=86400, stats=None, ts_range=None):
     sp = co.CovisSpec(window=window, max_gap=max_gap, kinds=tuple(kinds))
+    if ts_range is not None:
+        sp.ts_min, sp.ts_max = ts_range
     return co.covis_topk_numpy(ev.aid, ev.ts, ev.type, ev.sess_off, sp, k=k, stats=stats)
 
 
@@ -289,6 +293,46 @@ def test_packed_heavy_layout_counter_limit(gpu_device, n_sess):
         _assert_rows_equal(got, want, kinds)
         wx, wy, ww = want['click_weighted']
         assert ww[(wx == x) & (wy == y)][0] == n_sess * 65536
+
+
+def _hub_and_random_events(n_hub, seed):
+    """``n_hub`` sessions that all hold the aids 7 and 11 (heavy aids, as in test_packed_heavy_layout_counter_limit) at
+    start times spread over the whole ts range, followed by 2,000 generated sessions of every window length class."""
+    rng = np.random.default_rng(seed)
+    gen = generate_sessions(2000, n_aids=3000, seed=seed)
+    z = rng.integers(100, gen.n_aids, size=(n_hub, 3)).astype(np.uint32)
+    aid = np.concatenate([np.full((n_hub, 1), 7, np.uint32), np.full((n_hub, 1), 11, np.uint32), z], axis=1)
+    t_start = rng.integers(int(gen.ts.min()), int(gen.ts.max()), size=(n_hub, 1))
+    ts = (t_start + np.cumsum(rng.integers(1, 30, size=aid.shape), axis=1)).astype(np.int32)
+    typ = rng.integers(0, 3, size=aid.shape).astype(np.uint8)
+    off = np.concatenate([np.arange(n_hub, dtype=np.int64) * 5, gen.sess_off + 5 * n_hub])
+    return Events(aid=np.concatenate([aid.ravel(), gen.aid]), ts=np.concatenate([ts.ravel(), gen.ts]),
+                  type=np.concatenate([typ.ravel(), gen.type]), sess_off=off, n_aids=gen.n_aids)
+
+
+@pytest.mark.parametrize('packed_heavy', [1, 0], ids=['packed-heavy', 'wide-heavy'])
+@pytest.mark.parametrize('kinds,options', [(NOFILT, {'fused': 2}), (NOFILT, {'fused': 1}), (cs.ALL_KINDS, {})],
+                         ids=['lists', 'fused-rows', 'class-kernels'])
+def test_time_weight_clamps_events_outside_ts_range(gpu_device, kinds, options, packed_heavy):
+    """ts_min / ts_max come from the caller (SPEC-COVIS 6: global over all chunks and ranks), so an event may lie outside
+    them: its time extra is clamped to [0, 3 * 65536]. Unclamped, t < t0 wrapped to ~2^32 and the packed heavy sums
+    (aid_y << 36 | sum) carried into the aid_y bits. Every expand kernel that computes the extra (component lists, fused
+    register rows, class-sorted kernels), packed and wide heavy layouts, with the aids 7 and 11 above the heavy threshold;
+    a narrowed range (events before t0 and after t1) and an empty one (t0 == t1) against the clamping oracle."""
+    ev = _hub_and_random_events(4095, seed=91)
+    lo, hi = int(ev.ts.min()), int(ev.ts.max())
+    q1, q3 = (int(v) for v in np.quantile(ev.ts, [0.25, 0.75]))
+    mid = (lo + hi) // 2
+    for ts_range in ((q1, q3), (mid, mid)):
+        assert (ev.ts < ts_range[0]).sum() > 1000 and (ev.ts > ts_range[1]).sum() > 1000
+        want = _oracle_rows(ev, kinds, ts_range=ts_range)
+        b, got = _build(ev, gpu_device, kinds=kinds, options=dict(options, packed_heavy=packed_heavy), ts_range=ts_range)
+        assert b.stats()['items_l'] >= 2                  # 7 and 11 are heavy aids
+        for kind in kinds:
+            assert (got[kind][1] < ev.n_aids).all(), f'{kind}: aid_y out of range'
+        _assert_rows_equal(got, want, kinds)
+        if ts_range[0] == ts_range[1]:
+            assert (want['time_weighted'][2] % cs.Q16 == 0).all()     # no time extra at all
 
 
 @pytest.mark.parametrize('options', [{'bucket_index': 0}, {'packed_heavy': 0}, {'guess': 0}, {'partition': 0},
@@ -547,6 +591,163 @@ def test_sharded_builder_two_ranks_on_one_gpu(gpu_device):
             parts.append(rows[kind])
         merged[kind] = tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
     _assert_rows_equal(merged, want, cs.ALL_KINDS)
+
+
+# ---- the chunked exchange (exchange_runs_chunked) with several ranks ---------------------------------------------------
+# Configurations run one after another in the same worker processes: 'single' is the one-piece exchange_runs (control),
+# an int is exchange_runs_chunked with that many run-slot ranges. Every configuration is built twice (reset -> feed ->
+# finalize) so that state cached by the first build would show in the second.
+CHUNKED_CONFIGS = ('single', 2, 4, 7)
+EMPTY_OWNER = 1                      # owner range without any aid_x: that rank receives zero runs and zero records
+
+
+def _skewed_shards(world):
+    """Events and per-rank session ranges [lo, hi) of unequal shards: one rank holds all generated sessions, one holds a
+    single 2-event session (2 run slots: fewer than 4 or 7 ranges), and with 3 ranks rank 0 holds none. The aids leave
+    the owner range of rank EMPTY_OWNER empty."""
+    from otto_amd.covisitation.distributed import owner_bounds
+    n_aids = 900
+    bounds = owner_bounds(n_aids, world)
+    gap_lo, gap_hi = bounds[EMPTY_OWNER], bounds[EMPTY_OWNER + 1]
+    gen = generate_sessions(3000, n_aids=n_aids - (gap_hi - gap_lo), seed=61)
+    gen_aid = np.where(gen.aid >= gap_lo, gen.aid + (gap_hi - gap_lo), gen.aid).astype(np.uint32)
+    t = int(gen.ts.min()) + 1000
+    tiny = (np.array([3, 5], np.uint32), np.array([t, t + 40], np.int32), np.array([0, 1], np.uint8))
+    if world == 2:        # rank 0: the tiny session, rank 1: everything else
+        parts, shards = [tiny, (gen_aid, gen.ts, gen.type)], [(0, 1), (1, 3001)]
+        lens = np.concatenate([[2], np.diff(gen.sess_off)])
+    else:                 # rank 0: nothing, rank 1: the generated sessions, rank 2: the tiny session
+        parts, shards = [(gen_aid, gen.ts, gen.type), tiny], [(0, 0), (0, 3000), (3000, 3001)]
+        lens = np.concatenate([np.diff(gen.sess_off), [2]])
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    ev = Events(aid=np.concatenate([p[0] for p in parts]), ts=np.concatenate([p[1] for p in parts]),
+                type=np.concatenate([p[2] for p in parts]), sess_off=off, n_aids=n_aids)
+    return ev, shards
+
+
+def _chunked_worker(rank, world, port, q, root):
+    import os
+    import sys
+    import traceback
+    from datetime import timedelta
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    sys.path[:0] = [root, os.path.join(root, 'oracle')]
+    import torch
+    import torch.distributed as dist
+    from otto_amd.covisitation.distributed import ShardedCovisBuilder, global_ts_range
+    from otto_amd.covisitation.engine import CovisBuilder, topk_to_rows
+    res, cfg = {}, None
+    try:
+        dist.init_process_group('gloo', rank=rank, world_size=world, timeout=timedelta(seconds=60))
+        dev = torch.device('cuda:0')
+        torch.cuda.set_device(dev)
+        ev, shards = _skewed_shards(world)
+        lo, hi = shards[rank]
+        e0, e1 = int(ev.sess_off[lo]), int(ev.sess_off[hi])
+        aid = torch.from_numpy(ev.aid[e0:e1].astype(np.int32)).to(dev)
+        ts = torch.from_numpy(ev.ts[e0:e1]).to(dev)
+        typ = torch.from_numpy(ev.type[e0:e1]).to(dev)
+        off = torch.from_numpy(ev.sess_off[lo:hi + 1] - e0).to(dev)
+        ts_min, ts_max = global_ts_range(ts.cpu())
+        # this rank's own check: its rows == the single-context build of all events, restricted to its aid range
+        single = CovisBuilder(ev.n_aids, kinds=cs.ALL_KINDS, ts_min=ts_min, ts_max=ts_max, device=dev)
+        single.feed(*_to_dev(ev, dev))
+        ref = {k: topk_to_rows(*v) for k, v in single.finalize(k=20).items()}
+        for cfg in CHUNKED_CONFIGS:
+            chunked = cfg != 'single'
+            b = ShardedCovisBuilder(ev.n_aids, cs.ALL_KINDS, ts_min, ts_max, dev, stage_device='cpu',
+                                    exchange_chunks=cfg if chunked else 0, exchange='chunked' if chunked else 'single')
+            assert b.local.want_time and b.local.filter_kinds
+            builds, mism = [], []
+            for _ in range(2):
+                b.reset()
+                b.feed(aid, ts, typ, off)
+                out = b.finalize(k=20)
+                rows = {k: topk_to_rows(*out[k]) for k in cs.ALL_KINDS}
+                x_lo, x_hi = b.bounds[rank], b.bounds[rank + 1]
+                for k in cs.ALL_KINDS:
+                    sel = (ref[k][0] >= x_lo) & (ref[k][0] < x_hi)
+                    if not all(np.array_equal(g, w[sel]) for g, w in zip(rows[k], ref[k])):
+                        mism.append(k)
+                builds.append(dict(rows=rows, exchange=b.last_exchange, run_slots=b.local.run_slots()))
+            res[cfg] = dict(builds=builds, mismatch=mism, bounds=b.bounds)
+            del b
+        q.put((rank, res, None))
+        dist.barrier()
+        dist.destroy_process_group()
+    except BaseException:
+        q.put((rank, res, (cfg, traceback.format_exc())))
+        raise
+
+
+@pytest.fixture(scope='module', params=[2, 3], ids=['world2', 'world3'])
+def chunked_exchange_runs(request, gpu_device):
+    """Spawns ``world`` gloo workers sharing this GPU (at most 3 + this process hold it), runs every CHUNKED_CONFIGS
+    entry in them, and returns (world, events, {rank: results}, {rank: (failed config, traceback)}). Cannot hang: the
+    process group times out after 60 s, the parent waits 150 s at most, then terminates whatever is still alive."""
+    import socket
+    import torch.multiprocessing as mp
+    from conftest import ROOT
+    from test_distributed_gloo import collect_workers
+    world = request.param
+    with socket.socket() as s:
+        s.bind(('127.0.0.1', 0))
+        port = s.getsockname()[1]
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    ps = [ctx.Process(target=_chunked_worker, args=(r, world, port, q, ROOT)) for r in range(world)]
+    for p in ps:
+        p.start()
+    res, errors = collect_workers(q, ps, 150)
+    from otto_amd.covisitation.distributed import owner_bounds
+    ev = _skewed_shards(world)[0]
+    single, want = _build(ev, gpu_device)                       # the single-context build of the same events
+    whole = single.export_all(owner_bounds(ev.n_aids, world))   # its per-owner runs / records
+    yield dict(world=world, ev=ev, res=res, errors=errors, want=want, whole=whole, oracle=_oracle_rows(ev, cs.ALL_KINDS))
+
+
+@pytest.mark.parametrize('cfg', CHUNKED_CONFIGS, ids=lambda c: f'chunks{c}' if c != 'single' else 'single-piece')
+def test_chunked_exchange_multi_rank_unequal_shards(gpu_device, chunked_exchange_runs, cfg):
+    """ShardedCovisBuilder with 2 or 3 processes on this GPU over gloo (staged through host memory), all 8 kinds (time
+    channel and filter kinds on), through exchange_runs_chunked with 2, 4 and 7 run-slot ranges and through the
+    one-piece exchange_runs. The shards are as unequal as they get: a rank with fewer run slots than ranges, with 3 ranks
+    a rank without sessions, and an owner that receives nothing. Every rank's rows == the single-context build of its aid
+    range, the union == the single-context build and the oracle, the exchanged totals add up, a second build in the same
+    processes gives the same rows."""
+    run = chunked_exchange_runs
+    world, ev, res, errors, want, whole = (run[k] for k in ('world', 'ev', 'res', 'errors', 'want', 'whole'))
+    failed = {r: e for r, e in errors.items() if e[0] is None or CHUNKED_CONFIGS.index(e[0]) <= CHUNKED_CONFIGS.index(cfg)}
+    assert not failed, '\n'.join(f'rank {r} (config {e[0]}):\n{e[1]}' for r, e in sorted(failed.items()))
+    per = {r: res[r][cfg] for r in range(world)}
+    bounds = per[0]['bounds']
+    # preconditions of the edges this test is about
+    slots = [per[r]['builds'][0]['run_slots'] for r in range(world)]
+    assert max(slots) > 1000 and min(s for s in slots if s) == 2
+    if cfg != 'single':
+        assert min(slots) < cfg or cfg == 2 and world == 2, slots   # a rank with fewer run slots than ranges
+    if world == 3:
+        assert slots[0] == 0                                          # a rank without a session
+    assert not ((ev.aid >= bounds[EMPTY_OWNER]) & (ev.aid < bounds[EMPTY_OWNER + 1])).any()
+    assert cs.TIME_KIND in cs.ALL_KINDS
+    # totals: per owner as the single-context export plans them; sent == received
+    for i in range(2):
+        ex = [tuple(per[r]['builds'][i]['exchange']) for r in range(world)]
+        assert ex[EMPTY_OWNER][2:] == (0, 0)
+        assert [e[2] for e in ex] == whole[3] and [e[3] for e in ex] == whole[4]
+        assert sum(e[0] for e in ex) == sum(e[2] for e in ex) == sum(whole[3])
+        assert sum(e[1] for e in ex) == sum(e[3] for e in ex) == sum(whole[4])
+    _assert_rows_equal(want, run['oracle'], cs.ALL_KINDS)
+    for r in range(world):
+        assert not per[r]['mismatch'], f'rank {r}: rows of {per[r]["mismatch"]} differ from its range of the single build'
+        for i in range(2):
+            for kind in cs.ALL_KINDS:
+                gx = per[r]['builds'][i]['rows'][kind][0]
+                assert ((gx >= bounds[r]) & (gx < bounds[r + 1])).all(), f'rank {r}: {kind} rows outside its range'
+        _assert_rows_equal(per[r]['builds'][1]['rows'], per[r]['builds'][0]['rows'], cs.ALL_KINDS)
+    for i in range(2):
+        merged = {k: tuple(np.concatenate([per[r]['builds'][i]['rows'][k][j] for r in range(world)]) for j in range(3))
+                  for k in cs.ALL_KINDS}
+        _assert_rows_equal(merged, want, cs.ALL_KINDS)
 
 
 @pytest.fixture(scope='module')

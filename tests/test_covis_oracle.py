@@ -123,6 +123,39 @@ def test_c_restatement_matches_numpy_and_hand_values():
     assert d == HAND_TIME
 
 
+def test_time_extra_is_clamped_to_the_given_ts_range():
+    """SPEC-COVIS 6: ts_min / ts_max come from the caller; an event outside [t0, t1] counts as t0 or t1, so every time
+    extra lies in [0, 3 * 65536]. The three restatements (Python loops, NumPy, C) and expand_window_python agree, by hand
+    on one pair and on generated sessions with events on both sides of the range."""
+    import __graft_entry__ as g
+    g._run(['make', 'all'], os.path.join(g.ROOT, 'oracle'))
+    import covis_oracle_c as coc
+    aid = np.array([1, 2, 3, 4], dtype=np.uint32)
+    ts = np.array([0, 1, 300, 301], dtype=np.int32) + T
+    off = np.array([0, 2, 4], dtype=np.int64)
+    sp = co.CovisSpec(kinds=('time_weighted',), ts_min=T + 100, ts_max=T + 200)
+    # (1, 2) at ts T < t0: no extra; (3, 4) at T + 300 > t1: the full 3 * 65536
+    want = {(1, 2): Q, (2, 1): Q, (3, 4): 4 * Q, (4, 3): 4 * Q}
+    assert co.covis_pairs_python(aid, ts, np.zeros(4, np.uint8), off, sp)['time_weighted'] == want
+    x, y, w = co.covis_pairs_numpy(aid, ts, np.zeros(4, np.uint8), off, sp)['time_weighted']
+    assert dict(zip(zip(x.tolist(), y.tolist()), w.tolist())) == want
+    assert [r[4] for r in co.expand_window_python(aid, ts, np.zeros(4, np.uint8), 2, 4, sp, (), T + 100, T + 200)] == [3 * Q] * 2
+    ev = generate_sessions(600, n_aids=200, seed=19)
+    q1, q3 = (int(v) for v in np.quantile(ev.ts, [0.25, 0.75]))
+    for t0, t1 in ((q1, q3), (q1, q1)):
+        sp = co.CovisSpec(ts_min=t0, ts_max=t1)
+        want = co.covis_topk_numpy(ev.aid, ev.ts, ev.type, ev.sess_off, sp, k=20)
+        py = co.covis_pairs_python(ev.aid, ev.ts, ev.type, ev.sess_off, sp)['time_weighted']
+        x, y, w = co.covis_pairs_numpy(ev.aid, ev.ts, ev.type, ev.sess_off, sp)['time_weighted']
+        assert dict(zip(zip(x.tolist(), y.tolist()), w.tolist())) == py
+        got = coc.covis_topk_c(ev.aid, ev.ts, ev.type, ev.sess_off, ev.n_aids, co.ALL_KINDS, k=20, threads=2, ts_min=t0, ts_max=t1)
+        for kind in co.ALL_KINDS:
+            for a_, b_ in zip(got[kind], want[kind]):
+                assert np.array_equal(a_, b_), kind
+        if t0 == t1:
+            assert (w % Q == 0).all()                    # no extra without a time span
+
+
 def test_c_restatement_under_address_and_undefined_behaviour_sanitizers(tmp_path):
     """SURVEY.md section 5 (CPU-side sanitizers; never on the GPU box): `make -C oracle asan` builds covis_oracle.c with
     -fsanitize=address,undefined behind a file-driven main; it runs the hand-derived micro-sessions, random sessions with
