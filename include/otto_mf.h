@@ -71,6 +71,28 @@ int otto_mf_step_sparse_adam(otto_mf_ctx* ctx, float* d_E1, float* d_m1, float* 
                              int32_t loss_kind, double lr, double beta1, double beta2, double eps, int64_t t,
                              float* d_loss_out, void* stream);
 
+/* Data-parallel SparseAdam: one otto_mf_step_sparse_adam over the union of W ranks' batches, split around the caller's
+ * all-gather. Table 1 is private (rank r owns rows [priv_lo, priv_hi) and their moments), table 2 is replicated on every
+ * rank; a shared_table context has no private table (E1 == E2, both index columns are exported, priv_lo/hi ignored).
+ *
+ * otto_mf_dp_local: forward, loss and coef = dL/dout / B_global over the B_local local samples (B_local = 0 is valid).
+ *   Private rows get Adam in place, exactly as in otto_mf_step_sparse_adam. Replicated rows are NOT updated: each distinct
+ *   row touched here gets one entry of the export list, d_ids[i] (int32) and d_rows[i][0..d) = its coalesced gradient row,
+ *   i < *d_count (device int64). cap >= B_local (2 * B_local for a shared table). *d_loss_out (device float) = the local
+ *   loss SUM / B_global, so the ranks' values add up to the global mean. A private id outside [priv_lo, priv_hi) is
+ *   skipped and counted like an id outside its table (otto_mf_check reports both).
+ * otto_mf_dp_apply: d_ids [W][cap], d_rows [W][cap][d] and d_counts [W] are the export lists of ranks 0..W-1 as gathered
+ *   (entries past a rank's count are padding and never read). Each row's entries are summed in rank order without float
+ *   atomics and Adam is applied once per row, so every replica of table 2 and its moments stays bit-identical. d_rows is
+ *   consumed (accumulated in place). Counts are read on the device: no host synchronisation. */
+int otto_mf_dp_local(otto_mf_ctx* ctx, float* d_E1, float* d_m1, float* d_v1, const float* d_E2, const int64_t* d_i1,
+                     const int64_t* d_i2, const int64_t* d_target, int64_t B_local, int64_t B_global, int64_t priv_lo,
+                     int64_t priv_hi, int32_t loss_kind, double lr, double beta1, double beta2, double eps, int64_t t,
+                     int32_t* d_ids, float* d_rows, int64_t cap, int64_t* d_count, float* d_loss_out, void* stream);
+int otto_mf_dp_apply(otto_mf_ctx* ctx, float* d_E2, float* d_m2, float* d_v2, const int32_t* d_ids, float* d_rows,
+                     const int64_t* d_counts, int32_t W, int64_t cap, double lr, double beta1, double beta2, double eps,
+                     int64_t t, void* stream);
+
 /* BPR-SGD over B (user, positive item) rows: negative j ~ U{0..n2-1} from a counter-based RNG keyed by
  * (seed, epoch, row0 + b), redrawn while j == i; x = <U_u, V_i - V_j>; loss = softplus(-x);
  * U_u += lr*(s*(V_i-V_j) - l2*U_u), V_i += lr*(s*U_u - l2*V_i), V_j += lr*(-s*U_u - l2*V_j), s = sigmoid(-x).

@@ -141,6 +141,10 @@ SIGNATURES = {
     'otto_mf_check': (_i32, [_vp, _p_i64, _vp]),
     'otto_mf_step_sparse_adam': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32,
                                         C.c_double, C.c_double, C.c_double, C.c_double, _i64, _vp, _vp]),
+    'otto_mf_dp_local': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, C.c_double, C.c_double,
+                                C.c_double, C.c_double, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    'otto_mf_dp_apply': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, C.c_double, C.c_double, C.c_double,
+                                C.c_double, _i64, _vp]),
     'otto_mf_bpr_step': (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_uint64, C.c_uint64, _i64, C.c_float, C.c_float,
                                 _i32, _vp, _vp, _vp]),
     'otto_mf_score_topk': (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp]),

@@ -19,6 +19,8 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
+
 namespace otto {
 
 constexpr int32_t OWNER_FREE = 0x7F7F7F7F;   // memset(0x7F) pattern; larger than any occurrence id
@@ -298,6 +300,226 @@ __global__ __launch_bounds__(256) void k_rmf_apply(StepArgs a) {
         adam_row(E, (first ? a.m1 : a.m2) + r * a.d + 4 * gl, (first ? a.v1 : a.v2) + r * a.d + 4 * gl, ld4(E),
                  ld4(a.grad + o * a.d + 4 * gl), a);
         if (gl == 0) (first ? a.cnt1 : a.cnt2)[r] = 0;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Data-parallel SparseAdam step, split around the caller's all-gather.
+//   local half  k_dp_fwd / k_dp_acc / k_dp_fin: the single-GPU step's three phases over one rank's batch, with the loss
+//               divided by the GLOBAL batch size. Rows of the private table (sessions) get Adam in place exactly as in
+//               k_rmf_*; rows of the replicated table (aids; both columns of a shared table) are not updated: every
+//               distinct row takes one entry of a compact export list (ids[pos], rows[pos][d] = its coalesced gradient).
+//               A duplicated row's entry is claimed and zeroed by its second arriver in k_dp_fwd and accumulated with
+//               row-contiguous float atomics in k_dp_acc; a single-occurrence row claims its entry in k_dp_acc and stores
+//               its gradient row plainly. k_dp_fin applies the private duplicates and clears the remaining counters.
+//   apply half  k_dpa_claim / k_dpa_sum (ranks 1..W-1) / k_dpa_adam over the gathered [W][cap] lists: the smallest
+//               flat entry of a row (atomicMin on the row's owner word) owns it, the other ranks' entries are added into
+//               the owner's row in rank order with plain loads and stores (one launch per rank: a row is in a rank's
+//               list at most once, so no two adders meet), then Adam once per owner entry. No float atomic touches the
+//               cross-rank sum, so every replica computes the same bits.
+// ---------------------------------------------------------------------------
+struct DpArgs {
+    StepArgs a;
+    int priv;                   // 1: table 1 is private (MatrixFactorization); 0: shared table, both columns export
+    int64_t lo, hi;             // private rows this rank owns
+    int32_t* ids;               // [cap] export list
+    float* rows;                // [cap, d]
+    unsigned long long* count;  // distinct rows exported
+    float inv_bg;               // 1 / B_global
+};
+
+__device__ __forceinline__ bool dp_ok(const DpArgs& p, int64_t r1, int64_t r2) {
+    return rows_ok(p.a, r1, r2) && (!p.priv || (r1 >= p.lo && r1 < p.hi));
+}
+
+// the group leader's value for every lane of the group (G <= 64 lanes inside one wave)
+__device__ __forceinline__ int32_t from_leader(int32_t v, int gl) {
+    return __shfl(v, (int)((threadIdx.x & 63) - gl), 64);
+}
+
+__global__ __launch_bounds__(256) void k_dp_fwd(DpArgs p) {
+    const StepArgs& a = p.a;
+    const int G = a.G;
+    const int gl = threadIdx.x & (G - 1);
+    const int64_t gpb = 256 / G;
+    float lsum = 0.f;
+    for (int64_t b = (int64_t)blockIdx.x * gpb + threadIdx.x / G; b < a.B; b += (int64_t)gridDim.x * gpb) {
+        const int64_t r1 = a.i1[b], r2 = a.i2[b];
+        if (!dp_ok(p, r1, r2)) {
+            if (gl == 0) { atomicAdd(a.err, 1u); a.role[b] = 0; a.role[a.B + b] = 0; }
+            continue;
+        }
+        const float4 e1 = ld4(a.E1 + r1 * a.d + 4 * gl);
+        const float4 e2 = ld4(a.E2 + r2 * a.d + 4 * gl);
+        const float out = group_sum(dot4(e1, e2), G);
+        int32_t s1 = -1, s2 = -1;   // export entry claimed by this occurrence (second arriver of an exported row)
+        uint32_t old1 = 0;
+        if (gl == 0) {
+            float l, g;
+            loss_grad(a.loss_kind, out, (float)a.target[b], &l, &g);
+            lsum += l;
+            a.coef[b] = g * p.inv_bg;
+            old1 = atomicAdd(&a.cnt1[r1], 1u);
+            const uint32_t old2 = atomicAdd(&a.cnt2[r2], 1u);
+            a.role[b] = old1 == 1u;
+            a.role[a.B + b] = old2 == 1u;
+            if (old1 == 1u) {
+                if (p.priv) {
+                    a.slot1[r1] = (int32_t)b;
+                } else {
+                    s1 = (int32_t)atomicAdd(p.count, 1ull);
+                    p.ids[s1] = (int32_t)r1;
+                    a.slot1[r1] = s1;
+                }
+            }
+            if (old2 == 1u) {
+                s2 = (int32_t)atomicAdd(p.count, 1ull);
+                p.ids[s2] = (int32_t)r2;
+                a.slot2[r2] = s2;
+            }
+        }
+        old1 = (uint32_t)from_leader((int32_t)old1, gl);
+        s1 = from_leader(s1, gl);
+        s2 = from_leader(s2, gl);
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (p.priv && old1 == 1u) st4(a.grad + b * a.d + 4 * gl, z);
+        if (s1 >= 0) st4(p.rows + (int64_t)s1 * a.d + 4 * gl, z);
+        if (s2 >= 0) st4(p.rows + (int64_t)s2 * a.d + 4 * gl, z);
+    }
+    block_loss_partial<256>(lsum, a.partial);
+}
+
+// one exported occurrence's gradient row: a single-occurrence row claims its entry and stores, a duplicated row adds
+// into the entry its second arriver claimed
+__device__ __forceinline__ void dp_export(const DpArgs& p, uint32_t c, int64_t r, uint32_t* cnt, const int32_t* slot,
+                                          float4 g, int gl) {
+    const StepArgs& a = p.a;
+    if (c == 1u) {
+        int32_t s = 0;
+        if (gl == 0) {
+            s = (int32_t)atomicAdd(p.count, 1ull);
+            p.ids[s] = (int32_t)r;
+            cnt[r] = 0;
+        }
+        s = from_leader(s, gl);
+        st4(p.rows + (int64_t)s * a.d + 4 * gl, g);
+    } else {
+        atomic_add4(p.rows + (int64_t)slot[r] * a.d + 4 * gl, g);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_dp_acc(DpArgs p) {
+    const StepArgs& a = p.a;
+    const int G = a.G;
+    const int gl = threadIdx.x & (G - 1);
+    const int64_t gpb = 256 / G;
+    for (int64_t b = (int64_t)blockIdx.x * gpb + threadIdx.x / G; b < a.B; b += (int64_t)gridDim.x * gpb) {
+        const int64_t r1 = a.i1[b], r2 = a.i2[b];
+        if (!dp_ok(p, r1, r2)) continue;
+        const uint32_t c1 = a.cnt1[r1], c2 = a.cnt2[r2];
+        const float c = a.coef[b];
+        float* p1 = a.E1 + r1 * a.d + 4 * gl;
+        const float4 e1 = ld4(p1), e2 = ld4(a.E2 + r2 * a.d + 4 * gl);
+        const float4 g1 = make_float4(c * e2.x, c * e2.y, c * e2.z, c * e2.w);
+        const float4 g2 = make_float4(c * e1.x, c * e1.y, c * e1.z, c * e1.w);
+        // every lane of the group has read both counters and both rows before anything is written
+        __builtin_amdgcn_wave_barrier();
+        if (!p.priv) {
+            dp_export(p, c1, r1, a.cnt1, a.slot1, g1, gl);
+        } else if (c1 == 1u) {
+            adam_row(p1, a.m1 + r1 * a.d + 4 * gl, a.v1 + r1 * a.d + 4 * gl, e1, g1, a);
+            if (gl == 0) a.cnt1[r1] = 0;
+        } else {
+            atomic_add4(a.grad + (int64_t)a.slot1[r1] * a.d + 4 * gl, g1);
+        }
+        dp_export(p, c2, r2, a.cnt2, a.slot2, g2, gl);
+    }
+}
+
+// second arrivers: private duplicated rows get Adam from their slot; every duplicated row's counter is cleared
+__global__ __launch_bounds__(256) void k_dp_fin(DpArgs p) {
+    const StepArgs& a = p.a;
+    const int G = a.G;
+    const int gl = threadIdx.x & (G - 1);
+    const int64_t gpb = 256 / G;
+    for (int64_t o = (int64_t)blockIdx.x * gpb + threadIdx.x / G; o < 2 * a.B; o += (int64_t)gridDim.x * gpb) {
+        if (!a.role[o]) continue;
+        const bool first = o < a.B;
+        const int64_t r = first ? a.i1[o] : a.i2[o - a.B];
+        if (first && p.priv) {
+            float* E = a.E1 + r * a.d + 4 * gl;
+            adam_row(E, a.m1 + r * a.d + 4 * gl, a.v1 + r * a.d + 4 * gl, ld4(E), ld4(a.grad + o * a.d + 4 * gl), a);
+        }
+        if (gl == 0) (first ? a.cnt1 : a.cnt2)[r] = 0;
+    }
+}
+
+struct DpApplyArgs {
+    float* E; float* m; float* v;
+    const int32_t* ids;         // [W][cap]
+    float* rows;                // [W][cap][d]; owner entries accumulate in place
+    const int64_t* counts;      // [W]
+    int W;
+    int64_t cap, n;
+    int d, G;
+    int32_t* owner;             // [n] OWNER_FREE between steps
+    uint32_t* err;
+    StepArgs hp;                // Adam hyper-parameters (omb1, omb2, eps, step_size)
+};
+
+__device__ __forceinline__ int64_t dpa_count(const DpApplyArgs& a, int r) {
+    const int64_t c = a.counts[r];
+    return c < 0 ? 0 : (c > a.cap ? a.cap : c);
+}
+
+__global__ __launch_bounds__(256) void k_dpa_claim(DpApplyArgs a) {
+    const int64_t total = (int64_t)a.W * a.cap;
+    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
+        const int r = (int)(o / a.cap);
+        if (o - (int64_t)r * a.cap >= dpa_count(a, r)) continue;
+        const int32_t id = a.ids[o];
+        if ((uint32_t)id >= (uint64_t)a.n) {    // a corrupted exchange: skip and report (otto_mf_check)
+            atomicAdd(a.err, 1u);
+            continue;
+        }
+        atomicMin(&a.owner[id], (int32_t)o);
+    }
+}
+
+// rank r's entries into their owners' rows (launched for r = 1 .. W-1 in order)
+__global__ __launch_bounds__(256) void k_dpa_sum(DpApplyArgs a, int r) {
+    const int G = a.G;
+    const int gl = threadIdx.x & (G - 1);
+    const int64_t gpb = 256 / G;
+    const int64_t n = dpa_count(a, r);
+    for (int64_t i = (int64_t)blockIdx.x * gpb + threadIdx.x / G; i < n; i += (int64_t)gridDim.x * gpb) {
+        const int64_t o = (int64_t)r * a.cap + i;
+        const int32_t id = a.ids[o];
+        if ((uint32_t)id >= (uint64_t)a.n) continue;
+        const int64_t own = a.owner[id];
+        if (own == o) continue;
+        float* dst = a.rows + own * a.d + 4 * gl;
+        const float4 x = ld4(dst), y = ld4(a.rows + o * a.d + 4 * gl);
+        st4(dst, make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w));
+    }
+}
+
+__global__ __launch_bounds__(256) void k_dpa_adam(DpApplyArgs a) {
+    const int G = a.G;
+    const int gl = threadIdx.x & (G - 1);
+    const int64_t gpb = 256 / G;
+    const int64_t total = (int64_t)a.W * a.cap;
+    for (int64_t o = (int64_t)blockIdx.x * gpb + threadIdx.x / G; o < total; o += (int64_t)gridDim.x * gpb) {
+        const int r = (int)(o / a.cap);
+        if (o - (int64_t)r * a.cap >= dpa_count(a, r)) continue;
+        const int32_t id = a.ids[o];
+        if ((uint32_t)id >= (uint64_t)a.n || a.owner[id] != (int32_t)o) continue;
+        float* E = a.E + (int64_t)id * a.d + 4 * gl;
+        adam_row(E, a.m + (int64_t)id * a.d + 4 * gl, a.v + (int64_t)id * a.d + 4 * gl, ld4(E),
+                 ld4(a.rows + o * a.d + 4 * gl), a.hp);
+        // every lane of the group has read the owner word before the leader releases it
+        __builtin_amdgcn_wave_barrier();
+        if (gl == 0) a.owner[id] = OWNER_FREE;
     }
 }
 
@@ -816,6 +1038,86 @@ extern "C" int otto_mf_step_sparse_adam(otto_mf_ctx* c, float* E1, float* m1, fl
     k_loss_final<<<1, 256, 0, s>>>(c->partial.as<float>(), grid, 1.0f / (float)B, loss_out, nullptr, 0, MF_GRID_MAX, 0.0);
     k_rmf_acc<<<grid, 256, 0, s>>>(a);
     k_rmf_apply<<<mf_grid(2 * B, c->G), 256, 0, s>>>(a);
+    OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
+static void adam_params(StepArgs* a, double lr, double beta1, double beta2, double eps, int64_t t) {
+    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
+    a->omb1 = (float)(1.0 - beta1); a->omb2 = (float)(1.0 - beta2); a->eps = (float)eps;
+    a->step_size = (float)(lr * sqrt(bc2) / bc1);
+}
+
+extern "C" int otto_mf_dp_local(otto_mf_ctx* c, float* E1, float* m1, float* v1, const float* E2, const int64_t* i1,
+                                const int64_t* i2, const int64_t* target, int64_t B_local, int64_t B_global, int64_t priv_lo,
+                                int64_t priv_hi, int32_t loss_kind, double lr, double beta1, double beta2, double eps,
+                                int64_t t, int32_t* d_ids, float* d_rows, int64_t cap, int64_t* d_count, float* loss_out,
+                                void* stream) {
+    OTTO_REQUIRE(c, "null ctx");
+    OTTO_REQUIRE(B_local >= 0 && B_local <= c->max_batch, "local batch %lld outside [0, max_batch=%lld]",
+                 (long long)B_local, (long long)c->max_batch);
+    OTTO_REQUIRE(B_global >= B_local && B_global > 0, "global batch %lld must be positive and >= the local batch %lld",
+                 (long long)B_global, (long long)B_local);
+    OTTO_REQUIRE(E1 && E2 && d_ids && d_rows && d_count && loss_out, "null argument");
+    OTTO_REQUIRE(B_local == 0 || (i1 && i2 && target), "null index / target pointer");
+    OTTO_REQUIRE(c->shared || (m1 && v1), "null private moment pointer");
+    OTTO_REQUIRE(loss_kind == OTTO_MF_LOSS_MSE || loss_kind == OTTO_MF_LOSS_BCE, "unknown loss kind %d", loss_kind);
+    OTTO_REQUIRE(t >= 1, "step count t must be >= 1");
+    OTTO_REQUIRE(c->n2 < 0x7FFFFFFFll, "replicated table has %lld rows (export ids are int32)", (long long)c->n2);
+    OTTO_REQUIRE(cap >= (c->shared ? 2 : 1) * B_local, "export capacity %lld < %s local batch %lld", (long long)cap,
+                 c->shared ? "2 x" : "", (long long)B_local);
+    OTTO_REQUIRE(!c->shared || E1 == E2, "shared_table context needs identical table pointers");
+    OTTO_REQUIRE(c->shared || (0 <= priv_lo && priv_lo <= priv_hi && priv_hi <= c->n1),
+                 "private row range [%lld, %lld) outside [0, %lld]", (long long)priv_lo, (long long)priv_hi, (long long)c->n1);
+    hipStream_t s = (hipStream_t)stream;
+    OTTO_HIP(hipMemsetAsync(d_count, 0, 8, s));
+    if (B_local == 0) {
+        OTTO_HIP(hipMemsetAsync(loss_out, 0, 4, s));
+        return 0;
+    }
+    const int grid = mf_grid(B_local, c->G);
+    DpArgs p;
+    memset(&p, 0, sizeof p);
+    StepArgs& a = p.a;
+    a.E1 = E1; a.m1 = m1; a.v1 = v1; a.E2 = const_cast<float*>(E2);
+    a.i1 = i1; a.i2 = i2; a.target = target; a.B = B_local; a.n1 = c->n1; a.n2 = c->n2; a.d = c->d; a.G = c->G;
+    a.loss_kind = loss_kind;
+    a.partial = c->partial.as<float>(); a.coef = c->coef.as<float>();
+    a.cnt1 = c->cnt1.as<uint32_t>(); a.cnt2 = c->shared ? a.cnt1 : c->cnt2.as<uint32_t>();
+    a.slot1 = c->slot1.as<int32_t>(); a.slot2 = c->shared ? a.slot1 : c->slot2.as<int32_t>();
+    a.role = c->role.as<uint8_t>(); a.grad = c->grad.as<float>(); a.err = c->err.as<uint32_t>();
+    adam_params(&a, lr, beta1, beta2, eps, t);
+    p.priv = !c->shared; p.lo = priv_lo; p.hi = priv_hi;
+    p.ids = d_ids; p.rows = d_rows; p.count = reinterpret_cast<unsigned long long*>(d_count);
+    p.inv_bg = 1.0f / (float)B_global;
+    k_dp_fwd<<<grid, 256, 0, s>>>(p);
+    k_loss_final<<<1, 256, 0, s>>>(c->partial.as<float>(), grid, p.inv_bg, loss_out, nullptr, 0, MF_GRID_MAX, 0.0);
+    k_dp_acc<<<grid, 256, 0, s>>>(p);
+    k_dp_fin<<<mf_grid(2 * B_local, c->G), 256, 0, s>>>(p);
+    OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int otto_mf_dp_apply(otto_mf_ctx* c, float* E2, float* m2, float* v2, const int32_t* d_ids, float* d_rows,
+                                const int64_t* d_counts, int32_t W, int64_t cap, double lr, double beta1, double beta2,
+                                double eps, int64_t t, void* stream) {
+    OTTO_REQUIRE(c, "null ctx");
+    OTTO_REQUIRE(E2 && m2 && v2 && d_ids && d_rows && d_counts, "null argument");
+    OTTO_REQUIRE(W >= 1, "world size %d must be >= 1", W);
+    OTTO_REQUIRE(cap >= 1 && (int64_t)W * cap < 0x7F000000ll, "W x cap = %d x %lld out of range", W, (long long)cap);
+    OTTO_REQUIRE(t >= 1, "step count t must be >= 1");
+    hipStream_t s = (hipStream_t)stream;
+    DpApplyArgs a;
+    memset(&a, 0, sizeof a);
+    a.E = E2; a.m = m2; a.v = v2; a.ids = d_ids; a.rows = d_rows; a.counts = d_counts; a.W = W; a.cap = cap;
+    a.n = c->n2; a.d = c->d; a.G = c->G;
+    a.owner = c->shared ? c->owner1.as<int32_t>() : c->owner2.as<int32_t>();
+    a.err = c->err.as<uint32_t>();
+    adam_params(&a.hp, lr, beta1, beta2, eps, t);
+    const int64_t total = (int64_t)W * cap;
+    k_dpa_claim<<<(int)std::min<int64_t>((total + 255) / 256, MF_GRID_MAX), 256, 0, s>>>(a);
+    for (int r = 1; r < W; ++r) k_dpa_sum<<<mf_grid(cap, c->G), 256, 0, s>>>(a, r);
+    k_dpa_adam<<<mf_grid(total, c->G), 256, 0, s>>>(a);
     OTTO_HIP(hipGetLastError());
     return 0;
 }

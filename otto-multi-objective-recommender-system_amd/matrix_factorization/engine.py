@@ -115,6 +115,48 @@ class MFEngine:
                 B, int(loss_kind), float(lr), float(betas[0]), float(betas[1]), float(eps), int(t_step), _ptr(loss_out),
                 self._stream()), 'otto_mf_step_sparse_adam')
 
+    def dp_local(self, E1, m1, v1, E2, i1, i2, target, batch_global, priv_lo, priv_hi, loss_kind, lr, betas, eps, t_step,
+                 ids, rows, count, loss_out):
+        """Local half of the data-parallel SparseAdam step (``otto_mf_dp_local``): private rows of table 1 in
+        ``[priv_lo, priv_hi)`` updated in place, the replicated rows' coalesced gradients written to the export list
+        ``ids`` int32 [cap] / ``rows`` float32 [cap, d] with their number in ``count`` (int64 [1]); ``loss_out`` = local
+        loss sum / ``batch_global``. A shared-table engine passes ``E1 is E2`` and no moments (``m1 = v1 = None``)."""
+        t = self.torch
+        self._tables(E1, E2)
+        B = self._idx(i1, i2, (('target', target),))
+        if not self.shared:
+            _chk('m1', m1, t.float32, self.device)
+            _chk('v1', v1, t.float32, self.device)
+        _chk('ids', ids, t.int32, self.device)
+        _chk('rows', rows, t.float32, self.device)
+        _chk('count', count, t.int64, self.device)
+        cap = ids.numel()
+        if rows.shape != (cap, self.d) or count.numel() < 1 or loss_out.numel() < 1:
+            raise ValueError(f'export buffers: ids [{cap}], rows {tuple(rows.shape)} != [{cap}, {self.d}]')
+        with t.cuda.device(self.device):
+            _lib.check(self._lib.otto_mf_dp_local(
+                self._ctx, _ptr(E1), _ptr(m1), _ptr(v1), _ptr(E2), _ptr(i1), _ptr(i2), _ptr(target), B, int(batch_global),
+                int(priv_lo), int(priv_hi), int(loss_kind), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                int(t_step), _ptr(ids), _ptr(rows), cap, _ptr(count), _ptr(loss_out), self._stream()), 'otto_mf_dp_local')
+
+    def dp_apply(self, E2, m2, v2, ids, rows, counts, lr, betas, eps, t_step):
+        """Apply half (``otto_mf_dp_apply``): the gathered export lists ``ids`` int32 [W, cap], ``rows`` float32
+        [W, cap, d] (consumed), ``counts`` int64 [W] summed in rank order and applied with Adam to the replicated table."""
+        t = self.torch
+        _chk('E2', E2, t.float32, self.device)
+        if E2.shape != (self.n2, self.d):
+            raise ValueError(f'table shape {tuple(E2.shape)} != ({self.n2},{self.d})')
+        for n, x, dt in (('m2', m2, t.float32), ('v2', v2, t.float32), ('ids', ids, t.int32), ('rows', rows, t.float32),
+                         ('counts', counts, t.int64)):
+            _chk(n, x, dt, self.device)
+        if ids.dim() != 2 or rows.shape != (ids.shape[0], ids.shape[1], self.d) or counts.shape != (ids.shape[0],):
+            raise ValueError(f'gathered buffers: ids {tuple(ids.shape)}, rows {tuple(rows.shape)}, counts {tuple(counts.shape)}')
+        W, cap = ids.shape
+        with t.cuda.device(self.device):
+            _lib.check(self._lib.otto_mf_dp_apply(
+                self._ctx, _ptr(E2), _ptr(m2), _ptr(v2), _ptr(ids), _ptr(rows), _ptr(counts), int(W), int(cap), float(lr),
+                float(betas[0]), float(betas[1]), float(eps), int(t_step), self._stream()), 'otto_mf_dp_apply')
+
     def bpr_step(self, U, V, u, i, seed, epoch, row0, lr, l2=0.0, mode=BPR_HOGWILD, loss_sum=None, neg_out=None):
         t = self.torch
         self._tables(U, V)

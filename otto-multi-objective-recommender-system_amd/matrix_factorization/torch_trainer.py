@@ -29,6 +29,7 @@ if __package__ in (None, ''):   # run as a script from its own directory, like t
 from .. import settings
 from . import torch_modules, torch_utils, torch_optim, metrics, visualization
 from .data import DeviceBatchLoader, build_aid_pairs_device, build_sessions_aids  # noqa: F401
+from .distributed import DataParallelSparseAdam, ShardedBatchLoader, full_state_dict
 from .torch_optim import loss_kind
 
 
@@ -63,18 +64,32 @@ class _LossLog:
 def train(train_loader, model, criterion, optimizer, device, scheduler=None):
     """Train ``model`` for one pass over ``train_loader``; returns the mean of the batch losses
     (reference ``train()``, ``torch_trainer.py:24-84``).  ``optimizer`` must be
-    ``torch_optim.SparseAdam`` (what the reference's configs name)."""
+    ``torch_optim.SparseAdam`` (what the reference's configs name).
+
+    Data parallel: a :class:`~.distributed.DataParallelSparseAdam` with a :class:`~.distributed.ShardedBatchLoader`;
+    every step is the global batch's step, and the epoch's loss is combined with one all-reduce, so every rank returns
+    the same number."""
     if not isinstance(optimizer, torch_optim.SparseAdam):
         raise ValueError('the fused trainer supports optimizer: SparseAdam (models/*/config.yaml)')
+    dp = isinstance(optimizer, DataParallelSparseAdam)
+    if dp != isinstance(train_loader, ShardedBatchLoader):
+        raise ValueError('data-parallel training needs both DataParallelSparseAdam and ShardedBatchLoader')
     model.train()
     log = _LossLog(torch.device(device))
-    for inputs, _ in train_loader:
+    for k, (inputs, _) in enumerate(train_loader):
         i1, i2, targets = _unpack(model, inputs, device)
-        optimizer.fused_step(model, i1, i2, targets, criterion, log.slot())
+        if dp:
+            optimizer.fused_step(model, i1, i2, targets, criterion, log.slot(), batch_global=train_loader.batch_global(k),
+                                 private_rows=train_loader.private_rows, max_local_batch=train_loader.max_local_batch)
+        else:
+            optimizer.fused_step(model, i1, i2, targets, criterion, log.slot())
         if scheduler is not None:
             scheduler.step()
     if log.n:
         model.engine(1).check()          # out-of-range row ids were skipped in the kernels: raise here, once per epoch
+    if dp:
+        # each step's value is this rank's loss sum / B_global: the ranks' sums add up to the step's mean loss
+        return float(optimizer.all_reduce_sum([log.values().sum()])[0] / max(log.n, 1)) if log.n else float('nan')
     return float(np.mean(log.values()))
 
 
@@ -84,7 +99,13 @@ def validate(val_loader, model, criterion, device, scores=False):
 
     The reference moves every batch's predictions to the host and scores them with scikit-learn (``:144-158``); here the
     eval kernel keeps running sums (MAE, MSE, accuracy) and only the classification model's ROC-AUC needs the predictions,
-    which stay on the device for one sort."""
+    which stay on the device for one sort.
+
+    With a :class:`~.distributed.ShardedBatchLoader` each rank evaluates its shard: batch losses are weighted by
+    ``B_local / B_global`` and summed over ranks, the running sums are all-reduced, and ROC-AUC is computed from the
+    all-gathered predictions; every rank returns the same values."""
+    if isinstance(val_loader, ShardedBatchLoader):
+        return _validate_sharded(val_loader, model, criterion, device, scores)
     model.eval()
     dev = torch.device(device)
     log = _LossLog(dev)
@@ -116,6 +137,65 @@ def validate(val_loader, model, criterion, device, scores=False):
     return val_loss, val_scores
 
 
+def _validate_sharded(loader, model, criterion, device, scores):
+    from . import distributed as dd
+    model.eval()
+    dev = torch.device(device)
+    log = _LossLog(dev)
+    kind = loss_kind(criterion)
+    E1, E2, _ = model._tables()
+    classification = isinstance(model, torch_modules.CollaborativeFiltering)
+    group, stage = loader.group, loader.stage
+    eng = model.engine(max(loader.max_local_batch, 1))
+    if scores:
+        eng.read_sums(reset=True)
+    truth, predictions = [], []
+    with torch.no_grad():
+        for k, (inputs, _) in enumerate(loader):
+            i1, i2, targets = _unpack(model, inputs, device)
+            slot = log.slot()
+            B = i1.numel()
+            if B == 0:
+                slot.zero_()
+                continue
+            pred = torch.empty(B, dtype=torch.float32, device=dev) if scores and classification else None
+            (eng.eval_sums if scores else eng.eval)(E1.data, E2.data, i1, i2, targets, kind, slot, pred)
+            slot.mul_(B / loader.batch_global(k))
+            if pred is not None:
+                truth.append(targets)
+                predictions.append(pred)
+    eng.check()
+    world = loader.world
+    red = torch.tensor([log.values().sum()] + (list(eng.read_sums(reset=True)) if scores else []), dtype=torch.float64)
+    if world > 1:
+        dd._all_reduce(red, dd.dist.ReduceOp.SUM, group, stage)
+    red = red.tolist()
+    val_loss = red[0] / max(log.n, 1) if log.n else float('nan')
+    val_scores = None
+    if scores:
+        auc = None
+        if classification:
+            n_max = max(loader.sizes)
+            t_loc = torch.zeros(n_max, dtype=torch.float32, device=dev)
+            p_loc = torch.zeros(n_max, dtype=torch.float32, device=dev)
+            if truth:
+                t_cat, p_cat = torch.cat(truth), torch.cat(predictions)
+                t_loc[:t_cat.numel()] = t_cat.to(torch.float32)
+                p_loc[:p_cat.numel()] = p_cat
+            t_all = torch.empty((world, n_max), dtype=torch.float32, device=dev)
+            p_all = torch.empty((world, n_max), dtype=torch.float32, device=dev)
+            if world > 1:
+                dd._all_gather(t_all, t_loc, group, stage)
+                dd._all_gather(p_all, p_loc, group, stage)
+            else:
+                t_all[0], p_all[0] = t_loc, p_loc
+            t_g = torch.cat([t_all[r, :n] for r, n in enumerate(loader.sizes)])
+            p_g = torch.cat([p_all[r, :n] for r, n in enumerate(loader.sizes)])
+            auc = metrics.roc_auc(t_g, torch.sigmoid(p_g))
+        val_scores = metrics.scores_from_sums(tuple(red[1:5]), classification, auc)
+    return val_loss, val_scores
+
+
 def build_optimizer(name, params, args):
     """``getattr(optim, name)`` of the reference (``:352``) with SparseAdam mapped to the fused one."""
     if name == 'SparseAdam':
@@ -123,9 +203,62 @@ def build_optimizer(name, params, args):
     raise ValueError(f'optimizer {name} is not supported by the fused trainer (SparseAdam only)')
 
 
+DISTRIBUTED_KEYS = {'backend', 'device'}
+
+
+def _distributed_setup(config):
+    """The optional ``training.distributed`` section: ``{backend: nccl | gloo, device: local_rank | configured}``. The
+    process group comes from the ``RANK`` / ``WORLD_SIZE`` / ``MASTER_ADDR`` / ``MASTER_PORT`` environment a
+    ``torchrun``-style launcher (``python -m torch.distributed.run``) sets. Returns None when the section is absent."""
+    sec = config['training'].get('distributed')
+    if sec is None:
+        return None
+    if not isinstance(sec, dict):
+        raise ValueError('training.distributed must be a mapping such as {backend: nccl}')
+    unknown = set(sec) - DISTRIBUTED_KEYS
+    if unknown:
+        raise ValueError(f'training.distributed: unsupported key(s) {sorted(unknown)} (supported: {sorted(DISTRIBUTED_KEYS)})')
+    backend = sec.get('backend', 'nccl')
+    if backend not in ('nccl', 'gloo'):
+        raise ValueError(f"training.distributed.backend must be 'nccl' or 'gloo' (got {backend!r})")
+    placement = sec.get('device', 'local_rank')
+    if placement not in ('local_rank', 'configured'):
+        raise ValueError(f"training.distributed.device must be 'local_rank' or 'configured' (got {placement!r})")
+    if config['training']['optimizer'] != 'SparseAdam':
+        raise ValueError('data-parallel training supports optimizer: SparseAdam only')
+    import os
+    missing = [k for k in ('RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT') if k not in os.environ]
+    if missing:
+        raise ValueError(f'training.distributed needs a torchrun-style launcher: {", ".join(missing)} not set '
+                         '(python -m torch.distributed.run --nproc_per_node=N torch_trainer.py <config>)')
+    import torch.distributed as dist
+    device = torch.device(f'cuda:{int(os.environ.get("LOCAL_RANK", 0))}') if placement == 'local_rank' \
+        else torch.device(config['training']['device'])
+    torch.cuda.set_device(device)
+    owned = not dist.is_initialized()
+    if owned:
+        dist.init_process_group(backend)
+    return dict(backend=backend, device=device, rank=dist.get_rank(), world=dist.get_world_size(), owned=owned)
+
+
 def run(config, df=None):
-    """Everything below ``__main__`` in the reference (``torch_trainer.py:172-505``)."""
+    """Everything below ``__main__`` in the reference (``torch_trainer.py:172-505``).
+
+    With a ``training.distributed`` section (:func:`_distributed_setup`) every rank trains its shard with
+    :class:`~.distributed.DataParallelSparseAdam`; rank 0 alone builds the dataset file, writes checkpoints (with every
+    rank's session rows, :func:`~.distributed.full_state_dict`) and the learning curve. Without it nothing changes."""
     import pandas as pd
+    dpc = _distributed_setup(config)
+    try:
+        return _run(config, df, pd, dpc)
+    finally:
+        if dpc is not None and dpc['owned']:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+
+
+def _run(config, df, pd, dpc):
+    lead = dpc is None or dpc['rank'] == 0
     cls = config['model']['model_class']
     if cls == 'CollaborativeFiltering':
         root, fname, score_keys = pathlib.Path(settings.DATA / 'collaborative_filtering'), 'aid_pairs.parquet', ('accuracy', 'roc_auc')
@@ -135,7 +268,7 @@ def run(config, df=None):
     else:
         raise ValueError('Invalid model')
     root.mkdir(parents=True, exist_ok=True)
-    if not config['dataset']['load_dataset']:
+    if not config['dataset']['load_dataset'] and lead:
         if df is None:
             df = pd.concat((pd.read_pickle(settings.DATA / 'train.pkl'), pd.read_pickle(settings.DATA / 'test.pkl')),
                            axis=0, ignore_index=True)
@@ -153,16 +286,31 @@ def run(config, df=None):
             ds = build_sessions_aids(df)
         ds.to_parquet(root / fname)
         logging.info(f'{fname} is saved to {root}')
-    else:
+    elif lead:
         logging.info(f'Using pre-computed dataset from {root / fname}')
+    if dpc is not None:
+        import torch.distributed as dist
+        dist.barrier()            # rank 0 has written the dataset file
 
     tr = config['training']
-    device = torch.device(tr['device'])
+    device = torch.device(tr['device']) if dpc is None else dpc['device']
     torch_utils.set_seed(tr['random_state'], deterministic_cudnn=tr['deterministic_cudnn'])
-    train_loader = DeviceBatchLoader.from_parquet(root / fname, tr['training_batch_size'], shuffle=True, device=device,
-                                                  seed=tr['random_state'])
-    val_loader = DeviceBatchLoader(train_loader.columns, tr['validation_batch_size'], shuffle=True, device=device,
-                                   seed=tr['random_state'] + 1)       # validation file == training file (reference :307-311)
+    if dpc is None:
+        train_loader = DeviceBatchLoader.from_parquet(root / fname, tr['training_batch_size'], shuffle=True, device=device,
+                                                      seed=tr['random_state'])
+        val_loader = DeviceBatchLoader(train_loader.columns, tr['validation_batch_size'], shuffle=True, device=device,
+                                       seed=tr['random_state'] + 1)       # validation file == training file (reference :307-311)
+    else:
+        import pyarrow.parquet as pq
+        table = pq.read_table(str(root / fname))
+        cols = {n: table.column(n).to_numpy() for n in table.column_names if not n.startswith('__')}
+        shard = dict(shard_key=None) if cls == 'CollaborativeFiltering' else \
+            dict(shard_key='session', n_keys=config['model']['n_sessions'])
+        train_loader = ShardedBatchLoader(cols, tr['training_batch_size'], shuffle=True, device=device, seed=tr['random_state'],
+                                          **shard)
+        val_loader = ShardedBatchLoader(cols, tr['validation_batch_size'], shuffle=True, device=device,
+                                        seed=tr['random_state'] + 1, **shard)
+        del table, cols
     model_root = pathlib.Path(settings.MODELS / config['persistence']['model_directory'])
     model_root.mkdir(parents=True, exist_ok=True)
     criterion = getattr(torch.nn, tr['loss_function'])(**tr['loss_args'])
@@ -178,7 +326,9 @@ def run(config, df=None):
     if m['model_checkpoint_path'] is not None:
         model.load_state_dict(torch.load(m['model_checkpoint_path'], weights_only=True))
     model.to(device)
-    optimizer = build_optimizer(tr['optimizer'], model.parameters(), tr['optimizer_args'])
+    optimizer = build_optimizer(tr['optimizer'], model.parameters(), tr['optimizer_args']) if dpc is None else \
+        DataParallelSparseAdam(model.parameters(), **tr['optimizer_args'])
+    state = (lambda: model.state_dict()) if dpc is None else (lambda: full_state_dict(model, train_loader))
     plateau = tr['lr_scheduler'] == 'ReduceLROnPlateau'
     scheduler = getattr(optim.lr_scheduler, tr['lr_scheduler'])(optimizer, **tr['lr_scheduler_args'])
 
@@ -191,12 +341,16 @@ def run(config, df=None):
         logging.info(f'Epoch {epoch} - Training Loss: {train_loss:.4f} - Validation Loss: {val_loss:.4f} - '
                      + ' '.join(f'{k}: {v:.4f}' for k, v in (val_scores or {}).items()))
         if epoch in config['persistence']['save_epoch_model']:
-            torch.save(model.state_dict(), model_root / f'model_epoch_{epoch}.pt')
-            logging.info(f'Saved model_epoch_{epoch}.pt to {model_root}')
+            sd = state()          # collective in data-parallel runs: every rank takes part, rank 0 writes
+            if lead:
+                torch.save(sd, model_root / f'model_epoch_{epoch}.pt')
+                logging.info(f'Saved model_epoch_{epoch}.pt to {model_root}')
         best_val_loss = np.min(summary['val_loss']) if len(summary['val_loss']) > 0 else np.inf
         if val_loss < best_val_loss and config['persistence']['save_best_model']:
-            torch.save(model.state_dict(), model_root / 'model_best.pt')
-            logging.info(f'Saved model_best.pt (validation loss decreased from {best_val_loss:.6f} to {val_loss:.6f})')
+            sd = state()
+            if lead:
+                torch.save(sd, model_root / 'model_best.pt')
+                logging.info(f'Saved model_best.pt (validation loss decreased from {best_val_loss:.6f} to {val_loss:.6f})')
         summary['train_loss'].append(train_loss)
         summary['val_loss'].append(val_loss)
         for k in score_keys:
@@ -208,7 +362,7 @@ def run(config, df=None):
             break
     best_epoch = int(np.argmin(summary['val_loss']))
     scores = {'val_loss': summary['val_loss'][best_epoch], **{f'val_{k}': summary[f'val_{k}'][best_epoch] for k in score_keys}}
-    if config['persistence']['visualize_learning_curve']:
+    if config['persistence']['visualize_learning_curve'] and lead:
         visualization.visualize_learning_curve(training_losses=summary['train_loss'], validation_losses=summary['val_loss'],
                                                validation_scores={f'val_{k}': summary[f'val_{k}'] for k in score_keys},
                                                path=str(model_root / 'learning_curve.png'))
