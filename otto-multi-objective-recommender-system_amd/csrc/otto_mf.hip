@@ -159,8 +159,8 @@ __global__ __launch_bounds__(256) void k_mf_fwd(FwdArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// SparseAdam step (train() body). torch coalesces duplicate rows of the sparse gradient before the non-linear
-// update; here, without a sort:
+// SparseAdam step (train() body): one kernel family, two modes. torch coalesces duplicate rows of the sparse gradient
+// before the non-linear update; here, without a sort:
 //   phase 1  k_rmf_fwd   : forward + loss + dL/dout per sample; every occurrence bumps its row's counter with ONE
 //                          returning atomic. The SECOND arriver of a row learns that the row is duplicated: it zeroes
 //                          its own slot of the [2B, d] gradient buffer and publishes the slot id in slot[row].
@@ -170,6 +170,21 @@ __global__ __launch_bounds__(256) void k_mf_fwd(FwdArgs a) {
 //                          (global_atomic_add_f32, 16 bytes per lane, contiguous per row).
 //   phase 3  k_rmf_apply : the second arriver of each duplicated row applies Adam from its slot and clears the counter.
 // Counters are zero between steps (phase 2 / 3 clear exactly the rows they finish).
+//
+// EXPORT = false is the single-GPU step (otto_mf_step_sparse_adam), EXPORT = true the local half of the data-parallel
+// step (otto_mf_dp_local), split around the caller's all-gather:
+//   local half  the same three phases over one rank's batch, with the loss divided by the GLOBAL batch size (inv_b) and
+//               samples whose private row lies outside [lo, hi) skipped. Rows of the private table (sessions) are
+//               handled as in the single step; rows of an EXPORTED table (the replicated aids; both columns of a shared
+//               table) are not updated: every distinct row takes one entry of a compact export list (ids[pos],
+//               rows[pos][d] = its coalesced gradient). A duplicated row's entry is claimed and zeroed by its second
+//               arriver in phase 1 and accumulated with row-contiguous float atomics in phase 2; a single-occurrence row
+//               claims its entry in phase 2 and stores its gradient row plainly. Phase 3 only clears their counters.
+//   apply half  k_dpa_claim / k_dpa_sum (ranks 1..W-1) / k_dpa_adam over the gathered [W][cap] lists: the smallest
+//               flat entry of a row (atomicMin on the row's owner word) owns it, the other ranks' entries are added into
+//               the owner's row in rank order with plain loads and stores (one launch per rank: a row is in a rank's
+//               list at most once, so no two adders meet), then Adam once per owner entry. No float atomic touches the
+//               cross-rank sum, so every replica computes the same bits.
 // ---------------------------------------------------------------------------
 struct StepArgs {
     float* E1; float* m1; float* v1;
@@ -183,15 +198,22 @@ struct StepArgs {
     int G;
     int loss_kind;
     float* partial;
-    float* coef;            // [B] dL/dout / B
+    float* coef;            // [B] dL/dout * inv_b
     uint32_t* cnt1;         // [n1] occurrences of the row in this batch
     uint32_t* cnt2;         // [n2] (== cnt1 for a shared table)
     int32_t* slot1;         // [n1] duplicated rows: occurrence id whose gradient slot accumulates the row
-    int32_t* slot2;
+    int32_t* slot2;         //      (export entry of an exported row)
     uint8_t* role;          // [2B] 1: this occurrence applies its slot in phase 3
     float* grad;            // [2B, d]
     uint32_t* err;
     float omb1, omb2, eps, step_size;   // 1-beta1, 1-beta2
+    float inv_b;            // 1 / B; 1 / B_global in the data-parallel local half
+    // EXPORT = true only
+    int shared;             // 1: shared table, both columns export; 0: table 1 is private
+    int64_t lo, hi;         // private rows this rank owns
+    int32_t* ids;           // [cap] export list
+    float* rows;            // [cap, d]
+    unsigned long long* count;  // distinct rows exported
 };
 
 __device__ __forceinline__ float adam1(float g, float& m, float& v, float omb1, float omb2, float eps, float step_size) {
@@ -211,19 +233,34 @@ __device__ __forceinline__ void adam_row(float* E, float* M, float* V, float4 p,
     st4(E, p); st4(M, m); st4(V, v);
 }
 
-__device__ __forceinline__ bool rows_ok(const StepArgs& a, int64_t r1, int64_t r2) {
-    return (uint64_t)r1 < (uint64_t)a.n1 && (uint64_t)r2 < (uint64_t)a.n2;
+// table 2 is exported in the data-parallel local half, table 1 only when it is table 2 (shared table)
+template <bool EXPORT>
+__device__ __forceinline__ bool exported(const StepArgs& a, bool table2) {
+    return EXPORT && (table2 || a.shared);
 }
 
+template <bool EXPORT>
+__device__ __forceinline__ bool rows_ok(const StepArgs& a, int64_t r1, int64_t r2) {
+    const bool ok = (uint64_t)r1 < (uint64_t)a.n1 && (uint64_t)r2 < (uint64_t)a.n2;
+    if constexpr (EXPORT) return ok && (a.shared || (r1 >= a.lo && r1 < a.hi));
+    return ok;
+}
+
+// the group leader's value for every lane of the group (G <= 64 lanes inside one wave)
+__device__ __forceinline__ int32_t from_leader(int32_t v, int gl) {
+    return __shfl(v, (int)((threadIdx.x & 63) - gl), 64);
+}
+
+template <bool EXPORT>
 __global__ __launch_bounds__(256) void k_rmf_fwd(StepArgs a) {
     const int G = a.G;
     const int gl = threadIdx.x & (G - 1);
     const int64_t gpb = 256 / G;
+    const bool x1 = exported<EXPORT>(a, false), x2 = exported<EXPORT>(a, true);
     float lsum = 0.f;
-    const float invB = 1.0f / (float)a.B;
     for (int64_t b = (int64_t)blockIdx.x * gpb + threadIdx.x / G; b < a.B; b += (int64_t)gridDim.x * gpb) {
         const int64_t r1 = a.i1[b], r2 = a.i2[b];
-        if (!rows_ok(a, r1, r2)) {
+        if (!rows_ok<EXPORT>(a, r1, r2)) {
             if (gl == 0) { atomicAdd(a.err, 1u); a.role[b] = 0; a.role[a.B + b] = 0; }
             continue;
         }
@@ -231,24 +268,47 @@ __global__ __launch_bounds__(256) void k_rmf_fwd(StepArgs a) {
         const float4 e2 = ld4(a.E2 + r2 * a.d + 4 * gl);
         const float out = group_sum(dot4(e1, e2), G);
         uint32_t old1 = 0, old2 = 0;
+        int32_t s1 = -1, s2 = -1;   // export entry claimed by this occurrence (second arriver of an exported row)
         if (gl == 0) {
             float l, g;
             loss_grad(a.loss_kind, out, (float)a.target[b], &l, &g);
             lsum += l;
-            a.coef[b] = g * invB;
+            a.coef[b] = g * a.inv_b;
             old1 = atomicAdd(&a.cnt1[r1], 1u);
             old2 = atomicAdd(&a.cnt2[r2], 1u);
             a.role[b] = old1 == 1u;
             a.role[a.B + b] = old2 == 1u;
-            if (old1 == 1u) a.slot1[r1] = (int32_t)b;
-            if (old2 == 1u) a.slot2[r2] = (int32_t)(a.B + b);
+            if (old1 == 1u) {
+                if (x1) {
+                    s1 = (int32_t)atomicAdd(a.count, 1ull);
+                    a.ids[s1] = (int32_t)r1;
+                    a.slot1[r1] = s1;
+                } else {
+                    a.slot1[r1] = (int32_t)b;
+                }
+            }
+            if (old2 == 1u) {
+                if (x2) {
+                    s2 = (int32_t)atomicAdd(a.count, 1ull);
+                    a.ids[s2] = (int32_t)r2;
+                    a.slot2[r2] = s2;
+                } else {
+                    a.slot2[r2] = (int32_t)(a.B + b);
+                }
+            }
         }
-        // the group leader's ranks, for every lane of the group (G <= 64 lanes inside one wave)
-        old1 = (uint32_t)__shfl((int)old1, (int)((threadIdx.x & 63) - gl), 64);
-        old2 = (uint32_t)__shfl((int)old2, (int)((threadIdx.x & 63) - gl), 64);
+        old1 = (uint32_t)from_leader((int32_t)old1, gl);
+        if (EXPORT) {
+            s1 = from_leader(s1, gl);
+            s2 = from_leader(s2, gl);
+        } else {
+            old2 = (uint32_t)from_leader((int32_t)old2, gl);
+        }
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (old1 == 1u) st4(a.grad + b * a.d + 4 * gl, z);
-        if (old2 == 1u) st4(a.grad + (a.B + b) * a.d + 4 * gl, z);
+        if (!x1 && old1 == 1u) st4(a.grad + b * a.d + 4 * gl, z);
+        if (!x2 && old2 == 1u) st4(a.grad + (a.B + b) * a.d + 4 * gl, z);
+        if (s1 >= 0) st4(a.rows + (int64_t)s1 * a.d + 4 * gl, z);
+        if (s2 >= 0) st4(a.rows + (int64_t)s2 * a.d + 4 * gl, z);
     }
     block_loss_partial<256>(lsum, a.partial);
 }
@@ -257,13 +317,45 @@ __device__ __forceinline__ void atomic_add4(float* p, float4 v) {
     atomicAdd(p + 0, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
 }
 
+// one occurrence's gradient row of a row that is not exported: Adam in place for a single-occurrence row (p = the row,
+// e = its value), an add into the published slot for a duplicated row
+__device__ __forceinline__ void update_row(const StepArgs& a, uint32_t c, int64_t r, float* p, float* M, float* V,
+                                           uint32_t* cnt, const int32_t* slot, float4 e, float4 g, int gl) {
+    if (c == 1u) {
+        adam_row(p, M + r * a.d + 4 * gl, V + r * a.d + 4 * gl, e, g, a);
+        if (gl == 0) cnt[r] = 0;
+    } else {
+        atomic_add4(a.grad + (int64_t)slot[r] * a.d + 4 * gl, g);
+    }
+}
+
+// one exported occurrence's gradient row: a single-occurrence row claims its entry and stores, a duplicated row adds
+// into the entry its second arriver claimed
+__device__ __forceinline__ void dp_export(const StepArgs& a, uint32_t c, int64_t r, uint32_t* cnt, const int32_t* slot,
+                                          float4 g, int gl) {
+    if (c == 1u) {
+        int32_t s = 0;
+        if (gl == 0) {
+            s = (int32_t)atomicAdd(a.count, 1ull);
+            a.ids[s] = (int32_t)r;
+            cnt[r] = 0;
+        }
+        s = from_leader(s, gl);
+        st4(a.rows + (int64_t)s * a.d + 4 * gl, g);
+    } else {
+        atomic_add4(a.rows + (int64_t)slot[r] * a.d + 4 * gl, g);
+    }
+}
+
+template <bool EXPORT>
 __global__ __launch_bounds__(256) void k_rmf_acc(StepArgs a) {
     const int G = a.G;
     const int gl = threadIdx.x & (G - 1);
     const int64_t gpb = 256 / G;
+    const bool x1 = exported<EXPORT>(a, false), x2 = exported<EXPORT>(a, true);
     for (int64_t b = (int64_t)blockIdx.x * gpb + threadIdx.x / G; b < a.B; b += (int64_t)gridDim.x * gpb) {
         const int64_t r1 = a.i1[b], r2 = a.i2[b];
-        if (!rows_ok(a, r1, r2)) continue;
+        if (!rows_ok<EXPORT>(a, r1, r2)) continue;
         const uint32_t c1 = a.cnt1[r1], c2 = a.cnt2[r2];
         const float c = a.coef[b];
         float* p1 = a.E1 + r1 * a.d + 4 * gl;
@@ -273,21 +365,15 @@ __global__ __launch_bounds__(256) void k_rmf_acc(StepArgs a) {
         const float4 g2 = make_float4(c * e1.x, c * e1.y, c * e1.z, c * e1.w);
         // every lane of the group has read both counters and both rows before anything is written
         __builtin_amdgcn_wave_barrier();
-        if (c1 == 1u) {
-            adam_row(p1, a.m1 + r1 * a.d + 4 * gl, a.v1 + r1 * a.d + 4 * gl, e1, g1, a);
-            if (gl == 0) a.cnt1[r1] = 0;
-        } else {
-            atomic_add4(a.grad + (int64_t)a.slot1[r1] * a.d + 4 * gl, g1);
-        }
-        if (c2 == 1u) {
-            adam_row(p2, a.m2 + r2 * a.d + 4 * gl, a.v2 + r2 * a.d + 4 * gl, e2, g2, a);
-            if (gl == 0) a.cnt2[r2] = 0;
-        } else {
-            atomic_add4(a.grad + (int64_t)a.slot2[r2] * a.d + 4 * gl, g2);
-        }
+        if (x1) dp_export(a, c1, r1, a.cnt1, a.slot1, g1, gl);
+        else update_row(a, c1, r1, p1, a.m1, a.v1, a.cnt1, a.slot1, e1, g1, gl);
+        if (x2) dp_export(a, c2, r2, a.cnt2, a.slot2, g2, gl);
+        else update_row(a, c2, r2, p2, a.m2, a.v2, a.cnt2, a.slot2, e2, g2, gl);
     }
 }
 
+// second arrivers: a duplicated row that is not exported gets Adam from its slot; every duplicated row's counter is cleared
+template <bool EXPORT>
 __global__ __launch_bounds__(256) void k_rmf_apply(StepArgs a) {
     const int G = a.G;
     const int gl = threadIdx.x & (G - 1);
@@ -296,159 +382,10 @@ __global__ __launch_bounds__(256) void k_rmf_apply(StepArgs a) {
         if (!a.role[o]) continue;
         const bool first = o < a.B;
         const int64_t r = first ? a.i1[o] : a.i2[o - a.B];
-        float* E = (first ? a.E1 : a.E2) + r * a.d + 4 * gl;
-        adam_row(E, (first ? a.m1 : a.m2) + r * a.d + 4 * gl, (first ? a.v1 : a.v2) + r * a.d + 4 * gl, ld4(E),
-                 ld4(a.grad + o * a.d + 4 * gl), a);
-        if (gl == 0) (first ? a.cnt1 : a.cnt2)[r] = 0;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Data-parallel SparseAdam step, split around the caller's all-gather.
-//   local half  k_dp_fwd / k_dp_acc / k_dp_fin: the single-GPU step's three phases over one rank's batch, with the loss
-//               divided by the GLOBAL batch size. Rows of the private table (sessions) get Adam in place exactly as in
-//               k_rmf_*; rows of the replicated table (aids; both columns of a shared table) are not updated: every
-//               distinct row takes one entry of a compact export list (ids[pos], rows[pos][d] = its coalesced gradient).
-//               A duplicated row's entry is claimed and zeroed by its second arriver in k_dp_fwd and accumulated with
-//               row-contiguous float atomics in k_dp_acc; a single-occurrence row claims its entry in k_dp_acc and stores
-//               its gradient row plainly. k_dp_fin applies the private duplicates and clears the remaining counters.
-//   apply half  k_dpa_claim / k_dpa_sum (ranks 1..W-1) / k_dpa_adam over the gathered [W][cap] lists: the smallest
-//               flat entry of a row (atomicMin on the row's owner word) owns it, the other ranks' entries are added into
-//               the owner's row in rank order with plain loads and stores (one launch per rank: a row is in a rank's
-//               list at most once, so no two adders meet), then Adam once per owner entry. No float atomic touches the
-//               cross-rank sum, so every replica computes the same bits.
-// ---------------------------------------------------------------------------
-struct DpArgs {
-    StepArgs a;
-    int priv;                   // 1: table 1 is private (MatrixFactorization); 0: shared table, both columns export
-    int64_t lo, hi;             // private rows this rank owns
-    int32_t* ids;               // [cap] export list
-    float* rows;                // [cap, d]
-    unsigned long long* count;  // distinct rows exported
-    float inv_bg;               // 1 / B_global
-};
-
-__device__ __forceinline__ bool dp_ok(const DpArgs& p, int64_t r1, int64_t r2) {
-    return rows_ok(p.a, r1, r2) && (!p.priv || (r1 >= p.lo && r1 < p.hi));
-}
-
-// the group leader's value for every lane of the group (G <= 64 lanes inside one wave)
-__device__ __forceinline__ int32_t from_leader(int32_t v, int gl) {
-    return __shfl(v, (int)((threadIdx.x & 63) - gl), 64);
-}
-
-__global__ __launch_bounds__(256) void k_dp_fwd(DpArgs p) {
-    const StepArgs& a = p.a;
-    const int G = a.G;
-    const int gl = threadIdx.x & (G - 1);
-    const int64_t gpb = 256 / G;
-    float lsum = 0.f;
-    for (int64_t b = (int64_t)blockIdx.x * gpb + threadIdx.x / G; b < a.B; b += (int64_t)gridDim.x * gpb) {
-        const int64_t r1 = a.i1[b], r2 = a.i2[b];
-        if (!dp_ok(p, r1, r2)) {
-            if (gl == 0) { atomicAdd(a.err, 1u); a.role[b] = 0; a.role[a.B + b] = 0; }
-            continue;
-        }
-        const float4 e1 = ld4(a.E1 + r1 * a.d + 4 * gl);
-        const float4 e2 = ld4(a.E2 + r2 * a.d + 4 * gl);
-        const float out = group_sum(dot4(e1, e2), G);
-        int32_t s1 = -1, s2 = -1;   // export entry claimed by this occurrence (second arriver of an exported row)
-        uint32_t old1 = 0;
-        if (gl == 0) {
-            float l, g;
-            loss_grad(a.loss_kind, out, (float)a.target[b], &l, &g);
-            lsum += l;
-            a.coef[b] = g * p.inv_bg;
-            old1 = atomicAdd(&a.cnt1[r1], 1u);
-            const uint32_t old2 = atomicAdd(&a.cnt2[r2], 1u);
-            a.role[b] = old1 == 1u;
-            a.role[a.B + b] = old2 == 1u;
-            if (old1 == 1u) {
-                if (p.priv) {
-                    a.slot1[r1] = (int32_t)b;
-                } else {
-                    s1 = (int32_t)atomicAdd(p.count, 1ull);
-                    p.ids[s1] = (int32_t)r1;
-                    a.slot1[r1] = s1;
-                }
-            }
-            if (old2 == 1u) {
-                s2 = (int32_t)atomicAdd(p.count, 1ull);
-                p.ids[s2] = (int32_t)r2;
-                a.slot2[r2] = s2;
-            }
-        }
-        old1 = (uint32_t)from_leader((int32_t)old1, gl);
-        s1 = from_leader(s1, gl);
-        s2 = from_leader(s2, gl);
-        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (p.priv && old1 == 1u) st4(a.grad + b * a.d + 4 * gl, z);
-        if (s1 >= 0) st4(p.rows + (int64_t)s1 * a.d + 4 * gl, z);
-        if (s2 >= 0) st4(p.rows + (int64_t)s2 * a.d + 4 * gl, z);
-    }
-    block_loss_partial<256>(lsum, a.partial);
-}
-
-// one exported occurrence's gradient row: a single-occurrence row claims its entry and stores, a duplicated row adds
-// into the entry its second arriver claimed
-__device__ __forceinline__ void dp_export(const DpArgs& p, uint32_t c, int64_t r, uint32_t* cnt, const int32_t* slot,
-                                          float4 g, int gl) {
-    const StepArgs& a = p.a;
-    if (c == 1u) {
-        int32_t s = 0;
-        if (gl == 0) {
-            s = (int32_t)atomicAdd(p.count, 1ull);
-            p.ids[s] = (int32_t)r;
-            cnt[r] = 0;
-        }
-        s = from_leader(s, gl);
-        st4(p.rows + (int64_t)s * a.d + 4 * gl, g);
-    } else {
-        atomic_add4(p.rows + (int64_t)slot[r] * a.d + 4 * gl, g);
-    }
-}
-
-__global__ __launch_bounds__(256) void k_dp_acc(DpArgs p) {
-    const StepArgs& a = p.a;
-    const int G = a.G;
-    const int gl = threadIdx.x & (G - 1);
-    const int64_t gpb = 256 / G;
-    for (int64_t b = (int64_t)blockIdx.x * gpb + threadIdx.x / G; b < a.B; b += (int64_t)gridDim.x * gpb) {
-        const int64_t r1 = a.i1[b], r2 = a.i2[b];
-        if (!dp_ok(p, r1, r2)) continue;
-        const uint32_t c1 = a.cnt1[r1], c2 = a.cnt2[r2];
-        const float c = a.coef[b];
-        float* p1 = a.E1 + r1 * a.d + 4 * gl;
-        const float4 e1 = ld4(p1), e2 = ld4(a.E2 + r2 * a.d + 4 * gl);
-        const float4 g1 = make_float4(c * e2.x, c * e2.y, c * e2.z, c * e2.w);
-        const float4 g2 = make_float4(c * e1.x, c * e1.y, c * e1.z, c * e1.w);
-        // every lane of the group has read both counters and both rows before anything is written
-        __builtin_amdgcn_wave_barrier();
-        if (!p.priv) {
-            dp_export(p, c1, r1, a.cnt1, a.slot1, g1, gl);
-        } else if (c1 == 1u) {
-            adam_row(p1, a.m1 + r1 * a.d + 4 * gl, a.v1 + r1 * a.d + 4 * gl, e1, g1, a);
-            if (gl == 0) a.cnt1[r1] = 0;
-        } else {
-            atomic_add4(a.grad + (int64_t)a.slot1[r1] * a.d + 4 * gl, g1);
-        }
-        dp_export(p, c2, r2, a.cnt2, a.slot2, g2, gl);
-    }
-}
-
-// second arrivers: private duplicated rows get Adam from their slot; every duplicated row's counter is cleared
-__global__ __launch_bounds__(256) void k_dp_fin(DpArgs p) {
-    const StepArgs& a = p.a;
-    const int G = a.G;
-    const int gl = threadIdx.x & (G - 1);
-    const int64_t gpb = 256 / G;
-    for (int64_t o = (int64_t)blockIdx.x * gpb + threadIdx.x / G; o < 2 * a.B; o += (int64_t)gridDim.x * gpb) {
-        if (!a.role[o]) continue;
-        const bool first = o < a.B;
-        const int64_t r = first ? a.i1[o] : a.i2[o - a.B];
-        if (first && p.priv) {
-            float* E = a.E1 + r * a.d + 4 * gl;
-            adam_row(E, a.m1 + r * a.d + 4 * gl, a.v1 + r * a.d + 4 * gl, ld4(E), ld4(a.grad + o * a.d + 4 * gl), a);
+        if (!exported<EXPORT>(a, !first)) {
+            float* E = (first ? a.E1 : a.E2) + r * a.d + 4 * gl;
+            adam_row(E, (first ? a.m1 : a.m2) + r * a.d + 4 * gl, (first ? a.v1 : a.v2) + r * a.d + 4 * gl, ld4(E),
+                     ld4(a.grad + o * a.d + 4 * gl), a);
         }
         if (gl == 0) (first ? a.cnt1 : a.cnt2)[r] = 0;
     }
@@ -1010,19 +947,17 @@ extern "C" int otto_mf_read_sums(otto_mf_ctx* c, double* h_sums, int32_t reset, 
     return 0;
 }
 
-extern "C" int otto_mf_step_sparse_adam(otto_mf_ctx* c, float* E1, float* m1, float* v1, float* E2, float* m2, float* v2,
-                                        const int64_t* i1, const int64_t* i2, const int64_t* target, int64_t B,
-                                        int32_t loss_kind, double lr, double beta1, double beta2, double eps, int64_t t,
-                                        float* loss_out, void* stream) {
-    OTTO_TRY(check_batch(c, B));
-    OTTO_REQUIRE(E1 && m1 && v1 && E2 && m2 && v2 && i1 && i2 && target && loss_out, "null argument");
-    OTTO_REQUIRE(loss_kind == OTTO_MF_LOSS_MSE || loss_kind == OTTO_MF_LOSS_BCE, "unknown loss kind %d", loss_kind);
-    OTTO_REQUIRE(t >= 1, "step count t must be >= 1");
-    OTTO_REQUIRE(!c->shared || (E1 == E2 && m1 == m2 && v1 == v2), "shared_table context needs identical table pointers");
-    hipStream_t s = (hipStream_t)stream;
-    const int grid = mf_grid(B, c->G);
+static void adam_params(StepArgs* a, double lr, double beta1, double beta2, double eps, int64_t t) {
     // torch: step_size = lr * sqrt(1 - beta2^t) / (1 - beta1^t), evaluated in double on the host
     const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
+    a->omb1 = (float)(1.0 - beta1); a->omb2 = (float)(1.0 - beta2); a->eps = (float)eps;
+    a->step_size = (float)(lr * sqrt(bc2) / bc1);
+}
+
+// the step's arguments of both modes; the data-parallel caller adds the export fields
+static StepArgs step_args(otto_mf_ctx* c, float* E1, float* m1, float* v1, float* E2, float* m2, float* v2, const int64_t* i1,
+                          const int64_t* i2, const int64_t* target, int64_t B, int64_t B_div, int32_t loss_kind, double lr,
+                          double beta1, double beta2, double eps, int64_t t) {
     StepArgs a;
     memset(&a, 0, sizeof a);
     a.E1 = E1; a.m1 = m1; a.v1 = v1; a.E2 = E2; a.m2 = m2; a.v2 = v2;
@@ -1032,20 +967,34 @@ extern "C" int otto_mf_step_sparse_adam(otto_mf_ctx* c, float* E1, float* m1, fl
     a.cnt1 = c->cnt1.as<uint32_t>(); a.cnt2 = c->shared ? a.cnt1 : c->cnt2.as<uint32_t>();
     a.slot1 = c->slot1.as<int32_t>(); a.slot2 = c->shared ? a.slot1 : c->slot2.as<int32_t>();
     a.role = c->role.as<uint8_t>(); a.grad = c->grad.as<float>(); a.err = c->err.as<uint32_t>();
-    a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
-    a.step_size = (float)(lr * sqrt(bc2) / bc1);
-    k_rmf_fwd<<<grid, 256, 0, s>>>(a);
-    k_loss_final<<<1, 256, 0, s>>>(c->partial.as<float>(), grid, 1.0f / (float)B, loss_out, nullptr, 0, MF_GRID_MAX, 0.0);
-    k_rmf_acc<<<grid, 256, 0, s>>>(a);
-    k_rmf_apply<<<mf_grid(2 * B, c->G), 256, 0, s>>>(a);
+    adam_params(&a, lr, beta1, beta2, eps, t);
+    a.inv_b = 1.0f / (float)B_div;
+    a.shared = c->shared;
+    return a;
+}
+
+template <bool EXPORT>
+static int launch_step(otto_mf_ctx* c, const StepArgs& a, float* loss_out, hipStream_t s) {
+    const int grid = mf_grid(a.B, c->G);
+    k_rmf_fwd<EXPORT><<<grid, 256, 0, s>>>(a);
+    k_loss_final<<<1, 256, 0, s>>>(a.partial, grid, a.inv_b, loss_out, nullptr, 0, MF_GRID_MAX, 0.0);
+    k_rmf_acc<EXPORT><<<grid, 256, 0, s>>>(a);
+    k_rmf_apply<EXPORT><<<mf_grid(2 * a.B, c->G), 256, 0, s>>>(a);
     OTTO_HIP(hipGetLastError());
     return 0;
 }
 
-static void adam_params(StepArgs* a, double lr, double beta1, double beta2, double eps, int64_t t) {
-    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
-    a->omb1 = (float)(1.0 - beta1); a->omb2 = (float)(1.0 - beta2); a->eps = (float)eps;
-    a->step_size = (float)(lr * sqrt(bc2) / bc1);
+extern "C" int otto_mf_step_sparse_adam(otto_mf_ctx* c, float* E1, float* m1, float* v1, float* E2, float* m2, float* v2,
+                                        const int64_t* i1, const int64_t* i2, const int64_t* target, int64_t B,
+                                        int32_t loss_kind, double lr, double beta1, double beta2, double eps, int64_t t,
+                                        float* loss_out, void* stream) {
+    OTTO_TRY(check_batch(c, B));
+    OTTO_REQUIRE(E1 && m1 && v1 && E2 && m2 && v2 && i1 && i2 && target && loss_out, "null argument");
+    OTTO_REQUIRE(loss_kind == OTTO_MF_LOSS_MSE || loss_kind == OTTO_MF_LOSS_BCE, "unknown loss kind %d", loss_kind);
+    OTTO_REQUIRE(t >= 1, "step count t must be >= 1");
+    OTTO_REQUIRE(!c->shared || (E1 == E2 && m1 == m2 && v1 == v2), "shared_table context needs identical table pointers");
+    const StepArgs a = step_args(c, E1, m1, v1, E2, m2, v2, i1, i2, target, B, B, loss_kind, lr, beta1, beta2, eps, t);
+    return launch_step<false>(c, a, loss_out, (hipStream_t)stream);
 }
 
 extern "C" int otto_mf_dp_local(otto_mf_ctx* c, float* E1, float* m1, float* v1, const float* E2, const int64_t* i1,
@@ -1075,27 +1024,12 @@ extern "C" int otto_mf_dp_local(otto_mf_ctx* c, float* E1, float* m1, float* v1,
         OTTO_HIP(hipMemsetAsync(loss_out, 0, 4, s));
         return 0;
     }
-    const int grid = mf_grid(B_local, c->G);
-    DpArgs p;
-    memset(&p, 0, sizeof p);
-    StepArgs& a = p.a;
-    a.E1 = E1; a.m1 = m1; a.v1 = v1; a.E2 = const_cast<float*>(E2);
-    a.i1 = i1; a.i2 = i2; a.target = target; a.B = B_local; a.n1 = c->n1; a.n2 = c->n2; a.d = c->d; a.G = c->G;
-    a.loss_kind = loss_kind;
-    a.partial = c->partial.as<float>(); a.coef = c->coef.as<float>();
-    a.cnt1 = c->cnt1.as<uint32_t>(); a.cnt2 = c->shared ? a.cnt1 : c->cnt2.as<uint32_t>();
-    a.slot1 = c->slot1.as<int32_t>(); a.slot2 = c->shared ? a.slot1 : c->slot2.as<int32_t>();
-    a.role = c->role.as<uint8_t>(); a.grad = c->grad.as<float>(); a.err = c->err.as<uint32_t>();
-    adam_params(&a, lr, beta1, beta2, eps, t);
-    p.priv = !c->shared; p.lo = priv_lo; p.hi = priv_hi;
-    p.ids = d_ids; p.rows = d_rows; p.count = reinterpret_cast<unsigned long long*>(d_count);
-    p.inv_bg = 1.0f / (float)B_global;
-    k_dp_fwd<<<grid, 256, 0, s>>>(p);
-    k_loss_final<<<1, 256, 0, s>>>(c->partial.as<float>(), grid, p.inv_bg, loss_out, nullptr, 0, MF_GRID_MAX, 0.0);
-    k_dp_acc<<<grid, 256, 0, s>>>(p);
-    k_dp_fin<<<mf_grid(2 * B_local, c->G), 256, 0, s>>>(p);
-    OTTO_HIP(hipGetLastError());
-    return 0;
+    // the exported table's moments are never touched here (otto_mf_dp_apply updates it)
+    StepArgs a = step_args(c, E1, m1, v1, const_cast<float*>(E2), nullptr, nullptr, i1, i2, target, B_local, B_global,
+                           loss_kind, lr, beta1, beta2, eps, t);
+    a.lo = priv_lo; a.hi = priv_hi;
+    a.ids = d_ids; a.rows = d_rows; a.count = reinterpret_cast<unsigned long long*>(d_count);
+    return launch_step<true>(c, a, loss_out, s);
 }
 
 extern "C" int otto_mf_dp_apply(otto_mf_ctx* c, float* E2, float* m2, float* v2, const int32_t* d_ids, float* d_rows,

@@ -12,24 +12,19 @@ import numpy as np
 import torch
 
 
-class DeviceBatchLoader:
+class _BatchLoader:
+    """``(dict_of_int64_device_tensors, None)`` batches of ``self.columns``: the row ranges ``_batch_bounds()`` gives, of a
+    fresh random permutation every epoch when ``shuffle`` is on."""
 
-    def __init__(self, columns, batch_size, shuffle=True, drop_last=False, device='cuda:0', seed=None):
+    def __init__(self, columns, shuffle, device, seed):
         self.device = torch.device(device)
         self.columns = {k: (v if torch.is_tensor(v) else torch.from_numpy(np.array(v, dtype=np.int64))).to(
             device=self.device, dtype=torch.int64).contiguous() for k, v in columns.items()}
         self.n = next(iter(self.columns.values())).numel()
-        self.batch_size, self.shuffle, self.drop_last = int(batch_size), shuffle, drop_last
+        self.shuffle = shuffle
         self.gen = torch.Generator(device=self.device)
         if seed is not None:
             self.gen.manual_seed(seed)
-
-    @classmethod
-    def from_parquet(cls, path, batch_size, shuffle=True, drop_last=False, device='cuda:0', seed=None):
-        import pyarrow.parquet as pq
-        table = pq.read_table(str(path))
-        return cls({name: table.column(name).to_numpy() for name in table.column_names if not name.startswith('__')},
-                   batch_size, shuffle, drop_last, device, seed)
 
     def check_ranges(self, limits):
         """``limits``: column -> table size. Raises ValueError when a column holds an id outside [0, size): the YAML's
@@ -43,18 +38,34 @@ class DeviceBatchLoader:
             if lo < 0 or hi >= int(size):
                 raise ValueError(f"column '{name}' holds ids in [{lo}, {hi}] but its embedding table has {int(size)} rows")
 
-    def __len__(self):
-        return self.n // self.batch_size if self.drop_last else (self.n + self.batch_size - 1) // self.batch_size
-
     def __iter__(self):
         perm = torch.randperm(self.n, device=self.device, generator=self.gen) if self.shuffle else None
-        for b in range(len(self)):
-            lo, hi = b * self.batch_size, min(self.n, (b + 1) * self.batch_size)
+        for lo, hi in self._batch_bounds():
             if perm is None:
                 yield {k: v[lo:hi] for k, v in self.columns.items()}, None
             else:
                 idx = perm[lo:hi]
                 yield {k: v[idx] for k, v in self.columns.items()}, None
+
+
+class DeviceBatchLoader(_BatchLoader):
+
+    def __init__(self, columns, batch_size, shuffle=True, drop_last=False, device='cuda:0', seed=None):
+        super().__init__(columns, shuffle, device, seed)
+        self.batch_size, self.drop_last = int(batch_size), drop_last
+
+    @classmethod
+    def from_parquet(cls, path, batch_size, shuffle=True, drop_last=False, device='cuda:0', seed=None):
+        import pyarrow.parquet as pq
+        table = pq.read_table(str(path))
+        return cls({name: table.column(name).to_numpy() for name in table.column_names if not name.startswith('__')},
+                   batch_size, shuffle, drop_last, device, seed)
+
+    def __len__(self):
+        return self.n // self.batch_size if self.drop_last else (self.n + self.batch_size - 1) // self.batch_size
+
+    def _batch_bounds(self):
+        return ((b * self.batch_size, min(self.n, (b + 1) * self.batch_size)) for b in range(len(self)))
 
 
 def _ts_seconds(ts):

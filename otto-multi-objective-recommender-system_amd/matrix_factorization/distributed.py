@@ -21,6 +21,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .data import _BatchLoader
 from .torch_optim import SparseAdam, loss_kind
 
 
@@ -120,7 +121,7 @@ def global_batch_sizes(sizes, steps):
     return sum(np.diff((k * int(n)) // steps) for n in sizes) if steps else np.zeros(0, np.int64)
 
 
-class ShardedBatchLoader:
+class ShardedBatchLoader(_BatchLoader):
     """Rank ``rank``'s part of the data-parallel epoch: same ``(dict_of_int64_device_tensors, None)`` batches as
     :class:`~.data.DeviceBatchLoader`, ``len()`` = ``n_steps`` on every rank.
 
@@ -132,31 +133,28 @@ class ShardedBatchLoader:
 
     def __init__(self, columns, batch_size, shard_key='session', n_keys=None, shuffle=True, device='cuda:0', seed=None,
                  rank=None, world=None, group=None, stage_device=None):
-        self.device = torch.device(device)
         g_rank, g_world = _world(group)
         self.rank = g_rank if rank is None else int(rank)
         self.world = g_world if world is None else int(world)
         if not 0 <= self.rank < self.world:
             raise ValueError(f'rank {self.rank} outside world {self.world}')
         self.group, self.stage = group, _stage(group, stage_device)
-        cols = {k: (v if torch.is_tensor(v) else torch.from_numpy(np.array(v, dtype=np.int64))).to(
-            device=self.device, dtype=torch.int64).contiguous() for k, v in columns.items()}
-        self.n_total = next(iter(cols.values())).numel()
-        self.batch_size, self.shuffle, self.shard_key = int(batch_size), shuffle, shard_key
+        super().__init__(columns, shuffle, device, None if seed is None else int(seed) * 1000003 + self.rank)
+        self.n_total = self.n
+        self.batch_size, self.shard_key = int(batch_size), shard_key
         if shard_key is None:
             self.cuts = row_cuts(self.n_total, self.world)
             self.sizes = [self.cuts[r + 1] - self.cuts[r] for r in range(self.world)]
             lo, hi = self.cuts[self.rank], self.cuts[self.rank + 1]
-            self.columns = {k: v[lo:hi].contiguous() for k, v in cols.items()}
+            self.columns = {k: v[lo:hi].contiguous() for k, v in self.columns.items()}
             self.private_rows = None
         else:
-            self.cuts, self.sizes = session_cuts(cols[shard_key], self.world, n_keys)
+            self.cuts, self.sizes = session_cuts(self.columns[shard_key], self.world, n_keys)
             lo, hi = self.cuts[self.rank], self.cuts[self.rank + 1]
-            key = cols[shard_key]
+            key = self.columns[shard_key]
             keep = torch.nonzero((key >= lo) & (key < hi)).reshape(-1)
-            self.columns = {k: v[keep].contiguous() for k, v in cols.items()}
+            self.columns = {k: v[keep].contiguous() for k, v in self.columns.items()}
             self.private_rows = (lo, hi)
-        del cols
         self.n = next(iter(self.columns.values())).numel()
         assert self.n == self.sizes[self.rank]
         if rank is None and world is None and self.world > 1:
@@ -168,19 +166,6 @@ class ShardedBatchLoader:
         self.n_steps = n_steps(self.n_total, self.batch_size)
         self.global_sizes = global_batch_sizes(self.sizes, self.n_steps)
         self.max_local_batch = max(((n + self.n_steps - 1) // self.n_steps if self.n_steps else 0) for n in self.sizes)
-        self.gen = torch.Generator(device=self.device)
-        if seed is not None:
-            self.gen.manual_seed(int(seed) * 1000003 + self.rank)
-
-    def check_ranges(self, limits):
-        """As :meth:`~.data.DeviceBatchLoader.check_ranges`, over this rank's rows."""
-        for name, size in limits.items():
-            col = self.columns.get(name)
-            if col is None or col.numel() == 0:
-                continue
-            lo, hi = int(col.min()), int(col.max())
-            if lo < 0 or hi >= int(size):
-                raise ValueError(f"column '{name}' holds ids in [{lo}, {hi}] but its embedding table has {int(size)} rows")
 
     def batch_global(self, k):
         return int(self.global_sizes[k])
@@ -188,15 +173,8 @@ class ShardedBatchLoader:
     def __len__(self):
         return self.n_steps
 
-    def __iter__(self):
-        perm = torch.randperm(self.n, device=self.device, generator=self.gen) if self.shuffle else None
-        for k in range(self.n_steps):
-            lo, hi = local_batch_bounds(k, self.n, self.n_steps)
-            if perm is None:
-                yield {name: v[lo:hi] for name, v in self.columns.items()}, None
-            else:
-                idx = perm[lo:hi]
-                yield {name: v[idx] for name, v in self.columns.items()}, None
+    def _batch_bounds(self):
+        return (local_batch_bounds(k, self.n, self.n_steps) for k in range(self.n_steps))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -254,13 +232,7 @@ class DataParallelSparseAdam(SparseAdam):
         (``train()`` passes them); without them they are agreed by an all-reduce in this step. ``private_rows`` =
         the session rows ``[lo, hi)`` this rank owns (default: the whole table; ignored for a shared table)."""
         group = self.param_groups[0]
-        self._opt_called = True
-        E1, E2, shared = model._tables()
-        s1 = self._state(E1)
-        s2 = s1 if shared else self._state(E2)
-        s1['step'] += 1
-        if not shared:
-            s2['step'] += 1
+        E1, E2, shared, s1, s2 = self._begin_step(model)
         B = i1.numel()
         if batch_global is None:
             batch_global = self._agree(B, dist.ReduceOp.SUM) if self.world > 1 else B

@@ -40,12 +40,8 @@ class SparseAdam(torch.optim.Optimizer):
             st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
         return st
 
-    def step(self, closure=None):
-        raise RuntimeError('SparseAdam here is fused with forward/backward: call fused_step (torch_trainer.train does)')
-
-    def fused_step(self, model, i1, i2, targets, criterion, loss_out):
-        """One training batch; the mean pre-update loss lands in ``loss_out`` (1-element device tensor)."""
-        group = self.param_groups[0]
+    def _begin_step(self, model):
+        """The step's bookkeeping: ``model``'s tables, their state (``s2 is s1`` for a shared table), step counts + 1."""
         self._opt_called = True     # torch's LR schedulers only check that an optimizer step preceded scheduler.step()
         E1, E2, shared = model._tables()
         s1 = self._state(E1)
@@ -53,6 +49,15 @@ class SparseAdam(torch.optim.Optimizer):
         s1['step'] += 1
         if not shared:
             s2['step'] += 1
+        return E1, E2, shared, s1, s2
+
+    def step(self, closure=None):
+        raise RuntimeError('SparseAdam here is fused with forward/backward: call fused_step (torch_trainer.train does)')
+
+    def fused_step(self, model, i1, i2, targets, criterion, loss_out):
+        """One training batch; the mean pre-update loss lands in ``loss_out`` (1-element device tensor)."""
+        group = self.param_groups[0]
+        E1, E2, shared, s1, s2 = self._begin_step(model)
         model.engine(i1.numel()).step_sparse_adam(
             E1.data, s1['exp_avg'], s1['exp_avg_sq'], E2.data, s2['exp_avg'], s2['exp_avg_sq'],
             i1, i2, targets, loss_kind(criterion), group['lr'], group['betas'], group['eps'], s1['step'], loss_out)

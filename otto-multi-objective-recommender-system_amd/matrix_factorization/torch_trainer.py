@@ -29,6 +29,7 @@ if __package__ in (None, ''):   # run as a script from its own directory, like t
 from .. import settings
 from . import torch_modules, torch_utils, torch_optim, metrics, visualization
 from .data import DeviceBatchLoader, build_aid_pairs_device, build_sessions_aids  # noqa: F401
+from . import distributed as dd
 from .distributed import DataParallelSparseAdam, ShardedBatchLoader, full_state_dict
 from .torch_optim import loss_kind
 
@@ -78,19 +79,18 @@ def train(train_loader, model, criterion, optimizer, device, scheduler=None):
     log = _LossLog(torch.device(device))
     for k, (inputs, _) in enumerate(train_loader):
         i1, i2, targets = _unpack(model, inputs, device)
-        if dp:
-            optimizer.fused_step(model, i1, i2, targets, criterion, log.slot(), batch_global=train_loader.batch_global(k),
-                                 private_rows=train_loader.private_rows, max_local_batch=train_loader.max_local_batch)
-        else:
-            optimizer.fused_step(model, i1, i2, targets, criterion, log.slot())
+        step = dict(batch_global=train_loader.batch_global(k), private_rows=train_loader.private_rows,
+                    max_local_batch=train_loader.max_local_batch) if dp else {}
+        optimizer.fused_step(model, i1, i2, targets, criterion, log.slot(), **step)
         if scheduler is not None:
             scheduler.step()
     if log.n:
         model.engine(1).check()          # out-of-range row ids were skipped in the kernels: raise here, once per epoch
-    if dp:
-        # each step's value is this rank's loss sum / B_global: the ranks' sums add up to the step's mean loss
-        return float(optimizer.all_reduce_sum([log.values().sum()])[0] / max(log.n, 1)) if log.n else float('nan')
-    return float(np.mean(log.values()))
+    # data parallel: each step's value is this rank's loss sum / B_global, so the ranks' sums add up to the step's mean loss
+    total = log.values().sum()
+    if dp and log.n:
+        total = optimizer.all_reduce_sum([total])[0]
+    return float(total / log.n) if log.n else float('nan')
 
 
 def validate(val_loader, model, criterion, device, scores=False):
@@ -104,8 +104,7 @@ def validate(val_loader, model, criterion, device, scores=False):
     With a :class:`~.distributed.ShardedBatchLoader` each rank evaluates its shard: batch losses are weighted by
     ``B_local / B_global`` and summed over ranks, the running sums are all-reduced, and ROC-AUC is computed from the
     all-gathered predictions; every rank returns the same values."""
-    if isinstance(val_loader, ShardedBatchLoader):
-        return _validate_sharded(val_loader, model, criterion, device, scores)
+    sharded = isinstance(val_loader, ShardedBatchLoader)
     model.eval()
     dev = torch.device(device)
     log = _LossLog(dev)
@@ -113,87 +112,63 @@ def validate(val_loader, model, criterion, device, scores=False):
     E1, E2, _ = model._tables()
     classification = isinstance(model, torch_modules.CollaborativeFiltering)
     truth, predictions, eng = [], [], None
+    if sharded:         # every rank takes part in the collectives below, with or without rows of its own
+        eng = model.engine(max(val_loader.max_local_batch, 1))
+        if scores:
+            eng.read_sums(reset=True)
     with torch.no_grad():
-        for inputs, _ in val_loader:
+        for k, (inputs, _) in enumerate(val_loader):
             i1, i2, targets = _unpack(model, inputs, device)
-            if eng is None and scores:
-                model.engine(i1.numel()).read_sums(reset=True)       # start the epoch's running sums from zero
-            eng = model.engine(i1.numel())
-            if not scores:
-                eng.eval(E1.data, E2.data, i1, i2, targets, kind, log.slot(), None)
-                continue
-            pred = torch.empty(i1.numel(), dtype=torch.float32, device=dev) if classification else None
-            eng.eval_sums(E1.data, E2.data, i1, i2, targets, kind, log.slot(), pred)
-            if classification:
-                truth.append(targets)
-                predictions.append(pred)
-    val_loss = float(np.mean(log.values()))
-    val_scores = None
-    if eng is not None:
-        eng.check()
-    if scores and eng is not None:
-        auc = metrics.roc_auc(torch.cat(truth), torch.sigmoid(torch.cat(predictions))) if classification else None
-        val_scores = metrics.scores_from_sums(eng.read_sums(reset=True), classification, auc)
-    return val_loss, val_scores
-
-
-def _validate_sharded(loader, model, criterion, device, scores):
-    from . import distributed as dd
-    model.eval()
-    dev = torch.device(device)
-    log = _LossLog(dev)
-    kind = loss_kind(criterion)
-    E1, E2, _ = model._tables()
-    classification = isinstance(model, torch_modules.CollaborativeFiltering)
-    group, stage = loader.group, loader.stage
-    eng = model.engine(max(loader.max_local_batch, 1))
-    if scores:
-        eng.read_sums(reset=True)
-    truth, predictions = [], []
-    with torch.no_grad():
-        for k, (inputs, _) in enumerate(loader):
-            i1, i2, targets = _unpack(model, inputs, device)
-            slot = log.slot()
-            B = i1.numel()
-            if B == 0:
+            slot, B = log.slot(), i1.numel()
+            if B == 0:      # a rank's share of a step may be empty
                 slot.zero_()
                 continue
+            if eng is None and scores:
+                model.engine(B).read_sums(reset=True)       # start the epoch's running sums from zero
+            eng = model.engine(B)
             pred = torch.empty(B, dtype=torch.float32, device=dev) if scores and classification else None
             (eng.eval_sums if scores else eng.eval)(E1.data, E2.data, i1, i2, targets, kind, slot, pred)
-            slot.mul_(B / loader.batch_global(k))
+            if sharded:
+                slot.mul_(B / val_loader.batch_global(k))
             if pred is not None:
                 truth.append(targets)
                 predictions.append(pred)
-    eng.check()
-    world = loader.world
-    red = torch.tensor([log.values().sum()] + (list(eng.read_sums(reset=True)) if scores else []), dtype=torch.float64)
-    if world > 1:
-        dd._all_reduce(red, dd.dist.ReduceOp.SUM, group, stage)
-    red = red.tolist()
-    val_loss = red[0] / max(log.n, 1) if log.n else float('nan')
+    if eng is not None:
+        eng.check()
+    red = [log.values().sum()] + (list(eng.read_sums(reset=True)) if scores and eng is not None else [])
+    if sharded and val_loader.world > 1:
+        red = dd._all_reduce(torch.tensor(red, dtype=torch.float64), dd.dist.ReduceOp.SUM, val_loader.group,
+                             val_loader.stage).tolist()
+    val_loss = float(red[0] / log.n) if log.n else float('nan')
     val_scores = None
-    if scores:
+    if scores and eng is not None:
         auc = None
         if classification:
-            n_max = max(loader.sizes)
-            t_loc = torch.zeros(n_max, dtype=torch.float32, device=dev)
-            p_loc = torch.zeros(n_max, dtype=torch.float32, device=dev)
-            if truth:
-                t_cat, p_cat = torch.cat(truth), torch.cat(predictions)
-                t_loc[:t_cat.numel()] = t_cat.to(torch.float32)
-                p_loc[:p_cat.numel()] = p_cat
-            t_all = torch.empty((world, n_max), dtype=torch.float32, device=dev)
-            p_all = torch.empty((world, n_max), dtype=torch.float32, device=dev)
-            if world > 1:
-                dd._all_gather(t_all, t_loc, group, stage)
-                dd._all_gather(p_all, p_loc, group, stage)
-            else:
-                t_all[0], p_all[0] = t_loc, p_loc
-            t_g = torch.cat([t_all[r, :n] for r, n in enumerate(loader.sizes)])
-            p_g = torch.cat([p_all[r, :n] for r, n in enumerate(loader.sizes)])
-            auc = metrics.roc_auc(t_g, torch.sigmoid(p_g))
+            t_all, p_all = _gather_sharded(val_loader, truth, predictions, dev) if sharded else \
+                (torch.cat(truth), torch.cat(predictions))
+            auc = metrics.roc_auc(t_all, torch.sigmoid(p_all))
         val_scores = metrics.scores_from_sums(tuple(red[1:5]), classification, auc)
     return val_loss, val_scores
+
+
+def _gather_sharded(loader, truth, predictions, dev):
+    """Every rank's targets (as float32) and predictions, in rank order."""
+    world, n_max = loader.world, max(loader.sizes)
+    t_loc = torch.zeros(n_max, dtype=torch.float32, device=dev)
+    p_loc = torch.zeros(n_max, dtype=torch.float32, device=dev)
+    if truth:
+        t_cat, p_cat = torch.cat(truth), torch.cat(predictions)
+        t_loc[:t_cat.numel()] = t_cat.to(torch.float32)
+        p_loc[:p_cat.numel()] = p_cat
+    t_all = torch.empty((world, n_max), dtype=torch.float32, device=dev)
+    p_all = torch.empty((world, n_max), dtype=torch.float32, device=dev)
+    if world > 1:
+        dd._all_gather(t_all, t_loc, loader.group, loader.stage)
+        dd._all_gather(p_all, p_loc, loader.group, loader.stage)
+    else:
+        t_all[0], p_all[0] = t_loc, p_loc
+    return (torch.cat([t_all[r, :n] for r, n in enumerate(loader.sizes)]),
+            torch.cat([p_all[r, :n] for r, n in enumerate(loader.sizes)]))
 
 
 def build_optimizer(name, params, args):
