@@ -150,6 +150,9 @@ SIGNATURES = {
     'otto_mf_score_topk': (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp]),
     'otto_mf_score_workspace': (_i64, [_i64, _i64, _i32]),
     'otto_mf_topk_merge': (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
+    # include/otto_knn.h
+    'otto_knn_workspace': (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    'otto_knn_table': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -14,6 +14,7 @@
 //                            per-row top-k; the B x N score matrix is never materialised
 //                            (recbole/inference.py:76-80 materialises and copies it to the host)
 #include "common.h"
+#include "sclist.h"
 #include "../../include/otto_mf.h"
 
 #include <math.h>
@@ -642,23 +643,6 @@ struct ScoreArgs {
     int32_t* part_i;
 };
 
-// insert (score, id) into the sorted (desc) k-list of one row in LDS; the whole wave cooperates.
-// Returns the new k-th score (threshold).
-__device__ __forceinline__ float list_insert(volatile float* ls, volatile int32_t* li, int k, float sc, int32_t id) {
-    const unsigned l = lane_id();
-    const float cur = l < (unsigned)k ? ls[l] : -INFINITY;
-    // entries that stay ahead of the newcomer: higher score (ids arrive in ascending order, so on a
-    // tie the resident entry has the smaller id and stays ahead)
-    const bool ahead = l < (unsigned)k && cur >= sc;
-    const int pos = __popcll(__ballot(ahead));
-    const int32_t curi = l < (unsigned)k ? li[l] : 0;
-    __builtin_amdgcn_wave_barrier();
-    if ((int)l >= pos && (int)l + 1 < k) { ls[l + 1] = cur; li[l + 1] = curi; }
-    if ((int)l == pos && pos < k) { ls[l] = sc; li[l] = id; }
-    __builtin_amdgcn_wave_barrier();
-    return ls[k - 1];
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void k_score(ScoreArgs a) {
     constexpr int HD = D / 2;               // k range of one lane half
@@ -768,39 +752,9 @@ __global__ __launch_bounds__(64) void k_score_merge(const float* part_s, const i
     const int64_t row = blockIdx.x;
     if (row >= B) return;
     const unsigned l = lane_id();
-    float bs = -INFINITY;
-    int32_t bi = 0x7FFFFFFF;
-    const int total = nsplit * k;
-    for (int c0 = 0; c0 < total; c0 += 64) {
-        const int c = c0 + (int)l;
-        float cs = -INFINITY;
-        int32_t ci = 0x7FFFFFFF;
-        if (c < total) {
-            const int64_t o = ((int64_t)(c / k) * Bpad + row) * k + (c % k);
-            cs = part_s[o];
-            ci = part_i[o];
-            if (ci < 0) ci = 0x7FFFFFFF;          // -1: an empty slot of a gathered partial list
-        }
-        auto better = [](float s1, int32_t i1, float s2, int32_t i2) { return s1 > s2 || (s1 == s2 && i1 < i2); };
-        float ts = __shfl(bs, k - 1, 64);
-        int32_t ti = __shfl(bi, k - 1, 64);
-        uint64_t m = __ballot(ci != 0x7FFFFFFF && better(cs, ci, ts, ti));
-        while (m) {
-            const int src = __ffsll((unsigned long long)m) - 1;
-            const float s = __shfl(cs, src, 64);
-            const int32_t id = __shfl(ci, src, 64);
-            const float us = __shfl_up(bs, 1, 64);
-            const int32_t ui = __shfl_up(bi, 1, 64);
-            if (better(s, id, bs, bi)) {
-                if (l > 0 && better(s, id, us, ui)) { bs = us; bi = ui; }
-                else { bs = s; bi = id; }
-            }
-            ts = __shfl(bs, k - 1, 64);
-            ti = __shfl(bi, k - 1, 64);
-            m &= m - 1;
-            m &= __ballot(ci != 0x7FFFFFFF && better(cs, ci, ts, ti));
-        }
-    }
+    float bs;
+    int32_t bi;
+    merge_row_lists(part_s, part_i, nsplit, Bpad, row, k, bs, bi);
     if ((int)l < k) {
         ids[row * k + l] = bi == 0x7FFFFFFF ? -1 : bi;
         scores[row * k + l] = bs;
