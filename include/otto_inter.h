@@ -11,7 +11,9 @@
  *                              max, last position mean / sum / max.
  * Candidates come as the dense [n_sess][C] arrays otto_cand_lookup writes (-1 padded, one row per session, candidates
  * unique inside a row: the reference de-duplicates its rows at :33), events as the sorted SoA + CSR of the same sessions.
- * std is the sample standard deviation (ddof 1; NaN for a single row); NaN stands for polars' null.
+ * std is the sample standard deviation (ddof 1; NaN for a single row); NaN stands for polars' null. Sums run in float64 over
+ * scores shifted by the first score of the group, so std holds to float32 rounding over the generators' whole range (integer
+ * counts up to 65,535, recency weights in (0, 4]) however small the spread is against the mean.
  *
  * Conventions as in otto_covis.h.
  */

@@ -103,7 +103,8 @@ int otto_mf_bpr_step(otto_mf_ctx* ctx, float* d_U, float* d_V, const int64_t* d_
 
 /* scores[b, n] = <U[b], V[n]> over all N items, column `pad_col` (if >= 0) forced to -inf, per row the
  * k best (score desc, id asc): d_ids [B, k] int32, d_scores [B, k] float32.  Exact f32 MFMA, the B x N
- * matrix is never written.  k <= 32. */
+ * matrix is never written.  k <= 32.  A row with fewer than k valid items (N < k, or N = k with pad_col set) holds them
+ * first; the tail holds id -1 and score -inf. */
 int otto_mf_score_topk(const float* d_U, const float* d_V, int64_t B, int64_t N, int32_t d, int32_t k,
                        int64_t pad_col, int32_t* d_ids, float* d_scores, void* d_workspace, int64_t workspace_bytes,
                        void* stream);

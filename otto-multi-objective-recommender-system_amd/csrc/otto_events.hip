@@ -57,8 +57,9 @@ __global__ __launch_bounds__(256) void k_make_keys(const uint32_t* session, cons
     __shared__ unsigned long long s_or[4], s_and[4];
     unsigned long long vo = 0, va = ~0ull;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int64_t sec = ts[i] / ts_div;
-        if (sec < 0 || sec > 0x7FFFFFFFll) atomicAdd(bad, 1ull);
+        const int64_t t = ts[i];
+        const int64_t sec = t / ts_div;              // truncates: a stamp in (-ts_div, 0) would pass as second 0
+        if (t < 0 || sec > 0x7FFFFFFFll) atomicAdd(bad, 1ull);
         const uint64_t k = ((uint64_t)session[i] << 32) | (uint64_t)(uint32_t)sec;
         key[i] = k;
         idx[i] = (uint32_t)i;

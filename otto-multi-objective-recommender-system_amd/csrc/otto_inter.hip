@@ -14,7 +14,7 @@ struct AidAcc {              // per candidate aid, over all sessions
     double score_sum, score_sq;
     uint32_t rows, last_rows, occ_max, last_max;
     uint32_t score_max_bits;  // order-preserving image of the float
-    uint32_t pad;
+    uint32_t shift_bits;      // order-preserving image of the aid's shift K (0 = not chosen yet): score_sum / score_sq are over f - K
 };
 
 __device__ __forceinline__ uint32_t float_order(float f) {       // monotone float -> uint32
@@ -63,9 +63,21 @@ __global__ __launch_bounds__(256) void k_inter_rows(const uint32_t* aid, const u
         uint32_t rows = 0, last_rows = 0, occ_max = 0, last_max = 0, sc_max = 0, sc_min = 0xFFFFFFFFu;
         const int64_t cb = cand_off ? cand_off[s] : s * (int64_t)C;
         const int Cs = cand_off ? (int)(cand_off[s + 1] - cb) : C;
+        // Shifted sums: sum (f - K) and sum (f - K)^2 with K = the first score met (of the session here, of the aid below).
+        // sum f^2 - n mean^2 loses every digit when the mean is large against the spread (counts near 65,535 that differ
+        // by one); with K inside the data the two terms are of the size of the spread squared.
+        float K = 0.f;
+        bool have_k = false;
         for (int c0 = 0; c0 < Cs; c0 += 64) {
             const int c = c0 + (int)lane;
             const int32_t y = c < Cs ? cand[cb + c] : -1;
+            if (!have_k) {
+                const uint64_t mv = __ballot(y >= 0);
+                if (mv) {
+                    K = __shfl(y >= 0 ? score[cb + c] : 0.f, __ffsll((unsigned long long)mv) - 1, 64);
+                    have_k = true;
+                }
+            }
             uint32_t cnt[3] = {0, 0, 0}, last = 0;
             if (y >= 0) {
                 // four events per LDS read, no branch: a loop of one dependent LDS read + branch per event runs at one LDS
@@ -88,7 +100,8 @@ __global__ __launch_bounds__(256) void k_inter_rows(const uint32_t* aid, const u
                 r[0] = (uint16_t)occ; r[1] = (uint16_t)last; r[2] = (uint16_t)cnt[0]; r[3] = (uint16_t)cnt[1]; r[4] = (uint16_t)cnt[2];
                 const float f = score[cb + c];
                 const uint32_t fo = float_order(f);
-                sc_sum += (double)f; sc_sq += (double)f * (double)f;
+                const double fk = (double)f - (double)K;
+                sc_sum += fk; sc_sq += fk * fk;
                 sc_max = fo > sc_max ? fo : sc_max; sc_min = fo < sc_min ? fo : sc_min;
                 occ_sum += occ; occ_max = occ > occ_max ? occ : occ_max;
                 ++rows;
@@ -96,8 +109,10 @@ __global__ __launch_bounds__(256) void k_inter_rows(const uint32_t* aid, const u
                 if ((uint32_t)y < n_aids) {
                     AidAcc* a = acc + y;
                     atomicAdd(&a->rows, 1u);
-                    atomicAdd(&a->score_sum, (double)f);
-                    atomicAdd(&a->score_sq, (double)f * (double)f);
+                    const uint32_t k0 = atomicCAS(&a->shift_bits, 0u, fo);       // the first row of the aid sets its shift
+                    const double fa = (double)f - (double)float_unorder(k0 ? k0 : fo);
+                    atomicAdd(&a->score_sum, fa);
+                    atomicAdd(&a->score_sq, fa * fa);
                     atomicMax(&a->score_max_bits, fo);
                     if (occ) { atomicAdd(&a->occ_sum, (unsigned long long)occ); atomicMax(&a->occ_max, occ); }
                     if (last) { atomicAdd(&a->last_rows, 1u); atomicAdd(&a->last_sum, (unsigned long long)last); atomicMax(&a->last_max, last); }
@@ -116,8 +131,8 @@ __global__ __launch_bounds__(256) void k_inter_rows(const uint32_t* aid, const u
         if (lane == 0) {
             float* o = sess_feat + (size_t)s * OTTO_INTER_SESSION_FEATURES;
             if (nr > 0) {
-                const double mean = t_sc / nr;
-                o[0] = (float)mean;
+                const double mean = t_sc / nr;                // of f - K
+                o[0] = (float)((double)K + mean);
                 o[1] = nr > 1 ? (float)sqrt(fmax((t_sq - nr * mean * mean) / (nr - 1), 0.0)) : nanf_;
                 o[2] = float_unorder(n_sc);
                 o[3] = float_unorder(m_sc);
@@ -145,8 +160,8 @@ __global__ void k_inter_aids(const AidAcc* acc, uint32_t n_aids, float* out) {
         for (int q = 0; q < OTTO_INTER_AID_FEATURES; ++q) o[q] = nanf_;
         return;
     }
-    const double nr = (double)a.rows, mean = a.score_sum / nr;
-    o[0] = (float)mean;
+    const double nr = (double)a.rows, mean = a.score_sum / nr;       // of f - K
+    o[0] = (float)((double)float_unorder(a.shift_bits) + mean);
     o[1] = a.rows > 1 ? (float)sqrt(fmax((a.score_sq - nr * mean * mean) / (nr - 1), 0.0)) : nanf_;
     o[2] = float_unorder(a.score_max_bits);
     o[3] = (float)((double)a.occ_sum / nr);
