@@ -32,7 +32,7 @@ void set_error(const char* fmt, ...);
         }                                \
     } while (0)
 
-// Growable device buffer owned by a context.
+// Growable device buffer. Plain data: whoever holds one releases it (contexts hold OwnedBuf, below).
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
@@ -68,6 +68,15 @@ struct DevBuf {
     }
     template <typename T>
     T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// A DevBuf member of a context: freed when the context is deleted. DevBuf itself has no destructor because device_scratch
+// (below) keeps static DevBufs until the process exits, where a hipFree would call into a HIP runtime that may be gone.
+struct OwnedBuf : DevBuf {
+    OwnedBuf() = default;
+    OwnedBuf(const OwnedBuf&) = delete;
+    OwnedBuf& operator=(const OwnedBuf&) = delete;
+    ~OwnedBuf() { release(); }
 };
 
 // ---------------------------------------------------------------------------

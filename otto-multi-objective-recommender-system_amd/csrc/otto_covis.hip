@@ -3421,60 +3421,51 @@ using namespace otto;
 struct otto_covis_ctx {
     otto_covis_params p;
     // K1 products
-    DevBuf rec, tw, run_x, run_desc;
+    OwnedBuf rec, tw, run_x, run_desc;
     uint64_t rec_used = 0;    // record slots
     unsigned long long desc_totals[2] = {0, 0};   // statistics: shared-list runs, private-row records (otto_covis_stats)
     bool desc_totals_valid = false;
     uint64_t run_used = 0;    // run slots
     int64_t sessions = 0;
     // chunk scratch
-    DevBuf pair_base, ev_base, partial, cls_pos[N_WIN_CLASSES], sess_list, cls_byte;
+    OwnedBuf pair_base, ev_base, partial, cls_pos[N_WIN_CLASSES], sess_list, cls_byte;
     int fast_path = 1;
     int fused = 2;                 // no filter kind configured: 2 = k_expand_lists (component lists), 1 = k_expand_fused, 0 = class-sorted kernels
     // index
     bool index_valid = false;
-    DevBuf cnt64, run_start, run_rank, sorted_desc, item_start, boost, flag, counters;
-    DevBuf items[3];
+    OwnedBuf cnt64, run_start, run_rank, sorted_desc, item_start, boost, flag, counters;
+    OwnedBuf items[3];
     uint64_t n_items[3] = {0, 0, 0};
     uint64_t bin_pairs[3] = {0, 0, 0};
     uint64_t bin_runs[3] = {0, 0, 0};
     uint64_t n_pairs = 0, n_runs = 0;
     // partition pass of heavy aids
-    DevBuf litem_start, chunks, pcount, pcursor, pstart, prec, ptw, item_part;
+    OwnedBuf litem_start, chunks, pcount, pcursor, pstart, prec, ptw, item_part;
     uint64_t n_chunks = 0;
     int partition = 1;
     bool exact_round = false;      // set by finalize for the rounds that redo flagged aids
     int part_sized = 1;            // option "part_sized": capacity-sized buckets on the first attempt (no count pass); 0 = always counted
     int debug_skip = 0;
     // reduce scratch
-    DevBuf part_y, part_w;
-    DevBuf bcount, bstart, tmp_runs;          // bucketed index
+    OwnedBuf part_y, part_w;
+    OwnedBuf bcount, bstart, tmp_runs;        // bucketed index
     int bucket_index = 1;          // option "bucket_index": LDS-atomic index build (0 = global-atomic histogram)
     int s_wgs = 20;                // option "s_wgs": one-wave workgroups of the S bin per CU (A/B)
-    int p_wgs = 4;                 // option "p_wgs": workgroups of the partition scatter per CU (4 are resident: 38 KB of LDS each; chunks are dequeued
-                                   // dynamically, so the count no longer matters: 4 / 8 / 12 measure 2.92 ms; the static deal needed 12 for 2.99)
     int bkt_sh = 0;                // option "bkt_sh": log2 aids per index bucket (0 = from the aid space)
-    DevBuf lorder[3][3], lrank, lmode_start;   // [bin][mode] processing order of the tiers / layouts (heavy: pilots first)
-    uint64_t n_order[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    OwnedBuf lorder[3], lrank, lmode_start;    // [mode] processing order of the heavy bin's table layouts (pilots first)
+    uint64_t n_order[3] = {0, 0, 0};
     int packed_heavy = 2;          // option "packed_heavy": packed layout for heavy aids with < 4096 runs (1: 2^14 tables for every aid
                                    // above l_cap records, 2: 2^14 only for the aids that fit one table, 2^13 partitions of l_cap beyond)
     int items_allow_packed = -1;   // layout rule the L item list was built with (-1: not built)
-    DevBuf tau_w, tau_y;           // threshold guesses of partitioned heavy aids (per reduce pass)
+    OwnedBuf tau_w, tau_y;         // threshold guesses of partitioned heavy aids (per reduce pass)
     int guess = 1;                 // option "guess": single-pass top-k from a sibling partition's threshold
-    hipStream_t side = nullptr;    // the partition pass of the heavy aids runs here, beside the S / M bins
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool part_early = false;       // the partition of this pass is in flight on `side`
     uint64_t items_gen = 1;        // bumped whenever the heavy item list / partition chunks are rebuilt
     uint64_t part_gen = 0;         // items_gen the partition buckets in prec / ptw were filled for (0: none)
     bool part_has_tw = false;      // ... with the time channel alongside
-    int overlap_partition = 0;     // option "overlap_partition": measured at full OTTO shape, both kernels take twice as long side by
-                                   // side (partition 3.8 -> 6.2 ms, reduce S 2.9 -> 6.3 ms: the S bin's 20 workgroups per CU leave the
-                                   // partition workgroups no LDS), the step gains 0.4 ms of 31.5 and the per-kernel times stop adding up:
-                                   // off by default
     int hot = 2;                   // option "hot": 1 = top-k walks of the multi-wave bins over the heavy keys only, 2 = + single-wave
                                    // selection when the heavy keys are few (M bin), 0 = off (A/B)
-    DevBuf exp_run_pos, exp_rec_pos, exp_totals;
-    uint64_t exp_n_runs[64] = {0}, exp_n_recs[64] = {0};
+    OwnedBuf exp_run_pos, exp_rec_pos, exp_totals;
+    int64_t exp_n_runs[64] = {0}, exp_n_recs[64] = {0};   // per-owner counts of the last otto_covis_export_plan
     int exp_planned = 0;
     int64_t retries = 0;
     uint32_t l_cap = L_CAP;
@@ -3503,6 +3494,17 @@ static void tend(otto_covis_ctx* c, int i, hipStream_t s) {
     if (c->ev_ok) { (void)hipEventRecord(c->ev[2 * i + 1], s); c->ev_set[i] = true; }
 }
 
+// grid of the grid-stride kernels with 256-thread workgroups: one workgroup per 256 elements, capped
+static int strided_grid(int64_t n) {
+    const int64_t blocks = (n + 255) / 256;
+    return (int)(blocks < 256 * 32 ? blocks : 256 * 32);
+}
+// the runs changed (or how they are binned): the index and the run statistics of otto_covis_stats are stale
+static void invalidate(otto_covis_ctx* c) {
+    c->index_valid = false;
+    c->desc_totals_valid = false;
+}
+
 extern "C" const char* otto_last_error(void) { return g_err.c_str(); }
 
 extern "C" int otto_covis_create(otto_covis_ctx** out, const otto_covis_params* p) {
@@ -3523,10 +3525,6 @@ extern "C" int otto_covis_create(otto_covis_ctx** out, const otto_covis_params* 
     c->ev_ok = true;
     for (int i = 0; i < 2 * OTTO_COVIS_T_COUNT; ++i)
         if (hipEventCreate(&c->ev[i]) != hipSuccess) c->ev_ok = false;
-    if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
-        c->side = nullptr;                                  // no side stream: the partition stays on the caller's stream
-    }
     memset(c->ev_set, 0, sizeof c->ev_set);
     *out = c;
     return 0;
@@ -3534,27 +3532,16 @@ extern "C" int otto_covis_create(otto_covis_ctx** out, const otto_covis_params* 
 
 extern "C" void otto_covis_destroy(otto_covis_ctx* c) {
     if (!c) return;
-    DevBuf* all[] = {&c->rec, &c->tw, &c->run_x, &c->run_desc, &c->pair_base, &c->ev_base, &c->partial, &c->cnt64,
-                     &c->cls_pos[0], &c->cls_pos[1], &c->cls_pos[2], &c->cls_pos[3], &c->cls_pos[4], &c->cls_pos[5],
-                     &c->sess_list, &c->cls_byte,
-                     &c->run_start, &c->run_rank, &c->sorted_desc, &c->item_start, &c->boost, &c->flag, &c->counters,
-                     &c->items[0], &c->items[1], &c->items[2], &c->part_y, &c->part_w, &c->tau_w, &c->tau_y, &c->lorder[1][0], &c->lorder[1][1], &c->lorder[1][2], &c->lorder[2][0], &c->lorder[2][1], &c->lorder[2][2], &c->lrank, &c->lmode_start, &c->bcount, &c->bstart, &c->tmp_runs, &c->exp_run_pos, &c->exp_rec_pos, &c->exp_totals,
-                     &c->litem_start, &c->chunks, &c->pcount, &c->pcursor, &c->pstart, &c->prec, &c->ptw, &c->item_part};
-    for (DevBuf* b : all) b->release();
     if (c->ev_ok)
         for (int i = 0; i < 2 * OTTO_COVIS_T_COUNT; ++i) (void)hipEventDestroy(c->ev[i]);
-    if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    delete c;
+    delete c;                                            // the OwnedBuf members free the device memory
 }
 
 extern "C" int otto_covis_reset(otto_covis_ctx* c) {
     OTTO_REQUIRE(c, "null ctx");
     c->rec_used = c->run_used = 0;
     c->sessions = 0;
-    c->index_valid = false;
-    c->desc_totals_valid = false;
+    invalidate(c);
     c->n_pairs = c->n_runs = 0;
     c->n_items[0] = c->n_items[1] = c->n_items[2] = 0;
     memset(c->ev_set, 0, sizeof c->ev_set);
@@ -3578,104 +3565,40 @@ extern "C" int otto_covis_feed(otto_covis_ctx* c, const uint32_t* d_aid, const i
     OTTO_TRY(device_scan(WinPairs{d_sess_off, p.window}, n_sess, c->pair_base.as<uint64_t>(), c->partial.as<uint64_t>(), s));
     OTTO_TRY(device_scan(WinEvents{d_sess_off, p.window}, n_sess, c->ev_base.as<uint64_t>(), c->partial.as<uint64_t>(), s));
     OTTO_REQUIRE(n_sess < (1ll << 32), "more than 2^32 sessions in one chunk");
+    // no filter kind: one launch over the sessions in memory order (k_expand_lists / k_expand_fused), no class lists.
+    // Otherwise window classes (3 sizes x gap-free or not): one session list, six segments
     const bool fused = p.n_filters == 0 && c->fused;
-    if (fused) {
-        // no filter kinds: one fused launch over the sessions in memory order (k_expand_fused), no class lists
-        tend(c, OTTO_COVIS_T_WINSCAN, s);
-        uint64_t tot[2];
-        OTTO_HIP(hipMemcpyAsync(&tot[0], c->pair_base.as<uint64_t>() + n_sess, 8, hipMemcpyDeviceToHost, s));
-        OTTO_HIP(hipMemcpyAsync(&tot[1], c->ev_base.as<uint64_t>() + n_sess, 8, hipMemcpyDeviceToHost, s));
-        OTTO_HIP(hipStreamSynchronize(s));
-        const uint64_t n_ev = tot[1];
-        const bool lists = c->fused == 2;                  // component lists: n list slots per window behind the pair slots
-        const uint64_t n_slots = tot[0] + (lists ? n_ev : 0ull);
-        OTTO_REQUIRE(c->rec_used + n_slots < (1ull << DESC_SLOT_BITS), "record slot space exhausted");
-        OTTO_TRY(c->rec.ensure((size_t)(c->rec_used + n_slots + REC_PAD) * 4, (size_t)c->rec_used * 4, s));
-        if (p.want_time) OTTO_TRY(c->tw.ensure((size_t)(c->rec_used + n_slots) * 4, (size_t)c->rec_used * 4, s));
-        OTTO_TRY(c->run_x.ensure((size_t)(c->run_used + n_ev) * 4, (size_t)c->run_used * 4, s));
-        OTTO_TRY(c->run_desc.ensure((size_t)(c->run_used + n_ev) * 8, (size_t)c->run_used * 8, s));
-        tbegin(c, OTTO_COVIS_T_EXPAND, s);
-        ExpandArgs a;
-        memset(&a, 0, sizeof(a));
-        a.aid = d_aid; a.ts = d_ts; a.type = d_type; a.sess_off = d_sess_off;
-        a.pair_base = c->pair_base.as<uint64_t>(); a.ev_base = c->ev_base.as<uint64_t>();
-        a.rec = c->rec.as<uint32_t>(); a.tw = c->tw.as<uint32_t>();
-        a.run_x = c->run_x.as<uint32_t>(); a.run_desc = c->run_desc.as<uint64_t>();
-        a.rec_base = c->rec_used; a.run_base = c->run_used;
-        a.list_base = c->rec_used + tot[0];
-        a.window = p.window; a.max_gap = p.max_gap;
-        a.t0 = p.ts_min; a.tspan = (int64_t)p.ts_max - (int64_t)p.ts_min;
-        a.debug = c->debug_skip >> 4;
-        const int64_t tiles = (n_sess + 63) / 64;
-        const int64_t blocks = (tiles + 3) / 4;
-        int per_cu = 0, n_cu = 0, dev = 0;
-        OTTO_HIP(hipGetDevice(&dev));
-        OTTO_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        if (lists) {
-            if (p.want_time) OTTO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_expand_lists<true, false>, 256, 0));
-            else OTTO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_expand_lists<false, false>, 256, 0));
-        } else if (p.want_time) OTTO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_expand_fused<true, false>, 256, 0));
-        else OTTO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_expand_fused<false, false>, 256, 0));
-        const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 4) * (n_cu > 0 ? n_cu : 256);   // one round of resident workgroups
-        const int grid = (int)(blocks < resident ? blocks : resident);
-        kname(c, OTTO_COVIS_T_EXPAND, lists ? "k_expand_lists<%s, %s>" : "k_expand_fused<%s, %s>", p.want_time ? "true" : "false", a.debug ? "true" : "false");
-        if (lists) {
-            if (a.debug) {
-                if (p.want_time) k_expand_lists<true, true><<<grid, 256, 0, s>>>(a, n_sess);
-                else k_expand_lists<false, true><<<grid, 256, 0, s>>>(a, n_sess);
-            } else if (p.want_time) k_expand_lists<true, false><<<grid, 256, 0, s>>>(a, n_sess);
-            else k_expand_lists<false, false><<<grid, 256, 0, s>>>(a, n_sess);
-        } else if (a.debug) {
-            if (p.want_time) k_expand_fused<true, true><<<grid, 256, 0, s>>>(a, n_sess, c->fast_path);
-            else k_expand_fused<false, true><<<grid, 256, 0, s>>>(a, n_sess, c->fast_path);
-        } else if (p.want_time) k_expand_fused<true, false><<<grid, 256, 0, s>>>(a, n_sess, c->fast_path);
-        else k_expand_fused<false, false><<<grid, 256, 0, s>>>(a, n_sess, c->fast_path);
+    const bool lists = fused && c->fused == 2;             // component lists: n list slots per window behind the pair slots
+    if (!fused) {
+        const int use_fast = p.n_filters == 0 && c->fast_path;
+        OTTO_TRY(c->cls_byte.ensure((size_t)n_sess, 0, s));
+        OTTO_TRY(c->sess_list.ensure((size_t)(n_sess + 1) * 4, 0, s));
+        k_classify<<<(unsigned)((n_sess + 255) / 256), 256, 0, s>>>(d_sess_off, d_ts, p.window, p.max_gap, use_fast, n_sess,
+                                                                     c->cls_byte.as<uint8_t>());
         OTTO_HIP(hipGetLastError());
-        tend(c, OTTO_COVIS_T_EXPAND, s);
-        c->rec_used += n_slots;
-        c->run_used += n_ev;
-        c->sessions += n_sess;
-        c->index_valid = false;
-    c->desc_totals_valid = false;
-        return 0;
-    }
-    // filter kinds: window classes (3 sizes x gap-free or not): one session list, six segments
-    const int use_fast = p.n_filters == 0 && c->fast_path;
-    OTTO_TRY(c->cls_byte.ensure((size_t)n_sess, 0, s));
-    k_classify<<<(unsigned)((n_sess + 255) / 256), 256, 0, s>>>(d_sess_off, d_ts, p.window, p.max_gap, use_fast, n_sess,
-                                                                 c->cls_byte.as<uint8_t>());
-    OTTO_HIP(hipGetLastError());
-    for (int cl = 0; cl < N_WIN_CLASSES; ++cl) {
-        OTTO_TRY(c->cls_pos[cl].ensure((size_t)(n_sess + 1) * 8, 0, s));
-        OTTO_TRY(device_scan(WinClass{c->cls_byte.as<uint8_t>(), cl}, n_sess, c->cls_pos[cl].as<uint64_t>(), c->partial.as<uint64_t>(), s));
+        for (int cl = 0; cl < N_WIN_CLASSES; ++cl) {
+            OTTO_TRY(c->cls_pos[cl].ensure((size_t)(n_sess + 1) * 8, 0, s));
+            OTTO_TRY(device_scan(WinClass{c->cls_byte.as<uint8_t>(), cl}, n_sess, c->cls_pos[cl].as<uint64_t>(), c->partial.as<uint64_t>(), s));
+        }
     }
     tend(c, OTTO_COVIS_T_WINSCAN, s);
-    uint64_t totals[2 + N_WIN_CLASSES];
+    uint64_t totals[2 + N_WIN_CLASSES];                    // pairs, events (, sessions per class)
     OTTO_HIP(hipMemcpyAsync(&totals[0], c->pair_base.as<uint64_t>() + n_sess, 8, hipMemcpyDeviceToHost, s));
     OTTO_HIP(hipMemcpyAsync(&totals[1], c->ev_base.as<uint64_t>() + n_sess, 8, hipMemcpyDeviceToHost, s));
-    for (int cl = 0; cl < N_WIN_CLASSES; ++cl)
+    for (int cl = 0; !fused && cl < N_WIN_CLASSES; ++cl)
         OTTO_HIP(hipMemcpyAsync(&totals[2 + cl], c->cls_pos[cl].as<uint64_t>() + n_sess, 8, hipMemcpyDeviceToHost, s));
     OTTO_HIP(hipStreamSynchronize(s));
-    const uint64_t n_slots = totals[0], n_ev = totals[1];
+    const uint64_t n_ev = totals[1];
+    const uint64_t n_slots = totals[0] + (lists ? n_ev : 0ull);
     OTTO_REQUIRE(c->rec_used + n_slots < (1ull << DESC_SLOT_BITS), "record slot space exhausted");
-
     OTTO_TRY(c->rec.ensure((size_t)(c->rec_used + n_slots + REC_PAD) * 4, (size_t)c->rec_used * 4, s));
     if (p.want_time) OTTO_TRY(c->tw.ensure((size_t)(c->rec_used + n_slots) * 4, (size_t)c->rec_used * 4, s));
     OTTO_TRY(c->run_x.ensure((size_t)(c->run_used + n_ev) * 4, (size_t)c->run_used * 4, s));
     OTTO_TRY(c->run_desc.ensure((size_t)(c->run_used + n_ev) * 8, (size_t)c->run_used * 8, s));
-    OTTO_TRY(c->sess_list.ensure((size_t)(n_sess + 1) * 4, 0, s));
 
     tbegin(c, OTTO_COVIS_T_EXPAND, s);
-    ClassFill cf;
-    uint64_t lb = 0;
-    for (int cl = 0; cl < N_WIN_CLASSES; ++cl) {
-        cf.pos[cl] = c->cls_pos[cl].as<uint64_t>();
-        cf.base[cl] = lb;
-        lb += totals[2 + cl];
-    }
-    k_fill_classes<<<(unsigned)((n_sess + 255) / 256), 256, 0, s>>>(c->cls_byte.as<uint8_t>(), n_sess, cf, c->sess_list.as<uint32_t>());
-    OTTO_HIP(hipGetLastError());
     ExpandArgs a;
+    memset(&a, 0, sizeof(a));
     a.aid = d_aid; a.ts = d_ts; a.type = d_type; a.sess_off = d_sess_off;
     a.pair_base = c->pair_base.as<uint64_t>(); a.ev_base = c->ev_base.as<uint64_t>();
     a.rec = c->rec.as<uint32_t>(); a.tw = c->tw.as<uint32_t>();
@@ -3683,55 +3606,83 @@ extern "C" int otto_covis_feed(otto_covis_ctx* c, const uint32_t* d_aid, const i
     a.rec_base = c->rec_used; a.run_base = c->run_used;
     a.window = p.window; a.max_gap = p.max_gap;
     a.t0 = p.ts_min; a.tspan = (int64_t)p.ts_max - (int64_t)p.ts_min;
-    for (int f = 0; f < 4; ++f) a.fmask[f] = f < p.n_filters ? p.filter_mask[f] : 0u;
-    for (int cl = 0; cl < N_WIN_CLASSES; ++cl) {
-        a.sess_list = c->sess_list.as<uint32_t>() + cf.base[cl];
-        a.n_list = (int64_t)totals[2 + cl];
-        if (a.n_list == 0) continue;
-        const int size_cl = cl % 3;
-        const bool fast = cl >= 3;
-        const int wpw = size_cl == 0 ? 8 : (size_cl == 1 ? 4 : 2);
-        const int64_t waves = (a.n_list + wpw - 1) / wpw;
-        const int64_t blocks = (waves + 3) / 4;
-        const int grid = (int)(blocks < 256 * 16 ? blocks : 256 * 16);
-        const int variant = (p.want_time ? 2 : 0) | (p.n_filters > 0 ? 1 : 0);
-#define OTTO_EXPAND(G)                                                                   \
-        kname(c, OTTO_COVIS_T_EXPAND, fast ? "k_expand_fast<%d, %s>" : "k_expand<%d, %s, %s>", G, p.want_time ? "true" : "false", p.n_filters > 0 ? "true" : "false"); \
-        if (fast) {                                                                      \
-            if (p.want_time) k_expand_fast<G, true><<<grid, 256, 0, s>>>(a);             \
-            else k_expand_fast<G, false><<<grid, 256, 0, s>>>(a);                        \
-        } else switch (variant) {                                                        \
-            case 0: k_expand<G, false, false><<<grid, 256, 0, s>>>(a); break;            \
-            case 1: k_expand<G, false, true><<<grid, 256, 0, s>>>(a); break;             \
-            case 2: k_expand<G, true, false><<<grid, 256, 0, s>>>(a); break;             \
-            default: k_expand<G, true, true><<<grid, 256, 0, s>>>(a); break;             \
+    const int timed = p.want_time ? 1 : 0;
+    if (fused) {
+        a.list_base = c->rec_used + totals[0];
+        a.debug = c->debug_skip >> 4;
+        const int dbg = a.debug ? 1 : 0;
+        static const void* const kernels[2][2][2] = {      // [lists][TIME][DBG]
+            {{(const void*)k_expand_fused<false, false>, (const void*)k_expand_fused<false, true>},
+             {(const void*)k_expand_fused<true, false>, (const void*)k_expand_fused<true, true>}},
+            {{(const void*)k_expand_lists<false, false>, (const void*)k_expand_lists<false, true>},
+             {(const void*)k_expand_lists<true, false>, (const void*)k_expand_lists<true, true>}}};
+        const void* kern = kernels[lists][timed][dbg];
+        const int64_t tiles = (n_sess + 63) / 64;
+        const int64_t blocks = (tiles + 3) / 4;
+        int per_cu = 0, n_cu = 0, dev = 0;
+        OTTO_HIP(hipGetDevice(&dev));
+        OTTO_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+        OTTO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0));
+        const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 4) * (n_cu > 0 ? n_cu : 256);   // one round of resident workgroups
+        const int grid = (int)(blocks < resident ? blocks : resident);
+        kname(c, OTTO_COVIS_T_EXPAND, lists ? "k_expand_lists<%s, %s>" : "k_expand_fused<%s, %s>", timed ? "true" : "false", dbg ? "true" : "false");
+        void* args[] = {&a, &n_sess, &c->fast_path};       // (ExpandArgs, n_sess) for k_expand_lists, (ExpandArgs, n_sess, use_fast) for k_expand_fused
+        OTTO_HIP(hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, s));
+    } else {
+        ClassFill cf;
+        uint64_t lb = 0;
+        for (int cl = 0; cl < N_WIN_CLASSES; ++cl) {
+            cf.pos[cl] = c->cls_pos[cl].as<uint64_t>();
+            cf.base[cl] = lb;
+            lb += totals[2 + cl];
         }
-        if (size_cl == 0) { OTTO_EXPAND(8) } else if (size_cl == 1) { OTTO_EXPAND(16) } else { OTTO_EXPAND(32) }
-#undef OTTO_EXPAND
+        k_fill_classes<<<(unsigned)((n_sess + 255) / 256), 256, 0, s>>>(c->cls_byte.as<uint8_t>(), n_sess, cf, c->sess_list.as<uint32_t>());
         OTTO_HIP(hipGetLastError());
+        const int filt = p.n_filters > 0 ? 1 : 0;
+        for (int f = 0; f < p.n_filters; ++f) a.fmask[f] = p.filter_mask[f];
+        using ExpandFn = void (*)(ExpandArgs);
+        static const ExpandFn gap_free[3][2] = {           // [size class][TIME]
+            {k_expand_fast<8, false>, k_expand_fast<8, true>},
+            {k_expand_fast<16, false>, k_expand_fast<16, true>},
+            {k_expand_fast<32, false>, k_expand_fast<32, true>}};
+        static const ExpandFn general[3][2][2] = {         // [size class][TIME][FILT]
+            {{k_expand<8, false, false>, k_expand<8, false, true>}, {k_expand<8, true, false>, k_expand<8, true, true>}},
+            {{k_expand<16, false, false>, k_expand<16, false, true>}, {k_expand<16, true, false>, k_expand<16, true, true>}},
+            {{k_expand<32, false, false>, k_expand<32, false, true>}, {k_expand<32, true, false>, k_expand<32, true, true>}}};
+        for (int cl = 0; cl < N_WIN_CLASSES; ++cl) {
+            a.sess_list = c->sess_list.as<uint32_t>() + cf.base[cl];
+            a.n_list = (int64_t)totals[2 + cl];
+            if (a.n_list == 0) continue;
+            const int size_cl = cl % 3;                    // G = 8 / 16 / 32 lanes per window
+            const bool fast = cl >= 3;
+            const int wpw = size_cl == 0 ? 8 : (size_cl == 1 ? 4 : 2);
+            const int64_t waves = (a.n_list + wpw - 1) / wpw;
+            const int64_t blocks = (waves + 3) / 4;
+            const int grid = (int)(blocks < 256 * 16 ? blocks : 256 * 16);
+            const ExpandFn kern = fast ? gap_free[size_cl][timed] : general[size_cl][timed][filt];
+            kname(c, OTTO_COVIS_T_EXPAND, fast ? "k_expand_fast<%d, %s>" : "k_expand<%d, %s, %s>", 8 << size_cl, timed ? "true" : "false", filt ? "true" : "false");
+            kern<<<grid, 256, 0, s>>>(a);
+            OTTO_HIP(hipGetLastError());
+        }
     }
     tend(c, OTTO_COVIS_T_EXPAND, s);
 
     c->rec_used += n_slots;
     c->run_used += n_ev;
     c->sessions += n_sess;
-    c->index_valid = false;
-    c->desc_totals_valid = false;
+    invalidate(c);
     return 0;
 }
 
-// pre (nullable): the totals of k_aid_totals for this configuration -- no host synchronisation then
-static int build_items(otto_covis_ctx* c, int bin, int only_flagged, hipStream_t s, int allow_packed = 0, const uint64_t* pre = nullptr) {
+static int build_items(otto_covis_ctx* c, int bin, int only_flagged, hipStream_t s, int allow_packed = 0) {
     if (bin == 2) c->items_gen++;                        // the partition buckets of the previous list are stale
     const uint32_t n_aids = c->p.n_aids;
     ItemCount f{c->cnt64.as<uint64_t>(), c->boost.as<uint8_t>(), c->flag.as<uint32_t>(), bin, only_flagged, c->l_cap, allow_packed, -1};
     if (bin == 2) c->items_allow_packed = allow_packed;
     OTTO_TRY(device_scan(f, (int64_t)n_aids, c->item_start.as<uint64_t>(), c->partial.as<uint64_t>(), s));
-    uint64_t total = pre ? pre[8 + bin] : 0;
-    if (!pre) {
-        OTTO_HIP(hipMemcpyAsync(&total, c->item_start.as<uint64_t>() + n_aids, 8, hipMemcpyDeviceToHost, s));
-        OTTO_HIP(hipStreamSynchronize(s));
-    }
+    uint64_t total = 0;
+    OTTO_HIP(hipMemcpyAsync(&total, c->item_start.as<uint64_t>() + n_aids, 8, hipMemcpyDeviceToHost, s));
+    OTTO_HIP(hipStreamSynchronize(s));
     OTTO_REQUIRE(total < (1ull << 32), "too many work items (%llu)", (unsigned long long)total);
     c->n_items[bin] = total;
     if (total) {
@@ -3742,7 +3693,7 @@ static int build_items(otto_covis_ctx* c, int bin, int only_flagged, hipStream_t
     if (bin == 2) {
         // processing order per table layout (pilots first); item_start holds the item index of every heavy aid
         for (int mode = 0; mode < 3; ++mode) {
-            c->n_order[bin][mode] = 0;
+            c->n_order[mode] = 0;
             if (!total) continue;
             ItemCount fm = f;
             fm.mode = mode;
@@ -3750,17 +3701,15 @@ static int build_items(otto_covis_ctx* c, int bin, int only_flagged, hipStream_t
             OTTO_TRY(c->lmode_start.ensure((size_t)(n_aids + 1) * 8, 0, s));
             OTTO_TRY(device_scan(ItemAny{fm}, (int64_t)n_aids, c->lrank.as<uint64_t>(), c->partial.as<uint64_t>(), s));
             OTTO_TRY(device_scan(fm, (int64_t)n_aids, c->lmode_start.as<uint64_t>(), c->partial.as<uint64_t>(), s));
-            uint64_t n_pilots = pre ? pre[14 + mode] : 0, n_mode = pre ? pre[11 + mode] : 0;
-            if (!pre) {
-                OTTO_HIP(hipMemcpyAsync(&n_pilots, c->lrank.as<uint64_t>() + n_aids, 8, hipMemcpyDeviceToHost, s));
-                OTTO_HIP(hipMemcpyAsync(&n_mode, c->lmode_start.as<uint64_t>() + n_aids, 8, hipMemcpyDeviceToHost, s));
-                OTTO_HIP(hipStreamSynchronize(s));
-            }
-            c->n_order[bin][mode] = n_mode;
+            uint64_t n_pilots = 0, n_mode = 0;
+            OTTO_HIP(hipMemcpyAsync(&n_pilots, c->lrank.as<uint64_t>() + n_aids, 8, hipMemcpyDeviceToHost, s));
+            OTTO_HIP(hipMemcpyAsync(&n_mode, c->lmode_start.as<uint64_t>() + n_aids, 8, hipMemcpyDeviceToHost, s));
+            OTTO_HIP(hipStreamSynchronize(s));
+            c->n_order[mode] = n_mode;
             if (!n_mode) continue;
-            OTTO_TRY(c->lorder[bin][mode].ensure((size_t)n_mode * 4, 0, s));
+            OTTO_TRY(c->lorder[mode].ensure((size_t)n_mode * 4, 0, s));
             k_fill_order<<<(n_aids + 255) / 256, 256, 0, s>>>(fm, n_aids, c->item_start.as<uint64_t>(), c->lmode_start.as<uint64_t>(),
-                                                              c->lrank.as<uint64_t>(), n_pilots, c->lorder[bin][mode].as<uint32_t>());
+                                                              c->lrank.as<uint64_t>(), n_pilots, c->lorder[mode].as<uint32_t>());
             OTTO_HIP(hipGetLastError());
         }
     }
@@ -3770,11 +3719,9 @@ static int build_items(otto_covis_ctx* c, int bin, int only_flagged, hipStream_t
         OTTO_HIP(hipMemcpyAsync(c->litem_start.p, c->item_start.p, (size_t)(n_aids + 1) * 8, hipMemcpyDeviceToDevice, s));
         ChunkCount cf{c->cnt64.as<uint64_t>(), c->boost.as<uint8_t>(), c->flag.as<uint32_t>(), only_flagged, c->l_cap, allow_packed};
         OTTO_TRY(device_scan(cf, (int64_t)n_aids, c->item_start.as<uint64_t>(), c->partial.as<uint64_t>(), s));
-        uint64_t nch = pre ? pre[17] : 0;
-        if (!pre) {
-            OTTO_HIP(hipMemcpyAsync(&nch, c->item_start.as<uint64_t>() + n_aids, 8, hipMemcpyDeviceToHost, s));
-            OTTO_HIP(hipStreamSynchronize(s));
-        }
+        uint64_t nch = 0;
+        OTTO_HIP(hipMemcpyAsync(&nch, c->item_start.as<uint64_t>() + n_aids, 8, hipMemcpyDeviceToHost, s));
+        OTTO_HIP(hipStreamSynchronize(s));
         OTTO_REQUIRE(nch < (1ull << 32), "too many partition chunks");
         c->n_chunks = nch;
         if (nch) {
@@ -3844,7 +3791,7 @@ static int build_index(otto_covis_ctx* c, hipStream_t s) {
         k_bkt_fused<<<lgrid, BKT_THREADS, (size_t)12 << ba.sh, s>>>(ba, c->run_start.as<uint64_t>());
         OTTO_HIP(hipGetLastError());
     } else if (n_slots) {
-        int grid = (int)((n_slots + 255) / 256 < 256 * 32 ? (n_slots + 255) / 256 : 256 * 32);
+        const int grid = strided_grid(n_slots);
         kname(c, OTTO_COVIS_T_INDEX, "k_hist_runs + k_scatter_runs + k_scan_* + k_fill_*");
         k_hist_runs<<<grid, 256, 0, s>>>(c->run_x.as<uint32_t>(), c->run_desc.as<uint64_t>(), n_slots, c->cnt64.as<uint64_t>(),
                                          c->run_rank.as<uint32_t>(), n_aids);
@@ -3870,7 +3817,7 @@ static int build_index(otto_covis_ctx* c, hipStream_t s) {
     for (int bin = 0; bin < 3; ++bin) { c->bin_pairs[bin] = tot[2 + bin]; c->bin_runs[bin] = tot[5 + bin]; }
     if (!bucketed && n_slots) {
         OTTO_TRY(c->sorted_desc.ensure((size_t)(c->n_runs ? c->n_runs : 1) * 8, 0, s));
-        int grid = (int)((n_slots + 255) / 256 < 256 * 32 ? (n_slots + 255) / 256 : 256 * 32);
+        const int grid = strided_grid(n_slots);
         k_scatter_runs<<<grid, 256, 0, s>>>(c->run_x.as<uint32_t>(), c->run_desc.as<uint64_t>(), c->run_rank.as<uint32_t>(),
                                             n_slots, c->run_start.as<uint64_t>(), c->sorted_desc.as<uint64_t>(), n_aids);
         OTTO_HIP(hipGetLastError());
@@ -3888,9 +3835,9 @@ static int build_index(otto_covis_ctx* c, hipStream_t s) {
         }
         c->items_allow_packed = c->packed_heavy;
         for (int mode = 0; mode < 3; ++mode) {
-            c->n_order[2][mode] = tot[11 + mode];
-            OTTO_TRY(c->lorder[2][mode].ensure((size_t)(tot[11 + mode] ? tot[11 + mode] : 1) * 4, 0, s));
-            fa.order[mode] = c->lorder[2][mode].as<uint32_t>();
+            c->n_order[mode] = tot[11 + mode];
+            OTTO_TRY(c->lorder[mode].ensure((size_t)(tot[11 + mode] ? tot[11 + mode] : 1) * 4, 0, s));
+            fa.order[mode] = c->lorder[mode].as<uint32_t>();
             fa.n_pilots[mode] = tot[14 + mode];
         }
         OTTO_REQUIRE(tot[17] < (1ull << 32), "too many partition chunks");
@@ -3937,7 +3884,9 @@ static int run_partition(otto_covis_ctx* c, const ReduceArgs& a, bool time, hipS
                 c->litem_start.as<uint64_t>(), c->pcount.as<uint32_t>(), c->pcursor.as<uint32_t>(),
                 c->pstart.as<uint64_t>(), nullptr, nullptr, c->l_cap, c->p.window, a.allow_packed, c->flag.as<uint32_t>(),
                 c->counters.as<uint32_t>()};
-    const uint32_t pres = 256u * (uint32_t)c->p_wgs;
+    // scatter: 4 workgroups per CU are resident (38 KB of LDS each). The chunks are dequeued dynamically, so more make no
+    // difference: 4 / 8 / 12 per CU measure 2.92 ms (the static deal needed 12 for 2.99)
+    const uint32_t pres = 256u * 4u;
     const uint32_t pgrid = (uint32_t)(c->n_chunks < pres ? c->n_chunks : pres);
     const uint32_t cgrid = (uint32_t)(c->n_chunks < 256u * 8u ? c->n_chunks : 256u * 8u);
     // First attempt: buckets sized from the record counts the index already holds (2 x mean + margin), no count pass.
@@ -4018,12 +3967,7 @@ static int launch_reduce(otto_covis_ctx* c, ReduceArgs a, int bin, hipStream_t s
     } else {
         a.pstart = nullptr;
         if (c->partition && c->n_chunks) {
-            if (c->part_early) {
-                // launched on the side stream before the S / M bins (otto_covis_finalize): the heavy bin waits for it here
-                OTTO_HIP(hipStreamWaitEvent(s, c->ev_join, 0));
-                c->part_early = false;
-                c->part_gen = 0;
-            } else if (c->part_gen == c->items_gen && !c->exact_round && (GROUP != OTTO_COVIS_GROUP_TIME || c->part_has_tw)) {
+            if (c->part_gen == c->items_gen && !c->exact_round && (GROUP != OTTO_COVIS_GROUP_TIME || c->part_has_tw)) {
                 // the buckets of an earlier pass / group are still valid: every group partitions the same records of the same
                 // heavy item list the same way (a 7-kind build ran this pass three times)
             } else {
@@ -4040,10 +3984,10 @@ static int launch_reduce(otto_covis_ctx* c, ReduceArgs a, int bin, hipStream_t s
         tbegin(c, OTTO_COVIS_T_REDUCE_L, s);
         // the two table layouts of heavy aids: each kernel walks its own pilot-first order over the shared item list
         for (int mode = 2; mode >= 0; --mode) {
-            if (!c->n_order[2][mode]) continue;
+            if (!c->n_order[mode]) continue;
             ReduceArgs am = a;
-            am.order = c->lorder[2][mode].as<uint32_t>();
-            am.n_work = (uint32_t)c->n_order[2][mode];
+            am.order = c->lorder[mode].as<uint32_t>();
+            am.n_work = (uint32_t)c->n_order[mode];
             OTTO_HIP(hipMemsetAsync(wc, 0, 4, s));
             prof_begin();
             if (mode == 2) {
@@ -4161,19 +4105,6 @@ extern "C" int otto_covis_finalize(otto_covis_ctx* c, int group, int k, uint32_t
                 a.part_w = c->part_w.as<uint64_t>();
             }
             if (first) {
-                // the partition pass of the heavy aids (a gather that waits on memory) beside the S and M bins (LDS atomics):
-                // forked onto the side stream behind everything queued so far, joined where the heavy bin starts
-                if (c->overlap_partition && c->side && c->partition && c->n_chunks && c->n_items[2]) {
-                    ReduceArgs ap = a;
-                    ap.items = c->items[2].as<uint64_t>();
-                    ap.n_items = (uint32_t)c->n_items[2];
-                    ap.allow_packed = c->items_allow_packed > 0 ? c->items_allow_packed : 0;
-                    OTTO_HIP(hipEventRecord(c->ev_fork, s));
-                    OTTO_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-                    OTTO_TRY(run_partition(c, ap, group == OTTO_COVIS_GROUP_TIME, c->side));
-                    OTTO_HIP(hipEventRecord(c->ev_join, c->side));
-                    c->part_early = true;
-                }
                 OTTO_TRY(launch_reduce_group(c, a, 0, s));
                 OTTO_TRY(launch_reduce_group(c, a, 1, s));
             }
@@ -4203,8 +4134,7 @@ extern "C" int otto_covis_set_option(otto_covis_ctx* c, const char* name, int64_
         // records but more LDS-table overflows (each costs a re-partition round); any value is exact.
         OTTO_REQUIRE(value >= 64 && value <= (1ll << 30), "l_cap out of range");
         c->l_cap = (uint32_t)value;
-        c->index_valid = false;
-    c->desc_totals_valid = false;
+        invalidate(c);
         return 0;
     }
     if (strcmp(name, "debug_skip") == 0) { c->debug_skip = (int)value; return 0; }   // timing diagnostics, results invalid
@@ -4212,10 +4142,8 @@ extern "C" int otto_covis_set_option(otto_covis_ctx* c, const char* name, int64_
     if (strcmp(name, "bucket_index") == 0) { c->bucket_index = value != 0; return 0; }
     if (strcmp(name, "guess") == 0) { c->guess = value != 0; return 0; }           // threshold guessing on/off (A/B)
     if (strcmp(name, "fused") == 0) { c->fused = value < 0 ? 0 : (value > 2 ? 2 : (int)value); return 0; }   // 2 component lists, 1 fused register rows, 0 class-sorted kernels (A/B)
-    if (strcmp(name, "p_wgs") == 0) { c->p_wgs = value < 1 ? 1 : (value > 128 ? 128 : (int)value); return 0; }
     if (strcmp(name, "s_wgs") == 0) { c->s_wgs = value < 1 ? 1 : (value > 32 ? 32 : (int)value); return 0; }
     if (strcmp(name, "bkt_sh") == 0) { c->bkt_sh = (int)value; c->index_valid = false; return 0; }
-    if (strcmp(name, "overlap_partition") == 0) { c->overlap_partition = value != 0; return 0; }
     if (strcmp(name, "hot") == 0) { c->hot = value < 0 ? 0 : (value > 2 ? 2 : (int)value); return 0; }
     if (strcmp(name, "fast_path") == 0) { c->fast_path = value != 0; return 0; }   // gap-free window kernel on/off (A/B)
     if (strcmp(name, "part_sized") == 0) { c->part_sized = value != 0; return 0; }   // A/B: counted buckets only
@@ -4347,7 +4275,7 @@ extern "C" int otto_covis_export_runs(otto_covis_ctx* c, uint32_t x_lo, uint32_t
     OTTO_REQUIRE(d_hdr && d_rec, "null export buffers");
     OTTO_REQUIRE(!d_tw || c->p.want_time, "no time channel to export");
     const int64_t n_slots = (int64_t)c->run_used;
-    int grid = (int)((n_slots + 255) / 256 < 256 * 32 ? (n_slots + 255) / 256 : 256 * 32);
+    const int grid = strided_grid(n_slots);
     k_export<<<grid, 256, 0, s>>>(c->run_x.as<uint32_t>(), c->run_desc.as<uint64_t>(), n_slots, x_lo, x_hi,
                                   c->exp_run_pos.as<uint64_t>(), c->exp_rec_pos.as<uint64_t>(), c->rec.as<uint32_t>(),
                                   c->tw.as<uint32_t>(), d_hdr, d_rec, d_tw);
@@ -4374,67 +4302,11 @@ static int owner_args(otto_covis_ctx* c, int n_owners, const uint32_t* h_bounds,
     return 0;
 }
 
-extern "C" int otto_covis_export_plan(otto_covis_ctx* c, int n_owners, const uint32_t* h_bounds, int64_t* h_n_runs,
-                                      int64_t* h_n_recs, void* stream) {
+// Pass 1 of the per-owner export of the run slots [slot_lo, slot_hi) (slot_hi < 0: to the end): runs and records per owner.
+// Synchronises `s` once.
+static int export_plan_impl(otto_covis_ctx* c, int n_owners, const uint32_t* h_bounds, int64_t slot_lo, int64_t slot_hi,
+                            int64_t* h_n_runs, int64_t* h_n_recs, hipStream_t s) {
     OTTO_REQUIRE(h_n_runs && h_n_recs, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    OwnerArgs a;
-    OTTO_TRY(owner_args(c, n_owners, h_bounds, a));
-    OTTO_REQUIRE(c->run_used < (1ull << (64 - EXP_REC_BITS)) && c->rec_used < (1ull << EXP_REC_BITS), "too many runs for the packed export cursor");
-    OTTO_TRY(c->exp_totals.ensure(2 * MAX_OWNERS * 8, 0, s));
-    OTTO_HIP(hipMemsetAsync(c->exp_totals.p, 0, 2 * MAX_OWNERS * 8, s));
-    a.totals = c->exp_totals.as<unsigned long long>();
-    if (a.n_slots) {
-        const int64_t nb = (a.n_slots + 255) / 256;
-        k_export_plan<<<(unsigned)(nb < 256 * 8 ? nb : 256 * 8), 256, 0, s>>>(a);
-        OTTO_HIP(hipGetLastError());
-    }
-    unsigned long long t[MAX_OWNERS];
-    OTTO_HIP(hipMemcpyAsync(t, c->exp_totals.p, sizeof t, hipMemcpyDeviceToHost, s));
-    OTTO_HIP(hipStreamSynchronize(s));
-    for (int o = 0; o < n_owners; ++o) {
-        c->exp_n_runs[o] = t[o] >> EXP_REC_BITS;
-        c->exp_n_recs[o] = t[o] & ((1ull << EXP_REC_BITS) - 1ull);
-        h_n_runs[o] = (int64_t)c->exp_n_runs[o];
-        h_n_recs[o] = (int64_t)c->exp_n_recs[o];
-    }
-    c->exp_planned = n_owners;
-    return 0;
-}
-
-extern "C" int otto_covis_export_fill(otto_covis_ctx* c, int n_owners, const uint32_t* h_bounds, uint32_t* d_hdr,
-                                      uint32_t* d_rec, uint32_t* d_tw, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    OwnerArgs a;
-    OTTO_TRY(owner_args(c, n_owners, h_bounds, a));
-    OTTO_REQUIRE(c->exp_planned == n_owners, "call otto_covis_export_plan with the same owners first");
-    OTTO_REQUIRE(!d_tw || c->p.want_time, "no time channel to export");
-    uint64_t rb = 0, cb = 0;
-    for (int o = 0; o < n_owners; ++o) {
-        a.run_base[o] = rb;
-        a.rec_base[o] = cb;
-        rb += c->exp_n_runs[o];
-        cb += c->exp_n_recs[o];
-    }
-    if (rb == 0) return 0;
-    OTTO_REQUIRE(d_hdr && d_rec, "null export buffers");
-    OTTO_HIP(hipMemsetAsync(c->exp_totals.p, 0, 2 * MAX_OWNERS * 8, s));
-    a.totals = c->exp_totals.as<unsigned long long>();
-    a.rec = c->rec.as<uint32_t>();
-    a.tw = c->tw.as<uint32_t>();
-    a.o_hdr = d_hdr; a.o_rec = d_rec; a.o_tw = d_tw;
-    const int64_t nb = (a.n_slots + EXP_CHUNK - 1) / EXP_CHUNK;
-    k_export_fill<<<(unsigned)(nb < 256 * 8 ? nb : 256 * 8), 256, 0, s>>>(a);
-    OTTO_HIP(hipGetLastError());
-    return 0;
-}
-
-// The same two passes over a RANGE of run slots (chunked exchange: the fill of chunk c + 1 runs while chunk c is on the
-// links). The counts travel through the caller (plan_range -> fill_range), not through the context.
-extern "C" int otto_covis_export_plan_range(otto_covis_ctx* c, int n_owners, const uint32_t* h_bounds, int64_t slot_lo, int64_t slot_hi,
-                                            int64_t* h_n_runs, int64_t* h_n_recs, void* stream) {
-    OTTO_REQUIRE(h_n_runs && h_n_recs, "null argument");
-    hipStream_t s = (hipStream_t)stream;
     OwnerArgs a;
     OTTO_TRY(owner_args(c, n_owners, h_bounds, a, slot_lo, slot_hi));
     OTTO_REQUIRE(c->run_used < (1ull << (64 - EXP_REC_BITS)) && c->rec_used < (1ull << EXP_REC_BITS), "too many runs for the packed export cursor");
@@ -4453,17 +4325,18 @@ extern "C" int otto_covis_export_plan_range(otto_covis_ctx* c, int n_owners, con
         h_n_runs[o] = (int64_t)(t[o] >> EXP_REC_BITS);
         h_n_recs[o] = (int64_t)(t[o] & ((1ull << EXP_REC_BITS) - 1ull));
     }
-    c->exp_planned = 0;
     return 0;
 }
 
-extern "C" int otto_covis_export_fill_range(otto_covis_ctx* c, int n_owners, const uint32_t* h_bounds, int64_t slot_lo, int64_t slot_hi,
-                                            const int64_t* h_n_runs, const int64_t* h_n_recs, uint32_t* d_hdr, uint32_t* d_rec,
-                                            uint32_t* d_tw, void* stream) {
+// Pass 2: the runs of every owner, contiguous per owner, from the counts of pass 1 over the same slots. Counts read from the
+// context (otto_covis_export_fill) must have been planned for the same owners.
+static int export_fill_impl(otto_covis_ctx* c, int n_owners, const uint32_t* h_bounds, int64_t slot_lo, int64_t slot_hi,
+                            const int64_t* h_n_runs, const int64_t* h_n_recs, uint32_t* d_hdr, uint32_t* d_rec, uint32_t* d_tw,
+                            hipStream_t s) {
     OTTO_REQUIRE(h_n_runs && h_n_recs, "null argument");
-    hipStream_t s = (hipStream_t)stream;
     OwnerArgs a;
     OTTO_TRY(owner_args(c, n_owners, h_bounds, a, slot_lo, slot_hi));
+    OTTO_REQUIRE(h_n_runs != c->exp_n_runs || c->exp_planned == n_owners, "call otto_covis_export_plan with the same owners first");
     OTTO_REQUIRE(!d_tw || c->p.want_time, "no time channel to export");
     uint64_t rb = 0, cb = 0;
     for (int o = 0; o < n_owners; ++o) {
@@ -4484,6 +4357,38 @@ extern "C" int otto_covis_export_fill_range(otto_covis_ctx* c, int n_owners, con
     const int64_t nb = (a.n_slots + EXP_CHUNK - 1) / EXP_CHUNK;
     k_export_fill<<<(unsigned)(nb < 256 * 8 ? nb : 256 * 8), 256, 0, s>>>(a);
     OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
+// All run slots: the counts stay in the context between the two passes.
+extern "C" int otto_covis_export_plan(otto_covis_ctx* c, int n_owners, const uint32_t* h_bounds, int64_t* h_n_runs,
+                                      int64_t* h_n_recs, void* stream) {
+    OTTO_TRY(export_plan_impl(c, n_owners, h_bounds, 0, -1, h_n_runs, h_n_recs, (hipStream_t)stream));
+    memcpy(c->exp_n_runs, h_n_runs, (size_t)n_owners * 8);
+    memcpy(c->exp_n_recs, h_n_recs, (size_t)n_owners * 8);
+    c->exp_planned = n_owners;
+    return 0;
+}
+
+extern "C" int otto_covis_export_fill(otto_covis_ctx* c, int n_owners, const uint32_t* h_bounds, uint32_t* d_hdr,
+                                      uint32_t* d_rec, uint32_t* d_tw, void* stream) {
+    OTTO_REQUIRE(c, "null argument");
+    return export_fill_impl(c, n_owners, h_bounds, 0, -1, c->exp_n_runs, c->exp_n_recs, d_hdr, d_rec, d_tw, (hipStream_t)stream);
+}
+
+// The same two passes over a RANGE of run slots (chunked exchange: the fill of chunk c + 1 runs while chunk c is on the
+// links). The counts travel through the caller (plan_range -> fill_range), not through the context.
+extern "C" int otto_covis_export_plan_range(otto_covis_ctx* c, int n_owners, const uint32_t* h_bounds, int64_t slot_lo, int64_t slot_hi,
+                                            int64_t* h_n_runs, int64_t* h_n_recs, void* stream) {
+    OTTO_TRY(export_plan_impl(c, n_owners, h_bounds, slot_lo, slot_hi, h_n_runs, h_n_recs, (hipStream_t)stream));
+    c->exp_planned = 0;
+    return 0;
+}
+
+extern "C" int otto_covis_export_fill_range(otto_covis_ctx* c, int n_owners, const uint32_t* h_bounds, int64_t slot_lo, int64_t slot_hi,
+                                            const int64_t* h_n_runs, const int64_t* h_n_recs, uint32_t* d_hdr, uint32_t* d_rec,
+                                            uint32_t* d_tw, void* stream) {
+    OTTO_TRY(export_fill_impl(c, n_owners, h_bounds, slot_lo, slot_hi, h_n_runs, h_n_recs, d_hdr, d_rec, d_tw, (hipStream_t)stream));
     c->exp_planned = 0;
     return 0;
 }
@@ -4518,13 +4423,12 @@ extern "C" int otto_covis_import_runs(otto_covis_ctx* c, const uint32_t* d_hdr, 
         OTTO_HIP(hipMemcpyAsync(c->rec.as<uint32_t>() + c->rec_used, d_rec, (size_t)n_recs * 4, hipMemcpyDeviceToDevice, s));
     if (c->p.want_time && d_tw != c->tw.as<uint32_t>() + c->rec_used)
         OTTO_HIP(hipMemcpyAsync(c->tw.as<uint32_t>() + c->rec_used, d_tw, (size_t)n_recs * 4, hipMemcpyDeviceToDevice, s));
-    int grid = (int)((n_runs + 255) / 256 < 256 * 32 ? (n_runs + 255) / 256 : 256 * 32);
+    const int grid = strided_grid(n_runs);
     k_import<<<grid, 256, 0, s>>>(d_hdr, n_runs, c->exp_rec_pos.as<uint64_t>(), c->rec_used, c->run_used,
                                   c->run_x.as<uint32_t>(), c->run_desc.as<uint64_t>());
     OTTO_HIP(hipGetLastError());
     c->rec_used += (uint64_t)n_recs;
     c->run_used += (uint64_t)n_runs;
-    c->index_valid = false;
-    c->desc_totals_valid = false;
+    invalidate(c);
     return 0;
 }

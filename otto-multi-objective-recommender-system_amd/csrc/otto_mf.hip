@@ -771,15 +771,11 @@ using namespace otto;
 struct otto_mf_ctx {
     int64_t n1, n2, max_batch;
     int d, G, shared;
-    DevBuf owner1, owner2;          // BPR batch mode: row -> smallest occurrence id (OWNER_FREE between steps)
-    DevBuf cnt1, cnt2, slot1, slot2, role;   // SparseAdam step: occurrence counters (zero between steps), slots, roles
-    DevBuf grad, coef, neg, partial;
-    DevBuf err;                     // [0] u32: samples skipped because a row id was outside its table (sticky until read)
-    DevBuf sums;                    // [4] double: running sum|e|, sum e^2, hits, count of otto_mf_eval_sums
-    void release_all() {
-        DevBuf* all[] = {&owner1, &owner2, &cnt1, &cnt2, &slot1, &slot2, &role, &grad, &coef, &neg, &partial, &err, &sums};
-        for (DevBuf* b : all) b->release();
-    }
+    OwnedBuf owner1, owner2;        // BPR batch mode: row -> smallest occurrence id (OWNER_FREE between steps)
+    OwnedBuf cnt1, cnt2, slot1, slot2, role;   // SparseAdam step: occurrence counters (zero between steps), slots, roles
+    OwnedBuf grad, coef, neg, partial;
+    OwnedBuf err;                   // [0] u32: samples skipped because a row id was outside its table (sticky until read)
+    OwnedBuf sums;                  // [4] double: running sum|e|, sum e^2, hits, count of otto_mf_eval_sums
 };
 
 static int mf_grid(int64_t B, int G) {
@@ -801,7 +797,7 @@ extern "C" int otto_mf_create(otto_mf_ctx** out, int64_t n1, int64_t n2, int32_t
     c->n1 = n1; c->n2 = shared_table ? n1 : n2; c->d = d; c->G = d / 4; c->shared = shared_table != 0;
     c->max_batch = max_batch;
     int rc = 0;
-    auto fail = [&](int code) { c->release_all(); delete c; return code; };
+    auto fail = [&](int code) { delete c; return code; };
     // per-row words of table 1 (and of table 2 unless the table is shared)
     if ((rc = c->owner1.ensure((size_t)n1 * 4, 0, 0)) || (rc = c->cnt1.ensure((size_t)n1 * 4, 0, 0)) ||
         (rc = c->slot1.ensure((size_t)n1 * 4, 0, 0)))
@@ -826,8 +822,6 @@ extern "C" int otto_mf_create(otto_mf_ctx** out, int64_t n1, int64_t n2, int32_t
 }
 
 extern "C" void otto_mf_destroy(otto_mf_ctx* c) {
-    if (!c) return;
-    c->release_all();
     delete c;
 }
 

@@ -272,6 +272,19 @@ def test_context_reuse_across_streams_and_groups(gpu_device):
             _assert_rows_equal(got, want, kinds)
 
 
+def test_removed_options_are_unknown(gpu_device):
+    """`overlap_partition` (partition pass on a side stream) and `p_wgs` (workgroups of the partition scatter) were
+    removed: the library rejects them like any other unknown name, and still accepts a name it kept."""
+    from otto_amd._lib import OttoError
+    from otto_amd.covisitation.engine import CovisBuilder
+    b = CovisBuilder(1000, kinds=NOFILT, ts_min=0, ts_max=1, device=gpu_device)
+    for name, value in (('overlap_partition', 1), ('p_wgs', 8)):
+        with pytest.raises(OttoError, match=f"unknown option '{name}'"):
+            b.set_option(name, value)
+    b.set_option('s_wgs', 20)
+    b.close()
+
+
 @pytest.mark.parametrize('n_sess', [4095, 4096, 9000])
 def test_packed_heavy_layout_counter_limit(gpu_device, n_sess):
     """Heavy aids with fewer than 4096 runs use 12-bit packed counters (a pair gains at most one record per session
