@@ -153,6 +153,12 @@ SIGNATURES = {
     # include/otto_knn.h
     'otto_knn_workspace': (_i64, [_i64, _i64, _i32, _i32, _i32]),
     'otto_knn_table': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # include/otto_forest.h
+    'otto_forest_packed_bytes': (_i64, [_i32, _i64, _i64]),
+    'otto_forest_pack': (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64]),
+    'otto_forest_predict': (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, C.c_double, _vp]),
+    'otto_forest_leaves': (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    'otto_forest_session_topk': (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
