@@ -159,6 +159,13 @@ SIGNATURES = {
     'otto_forest_predict': (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, C.c_double, _vp]),
     'otto_forest_leaves': (_i32, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     'otto_forest_session_topk': (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    # include/otto_blend.h
+    'otto_blend_select_workspace': (_i64, [_i64]),
+    'otto_blend_robust_stats': (_i32, [_vp, _i64, _p_i64, C.POINTER(C.c_double), _vp, _i64, _vp]),
+    'otto_blend_scale': (_i32, [_vp, _i64, C.c_double, C.c_double, _vp, _vp]),
+    'otto_blend_join_workspace': (_i64, [_i64, _i32]),
+    'otto_blend_join': (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _p_i64, C.POINTER(C.c_double),
+                               C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _p_i64, _p_i64, _vp, _i64, _vp]),
 }
 
 _lib = None

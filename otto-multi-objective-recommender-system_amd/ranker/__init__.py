@@ -1,2 +1,4 @@
 """Callers on the candidate side of the hot path (SURVEY.md section 8 f): feature engineering over the candidate arrays the
 covisitation lookup leaves on the device."""
+
+from .blend import blend_predictions, blend_topk, robust_scale  # noqa: E402,F401
