@@ -917,12 +917,12 @@ __global__ void k_hist_runs(const uint32_t* run_x, const uint64_t* run_desc, int
 // ---- bucketed index: the same (cnt64, run_start, sorted_desc) without one global atomic per run -------------
 // The histogram / scatter pair above pays one returning memory-side atomic and two random 8-byte accesses per run.
 // Here the non-empty runs are first split into buckets of 2^SH consecutive aids (count -> scan -> scatter with one
-// cursor bump per (chunk, bucket)), then one workgroup per bucket counts and places its runs with LDS atomics
-// only; a bucket's slice of run_start / sorted_desc is a window of a few hundred KB, so those writes combine in L2.
+// cursor bump per (chunk, bucket)), then the workgroups of a bucket count and place its runs with LDS atomics only
+// and store them in pieces sorted by aid (k_bkt_count / k_bkt_scan / k_bkt_place below).
 constexpr int BKT_THREADS = 1024;
 constexpr int BKT_CHUNK = 16384;                      // run slots per pass-1 work item (staged in LDS: 128 KB of 8-byte records)
 constexpr int BKT_MAX_NB = 2048;                      // buckets (LDS histogram / offsets / cursors of pass 1)
-constexpr int BKT_MAX_SH = 13;                        // aids per bucket <= 8192: 13 bits of the bucketed record, 96 KB of LDS in k_bkt_fused
+constexpr int BKT_MAX_SH = 13;                        // aids per bucket <= 8192: 13 bits of the bucketed record, 64 KB of per-aid LDS arrays in k_bkt_count / k_bkt_place
 
 // Bucketed run record (8 bytes; the bucket is implied by the position): len - 1 (5 bits; only non-empty runs travel) |
 // first record slot << 5 (40 bits) | sp << 45 (6 bits) | (aid_x & (bucket size - 1)) << 51 (13 bits)
@@ -948,6 +948,9 @@ struct BktArgs {
     uint64_t* cnt64;
     const uint64_t* run_start;
     uint64_t* sorted_desc;
+    uint32_t parts;                // workgroups per bucket of k_bkt_count / k_bkt_place
+    unsigned long long* part_cnt;  // [nb][parts][1 << sh] runs << 36 | records of the aid in the part
+    uint32_t* part_pos;            // [nb][parts][1 << sh] place in sorted_desc of the part's first run of the aid
 };
 
 // Split without global atomics: workgroup w always takes the same range of consecutive chunks, so the count pass leaves ONE counter
@@ -1044,66 +1047,168 @@ __global__ __launch_bounds__(BKT_THREADS) void k_bkt_split(BktArgs a) {
     }
 }
 
-// count + scan + place of one bucket in ONE workgroup: the first run of aid x is the bucket's first run (bstart[b], known from
-// the split) + the runs of the bucket's aids before x, so the prefix is a block scan in LDS; the second walk over the bucket's
-// runs (4.6 MB of 8-byte records at OTTO shape) is served by the Infinity Cache.
-__global__ __launch_bounds__(BKT_THREADS) void k_bkt_fused(BktArgs a, uint64_t* run_start_out) {
-    extern __shared__ unsigned long long s_dyn[];          // [1 << sh]: runs << 36 | records, then start positions
-    uint32_t* s_cur = reinterpret_cast<uint32_t*>(s_dyn + ((size_t)1 << a.sh));   // [1 << sh] cursors
+// count -> scan -> place of the bucketed runs, S workgroups per bucket ("parts": equal slices of the bucket's runs), so that
+// every CU has work whatever the bucket sizes are:
+//   k_bkt_count: part (b, s) counts its runs per aid in LDS and leaves the partial counts (runs << 36 | records) in part_cnt
+//   k_bkt_scan : one workgroup per bucket adds the S partials of every aid (-> cnt64), scans the run counts over the bucket's
+//                aids (-> run_start: the bucket's first run is known from the split) and leaves, per (part, aid), the place of
+//                the part's first run of that aid in part_pos -- parts of one aid follow each other inside the aid's window
+//   k_bkt_place: part (b, s) walks its runs again in tiles; a tile is SORTED BY AID IN LDS exactly as the split sorts a chunk by
+//                bucket (returning LDS atomic on the aid's tile counter = rank, block scan = first stage position) and copied
+//                out with consecutive lanes on consecutive stage positions: the runs of one aid in a tile land as one contiguous
+//                piece at the aid's cursor. (Before, every run was stored on its own at start + cursor: 2.44 GB written for the
+//                1.05 GB of sorted_desc -- 64 workgroups per XCD with a window of ~1 MB each do not combine in a 4 MB L2.)
+// The order of the runs inside one aid is unspecified (LDS atomics), as it always was.
+constexpr int BKT_TILE_MAX = 16384;                   // runs per tile of k_bkt_place (16 per thread)
+constexpr int BKT_LDS_BYTES = 160 * 1024 - 256;       // dynamic LDS k_bkt_place may ask for (the CU's 160 KB less its static words)
+constexpr int BKT_MAX_PARTS = 64;
+constexpr int BKT_WGS_TARGET = 14 * 256;              // workgroups wanted per launch (k_bkt_place runs one per CU): 906 buckets at OTTO shape -> 4 parts each
+
+__host__ __device__ inline uint32_t bkt_tile(int sh) {            // largest tile (whole thousands of runs) beside the two per-aid arrays
+    const uint32_t room = ((uint32_t)BKT_LDS_BYTES - 4u * ((2u << sh) + 1u)) / 8u;
+    return room >= (uint32_t)BKT_TILE_MAX ? (uint32_t)BKT_TILE_MAX : room & ~(uint32_t)(BKT_THREADS - 1);
+}
+__host__ __device__ inline size_t bkt_place_lds(int sh) { return (size_t)bkt_tile(sh) * 8 + 4 * (((size_t)2 << sh) + 1); }
+
+// runs [*p0, *p1) of part s of bucket b
+__device__ __forceinline__ void bkt_part_range(const BktArgs& a, uint32_t b, uint32_t s, uint64_t* p0, uint64_t* p1) {
+    const uint64_t e0 = a.bscan[(size_t)b * a.bstride], n = a.bscan[(size_t)(b + 1) * a.bstride] - e0;
+    *p0 = e0 + n * s / a.parts;
+    *p1 = e0 + n * (s + 1) / a.parts;
+}
+
+__global__ __launch_bounds__(BKT_THREADS) void k_bkt_count(BktArgs a) {
+    extern __shared__ unsigned long long s_dyn[];          // [1 << sh]: runs << 36 | records
+    const uint32_t ab = 1u << a.sh;
+    const uint32_t b = blockIdx.x / a.parts, s = blockIdx.x % a.parts;
+    for (uint32_t i = threadIdx.x; i < ab; i += BKT_THREADS) s_dyn[i] = 0;
+    __syncthreads();
+    uint64_t p0, p1;
+    bkt_part_range(a, b, s, &p0, &p1);
+    constexpr int U = 8;
+    for (uint64_t i0 = p0 + threadIdx.x; i0 < p1; i0 += U * BKT_THREADS) {
+        uint64_t r[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint64_t i = i0 + (uint64_t)u * BKT_THREADS;
+            r[u] = i < p1 ? a.tmp[i] : 0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (i0 + (uint64_t)u * BKT_THREADS < p1)
+                atomicAdd(&s_dyn[bkt_xlow(r[u])], (1ull << CNT_REC_BITS) | desc_pairs(bkt_desc(r[u])));
+    }
+    __syncthreads();
+    unsigned long long* out = a.part_cnt + (size_t)blockIdx.x * ab;
+    for (uint32_t i = threadIdx.x; i < ab; i += BKT_THREADS) out[i] = s_dyn[i];
+}
+
+__global__ __launch_bounds__(BKT_THREADS) void k_bkt_scan(BktArgs a, uint64_t* run_start_out) {
     __shared__ uint32_t s_sc[BKT_THREADS / 64 + 1];
     const uint32_t ab = 1u << a.sh;
+    const uint32_t per = ab / BKT_THREADS > 0 ? ab / BKT_THREADS : 1u;       // thread t: aids t * per .. + per
+    const uint32_t b = blockIdx.x, x0 = b << a.sh;
+    const unsigned long long* pc = a.part_cnt + (size_t)b * a.parts * ab;
+    uint32_t* pp = a.part_pos + (size_t)b * a.parts * ab;
+    uint32_t mine = 0;
+    for (uint32_t q = 0; q < per; ++q) {
+        const uint32_t i = threadIdx.x * per + q;
+        if (i < ab) {
+            unsigned long long c64 = 0;
+            for (uint32_t s = 0; s < a.parts; ++s) c64 += pc[(size_t)s * ab + i];
+            if (x0 + i < a.n_aids) a.cnt64[x0 + i] = c64;
+            mine += (uint32_t)(c64 >> CNT_REC_BITS);
+        }
+    }
+    uint32_t tot;
+    const uint64_t e0 = a.bscan[(size_t)b * a.bstride];
+    uint32_t run = (uint32_t)e0 + block_excl_scan<uint32_t, BKT_THREADS>(mine, s_sc, &tot);      // run slots < 2^32
+    for (uint32_t q = 0; q < per; ++q) {
+        const uint32_t i = threadIdx.x * per + q;
+        if (i < ab) {
+            if (x0 + i < a.n_aids) run_start_out[x0 + i] = run;
+            for (uint32_t s = 0; s < a.parts; ++s) {
+                pp[(size_t)s * ab + i] = run;
+                run += (uint32_t)(pc[(size_t)s * ab + i] >> CNT_REC_BITS);
+            }
+        }
+    }
+    if (b == a.nb - 1 && threadIdx.x == 0) run_start_out[a.n_aids] = e0 + tot;
+}
+
+__global__ __launch_bounds__(BKT_THREADS) void k_bkt_place(BktArgs a) {
+    extern __shared__ unsigned long long s_dyn[];          // stage [tile] | s_pos [1 << sh] | s_tf [(1 << sh) + 1]
+    __shared__ uint32_t s_sc[BKT_THREADS / 64 + 1];
+    const uint32_t ab = 1u << a.sh, tile = bkt_tile(a.sh);
     const uint32_t per = ab / BKT_THREADS > 0 ? ab / BKT_THREADS : 1u;
-    for (uint32_t b = blockIdx.x; b < a.nb; b += gridDim.x) {
-        const uint32_t x0 = b << a.sh;
-        for (uint32_t i = threadIdx.x; i < ab; i += BKT_THREADS) { s_dyn[i] = 0; s_cur[i] = 0; }
-        __syncthreads();
-        const uint64_t e0 = a.bscan[(size_t)b * a.bstride], e1 = a.bscan[(size_t)(b + 1) * a.bstride];
-        for (uint64_t i0 = e0 + threadIdx.x; i0 < e1; i0 += 4 * BKT_THREADS) {
-            uint64_t r[4];
+    unsigned long long* s_stage = s_dyn;
+    uint32_t* s_pos = reinterpret_cast<uint32_t*>(s_dyn + tile);   // where the part's next run of the aid goes (absolute)
+    uint32_t* s_tf = s_pos + ab;                                    // tile: runs of the aid, then its first stage position; [ab] = runs of the tile
+    const uint32_t b = blockIdx.x / a.parts, s = blockIdx.x % a.parts;
+    uint64_t p0, p1;
+    bkt_part_range(a, b, s, &p0, &p1);
+    if (p0 == p1) return;
+    const uint32_t* pp = a.part_pos + (size_t)blockIdx.x * ab;
+    for (uint32_t i = threadIdx.x; i < ab; i += BKT_THREADS) { s_pos[i] = pp[i]; s_tf[i] = 0; }
+    constexpr int PER = BKT_TILE_MAX / BKT_THREADS;
+    uint64_t r[PER];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint64_t i = i0 + (uint64_t)u * BKT_THREADS;
-                r[u] = i < e1 ? a.tmp[i] : ~0ull;
-            }
+    for (int u = 0; u < PER; ++u) {
+        const uint64_t i = p0 + (uint32_t)u * BKT_THREADS + threadIdx.x;
+        r[u] = (uint32_t)u * BKT_THREADS + threadIdx.x < tile && i < p1 ? a.tmp[i] : 0ull;
+    }
+    __syncthreads();
+    for (uint64_t t0 = p0; t0 < p1; t0 += tile) {
+        const uint32_t n = p1 - t0 < tile ? (uint32_t)(p1 - t0) : tile;
+        uint32_t rk[PER];
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (r[u] != ~0ull) atomicAdd(&s_dyn[bkt_xlow(r[u])], (1ull << CNT_REC_BITS) | desc_pairs(bkt_desc(r[u])));
+        for (int u = 0; u < PER; ++u) {
+            rk[u] = 0;
+            if ((uint32_t)u * BKT_THREADS + threadIdx.x < n) rk[u] = atomicAdd(&s_tf[bkt_xlow(r[u])], 1u);
         }
         __syncthreads();
-        // counts out, exclusive scan of the run counts over the bucket's aids (thread t: aids t * per .. + per)
-        uint32_t mine = 0;
-        for (uint32_t q = 0; q < per; ++q) {
-            const uint32_t i = threadIdx.x * per + q;
-            if (i < ab) {
-                const unsigned long long c64 = s_dyn[i];
-                if (x0 + i < a.n_aids) a.cnt64[x0 + i] = c64;
-                mine += (uint32_t)(c64 >> CNT_REC_BITS);
+        {   // exclusive scan of the tile's counters; the cursors move on by the counts (the copy below looks back from the new cursor)
+            uint32_t mine = 0;
+            for (uint32_t q = 0; q < per; ++q) {
+                const uint32_t i = threadIdx.x * per + q;
+                if (i < ab) mine += s_tf[i];
             }
-        }
-        uint32_t tot;
-        uint32_t run = block_excl_scan<uint32_t, BKT_THREADS>(mine, s_sc, &tot);
-        for (uint32_t q = 0; q < per; ++q) {
-            const uint32_t i = threadIdx.x * per + q;
-            if (i < ab) {
-                const uint32_t n = (uint32_t)(s_dyn[i] >> CNT_REC_BITS);
-                s_dyn[i] = e0 + run;
-                if (x0 + i < a.n_aids) run_start_out[x0 + i] = e0 + run;
-                run += n;
+            uint32_t tot;
+            uint32_t run = block_excl_scan<uint32_t, BKT_THREADS>(mine, s_sc, &tot);
+            for (uint32_t q = 0; q < per; ++q) {
+                const uint32_t i = threadIdx.x * per + q;
+                if (i < ab) {
+                    const uint32_t h = s_tf[i];
+                    s_tf[i] = run;
+                    s_pos[i] += h;
+                    run += h;
+                }
             }
+            if (threadIdx.x == 0) s_tf[ab] = n;
         }
-        if (b == a.nb - 1 && threadIdx.x == 0) run_start_out[a.n_aids] = e1;
         __syncthreads();
-        for (uint64_t i0 = e0 + threadIdx.x; i0 < e1; i0 += 4 * BKT_THREADS) {
-            uint64_t r[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint64_t i = i0 + (uint64_t)u * BKT_THREADS;
-                r[u] = i < e1 ? a.tmp[i] : ~0ull;
-            }
+        for (int u = 0; u < PER; ++u)
+            if ((uint32_t)u * BKT_THREADS + threadIdx.x < n) s_stage[s_tf[bkt_xlow(r[u])] + rk[u]] = r[u];
+        __syncthreads();
+        // the next tile's records are requested before this tile's stores go out
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (r[u] != ~0ull) a.sorted_desc[s_dyn[bkt_xlow(r[u])] + atomicAdd(&s_cur[bkt_xlow(r[u])], 1u)] = bkt_desc(r[u]);
+        for (int u = 0; u < PER; ++u) {
+            const uint64_t i = t0 + tile + (uint32_t)u * BKT_THREADS + threadIdx.x;
+            r[u] = (uint32_t)u * BKT_THREADS + threadIdx.x < tile && i < p1 ? a.tmp[i] : 0ull;
         }
+        // stage position p of aid i goes to cursor[i] - (end of i's piece in the stage - p): whole lines wherever pieces are long
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const uint32_t p = (uint32_t)u * BKT_THREADS + threadIdx.x;
+            if (p < n) {
+                const uint64_t rec = s_stage[p];
+                const uint32_t i = bkt_xlow(rec);
+                a.sorted_desc[s_pos[i] - (s_tf[i + 1] - p)] = bkt_desc(rec);
+            }
+        }
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < ab; i += BKT_THREADS) s_tf[i] = 0;
         __syncthreads();
     }
 }
@@ -3448,7 +3553,7 @@ struct otto_covis_ctx {
     int debug_skip = 0;
     // reduce scratch
     OwnedBuf part_y, part_w;
-    OwnedBuf bcount, bstart, tmp_runs;        // bucketed index
+    OwnedBuf bcount, bstart, tmp_runs, bpart_cnt, bpart_pos;   // bucketed index
     int bucket_index = 1;          // option "bucket_index": LDS-atomic index build (0 = global-atomic histogram)
     int s_wgs = 20;                // option "s_wgs": one-wave workgroups of the S bin per CU (A/B)
     int bkt_sh = 0;                // option "bkt_sh": log2 aids per index bucket (0 = from the aid space)
@@ -3754,9 +3859,9 @@ static int build_index(otto_covis_ctx* c, hipStream_t s) {
     BktArgs ba;
     memset(&ba, 0, sizeof ba);
     // ~1000 buckets where the aid space allows it (measured at OTTO shape, 2^21 aids: buckets of 2^10 / 2^11 / 2^12 / 2^13 aids ->
-    // index 2.95 / 3.05 / 3.1 / 3.3 ms: a bucket's runs (1 - 2 MB) should stay inside one XCD's L2 between the count walk, the
-    // place walk and its scattered 8-byte stores; the pieces a 16 k-run chunk sends to a bucket are still 16 - 18 runs long);
-    // buckets of at most 2^13 aids (the record's 13 bits, 96 KB of LDS in k_bkt_fused)
+    // index 2.95 / 3.05 / 3.1 / 3.3 ms with one store per run in the place walk; not swept again since the place walk stores
+    // tiles sorted by aid: fewer aids per bucket make its pieces longer, more buckets make the split's pieces shorter);
+    // buckets of at most 2^13 aids (the record's 13 bits, 64 KB of per-aid LDS arrays in k_bkt_count / k_bkt_place)
     ba.sh = aid_bits - 10 < 10 ? 10 : (aid_bits - 10 > BKT_MAX_SH ? BKT_MAX_SH : aid_bits - 10);
     if (c->bkt_sh >= 8 && c->bkt_sh <= BKT_MAX_SH) ba.sh = c->bkt_sh;                 // option "bkt_sh" (A/B)
     ba.nb = (uint32_t)(((uint64_t)n_aids + (1ull << ba.sh) - 1) >> ba.sh);
@@ -3773,7 +3878,7 @@ static int build_index(otto_covis_ctx* c, hipStream_t s) {
         ba.bcnt_blk = c->bcount.as<uint32_t>();
         ba.bscan = c->bstart.as<uint64_t>();
         ba.bstride = (uint32_t)sgrid;
-        kname(c, OTTO_COVIS_T_INDEX, "k_bkt_split<false/true> + k_bkt_fused + k_aid_totals + k_items_fill");
+        kname(c, OTTO_COVIS_T_INDEX, "k_bkt_split<false/true> + k_bkt_count/scan/place + k_aid_totals + k_items_fill");
         k_bkt_split<false><<<sgrid, BKT_THREADS, 0, s>>>(ba);
         OTTO_HIP(hipGetLastError());
         OTTO_TRY(device_scan(BktCount{ba.bcnt_blk}, n_cells, c->bstart.as<uint64_t>(), c->partial.as<uint64_t>(), s));
@@ -3783,12 +3888,30 @@ static int build_index(otto_covis_ctx* c, hipStream_t s) {
         k_bkt_split<true><<<sgrid, BKT_THREADS, 0, s>>>(ba);
         OTTO_HIP(hipGetLastError());
         ba.cnt64 = c->cnt64.as<uint64_t>();
-        const int lgrid = (int)(ba.nb < 256u * 2u ? ba.nb : 256u * 2u);
-        // the split left every bucket's runs contiguous: counting / scanning / placing is one launch
+        // the split left every bucket's runs contiguous: count, scan and place them by parts of buckets
+        // ... enough parts to fill the machine, but a part stays two tiles long on average (run slots bound the runs): its fixed
+        // cost -- a bucket's worth of counters written, cursors read -- stays small beside its walk
+        {
+            const uint64_t tiles_per_bkt = ((uint64_t)n_slots / ba.nb + bkt_tile(ba.sh) - 1) / bkt_tile(ba.sh);
+            const uint64_t by_work = (tiles_per_bkt + 1) / 2, by_grid = (BKT_WGS_TARGET + ba.nb - 1) / ba.nb;
+            const uint64_t parts = by_work < by_grid ? by_work : by_grid;
+            ba.parts = (uint32_t)(parts < 1 ? 1 : (parts > (uint64_t)BKT_MAX_PARTS ? BKT_MAX_PARTS : parts));
+        }
+        const size_t n_part_cells = ((size_t)ba.nb * ba.parts) << ba.sh;
+        OTTO_TRY(c->bpart_cnt.ensure(n_part_cells * 8, 0, s));
+        OTTO_TRY(c->bpart_pos.ensure(n_part_cells * 4, 0, s));
+        ba.part_cnt = c->bpart_cnt.as<unsigned long long>();
+        ba.part_pos = c->bpart_pos.as<uint32_t>();
         OTTO_TRY(c->sorted_desc.ensure((size_t)n_slots * 8, 0, s));
         ba.sorted_desc = c->sorted_desc.as<uint64_t>();
-        OTTO_HIP(hipFuncSetAttribute((const void*)k_bkt_fused, hipFuncAttributeMaxDynamicSharedMemorySize, 12 << BKT_MAX_SH));
-        k_bkt_fused<<<lgrid, BKT_THREADS, (size_t)12 << ba.sh, s>>>(ba, c->run_start.as<uint64_t>());
+        const int pgrid = (int)(ba.nb * ba.parts);
+        OTTO_HIP(hipFuncSetAttribute((const void*)k_bkt_count, hipFuncAttributeMaxDynamicSharedMemorySize, 8 << BKT_MAX_SH));
+        k_bkt_count<<<pgrid, BKT_THREADS, (size_t)8 << ba.sh, s>>>(ba);
+        OTTO_HIP(hipGetLastError());
+        k_bkt_scan<<<(int)ba.nb, BKT_THREADS, 0, s>>>(ba, c->run_start.as<uint64_t>());
+        OTTO_HIP(hipGetLastError());
+        OTTO_HIP(hipFuncSetAttribute((const void*)k_bkt_place, hipFuncAttributeMaxDynamicSharedMemorySize, BKT_LDS_BYTES));
+        k_bkt_place<<<pgrid, BKT_THREADS, bkt_place_lds(ba.sh), s>>>(ba);
         OTTO_HIP(hipGetLastError());
     } else if (n_slots) {
         const int grid = strided_grid(n_slots);
