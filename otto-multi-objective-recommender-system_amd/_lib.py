@@ -131,6 +131,13 @@ SIGNATURES = {
     'otto_inter_workspace': (_i64, [_u32]),
     'otto_inter_features': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _u32, _vp, _vp, _vp, _vp, _i64, _vp]),
     'otto_inter_features_rows': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # include/otto_feat.h
+    'otto_feat_aid_table_workspace': (_i64, [_i64, _u32]),
+    'otto_feat_aid_table': (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _u32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    'otto_feat_session_table_workspace': (_i64, [_i64]),
+    'otto_feat_session_table': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _u32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    'otto_feat_matrix_workspace': (_i64, [_i64]),
+    'otto_feat_matrix': (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _i32, _vp, _vp, _i64, _vp]),
     # include/otto_mf.h
     'otto_mf_create': (_i32, [C.POINTER(_vp), _i64, _i64, _i32, _i64, _i32]),
     'otto_mf_destroy': (None, [_vp]),

@@ -2,3 +2,5 @@
 covisitation lookup leaves on the device."""
 
 from .blend import blend_predictions, blend_topk, robust_scale  # noqa: E402,F401
+from .features import (AID_COLUMNS, SESSION_COLUMNS, aid_feature_table, feature_matrix, session_feature_table,  # noqa: E402,F401
+                       to_frames)
