@@ -173,6 +173,15 @@ SIGNATURES = {
     'otto_blend_join_workspace': (_i64, [_i64, _i32]),
     'otto_blend_join': (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _p_i64, C.POINTER(C.c_double),
                                C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _p_i64, _p_i64, _vp, _i64, _vp]),
+    # include/otto_eval.h
+    'otto_eval_last_click': (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    'otto_eval_cutoffs': (_i32, [_vp, _vp, _i64, C.c_uint64, _vp, _p_i64, _vp]),
+    'otto_eval_split_workspace': (_i64, [_i64, _i64]),
+    'otto_eval_split_count': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _p_i64, _vp, _i64, _vp]),
+    'otto_eval_split': (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                               _vp]),
+    'otto_eval_hits_workspace': (_i64, [_i64]),
+    'otto_eval_hits': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _p_i64, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -89,7 +89,7 @@ constexpr int WAVE = 64;
 // device and the caller's stream on every call. Not thread-safe, like the contexts: one slot per entry point family, calls
 // of one family on one device must not overlap.
 enum { SCRATCH_CAND = 0, SCRATCH_RECENCY, SCRATCH_RECENCY_PRED, SCRATCH_EVENTS, SCRATCH_PAIRS_A, SCRATCH_PAIRS_B, SCRATCH_FOREST,
-       SCRATCH_FOREST_TOPK, SCRATCH_BLEND, SCRATCH_SLOTS };
+       SCRATCH_FOREST_TOPK, SCRATCH_BLEND, SCRATCH_EVAL, SCRATCH_SLOTS };
 inline int device_scratch(int slot, size_t bytes, void** out, hipStream_t s) {
     static DevBuf bufs[16][SCRATCH_SLOTS];
     int dev = 0;
@@ -97,6 +97,14 @@ inline int device_scratch(int slot, size_t bytes, void** out, hipStream_t s) {
     const int rc = bufs[dev][slot].ensure(bytes < 256 ? 256 : bytes, 0, s);
     *out = bufs[dev][slot].p;
     return rc;
+}
+
+// keyed counter hash (splitmix64 finaliser): the BPR negative sampler and the validation cutoffs draw from it
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
 }
 
 __device__ __forceinline__ unsigned lane_id() { return threadIdx.x & 63u; }

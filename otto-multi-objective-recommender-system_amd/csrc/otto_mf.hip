@@ -464,13 +464,7 @@ __global__ __launch_bounds__(256) void k_dpa_adam(DpApplyArgs a) {
 // ---------------------------------------------------------------------------
 // BPR
 // ---------------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
+// mix64: the keyed counter hash of common.h
 // negative item for global row `row`: uniform over [0, n_items) (multiply-high of 32 random bits),
 // redrawn (attempt 0..15) while equal to the positive; falls back to (pos + 1) % n_items
 __host__ __device__ __forceinline__ int64_t bpr_negative(uint64_t seed, uint64_t epoch, uint64_t row, int64_t pos,

@@ -1,6 +1,7 @@
 """Callers on the candidate side of the hot path (SURVEY.md section 8 f): feature engineering over the candidate arrays the
 covisitation lookup leaves on the device."""
 
+from . import evaluate  # noqa: E402,F401
 from .blend import blend_predictions, blend_topk, robust_scale  # noqa: E402,F401
 from .features import (AID_COLUMNS, SESSION_COLUMNS, aid_feature_table, feature_matrix, session_feature_table,  # noqa: E402,F401
                        to_frames)
