@@ -182,6 +182,19 @@ SIGNATURES = {
                                _vp]),
     'otto_eval_hits_workspace': (_i64, [_i64]),
     'otto_eval_hits': (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _p_i64, _vp, _i64, _vp]),
+    # include/otto_gbdt.h
+    'otto_gbdt_workspace_bytes': (_i64, [_i64, _i32, _i32]),
+    'otto_gbdt_bin': (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    'otto_gbdt_lambdarank': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, _vp, C.c_double, _i32, _i32, _vp, _vp,
+                                    _vp]),
+    'otto_gbdt_quantize': (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    'otto_gbdt_hist': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),
+    'otto_gbdt_best_split': (_i32, [_vp, _i32, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    'otto_gbdt_partition': (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    'otto_gbdt_add_tree': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'otto_gbdt_ap_at_k': (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+    'otto_gbdt_grow_tree': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

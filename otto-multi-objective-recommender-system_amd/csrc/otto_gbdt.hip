@@ -1,0 +1,936 @@
+// LambdaRank gradient-boosted tree training (SPEC-GBDT; include/otto_gbdt.h).
+//
+// Device, on the caller's stream:
+//   k_bin          a tile of 256 rows x 32 features goes through LDS: X is read along its rows, the bins are written
+//                  along theirs (uint8 [F, n]); one binary search over the feature's edges per value.
+//   k_lambdarank   one workgroup per query. Rank of a row = number of rows that order before it (broadcast LDS reads,
+//                  no sort network: cnt <= 1024), then one thread per rank adds that row's pairs in ascending rank of
+//                  the partner, in float64 with contraction off. Both rows of a pair compute the same lambda and eta.
+//   k_ap           the same ranking; one thread adds the precision terms in rank order.
+//   k_absmax, k_quantize   exact max reductions (atomicMax on the bits of a non-negative double), then q = rint(v * 2^e).
+//   k_hist         the hot path. grid = (row chunks, groups of 8 features). A workgroup keeps private int64 sums of qg and
+//                  qh and uint32 row counts for 8 features x 256 bins in LDS (40 KB) and adds with integer LDS atomics;
+//                  a row's (qg, qh) pair is one 8-byte load, its 8 bin bytes come from 8 feature rows of the feature-major
+//                  matrix, where ascending row ids (the partition is stable) keep a wave's loads in few lines. One
+//                  integer global atomic per touched (feature, bin, plane) and workgroup merges the result.
+//   k_hist_sub     larger child = parent - smaller child, in integers.
+//   k_best_split   one workgroup per leaf, one wave per feature in turn, 4 bins per lane: int64 prefix sums along the
+//                  bins, both NaN variants per edge, float64 gain in the pinned operation order, then a reduction under
+//                  the pinned tie order.
+//   k_part_count, k_part_scan, k_part_scatter   stable partition of a leaf's row list: left rows per 2048-row block, one
+//                  workgroup's exclusive scan of those counts, then the scatter.
+//   k_add_tree     one lane per row walks the tree over the bins; bounded, range-checked.
+// Host: otto_gbdt_grow_tree drives the leaf-wise loop: one small device-to-host copy per split.
+#include "common.h"
+#include "../../include/otto_covis.h"
+#include "../../include/otto_forest.h"
+#include "../../include/otto_gbdt.h"
+
+#include <math.h>
+#include <string.h>
+
+#include <cmath>
+#include <vector>
+
+namespace otto {
+namespace {
+
+constexpr int MAXQ = OTTO_GBDT_MAX_QUERY;
+constexpr int HIST_FG = 8;          // features per histogram workgroup
+constexpr int HIST_THREADS = 256;
+constexpr int PART_ROWS = 2048;     // rows per partition workgroup
+constexpr int SW = OTTO_GBDT_SPLIT_WORDS;
+// error words of a call
+constexpr int ERR_QUERY = 0, ERR_LABEL = 1, ERR_ROW = 2, ERR_WALK = 3, ERR_WORDS = 4;
+
+// order-preserving image of a score: larger = better; every NaN -> 1, below -inf; -0.0 = +0.0 (as otto_forest.hip)
+__device__ __forceinline__ uint64_t score_key(double x) {
+    if (x != x) return 1ull;
+    const uint64_t b = x == 0.0 ? 0ull : (uint64_t)__double_as_longlong(x);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// binning
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_bin(const float* X, int64_t ld, int64_t n, int F, const float* edges, const int32_t* n_edges,
+                                             uint8_t* bins) {
+    __shared__ float tile[256][33];
+    const int tid = threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * 256;
+    const int rows_here = (int)(n - row0 < 256 ? n - row0 : 256);
+    for (int f0 = 0; f0 < F; f0 += 32) {
+        const int nf = F - f0 < 32 ? F - f0 : 32;
+        // 8 rows x 32 columns per pass: a wave reads two rows' 128-byte runs
+        for (int r = tid >> 5; r < rows_here; r += 8) {
+            const int c = tid & 31;
+            if (c < nf) tile[r][c] = X[(row0 + r) * ld + f0 + c];
+        }
+        __syncthreads();
+        if (tid < rows_here) {
+            for (int c = 0; c < nf; ++c) {
+                const float x = tile[tid][c];
+                const float* e = edges + (int64_t)(f0 + c) * OTTO_GBDT_MAX_EDGES;
+                int lo = 0, hi = n_edges[f0 + c];
+                hi = hi < 0 ? 0 : (hi > OTTO_GBDT_MAX_EDGES ? OTTO_GBDT_MAX_EDGES : hi);
+                while (lo < hi) {                       // the number of edges < x
+                    const int mid = (lo + hi) >> 1;
+                    if (e[mid] < x) lo = mid + 1; else hi = mid;
+                }
+                bins[(int64_t)(f0 + c) * n + row0 + tid] = x != x ? (uint8_t)OTTO_GBDT_NAN_BIN : (uint8_t)lo;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// per-query ranking, shared by the objective and AP@k
+// ---------------------------------------------------------------------------------------------------------------------
+struct QueryLds {
+    uint64_t key[MAXQ];       // by position
+    double score[MAXQ];       // by rank
+    double disc[MAXQ];        // discount[r] (objective only)
+    uint16_t pos[MAXQ];       // by rank: the row's position in the query
+    uint8_t label[MAXQ];      // by rank
+    uint32_t lcnt[OTTO_GBDT_MAX_LABEL + 1];
+    double red[16];
+    double inv_max_dcg, factor;
+};
+
+// false (and the error word counted) for a query the spec refuses
+__device__ __forceinline__ bool query_range(const int64_t* query_off, int64_t q, int64_t n, int64_t* lo, int* cnt, uint32_t* err) {
+    const int64_t a = query_off[q], b = query_off[q + 1];
+    if (!(a >= 0 && a <= b && b <= n && b - a <= MAXQ)) {
+        if (threadIdx.x == 0) atomicAdd(err + ERR_QUERY, 1u);
+        return false;
+    }
+    *lo = a;
+    *cnt = (int)(b - a);
+    return true;
+}
+
+// fills s.score / s.pos / s.label by rank and s.lcnt; ends with a barrier
+__device__ __forceinline__ void rank_query(QueryLds& s, const double* score, const int32_t* label, int64_t lo, int cnt, uint32_t* err) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    for (int p = tid; p < cnt; p += nt) s.key[p] = score_key(score[lo + p]);
+    if (tid <= OTTO_GBDT_MAX_LABEL) s.lcnt[tid] = 0;
+    __syncthreads();
+    for (int p = tid; p < cnt; p += nt) {
+        const uint64_t k = s.key[p];
+        int r = 0;
+        for (int o = 0; o < cnt; ++o) {
+            const uint64_t ko = s.key[o];
+            r += (ko > k || (ko == k && o < p)) ? 1 : 0;
+        }
+        int lab = label[lo + p];
+        if (lab < 0 || lab > OTTO_GBDT_MAX_LABEL) {
+            atomicOr(err + ERR_LABEL, 1u);
+            lab = lab < 0 ? 0 : OTTO_GBDT_MAX_LABEL;
+        }
+        s.score[r] = score[lo + p];
+        s.pos[r] = (uint16_t)p;
+        s.label[r] = (uint8_t)lab;
+        atomicAdd(&s.lcnt[lab], 1u);
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ double label_gain(int lab) { return (double)((1u << lab) - 1u); }
+
+struct LambdaArgs {
+    const double* score;
+    const int32_t* label;
+    const int64_t* query_off;
+    int64_t Q, n;
+    const double* sigmoid;
+    double sig_lo, sig_factor;
+    const double* discount;
+    double sigma;
+    int T, norm;
+    double* grad;
+    double* hess;
+    uint32_t* err;
+};
+
+__global__ __launch_bounds__(256) void k_lambdarank(LambdaArgs a) {
+#pragma clang fp contract(off)
+    __shared__ QueryLds s;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    int64_t lo;
+    int cnt;
+    if (!query_range(a.query_off, blockIdx.x, a.n, &lo, &cnt, a.err)) return;   // grad / hess were zeroed
+    if (cnt == 0) return;
+    rank_query(s, a.score, a.label, lo, cnt, a.err);
+    for (int r = tid; r < cnt; r += nt) s.disc[r] = a.discount[r];
+    if (tid == 0) {
+        double sum = 0.0;
+        int r = 0;
+        for (int lab = OTTO_GBDT_MAX_LABEL; lab >= 0 && r < a.T; --lab) {
+            const double g = label_gain(lab);
+            for (uint32_t c = 0; c < s.lcnt[lab] && r < a.T; ++c, ++r) sum = sum + g * a.discount[r];
+        }
+        s.inv_max_dcg = sum > 0.0 ? 1.0 / sum : 0.0;
+    }
+    __syncthreads();
+    const int Tq = a.T < cnt ? a.T : cnt;
+    const double inv = s.inv_max_dcg;
+    const bool scale = a.norm && s.score[0] != s.score[cnt - 1];
+    const double neg_sigma = -a.sigma, sigma2 = a.sigma * a.sigma, top = (double)(OTTO_GBDT_SIGMOID_BINS - 1);
+    double part = 0.0;                                  // this thread's share of S = sum of -2 lambda
+    for (int r = tid; r < cnt; r += nt) {
+        const int lr = s.label[r];
+        const double sr = s.score[r], dr = s.disc[r], gr = label_gain(lr);
+        double g = 0.0, h = 0.0;
+        auto pair = [&](int o) {
+#pragma clang fp contract(off)
+            const int lo_ = s.label[o];
+            if (lo_ == lr) return;
+            const bool high = lr > lo_;
+            const double so = s.score[o];
+            const double d = high ? sr - so : so - sr;
+            const double go = label_gain(lo_);
+            const double dd = fabs(dr - s.disc[o]);
+            double delta = (high ? gr - go : go - gr) * dd * inv;
+            if (scale) delta = delta / (0.01 + fabs(d));
+            double x = (d - a.sig_lo) * a.sig_factor;
+            x = x > 0.0 ? x : 0.0;                      // NaN -> 0
+            x = x < top ? x : top;
+            const double p = a.sigmoid[(size_t)x];
+            const double lam = neg_sigma * delta * p;
+            const double eta = sigma2 * delta * p * (1.0 - p);
+            g = high ? g + lam : g - lam;
+            h = h + eta;
+            if (o > r) part = part + -2.0 * lam;        // each pair once, from its i side
+        };
+        const int first_end = r < Tq ? r : Tq;
+        for (int o = 0; o < first_end; ++o) pair(o);    // partners i < min(r, Tq): this row is the pair's j
+        if (r < Tq)
+            for (int o = r + 1; o < cnt; ++o) pair(o);  // partners j > r: this row is the pair's i
+        const int64_t row = lo + s.pos[r];
+        a.grad[row] = g;
+        a.hess[row] = h;
+    }
+    if (!a.norm) return;
+    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);   // S in any order: the spec does not pin it
+    if ((tid & 63) == 0) s.red[tid >> 6] = part;
+    __syncthreads();
+    if (tid == 0) {
+        double S = 0.0;
+        for (int w = 0; w < (nt + 63) / 64; ++w) S += s.red[w];
+        s.factor = S > 0.0 ? log2(1.0 + S) / S : 1.0;
+    }
+    __syncthreads();
+    const double f = s.factor;
+    if (f != 1.0)
+        for (int r = tid; r < cnt; r += nt) {           // each thread rescales the rows it wrote itself
+            const int64_t row = lo + s.pos[r];
+            a.grad[row] = a.grad[row] * f;
+            a.hess[row] = a.hess[row] * f;
+        }
+}
+
+__global__ __launch_bounds__(256) void k_ap(const double* score, const int32_t* label, const int64_t* query_off, int64_t n, int k,
+                                            double* ap, uint32_t* err) {
+#pragma clang fp contract(off)
+    __shared__ QueryLds s;
+    int64_t lo;
+    int cnt;
+    if (!query_range(query_off, blockIdx.x, n, &lo, &cnt, err)) {
+        if (threadIdx.x == 0) ap[blockIdx.x] = -1.0;
+        return;
+    }
+    if (cnt > 0) rank_query(s, score, label, lo, cnt, err);
+    if (threadIdx.x == 0) {
+        int64_t n_pos = 0;
+        if (cnt > 0)
+            for (int lab = 1; lab <= OTTO_GBDT_MAX_LABEL; ++lab) n_pos += s.lcnt[lab];
+        double sum = 0.0;
+        int hits = 0;
+        const int top = k < cnt ? k : cnt;
+        for (int r = 0; r < top; ++r)
+            if (s.label[r] > 0) {
+                ++hits;
+                sum = sum + (double)hits / (double)(r + 1);
+            }
+        ap[blockIdx.x] = n_pos > 0 ? sum / (double)(n_pos < k ? n_pos : k) : -1.0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// quantisation
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_absmax(const double* grad, const double* hess, int64_t n, unsigned long long* mx) {
+    double mg = 0.0, mh = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const double g = fabs(grad[i]), h = hess[i];
+        mg = g > mg ? g : mg;                           // NaN never wins
+        mh = h > mh ? h : mh;
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double og = __shfl_xor(mg, d, 64), oh = __shfl_xor(mh, d, 64);
+        mg = og > mg ? og : mg;
+        mh = oh > mh ? oh : mh;
+    }
+    if (lane_id() == 0) {                               // the bits of non-negative doubles order like the values
+        atomicMax(mx + 0, (unsigned long long)__double_as_longlong(mg));
+        atomicMax(mx + 1, (unsigned long long)__double_as_longlong(mh));
+    }
+}
+
+__device__ __forceinline__ int quant_exp(double m) {
+    if (!(m > 0.0)) return 0;
+    int x;
+    (void)frexp(m, &x);
+    return 30 - x;
+}
+
+__global__ __launch_bounds__(256) void k_quantize(const double* grad, const double* hess, int64_t n, const unsigned long long* mx,
+                                                  int2* gh, int32_t* exps) {
+    const double mg = __longlong_as_double((long long)mx[0]), mh = __longlong_as_double((long long)mx[1]);
+    const int eg = quant_exp(mg), eh = quant_exp(mh);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { exps[0] = eg; exps[1] = eh; }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        int2 q;
+        q.x = mg > 0.0 ? (int)rint(ldexp(grad[i], eg)) : 0;
+        q.y = mh > 0.0 ? (int)rint(ldexp(hess[i], eh)) : 0;
+        gh[i] = q;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// histogram
+// ---------------------------------------------------------------------------------------------------------------------
+// rows == nullptr: the rows are 0 .. n_rows - 1 (the root)
+__global__ __launch_bounds__(HIST_THREADS) void k_hist(const uint8_t* bins, int64_t n, int F, const int2* gh, const int32_t* rows,
+                                                       int64_t n_rows, int64_t chunk, unsigned long long* hist, uint32_t* err) {
+    __shared__ unsigned long long sg[HIST_FG * 256];
+    __shared__ unsigned long long sh[HIST_FG * 256];
+    __shared__ uint32_t sc[HIST_FG * 256];
+    const int tid = threadIdx.x;
+    const int f0 = blockIdx.y * HIST_FG;
+    const int nf = F - f0 < HIST_FG ? F - f0 : HIST_FG;
+    for (int j = tid; j < HIST_FG * 256; j += HIST_THREADS) { sg[j] = 0; sh[j] = 0; sc[j] = 0; }
+    __syncthreads();
+    const int64_t i0 = (int64_t)blockIdx.x * chunk;
+    const int64_t i1 = i0 + chunk < n_rows ? i0 + chunk : n_rows;
+    const uint8_t* col = bins + (int64_t)f0 * n;
+    bool bad = false;
+    for (int64_t i = i0 + tid; i < i1; i += HIST_THREADS) {
+        const int64_t rid = rows ? (int64_t)rows[i] : i;
+        if (rid < 0 || rid >= n) { bad = true; continue; }
+        const int2 q = gh[rid];
+        uint32_t b[HIST_FG];
+#pragma unroll
+        for (int f = 0; f < HIST_FG; ++f) b[f] = f < nf ? col[(int64_t)f * n + rid] : 0u;
+        const unsigned long long qg = (unsigned long long)(long long)q.x, qh = (unsigned long long)(long long)q.y;
+#pragma unroll
+        for (int f = 0; f < HIST_FG; ++f)
+            if (f < nf) {
+                const int j = f * 256 + (int)b[f];
+                atomicAdd(&sg[j], qg);
+                atomicAdd(&sh[j], qh);
+                atomicAdd(&sc[j], 1u);
+            }
+    }
+    if (bad) atomicOr(err + ERR_ROW, 1u);
+    __syncthreads();
+    const int64_t plane = (int64_t)F * 256;
+    unsigned long long* out = hist + (int64_t)f0 * 256;
+    for (int j = tid; j < nf * 256; j += HIST_THREADS) {
+        const uint32_t c = sc[j];
+        if (c) {
+            atomicAdd(out + j, sg[j]);
+            atomicAdd(out + plane + j, sh[j]);
+            atomicAdd(out + 2 * plane + j, (unsigned long long)c);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_hist_sub(int64_t* parent, const int64_t* small, int64_t words) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < words) parent[i] -= small[i];
+}
+
+int launch_hist(const uint8_t* bins, int64_t n, int F, const int32_t* gh, const int32_t* rows, int64_t n_rows, int64_t* hist,
+                uint32_t* err, hipStream_t s) {
+    OTTO_HIP(hipMemsetAsync(hist, 0, (size_t)3 * F * 256 * 8, s));
+    if (n_rows == 0) return 0;
+    // about 512 chunks for a large leaf; never below 2048 rows, so that the 6144 merge atomics of a workgroup stay small
+    // beside its LDS work
+    int64_t chunk = (n_rows + 511) / 512;
+    chunk = chunk < 2048 ? 2048 : (chunk + HIST_THREADS - 1) / HIST_THREADS * HIST_THREADS;
+    const dim3 grid((unsigned)((n_rows + chunk - 1) / chunk), (unsigned)((F + HIST_FG - 1) / HIST_FG));
+    k_hist<<<grid, HIST_THREADS, 0, s>>>(bins, n, F, (const int2*)gh, rows, n_rows, chunk, (unsigned long long*)hist, err);
+    OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// split search
+// ---------------------------------------------------------------------------------------------------------------------
+struct SplitParams {
+    int64_t min_data;
+    double min_hess, l2, min_gain;
+};
+struct SplitJobs {
+    const int64_t* hist[2];
+    int64_t* out[2];
+};
+struct Cand {
+    double gain;
+    int32_t found, f, b, dl;
+    int64_t cntL, gL, hL;
+};
+
+__device__ __forceinline__ bool cand_better(const Cand& a, const Cand& b) {
+    if (!a.found || !b.found) return a.found && !b.found;
+    if (a.gain != b.gain) return a.gain > b.gain;
+    if (a.f != b.f) return a.f < b.f;
+    if (a.b != b.b) return a.b < b.b;
+    return a.dl < b.dl;
+}
+
+__device__ __forceinline__ void cand_try(Cand& best, int f, int b, int dl, int64_t gL, int64_t hL, int64_t cL, int64_t gP, int64_t hP,
+                                         int64_t cP, int eg, int eh, const SplitParams& p) {
+#pragma clang fp contract(off)
+    const int64_t cR = cP - cL, gR = gP - gL, hR = hP - hL;
+    if (cL < p.min_data || cR < p.min_data) return;
+    const double GL = ldexp((double)gL, -eg), HL = ldexp((double)hL, -eh);
+    const double GR = ldexp((double)gR, -eg), HR = ldexp((double)hR, -eh);
+    if (HL < p.min_hess || HR < p.min_hess) return;
+    const double GP = ldexp((double)gP, -eg), HP = ldexp((double)hP, -eh);
+    const double tl = GL * GL / (HL + p.l2);
+    const double tr = GR * GR / (HR + p.l2);
+    const double tp = GP * GP / (HP + p.l2);
+    const double gain = (tl + tr) - tp;
+    if (!(gain > p.min_gain)) return;
+    Cand c;
+    c.gain = gain; c.found = 1; c.f = f; c.b = b; c.dl = dl; c.cntL = cL; c.gL = gL; c.hL = hL;
+    if (cand_better(c, best)) best = c;
+}
+
+__device__ __forceinline__ int64_t shfl64(int64_t v, int src) { return (int64_t)__shfl((long long)v, src, 64); }
+
+__global__ __launch_bounds__(256) void k_best_split(SplitJobs jobs, int F, const int32_t* n_edges, const int32_t* exps, SplitParams p) {
+    __shared__ Cand s_best[4];
+    const int64_t* hist = jobs.hist[blockIdx.x];
+    int64_t* out = jobs.out[blockIdx.x];
+    const int l = (int)lane_id(), w = threadIdx.x >> 6;
+    const int64_t plane = (int64_t)F * 256;
+    const int eg = exps[0], eh = exps[1];
+    // the parent's sums: all 256 bins of feature 0
+    int64_t gP = 0, hP = 0, cP = 0;
+    for (int e = 0; e < 4; ++e) {
+        gP += hist[l * 4 + e];
+        hP += hist[plane + l * 4 + e];
+        cP += hist[2 * plane + l * 4 + e];
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        gP += (int64_t)__shfl_xor((long long)gP, d, 64);
+        hP += (int64_t)__shfl_xor((long long)hP, d, 64);
+        cP += (int64_t)__shfl_xor((long long)cP, d, 64);
+    }
+    Cand best;
+    best.found = 0; best.gain = 0.0; best.f = best.b = best.dl = 0; best.cntL = best.gL = best.hL = 0;
+    for (int f = w; f < F; f += 4) {
+        const int64_t* hf = hist + (int64_t)f * 256 + l * 4;
+        int64_t g[4], h[4], c[4];
+        for (int e = 0; e < 4; ++e) { g[e] = hf[e]; h[e] = hf[plane + e]; c[e] = hf[2 * plane + e]; }
+        for (int e = 1; e < 4; ++e) { g[e] += g[e - 1]; h[e] += h[e - 1]; c[e] += c[e - 1]; }
+        const int64_t og = wave_incl_scan<int64_t>(g[3]) - g[3], oh = wave_incl_scan<int64_t>(h[3]) - h[3],
+                      oc = wave_incl_scan<int64_t>(c[3]) - c[3];
+        // bin 255 alone: lane 63's last element minus the one before it
+        const int64_t ng = shfl64(g[3] - g[2], 63), nh = shfl64(h[3] - h[2], 63), nc = shfl64(c[3] - c[2], 63);
+        int ne = n_edges[f];
+        ne = ne < 0 ? 0 : (ne > OTTO_GBDT_MAX_EDGES ? OTTO_GBDT_MAX_EDGES : ne);
+        for (int e = 0; e < 4; ++e) {
+            const int b = l * 4 + e;
+            if (b >= ne) break;
+            const int64_t gL = og + g[e], hL = oh + h[e], cL = oc + c[e];
+            cand_try(best, f, b, 0, gL, hL, cL, gP, hP, cP, eg, eh, p);
+            cand_try(best, f, b, 1, gL + ng, hL + nh, cL + nc, gP, hP, cP, eg, eh, p);
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        Cand o;
+        o.gain = __shfl_xor(best.gain, d, 64);
+        o.found = __shfl_xor(best.found, d, 64);
+        o.f = __shfl_xor(best.f, d, 64);
+        o.b = __shfl_xor(best.b, d, 64);
+        o.dl = __shfl_xor(best.dl, d, 64);
+        o.cntL = (int64_t)__shfl_xor((long long)best.cntL, d, 64);
+        o.gL = (int64_t)__shfl_xor((long long)best.gL, d, 64);
+        o.hL = (int64_t)__shfl_xor((long long)best.hL, d, 64);
+        if (cand_better(o, best)) best = o;
+    }
+    if (l == 0) s_best[w] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < 4; ++i)
+            if (cand_better(s_best[i], best)) best = s_best[i];
+        out[0] = best.found;
+        out[1] = best.f;
+        out[2] = best.b;
+        out[3] = best.dl;
+        out[4] = (int64_t)__double_as_longlong(best.gain);
+        out[5] = best.cntL;
+        out[6] = best.gL;
+        out[7] = best.hL;
+        out[8] = cP;
+        out[9] = gP;
+        out[10] = hP;
+        out[11] = 0;
+    }
+}
+
+int check_split_params(int64_t min_data, double min_hess, double l2, double min_gain) {
+    OTTO_REQUIRE(min_data >= 0, "min_data_in_leaf = %lld", (long long)min_data);
+    OTTO_REQUIRE(min_hess >= 0.0 && l2 >= 0.0 && min_gain == min_gain, "min_sum_hessian_in_leaf = %g, lambda_l2 = %g, "
+                 "min_gain_to_split = %g", min_hess, l2, min_gain);
+    OTTO_REQUIRE(min_hess + l2 > 0.0, "min_sum_hessian_in_leaf + lambda_l2 must be positive (a leaf value divides by H + lambda_l2)");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// stable partition
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool goes_left(uint32_t bin, int split_bin, int default_left) {
+    return bin == OTTO_GBDT_NAN_BIN ? default_left != 0 : (int)bin <= split_bin;
+}
+
+// rows == nullptr: the rows are 0 .. n_rows - 1; a row id outside [0, n) goes right unread
+__global__ __launch_bounds__(256) void k_part_count(const uint8_t* col, int64_t n, int split_bin, int default_left, const int32_t* rows,
+                                                    int64_t n_rows, uint32_t* block_left, uint32_t* err) {
+    __shared__ uint32_t s_n;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    const int64_t i0 = (int64_t)blockIdx.x * PART_ROWS;
+    uint32_t mine = 0;
+    for (int e = 0; e < PART_ROWS / 256; ++e) {
+        const int64_t i = i0 + e * 256 + threadIdx.x;
+        if (i < n_rows) {
+            const int64_t rid = rows ? (int64_t)rows[i] : i;
+            if (rid < 0 || rid >= n) atomicOr(err + ERR_ROW, 1u);
+            else mine += goes_left(col[rid], split_bin, default_left) ? 1u : 0u;
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
+    if (lane_id() == 0) atomicAdd(&s_n, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) block_left[blockIdx.x] = s_n;
+}
+
+// one workgroup: block_left becomes its own exclusive prefix sum (below 2^31, as n is), the total goes to n_left_out
+__global__ __launch_bounds__(256) void k_part_scan(uint32_t* block_left, uint32_t n_blocks, int64_t* n_left_out) {
+    __shared__ uint32_t smem[8];
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < n_blocks; b0 += 256) {
+        const uint32_t b = b0 + threadIdx.x;
+        const uint32_t c = b < n_blocks ? block_left[b] : 0u;
+        uint32_t tile;
+        const uint32_t ex = block_excl_scan<uint32_t, 256>(c, smem, &tile);
+        if (b < n_blocks) block_left[b] = carry + ex;
+        carry += tile;
+    }
+    if (threadIdx.x == 0) *n_left_out = (int64_t)carry;
+}
+
+__global__ __launch_bounds__(256) void k_part_scatter(const uint8_t* col, int64_t n, int split_bin, int default_left, const int32_t* rows,
+                                                      int64_t n_rows, const uint32_t* block_before, const int64_t* n_left, int32_t* out) {
+    __shared__ uint32_t smem[8];
+    const int64_t before = block_before[blockIdx.x], total = *n_left;   // left rows in front of this block, and in all
+    const int64_t i0 = (int64_t)blockIdx.x * PART_ROWS;
+    int64_t left_at = before, right_at = total + (i0 - before);
+    for (int e = 0; e < PART_ROWS / 256; ++e) {
+        const int64_t i = i0 + e * 256 + threadIdx.x;
+        int32_t rid = 0;
+        uint32_t left = 0;
+        const bool live = i < n_rows;
+        if (live) {
+            rid = rows ? rows[i] : (int32_t)i;
+            left = (rid >= 0 && rid < n && goes_left(col[rid], split_bin, default_left)) ? 1u : 0u;
+        }
+        uint32_t n_l;
+        const uint32_t ex = block_excl_scan<uint32_t, 256>(left, smem, &n_l);
+        if (live) {
+            if (left) out[left_at + ex] = rid;
+            else out[right_at + (threadIdx.x - ex)] = rid;
+        }
+        const int64_t live_here = n_rows - (i0 + e * 256) < 256 ? n_rows - (i0 + e * 256) : 256;
+        left_at += n_l;
+        right_at += (live_here > 0 ? live_here : 0) - n_l;
+    }
+}
+
+int64_t part_blocks(int64_t n_rows) { return (n_rows + PART_ROWS - 1) / PART_ROWS; }
+
+int launch_partition(const uint8_t* bins, int64_t n, int feature, int bin, int default_left, const int32_t* rows, int64_t n_rows,
+                     int32_t* out, int64_t* n_left, uint32_t* block_left, uint32_t* err, hipStream_t s) {
+    const unsigned nb = (unsigned)part_blocks(n_rows);
+    const uint8_t* col = bins + (int64_t)feature * n;
+    k_part_count<<<nb, 256, 0, s>>>(col, n, bin, default_left, rows, n_rows, block_left, err);
+    OTTO_HIP(hipGetLastError());
+    k_part_scan<<<1, 256, 0, s>>>(block_left, nb, n_left);
+    OTTO_HIP(hipGetLastError());
+    k_part_scatter<<<nb, 256, 0, s>>>(col, n, bin, default_left, rows, n_rows, block_left, n_left, out);
+    OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// score update
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_add_tree(const uint8_t* bins, int64_t n, int F, int L, const int32_t* sf, const int32_t* sb,
+                                                  const int32_t* dl, const int32_t* lc, const int32_t* rc, const double* lv,
+                                                  double* score, int32_t* leaf_out, uint32_t* err) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    int c = L > 1 ? 0 : -1;
+    for (int step = 0; step < L - 1 && c >= 0; ++step) {
+        if (c >= L - 1) break;
+        const int f = sf[c];
+        if (f < 0 || f >= F) break;
+        c = goes_left(bins[(int64_t)f * n + r], sb[c], dl[c]) ? lc[c] : rc[c];
+    }
+    const int leaf = ~c;
+    if (c >= 0 || leaf >= L) {
+        atomicOr(err + ERR_WALK, 1u);
+        return;
+    }
+    score[r] += lv[leaf];
+    if (leaf_out) leaf_out[r] = leaf;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host helpers
+// ---------------------------------------------------------------------------------------------------------------------
+int err_begin(uint32_t** err, hipStream_t s) {
+    void* scratch = nullptr;
+    OTTO_TRY(device_scratch(SCRATCH_GBDT, 256, &scratch, s));
+    *err = (uint32_t*)scratch;
+    OTTO_HIP(hipMemsetAsync(scratch, 0, 64, s));
+    return 0;
+}
+
+// drains the stream and turns the error words into a return code
+int err_end(uint32_t* err, hipStream_t s) {
+    uint32_t bad[ERR_WORDS] = {0, 0, 0, 0};
+    OTTO_HIP(hipMemcpyAsync(bad, err, sizeof(bad), hipMemcpyDeviceToHost, s));
+    OTTO_HIP(hipStreamSynchronize(s));
+    if (bad[ERR_QUERY]) {
+        set_error("%u quer%s with query_off not in 0 <= query_off[q] <= query_off[q+1] <= n or with more than %d rows: left "
+                  "zero", bad[ERR_QUERY], bad[ERR_QUERY] == 1 ? "y" : "ies", MAXQ);
+        return OTTO_EINVAL;
+    }
+    if (bad[ERR_LABEL]) {
+        set_error("a label outside 0..%d", OTTO_GBDT_MAX_LABEL);
+        return OTTO_EINVAL;
+    }
+    if (bad[ERR_ROW]) {
+        set_error("a row id outside [0, n) in a leaf's row list: skipped");
+        return OTTO_EINVAL;
+    }
+    if (bad[ERR_WALK]) {
+        set_error("a tree walk did not reach a leaf of its tree within n_leaves - 1 steps, or read a feature outside [0, F)");
+        return OTTO_EINVAL;
+    }
+    return 0;
+}
+
+int check_bins_args(const uint8_t* d_bins, int64_t n, int32_t F) {
+    OTTO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "n = %lld outside [0, 2^31)", (long long)n);
+    OTTO_REQUIRE(F >= 1 && F <= OTTO_FOREST_MAX_FEATURES, "F must be in [1, %d] (got %d)", OTTO_FOREST_MAX_FEATURES, F);
+    OTTO_REQUIRE(d_bins || n == 0, "null d_bins");
+    return 0;
+}
+
+int check_query_args(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n) {
+    OTTO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "n = %lld outside [0, 2^31)", (long long)n);
+    OTTO_REQUIRE(Q >= 0 && Q < ((int64_t)1 << 31), "Q = %lld outside [0, 2^31)", (long long)Q);
+    OTTO_REQUIRE(d_query_off || Q == 0, "null d_query_off");
+    OTTO_REQUIRE((d_score && d_label) || n == 0, "null d_score or d_label");
+    return 0;
+}
+
+int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+
+struct WorkLayout {
+    int64_t rows_a, rows_b, block_left, n_left, split, hist, total;
+};
+WorkLayout work_layout(int64_t n, int32_t F, int32_t num_leaves) {
+    WorkLayout w;
+    int64_t at = 0;
+    w.rows_a = at; at += align256(n * 4);
+    w.rows_b = at; at += align256(n * 4);
+    w.block_left = at; at += align256(part_blocks(n) * 4);
+    w.n_left = at; at += 256;
+    w.split = at; at += align256((int64_t)2 * SW * 8);
+    w.hist = at; at += (int64_t)num_leaves * 3 * F * 256 * 8;
+    w.total = at;
+    return w;
+}
+
+}  // namespace
+}  // namespace otto
+
+using namespace otto;
+
+extern "C" int64_t otto_gbdt_workspace_bytes(int64_t n, int32_t F, int32_t num_leaves) {
+    if (n < 0 || n >= ((int64_t)1 << 31) || F < 1 || F > OTTO_FOREST_MAX_FEATURES || num_leaves < 1 ||
+        num_leaves > OTTO_FOREST_MAX_LEAVES)
+        return 0;
+    return work_layout(n, F, num_leaves).total;
+}
+
+extern "C" int otto_gbdt_bin(const float* d_X, int64_t ld, int64_t n, int32_t F, const float* d_edges, const int32_t* d_n_edges,
+                             uint8_t* d_bins, void* stream) {
+    OTTO_TRY(check_bins_args(d_bins, n, F));
+    OTTO_REQUIRE(ld >= F, "row stride ld = %lld below F = %d", (long long)ld, F);
+    if (n == 0) return 0;
+    OTTO_REQUIRE(d_X && d_edges && d_n_edges, "null argument");
+    k_bin<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(d_X, ld, n, F, d_edges, d_n_edges, d_bins);
+    OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int otto_gbdt_lambdarank(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n,
+                                    const double* d_sigmoid, double sigmoid_lo, double sigmoid_factor, const double* d_discount,
+                                    double sigma, int32_t truncation_level, int32_t norm, double* d_grad, double* d_hess,
+                                    void* stream) {
+    OTTO_TRY(check_query_args(d_score, d_label, d_query_off, Q, n));
+    OTTO_REQUIRE(sigma > 0.0 && sigmoid_factor > 0.0 && sigmoid_lo == sigmoid_lo, "sigma = %g, sigmoid_factor = %g", sigma,
+                 sigmoid_factor);
+    OTTO_REQUIRE(truncation_level >= 1, "truncation_level = %d", truncation_level);
+    OTTO_REQUIRE((d_grad && d_hess) || n == 0, "null d_grad or d_hess");
+    hipStream_t s = (hipStream_t)stream;
+    if (n) {
+        OTTO_HIP(hipMemsetAsync(d_grad, 0, (size_t)n * 8, s));
+        OTTO_HIP(hipMemsetAsync(d_hess, 0, (size_t)n * 8, s));
+    }
+    if (Q == 0) return 0;
+    OTTO_REQUIRE(d_sigmoid && d_discount, "null d_sigmoid or d_discount");
+    uint32_t* err = nullptr;
+    OTTO_TRY(err_begin(&err, s));
+    LambdaArgs a{d_score, d_label, d_query_off, Q, n, d_sigmoid, sigmoid_lo, sigmoid_factor, d_discount, sigma,
+                 truncation_level > MAXQ ? MAXQ : truncation_level, norm != 0, d_grad, d_hess, err};
+    // short queries (OTTO: 50 to 100 candidates) get one wave, long ones four
+    const unsigned threads = n / Q <= 96 ? 64 : 256;
+    k_lambdarank<<<(unsigned)Q, threads, 0, s>>>(a);
+    OTTO_HIP(hipGetLastError());
+    return err_end(err, s);
+}
+
+extern "C" int otto_gbdt_quantize(const double* d_grad, const double* d_hess, int64_t n, int32_t* d_gh, int32_t* d_exp, void* stream) {
+    OTTO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "n = %lld outside [0, 2^31)", (long long)n);
+    OTTO_REQUIRE(d_exp, "null d_exp");
+    OTTO_REQUIRE((d_grad && d_hess && d_gh) || n == 0, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    void* scratch = nullptr;
+    OTTO_TRY(device_scratch(SCRATCH_GBDT_MAX, 256, &scratch, s));
+    OTTO_HIP(hipMemsetAsync(scratch, 0, 16, s));
+    const unsigned grid = (unsigned)(n == 0 ? 1 : (n + 1023) / 1024 < 2048 ? (n + 1023) / 1024 : 2048);
+    k_absmax<<<grid, 256, 0, s>>>(d_grad, d_hess, n, (unsigned long long*)scratch);
+    OTTO_HIP(hipGetLastError());
+    k_quantize<<<grid, 256, 0, s>>>(d_grad, d_hess, n, (const unsigned long long*)scratch, (int2*)d_gh, d_exp);
+    OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int otto_gbdt_hist(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_rows, int64_t n_rows,
+                              int64_t* d_hist, void* stream) {
+    OTTO_TRY(check_bins_args(d_bins, n, F));
+    OTTO_REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows = %lld outside [0, 2^31)", (long long)n_rows);
+    OTTO_REQUIRE(d_hist, "null d_hist");
+    OTTO_REQUIRE((d_gh && d_rows) || n_rows == 0, "null d_gh or d_rows");
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t* err = nullptr;
+    OTTO_TRY(err_begin(&err, s));
+    OTTO_TRY(launch_hist(d_bins, n, F, d_gh, d_rows, n_rows, d_hist, err, s));
+    return err_end(err, s);
+}
+
+extern "C" int otto_gbdt_best_split(const int64_t* d_hist, int32_t F, const int32_t* d_n_edges, const int32_t* d_exp,
+                                    int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2,
+                                    double min_gain_to_split, int64_t* d_split, void* stream) {
+    OTTO_REQUIRE(F >= 1 && F <= OTTO_FOREST_MAX_FEATURES, "F must be in [1, %d] (got %d)", OTTO_FOREST_MAX_FEATURES, F);
+    OTTO_REQUIRE(d_hist && d_n_edges && d_exp && d_split, "null argument");
+    OTTO_TRY(check_split_params(min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split));
+    SplitJobs jobs{{d_hist, d_hist}, {d_split, d_split}};
+    SplitParams p{min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split};
+    k_best_split<<<1, 256, 0, (hipStream_t)stream>>>(jobs, F, d_n_edges, d_exp, p);
+    OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int otto_gbdt_partition(const uint8_t* d_bins, int64_t n, int32_t feature, int32_t bin, int32_t default_left,
+                                   const int32_t* d_rows, int64_t n_rows, int32_t* d_out, int64_t* d_n_left, void* d_work,
+                                   int64_t work_bytes, void* stream) {
+    OTTO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "n = %lld outside [0, 2^31)", (long long)n);
+    OTTO_REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows = %lld outside [0, 2^31)", (long long)n_rows);
+    OTTO_REQUIRE(feature >= 0 && feature < OTTO_FOREST_MAX_FEATURES, "feature = %d", feature);
+    OTTO_REQUIRE(bin >= 0 && bin < OTTO_GBDT_MAX_EDGES, "bin = %d outside [0, %d)", bin, OTTO_GBDT_MAX_EDGES);
+    OTTO_REQUIRE(d_n_left, "null d_n_left");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_rows == 0) {
+        OTTO_HIP(hipMemsetAsync(d_n_left, 0, 8, s));
+        return 0;
+    }
+    OTTO_REQUIRE(d_bins && d_rows && d_out, "null argument");
+    OTTO_REQUIRE(d_work && work_bytes >= part_blocks(n_rows) * 4, "d_work holds %lld bytes, the partition needs %lld",
+                 (long long)work_bytes, (long long)(part_blocks(n_rows) * 4));
+    uint32_t* err = nullptr;
+    OTTO_TRY(err_begin(&err, s));
+    OTTO_TRY(launch_partition(d_bins, n, feature, bin, default_left, d_rows, n_rows, d_out, d_n_left, (uint32_t*)d_work, err, s));
+    return err_end(err, s);
+}
+
+extern "C" int otto_gbdt_add_tree(const uint8_t* d_bins, int64_t n, int32_t F, int32_t n_leaves, const int32_t* d_split_feature,
+                                  const int32_t* d_split_bin, const int32_t* d_default_left, const int32_t* d_left_child,
+                                  const int32_t* d_right_child, const double* d_leaf_value, double* d_score, int32_t* d_leaf,
+                                  void* stream) {
+    OTTO_TRY(check_bins_args(d_bins, n, F));
+    OTTO_REQUIRE(n_leaves >= 1 && n_leaves <= OTTO_FOREST_MAX_LEAVES, "n_leaves = %d outside [1, %d]", n_leaves, OTTO_FOREST_MAX_LEAVES);
+    if (n == 0) return 0;
+    OTTO_REQUIRE(d_leaf_value && d_score, "null d_leaf_value or d_score");
+    OTTO_REQUIRE(n_leaves == 1 || (d_split_feature && d_split_bin && d_default_left && d_left_child && d_right_child), "null node array");
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t* err = nullptr;
+    OTTO_TRY(err_begin(&err, s));
+    k_add_tree<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_bins, n, F, n_leaves, d_split_feature, d_split_bin, d_default_left,
+                                                            d_left_child, d_right_child, d_leaf_value, d_score, d_leaf, err);
+    OTTO_HIP(hipGetLastError());
+    return err_end(err, s);
+}
+
+extern "C" int otto_gbdt_ap_at_k(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n,
+                                 int32_t k, double* d_ap, void* stream) {
+    OTTO_TRY(check_query_args(d_score, d_label, d_query_off, Q, n));
+    OTTO_REQUIRE(k >= 1 && k <= MAXQ, "k must be in [1, %d] (got %d)", MAXQ, k);
+    if (Q == 0) return 0;
+    OTTO_REQUIRE(d_ap, "null d_ap");
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t* err = nullptr;
+    OTTO_TRY(err_begin(&err, s));
+    k_ap<<<(unsigned)Q, n / Q <= 96 ? 64 : 256, 0, s>>>(d_score, d_label, d_query_off, n, k, d_ap, err);
+    OTTO_HIP(hipGetLastError());
+    return err_end(err, s);
+}
+
+extern "C" int otto_gbdt_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_exp,
+                                   const int32_t* d_n_edges, const float* h_edges, int32_t num_leaves, int64_t min_data_in_leaf,
+                                   double min_sum_hessian_in_leaf, double lambda_l2, double min_gain_to_split, double learning_rate,
+                                   int32_t* h_n_leaves, int32_t* h_split_feature, int32_t* h_split_bin, double* h_threshold,
+                                   int8_t* h_decision_type, int32_t* h_left_child, int32_t* h_right_child, double* h_split_gain,
+                                   double* h_leaf_value, int64_t* h_leaf_count, int64_t* h_hist_rows, void* d_work,
+                                   int64_t work_bytes, void* stream) {
+    OTTO_TRY(check_bins_args(d_bins, n, F));
+    OTTO_REQUIRE(n >= 1, "n = 0: nothing to grow a tree on");
+    OTTO_REQUIRE(num_leaves >= 2 && num_leaves <= OTTO_FOREST_MAX_LEAVES, "num_leaves = %d outside [2, %d]", num_leaves,
+                 OTTO_FOREST_MAX_LEAVES);
+    OTTO_TRY(check_split_params(min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split));
+    OTTO_REQUIRE(d_gh && d_exp && d_n_edges && h_edges && h_n_leaves && h_split_feature && h_split_bin && h_threshold &&
+                 h_decision_type && h_left_child && h_right_child && h_split_gain && h_leaf_value && h_leaf_count, "null argument");
+    const WorkLayout w = work_layout(n, F, num_leaves);
+    OTTO_REQUIRE(d_work && work_bytes >= w.total, "d_work holds %lld bytes, otto_gbdt_workspace_bytes asks for %lld",
+                 (long long)work_bytes, (long long)w.total);
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)d_work;
+    int32_t* rows_a = (int32_t*)(base + w.rows_a);
+    int32_t* rows_b = (int32_t*)(base + w.rows_b);
+    uint32_t* block_left = (uint32_t*)(base + w.block_left);
+    int64_t* d_n_left = (int64_t*)(base + w.n_left);
+    int64_t* d_split = (int64_t*)(base + w.split);
+    int64_t* hist0 = (int64_t*)(base + w.hist);
+    const int64_t hist_words = (int64_t)3 * F * 256;
+    SplitParams p{min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split};
+    uint32_t* err = nullptr;
+    OTTO_TRY(err_begin(&err, s));
+    int32_t exps[2];
+    OTTO_HIP(hipMemcpyAsync(exps, d_exp, 8, hipMemcpyDeviceToHost, s));
+
+    struct Leaf {
+        int64_t begin, cnt, gq, hq;
+        int slot;           // which histogram of the workspace is this leaf's
+        int parent, side;   // the internal node that points here (-1: the root), 0 left / 1 right
+        bool rows_set;      // false: the root before its first partition (rows 0 .. n - 1, no list)
+        int64_t split[SW];
+    };
+    std::vector<Leaf> leaves(1);
+    leaves[0] = Leaf{0, n, 0, 0, 0, -1, 0, false, {0}};
+    int64_t hist_rows = n;
+    OTTO_TRY(launch_hist(d_bins, n, F, d_gh, nullptr, n, hist0, err, s));
+    {
+        SplitJobs jobs{{hist0, hist0}, {d_split, d_split}};
+        k_best_split<<<1, 256, 0, s>>>(jobs, F, d_n_edges, d_exp, p);
+        OTTO_HIP(hipGetLastError());
+        OTTO_HIP(hipMemcpyAsync(leaves[0].split, d_split, SW * 8, hipMemcpyDeviceToHost, s));
+        OTTO_HIP(hipStreamSynchronize(s));
+        leaves[0].gq = leaves[0].split[9];
+        leaves[0].hq = leaves[0].split[10];
+    }
+    auto gain_of = [](const Leaf& l) { double g; memcpy(&g, &l.split[4], 8); return g; };
+    int n_nodes = 0;
+    while ((int)leaves.size() < num_leaves) {
+        int best = -1;
+        for (int i = 0; i < (int)leaves.size(); ++i)
+            if (leaves[i].split[0] && (best < 0 || gain_of(leaves[i]) > gain_of(leaves[best]))) best = i;
+        if (best < 0) break;
+        const int node = n_nodes++, right = (int)leaves.size();
+        Leaf P = leaves[best];
+        const int f = (int)P.split[1], b = (int)P.split[2], dl = (int)P.split[3];
+        OTTO_REQUIRE(f >= 0 && f < F && b >= 0 && b < OTTO_GBDT_MAX_EDGES && P.split[5] >= 0 && P.split[5] <= P.cnt,
+                     "the split search returned feature %d, bin %d, %lld of %lld rows left", f, b, (long long)P.split[5],
+                     (long long)P.cnt);
+        h_split_feature[node] = f;
+        h_split_bin[node] = b;
+        h_threshold[node] = (double)h_edges[(int64_t)f * OTTO_GBDT_MAX_EDGES + b];
+        h_decision_type[node] = (int8_t)((2 << 2) | (dl ? 2 : 0));
+        h_split_gain[node] = gain_of(P);
+        h_left_child[node] = ~best;
+        h_right_child[node] = ~right;
+        if (P.parent >= 0) (P.side ? h_right_child : h_left_child)[P.parent] = node;
+        // stable partition of the leaf's rows into the other buffer, then back into place
+        OTTO_TRY(launch_partition(d_bins, n, f, b, dl, P.rows_set ? rows_a + P.begin : nullptr, P.cnt, rows_b + P.begin, d_n_left,
+                                  block_left, err, s));
+        OTTO_HIP(hipMemcpyAsync(rows_a + P.begin, rows_b + P.begin, (size_t)P.cnt * 4, hipMemcpyDeviceToDevice, s));
+        const int64_t cL = P.split[5], cR = P.cnt - cL;
+        Leaf L{P.begin, cL, P.split[6], P.split[7], P.slot, node, 0, true, {0}};
+        Leaf R{P.begin + cL, cR, P.gq - P.split[6], P.hq - P.split[7], right, node, 1, true, {0}};
+        if (right + 1 < num_leaves) {
+            // the smaller child's histogram is built, the larger one is the parent's minus that
+            Leaf& small = cL <= cR ? L : R;
+            Leaf& large = cL <= cR ? R : L;
+            small.slot = right;
+            large.slot = P.slot;
+            int64_t* hs = hist0 + (int64_t)small.slot * hist_words;
+            int64_t* hl = hist0 + (int64_t)large.slot * hist_words;
+            OTTO_TRY(launch_hist(d_bins, n, F, d_gh, rows_a + small.begin, small.cnt, hs, err, s));
+            hist_rows += small.cnt;
+            k_hist_sub<<<(unsigned)((hist_words + 255) / 256), 256, 0, s>>>(hl, hs, hist_words);
+            OTTO_HIP(hipGetLastError());
+            SplitJobs jobs{{hist0 + (int64_t)L.slot * hist_words, hist0 + (int64_t)R.slot * hist_words}, {d_split, d_split + SW}};
+            k_best_split<<<2, 256, 0, s>>>(jobs, F, d_n_edges, d_exp, p);
+            OTTO_HIP(hipGetLastError());
+            int64_t both[2 * SW];
+            OTTO_HIP(hipMemcpyAsync(both, d_split, sizeof(both), hipMemcpyDeviceToHost, s));
+            OTTO_HIP(hipStreamSynchronize(s));
+            memcpy(L.split, both, SW * 8);
+            memcpy(R.split, both + SW, SW * 8);
+            OTTO_REQUIRE(L.split[8] == cL && R.split[8] == cR && L.split[9] == L.gq && R.split[9] == R.gq,
+                         "the children's histograms disagree with the split that made them (node %d)", node);
+        }
+        leaves[best] = L;
+        leaves.push_back(R);
+    }
+    OTTO_TRY(err_end(err, s));
+    const double lr = learning_rate;
+    for (int i = 0; i < (int)leaves.size(); ++i) {
+        const double G = ldexp((double)leaves[i].gq, -exps[0]), H = ldexp((double)leaves[i].hq, -exps[1]);
+        h_leaf_value[i] = -(G / (H + lambda_l2)) * lr;
+        h_leaf_count[i] = leaves[i].cnt;
+    }
+    *h_n_leaves = (int32_t)leaves.size();
+    if (h_hist_rows) *h_hist_rows = hist_rows;
+    return 0;
+}

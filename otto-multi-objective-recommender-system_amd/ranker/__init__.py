@@ -5,3 +5,5 @@ from . import evaluate  # noqa: E402,F401
 from .blend import blend_predictions, blend_topk, robust_scale  # noqa: E402,F401
 from .features import (AID_COLUMNS, SESSION_COLUMNS, aid_feature_table, feature_matrix, session_feature_table,  # noqa: E402,F401
                        to_frames)
+from .gbdt import (BinMapper, TrainResult, ap_at_k, bin_matrix, fit_bins, lambdarank_gradients, train,  # noqa: E402,F401
+                   write_lightgbm_model)

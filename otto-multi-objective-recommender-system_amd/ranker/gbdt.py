@@ -1,0 +1,532 @@
+"""LambdaRank gradient-boosted tree training on the device (SPEC-GBDT): the bin mapper, thin Python
+over ``include/otto_gbdt.h``, the boosting loop and a LightGBM v3 model writer.
+
+What this replaces in the reference: ``lgb.train`` on the (session, candidate) matrix, one model per event type and fold
+(``src/ranker/lgb_trainer.py:134-165``). The caller keeps GroupKFold and the negative down-sampling
+(``lgb_trainer.py:81-128``), hands over the float32 matrix of ``ranker.features.feature_matrix`` with the rows of a
+session contiguous, and gets a :class:`~otto_amd.ranker.forest.Forest` that ``ranker.forest`` scores. LightGBM's own
+arithmetic is not reproduced: SPEC-GBDT states what is computed.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .. import _lib
+from .forest import MAX_FEATURES, MAX_LEAVES, Forest
+
+MAX_QUERY = 1024            # OTTO_GBDT_MAX_QUERY
+MAX_EDGES = 254             # OTTO_GBDT_MAX_EDGES
+NAN_BIN = 255               # OTTO_GBDT_NAN_BIN
+SIGMOID_BINS = 1 << 20      # OTTO_GBDT_SIGMOID_BINS
+MAX_LABEL = 31              # OTTO_GBDT_MAX_LABEL
+SPLIT_WORDS = 12            # OTTO_GBDT_SPLIT_WORDS
+
+# the values recorded in the reference's model dump and config (models/lightgbm/)
+DEFAULTS = {
+    'num_leaves': 128, 'min_data_in_leaf': 2000, 'min_sum_hessian_in_leaf': 1e-3, 'lambda_l2': 0.01, 'min_gain_to_split': 1e-5,
+    'learning_rate': 0.1, 'lambdarank_truncation_level': 30, 'lambdarank_norm': True, 'sigmoid': 1.0, 'max_bin': 255,
+    'eval_at': 20,
+}
+_ALIASES = {
+    'min_child_samples': 'min_data_in_leaf', 'min_child_weight': 'min_sum_hessian_in_leaf', 'reg_lambda': 'lambda_l2',
+    'reg_alpha': 'lambda_l1', 'min_split_gain': 'min_gain_to_split', 'eta': 'learning_rate', 'subsample': 'bagging_fraction',
+    'colsample_bytree': 'feature_fraction', 'max_leaves': 'num_leaves', 'ndcg_eval_at': 'eval_at', 'map_eval_at': 'eval_at',
+}
+_ROUND_KEYS = {'num_iterations', 'num_iteration', 'n_iter', 'num_tree', 'num_trees', 'num_round', 'num_rounds', 'nrounds',
+               'num_boost_round', 'n_estimators', 'max_iter', 'early_stopping_round', 'early_stopping_rounds', 'early_stopping',
+               'n_iter_no_change'}
+
+
+class BinMapper:
+    """Per feature at most 254 strictly increasing float32 edges: ``edges`` float32 [F, 254] (row f holds ``n_edges[f]``
+    edges, the rest is +inf padding), ``n_edges`` int32 [F]. ``bin(x)`` = the number of edges ``< x``; NaN -> 255."""
+
+    def __init__(self, edges, n_edges):
+        self.edges = np.ascontiguousarray(edges, dtype=np.float32)
+        self.n_edges = np.ascontiguousarray(n_edges, dtype=np.int32)
+        if self.edges.ndim != 2 or self.edges.shape[1] != MAX_EDGES or self.n_edges.shape != (self.edges.shape[0],):
+            raise ValueError(f'edges: expected float32 [F, {MAX_EDGES}] and n_edges int32 [F]')
+        if not 1 <= self.edges.shape[0] <= MAX_FEATURES:
+            raise ValueError(f'F must be in [1, {MAX_FEATURES}] (got {self.edges.shape[0]})')
+        for f, k in enumerate(self.n_edges):
+            e = self.edges[f, :k]
+            if not 0 <= k <= MAX_EDGES or np.isnan(e).any() or (k > 1 and not (e[1:] > e[:-1]).all()):
+                raise ValueError(f'feature {f}: the edges must be at most {MAX_EDGES}, not NaN and strictly increasing')
+        self._dev = {}
+
+    @property
+    def n_features(self):
+        return self.edges.shape[0]
+
+    def feature_edges(self, f):
+        return self.edges[f, :self.n_edges[f]]
+
+    def to(self, device):
+        import torch
+        device = torch.device(device)
+        if device not in self._dev:
+            self._dev[device] = (torch.from_numpy(self.edges).to(device), torch.from_numpy(self.n_edges).to(device))
+        return self._dev[device]
+
+
+def fit_bins(sample, max_bin=255):
+    """The :class:`BinMapper` of a row sample float32 [m, F] (host array or tensor), built in NumPy. Per feature, from the
+    non-NaN sample values: ``d <= max_bin`` distinct values ``v_0 < ... < v_{d-1}`` give the edges ``v_0 .. v_{d-2}``;
+    otherwise the edges are the deduplicated values at positions ``floor((i+1)*m/max_bin) - 1``, ``i = 0 .. max_bin-2``,
+    of the ``m`` sorted values."""
+    if hasattr(sample, 'detach'):
+        sample = sample.detach().cpu().numpy()
+    sample = np.asarray(sample)
+    if sample.ndim != 2 or sample.dtype != np.float32:
+        raise ValueError('sample: expected float32 [m, F]')
+    max_bin = int(max_bin)
+    if not 2 <= max_bin <= 255:
+        raise ValueError(f'max_bin must be in [2, 255] (got {max_bin})')
+    F = sample.shape[1]
+    edges = np.full((F, MAX_EDGES), np.inf, dtype=np.float32)
+    n_edges = np.zeros(F, dtype=np.int32)
+    for f in range(F):
+        v = sample[:, f]
+        v = np.sort(v[~np.isnan(v)])
+        u = np.unique(v)
+        if u.size <= max_bin:
+            e = u[:-1]
+        else:
+            m = v.size
+            pos = (np.arange(1, max_bin, dtype=np.int64) * m) // max_bin - 1
+            e = np.unique(v[pos])
+        edges[f, :e.size] = e
+        n_edges[f] = e.size
+    return BinMapper(edges, n_edges)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _np_ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _stream(dev):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _need_device(t, what):
+    if t.device.type != 'cuda':
+        raise _lib.OttoError(f'{what} needs a ROCm device (no CPU fallback)')
+
+
+def _check_1d(name, t, dtype, dev=None):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f'{name}: expected a contiguous 1-d {dtype} tensor')
+    if dev is not None and t.device != dev:
+        raise ValueError(f'{name} must be on {dev}')
+
+
+def bin_matrix(X, mapper):
+    """uint8 [F, n] (feature-major) bins of ``X`` float32 [n, >= F] on the device."""
+    import torch
+    if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.dtype != torch.float32:
+        raise ValueError('X: expected a float32 tensor [n, >= F]')
+    _need_device(X, 'bin_matrix')
+    F = mapper.n_features
+    if X.shape[1] < F:
+        raise ValueError(f'X has {X.shape[1]} columns, the mapper reads {F}')
+    n = int(X.shape[0])
+    if n and (X.stride(1) != 1 or X.stride(0) < F):
+        raise ValueError('X: expected row-major rows (stride(1) == 1)')
+    ld = int(X.stride(0)) if n else max(int(X.shape[1]), 1)
+    edges, n_edges = mapper.to(X.device)
+    bins = torch.empty((F, n), dtype=torch.uint8, device=X.device)
+    with torch.cuda.device(X.device):
+        _lib.check(_lib.lib().otto_gbdt_bin(_ptr(X), ld, n, F, _ptr(edges), _ptr(n_edges), _ptr(bins), _stream(X.device)),
+                   'otto_gbdt_bin')
+    return bins
+
+
+_TABLES = {}
+
+
+def sigmoid_table(sigma):
+    """(table float64 [2^20], lo, factor) of SPEC-GBDT, from NumPy."""
+    sigma = float(sigma)
+    lo, hi = -25.0 / sigma, 25.0 / sigma
+    factor = SIGMOID_BINS / (hi - lo)
+    i = np.arange(SIGMOID_BINS, dtype=np.float64)
+    return 1.0 / (1.0 + np.exp(sigma * (lo + i / factor))), lo, factor
+
+
+def discount_table():
+    return 1.0 / np.log2(2.0 + np.arange(MAX_QUERY, dtype=np.float64))
+
+
+def _tables(sigma, dev):
+    import torch
+    key = (float(sigma), dev)
+    if key not in _TABLES:
+        t, lo, factor = sigmoid_table(sigma)
+        _TABLES[key] = (torch.from_numpy(t).to(dev), lo, factor, torch.from_numpy(discount_table()).to(dev))
+    return _TABLES[key]
+
+
+def _check_queries(score, label, query_off):
+    import torch
+    _check_1d('score', score, torch.float64)
+    _need_device(score, 'the ranking objective')
+    _check_1d('label', label, torch.int32, score.device)
+    _check_1d('query_off', query_off, torch.int64, score.device)
+    if label.numel() != score.numel():
+        raise ValueError(f'label has {label.numel()} rows, score has {score.numel()}')
+    if query_off.numel() < 1:
+        raise ValueError('query_off: expected int64 [Q+1]')
+
+
+def lambdarank_gradients(score, label, query_off, sigma=1.0, truncation_level=30, norm=True, out=None):
+    """(grad, hess) float64 [n] of the LambdarankNDCG objective; ``score`` float64 [n], ``label`` int32 [n] in 0..31,
+    ``query_off`` int64 [Q+1], on the device. Raises ``OttoError`` for a query longer than ``MAX_QUERY`` or a malformed
+    ``query_off``: the rows of such a query are zero in ``out`` = (grad, hess), if the caller passed these tensors."""
+    import torch
+    _check_queries(score, label, query_off)
+    dev = score.device
+    table, lo, factor, disc = _tables(sigma, dev)
+    grad, hess = out if out is not None else (torch.empty_like(score), torch.empty_like(score))
+    _check_1d('grad', grad, torch.float64, dev)
+    _check_1d('hess', hess, torch.float64, dev)
+    if grad.numel() != score.numel() or hess.numel() != score.numel():
+        raise ValueError('out: expected two float64 tensors [n]')
+    with torch.cuda.device(dev):
+        rc = _lib.lib().otto_gbdt_lambdarank(_ptr(score), _ptr(label), _ptr(query_off), query_off.numel() - 1, score.numel(),
+                                             _ptr(table), lo, factor, _ptr(disc), float(sigma), int(truncation_level),
+                                             int(bool(norm)), _ptr(grad), _ptr(hess), _stream(dev))
+    _lib.check(rc, 'otto_gbdt_lambdarank')
+    return grad, hess
+
+
+def quantize_gradients(grad, hess):
+    """(gh int32 [n, 2], exp int32 [2]) of SPEC-GBDT's quantisation, on the device."""
+    import torch
+    _check_1d('grad', grad, torch.float64)
+    _need_device(grad, 'quantize_gradients')
+    _check_1d('hess', hess, torch.float64, grad.device)
+    if hess.numel() != grad.numel():
+        raise ValueError('grad and hess differ in length')
+    gh = torch.empty((grad.numel(), 2), dtype=torch.int32, device=grad.device)
+    exp = torch.empty(2, dtype=torch.int32, device=grad.device)
+    with torch.cuda.device(grad.device):
+        _lib.check(_lib.lib().otto_gbdt_quantize(_ptr(grad), _ptr(hess), grad.numel(), _ptr(gh), _ptr(exp), _stream(grad.device)),
+                   'otto_gbdt_quantize')
+    return gh, exp
+
+
+def _check_bins(bins):
+    import torch
+    if not isinstance(bins, torch.Tensor) or bins.dtype != torch.uint8 or bins.dim() != 2 or not bins.is_contiguous():
+        raise ValueError('bins: expected a contiguous uint8 tensor [F, n] (bin_matrix)')
+    _need_device(bins, 'the tree trainer')
+    return int(bins.shape[0]), int(bins.shape[1])
+
+
+def leaf_histogram(bins, gh, rows):
+    """int64 [3, F, 256] = (sum qg, sum qh, rows) of the leaf whose row ids are ``rows`` int32."""
+    import torch
+    F, n = _check_bins(bins)
+    _check_1d('rows', rows, torch.int32, bins.device)
+    hist = torch.empty((3, F, 256), dtype=torch.int64, device=bins.device)
+    with torch.cuda.device(bins.device):
+        _lib.check(_lib.lib().otto_gbdt_hist(_ptr(bins), n, F, _ptr(gh), _ptr(rows), rows.numel(), _ptr(hist), _stream(bins.device)),
+                   'otto_gbdt_hist')
+    return hist
+
+
+def best_split(hist, mapper, exp, min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split):
+    """The best split of a leaf histogram, or ``None``: dict(feature, bin, default_left, gain, cnt_left, g_left, h_left,
+    cnt, g, h) with the integer sums as Python ints."""
+    import torch
+    dev = hist.device
+    _, n_edges = mapper.to(dev)
+    out = torch.empty(SPLIT_WORDS, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().otto_gbdt_best_split(_ptr(hist), int(hist.shape[1]), _ptr(n_edges), _ptr(exp), int(min_data_in_leaf),
+                                                   float(min_sum_hessian_in_leaf), float(lambda_l2), float(min_gain_to_split),
+                                                   _ptr(out), _stream(dev)), 'otto_gbdt_best_split')
+    w = out.cpu().numpy()
+    if not w[0]:
+        return None
+    return dict(feature=int(w[1]), bin=int(w[2]), default_left=int(w[3]), gain=float(w[4:5].view(np.float64)[0]),
+                cnt_left=int(w[5]), g_left=int(w[6]), h_left=int(w[7]), cnt=int(w[8]), g=int(w[9]), h=int(w[10]))
+
+
+def partition_rows(bins, rows, feature, bin, default_left):
+    """(out int32 like ``rows``: the left rows in their order, then the right rows in theirs; n_left)."""
+    import torch
+    F, n = _check_bins(bins)
+    _check_1d('rows', rows, torch.int32, bins.device)
+    if not 0 <= int(feature) < F:
+        raise ValueError(f'feature {feature} outside [0, {F})')
+    out = torch.empty_like(rows)
+    n_left = torch.zeros(1, dtype=torch.int64, device=bins.device)
+    work = torch.empty(max(rows.numel() // 2048 + 1, 64), dtype=torch.int32, device=bins.device)
+    with torch.cuda.device(bins.device):
+        _lib.check(_lib.lib().otto_gbdt_partition(_ptr(bins), n, int(feature), int(bin), int(bool(default_left)), _ptr(rows),
+                                                  rows.numel(), _ptr(out), _ptr(n_left), _ptr(work), work.numel() * 4,
+                                                  _stream(bins.device)), 'otto_gbdt_partition')
+    return out, int(n_left.item())
+
+
+class BinTree:
+    """One tree in bin space (host arrays): ``split_feature``, ``split_bin``, ``default_left``, ``left_child``,
+    ``right_child`` int32 [L-1], ``threshold`` float64, ``decision_type`` int8, ``split_gain`` float64, ``leaf_value``
+    float64 [L], ``leaf_count`` int64 [L]; ``hist_rows``: rows the histogram kernel read for it."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def n_leaves(self):
+        return self.leaf_value.size
+
+    def to(self, dev):
+        import torch
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        return (t(self.split_feature), t(self.split_bin), t(self.default_left), t(self.left_child), t(self.right_child),
+                t(self.leaf_value))
+
+
+def workspace_bytes(n, F, num_leaves):
+    b = int(_lib.lib().otto_gbdt_workspace_bytes(int(n), int(F), int(num_leaves)))
+    if b <= 0:
+        raise _lib.OttoError(f'otto_gbdt_workspace_bytes refused n = {n}, F = {F}, num_leaves = {num_leaves}')
+    return b
+
+
+def grow_tree(bins, gh, exp, mapper, p, work=None):
+    """One leaf-wise tree over all rows: a :class:`BinTree`. ``p``: the resolved parameters (:func:`resolve_params`)."""
+    import torch
+    F, n = _check_bins(bins)
+    dev = bins.device
+    L = int(p['num_leaves'])
+    if work is None:
+        work = torch.empty(workspace_bytes(n, F, L), dtype=torch.uint8, device=dev)
+    _, n_edges = mapper.to(dev)
+    sf, sb, lc, rc = (np.zeros(L - 1, dtype=np.int32) for _ in range(4))
+    thr, gain = np.zeros(L - 1, dtype=np.float64), np.zeros(L - 1, dtype=np.float64)
+    dt = np.zeros(L - 1, dtype=np.int8)
+    lv, cnt = np.zeros(L, dtype=np.float64), np.zeros(L, dtype=np.int64)
+    n_leaves, hist_rows = C.c_int32(0), C.c_int64(0)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().otto_gbdt_grow_tree(
+            _ptr(bins), n, F, _ptr(gh), _ptr(exp), _ptr(n_edges), _np_ptr(mapper.edges), L, int(p['min_data_in_leaf']),
+            float(p['min_sum_hessian_in_leaf']), float(p['lambda_l2']), float(p['min_gain_to_split']), float(p['learning_rate']),
+            C.byref(n_leaves), _np_ptr(sf), _np_ptr(sb), _np_ptr(thr), _np_ptr(dt), _np_ptr(lc), _np_ptr(rc), _np_ptr(gain),
+            _np_ptr(lv), _np_ptr(cnt), C.byref(hist_rows), _ptr(work), work.numel(), _stream(dev)), 'otto_gbdt_grow_tree')
+    k = n_leaves.value
+    return BinTree(split_feature=sf[:k - 1], split_bin=sb[:k - 1], default_left=((dt[:k - 1] & 2) >> 1).astype(np.int32),
+                   left_child=lc[:k - 1], right_child=rc[:k - 1], threshold=thr[:k - 1], decision_type=dt[:k - 1],
+                   split_gain=gain[:k - 1], leaf_value=lv[:k], leaf_count=cnt[:k], hist_rows=hist_rows.value)
+
+
+def add_tree(bins, tree, score, want_leaf=False):
+    """``score[r] += leaf_value[leaf(r)]`` by routing the bins through ``tree``; returns leaf(r) int32 [n] if asked."""
+    import torch
+    F, n = _check_bins(bins)
+    _check_1d('score', score, torch.float64, bins.device)
+    if score.numel() != n:
+        raise ValueError(f'score has {score.numel()} rows, bins has {n}')
+    dev = bins.device
+    sf, sb, dl, lc, rc, lv = tree.to(dev)
+    leaf = torch.empty(n, dtype=torch.int32, device=dev) if want_leaf else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().otto_gbdt_add_tree(_ptr(bins), n, F, tree.n_leaves, _ptr(sf), _ptr(sb), _ptr(dl), _ptr(lc), _ptr(rc),
+                                                 _ptr(lv), _ptr(score), _ptr(leaf), _stream(dev)), 'otto_gbdt_add_tree')
+    return leaf
+
+
+def ap_at_k(score, label, query_off, k=20):
+    """Per-query AP@k float64 [Q] on the device (-1 for a query without a positive), in the objective's row order."""
+    import torch
+    _check_queries(score, label, query_off)
+    k = int(k)
+    if not 1 <= k <= MAX_QUERY:
+        raise ValueError(f'k must be in [1, {MAX_QUERY}] (got {k})')
+    dev = score.device
+    ap = torch.empty(query_off.numel() - 1, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().otto_gbdt_ap_at_k(_ptr(score), _ptr(label), _ptr(query_off), query_off.numel() - 1, score.numel(), k,
+                                                _ptr(ap), _stream(dev)), 'otto_gbdt_ap_at_k')
+    return ap
+
+
+def mean_ap(ap):
+    """The metric of SPEC-GBDT from per-query AP: ``np.sum(ap[ap >= 0]) / count`` on the host (nan without such a query)."""
+    ap = ap.detach().cpu().numpy() if hasattr(ap, 'detach') else np.asarray(ap)
+    ok = ap >= 0
+    return float(np.sum(ap[ok]) / ok.sum()) if ok.any() else float('nan')
+
+
+def resolve_params(params):
+    """LightGBM's key names and aliases -> the resolved dict. ``config['model'][event_type]`` of the reference's YAML can be
+    passed once the keys SPEC-GBDT refuses are taken out. Raises ``ValueError`` for what changes the arithmetic and is not
+    implemented: ``lambda_l1 != 0``, ``bagging_fraction < 1``, ``feature_fraction < 1``, ``feature_fraction_bynode < 1``,
+    categorical features, ``max_depth > 0``, ``num_leaves`` above ``OTTO_FOREST_MAX_LEAVES``, an ``objective`` other than
+    ``lambdarank``, a ``boosting`` other than ``gbdt``, a ``label_gain`` other than ``2^i - 1``; and for the round counts
+    (``num_iterations``, ``early_stopping_round`` and their aliases), which are arguments of :func:`train`. Every other key
+    (seeds, ``verbose``, ``n_jobs``, ``metric``, ...) changes no arithmetic here and is ignored. ``eval_at``: the first entry
+    of a list is the k of the validation metric."""
+    p = dict(DEFAULTS)
+    for key, val in dict(params or {}).items():
+        key = _ALIASES.get(key, key)
+        if key == 'lambda_l1':
+            if float(val) != 0.0:
+                raise ValueError('lambda_l1 != 0 is not supported (SPEC-GBDT has no L1 term)')
+        elif key == 'bagging_fraction':
+            if float(val) < 1.0:
+                raise ValueError('bagging_fraction < 1 is not supported (the row sample would follow LightGBM\'s unpinned RNG)')
+        elif key in ('feature_fraction', 'feature_fraction_bynode'):
+            if float(val) < 1.0:
+                raise ValueError(f'{key} < 1 is not supported (the column sample would follow LightGBM\'s unpinned RNG)')
+        elif key in ('categorical_feature', 'categorical_features', 'cat_feature'):
+            if val not in (None, '', 'auto') and len(val):
+                raise ValueError('categorical features are not supported (numerical splits only)')
+        elif key == 'max_depth':
+            if int(val) > 0:
+                raise ValueError('max_depth > 0 is not supported (growth is leaf-wise up to num_leaves)')
+        elif key in ('objective', 'objective_type', 'app', 'application', 'loss'):
+            if str(val) != 'lambdarank':
+                raise ValueError(f'objective {val!r} is not supported (only lambdarank)')
+        elif key in ('boosting', 'boosting_type', 'boost'):
+            if str(val) != 'gbdt':
+                raise ValueError(f'boosting {val!r} is not supported (only gbdt)')
+        elif key == 'label_gain':
+            if val is not None and [float(g) for g in val] != [float(2 ** i - 1) for i in range(len(val))]:
+                raise ValueError('a label_gain other than 2^i - 1 is not supported')
+        elif key in _ROUND_KEYS:
+            raise ValueError(f'{key} is not read from params: pass num_boost_round / early_stopping_rounds to train()')
+        elif key in DEFAULTS:
+            p[key] = val
+        # anything else (seeds, verbose, n_jobs, metric, ...) changes no arithmetic here
+    if isinstance(p['eval_at'], (list, tuple)):
+        p['eval_at'] = p['eval_at'][0]
+    p['num_leaves'], p['min_data_in_leaf'], p['eval_at'] = int(p['num_leaves']), int(p['min_data_in_leaf']), int(p['eval_at'])
+    p['lambdarank_truncation_level'], p['max_bin'] = int(p['lambdarank_truncation_level']), int(p['max_bin'])
+    p['lambdarank_norm'] = bool(p['lambdarank_norm'])
+    for key in ('min_sum_hessian_in_leaf', 'lambda_l2', 'min_gain_to_split', 'learning_rate', 'sigmoid'):
+        p[key] = float(p[key])
+    if p['num_leaves'] > MAX_LEAVES:
+        raise ValueError(f'num_leaves = {p["num_leaves"]} above OTTO_FOREST_MAX_LEAVES = {MAX_LEAVES}')
+    if p['num_leaves'] < 2:
+        raise ValueError(f'num_leaves = {p["num_leaves"]} below 2')
+    if p['min_data_in_leaf'] < 0 or p['min_sum_hessian_in_leaf'] < 0 or p['lambda_l2'] < 0 or p['sigmoid'] <= 0 \
+            or p['lambdarank_truncation_level'] < 1:
+        raise ValueError('min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2 must be >= 0, sigmoid > 0, truncation level >= 1')
+    return p
+
+
+def forest_from_trees(trees, n_features, feature_names=None):
+    """The :class:`Forest` of a list of :class:`BinTree`."""
+    cat = lambda name, dtype: np.concatenate([getattr(t, name) for t in trees]).astype(dtype)
+    node_off = np.concatenate([[0], np.cumsum([t.n_leaves - 1 for t in trees])]).astype(np.int64)
+    leaf_off = np.concatenate([[0], np.cumsum([t.n_leaves for t in trees])]).astype(np.int64)
+    return Forest(node_off, leaf_off, cat('split_feature', np.int32), cat('threshold', np.float64), cat('decision_type', np.int8),
+                  cat('left_child', np.int32), cat('right_child', np.int32), cat('leaf_value', np.float64), n_features,
+                  feature_names=feature_names, objective='lambdarank')
+
+
+class TrainResult:
+    """``forest``: the first ``best_iteration`` trees as a ``ranker.forest.Forest``; ``best_iteration``; ``history``: the
+    validation metric after every iteration (empty without a validation set); ``train_score`` float64 [n] on the device:
+    the raw score of every training row under ``forest``; ``trees``: the :class:`BinTree` list of ``forest``;
+    ``train_leaf`` int32 [n, T]: the leaf the trainer put every row in."""
+
+    def __init__(self, forest, best_iteration, history, train_score, trees, train_leaf):
+        self.forest, self.best_iteration, self.history = forest, best_iteration, history
+        self.train_score, self.trees, self.train_leaf = train_score, trees, train_leaf
+
+
+def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_round=100, early_stopping_rounds=None,
+          feature_names=None, keep_leaves=False):
+    """Boost LambdaRank trees on the device (SPEC-GBDT). ``bins`` uint8 [F, n] (:func:`bin_matrix`), ``label`` int32 [n],
+    ``query_off`` int64 [Q+1]; ``valid`` = (bins, label, query_off) of a validation set binned with the same mapper: its
+    mean AP@``eval_at`` is recorded after every tree, and with ``early_stopping_rounds`` training stops once that many
+    iterations have passed without a strict improvement and the forest is cut at the best iteration. ``keep_leaves``
+    also returns the leaf of every (row, tree). Raises ``OttoError`` if not a single tree could be grown."""
+    import torch
+    p = resolve_params(params)
+    F, n = _check_bins(bins)
+    dev = bins.device
+    if mapper.n_features != F:
+        raise ValueError(f'the mapper has {mapper.n_features} features, bins has {F}')
+    score = torch.zeros(n, dtype=torch.float64, device=dev)
+    _check_queries(score, label, query_off)
+    if valid is not None:
+        vbins, vlabel, voff = valid
+        if _check_bins(vbins)[0] != F:
+            raise ValueError('the validation bins have another feature count')
+        vscore = torch.zeros(vbins.shape[1], dtype=torch.float64, device=dev)
+        _check_queries(vscore, vlabel, voff)
+    elif early_stopping_rounds:
+        raise ValueError('early_stopping_rounds needs a validation set')
+    work = torch.empty(workspace_bytes(n, F, p['num_leaves']), dtype=torch.uint8, device=dev)
+    trees, leaves, history = [], [], []
+    best_metric, best_iter = None, 0
+    for it in range(int(num_boost_round)):
+        grad, hess = lambdarank_gradients(score, label, query_off, p['sigmoid'], p['lambdarank_truncation_level'],
+                                          p['lambdarank_norm'])
+        gh, exp = quantize_gradients(grad, hess)
+        tree = grow_tree(bins, gh, exp, mapper, p, work)
+        if tree.n_leaves < 2:
+            break
+        trees.append(tree)
+        leaf = add_tree(bins, tree, score, want_leaf=keep_leaves)
+        if keep_leaves:
+            leaves.append(leaf)
+        if valid is not None:
+            add_tree(vbins, tree, vscore)
+            m = mean_ap(ap_at_k(vscore, vlabel, voff, p['eval_at']))
+            history.append(m)
+            if best_metric is None or m > best_metric:
+                best_metric, best_iter = m, it + 1
+            if early_stopping_rounds and it + 1 - best_iter >= int(early_stopping_rounds):
+                break
+    if not trees:
+        raise _lib.OttoError('no tree could be grown: no split of the root is admissible (min_data_in_leaf, '
+                             'min_sum_hessian_in_leaf, min_gain_to_split) or every label of a query is the same')
+    if valid is None or not early_stopping_rounds:
+        best_iter = len(trees)
+    elif best_iter < len(trees):
+        score.zero_()                      # the same float64 additions in the same order: the bits of iteration best_iter
+        for tree in trees[:best_iter]:
+            add_tree(bins, tree, score)
+    trees = trees[:best_iter]
+    train_leaf = torch.stack(leaves[:best_iter], dim=1).contiguous() if keep_leaves else None
+    return TrainResult(forest_from_trees(trees, F, feature_names), best_iter, history, score, trees, train_leaf)
+
+
+def write_lightgbm_model(forest, feature_names=None):
+    """A text dump of ``forest`` in the layout of LightGBM's v3 model files, holding what
+    :func:`~otto_amd.ranker.forest.parse_lightgbm_model` reads, and read back by it to identical arrays (every float is
+    written with ``repr``, which round-trips a float64). It carries no ``feature_infos``, ``split_gain``, ``leaf_count`` or
+    ``internal_*`` lines; whether LightGBM's own loader accepts it has not been tried."""
+    names = list(feature_names) if feature_names is not None else list(forest.feature_names)
+    if len(names) != forest.n_features:
+        raise ValueError(f'{len(names)} feature_names for {forest.n_features} features')
+    if any((not str(s)) or any(ch.isspace() for ch in str(s)) for s in names):
+        raise ValueError('a feature name must be non-empty and hold no white space')
+    ints = lambda a: ' '.join(str(int(x)) for x in a)
+    floats = lambda a: ' '.join(repr(float(x)) for x in a)
+    blocks = []
+    for t in range(forest.n_trees):
+        n0, n1, l0, l1 = (int(x) for x in (forest.node_off[t], forest.node_off[t + 1], forest.leaf_off[t], forest.leaf_off[t + 1]))
+        lines = [f'Tree={t}', f'num_leaves={l1 - l0}', 'num_cat=0']
+        if l1 - l0 > 1:
+            lines += [f'split_feature={ints(forest.split_feature[n0:n1])}', f'threshold={floats(forest.threshold[n0:n1])}',
+                      f'decision_type={ints(forest.decision_type[n0:n1])}', f'left_child={ints(forest.left_child[n0:n1])}',
+                      f'right_child={ints(forest.right_child[n0:n1])}']
+        lines += [f'leaf_value={floats(forest.leaf_value[l0:l1])}', 'is_linear=0', 'shrinkage=1']
+        blocks.append('\n'.join(lines) + '\n\n')
+    head = ['tree', 'version=v3', 'num_class=1', 'num_tree_per_iteration=1', 'label_index=0',
+            f'max_feature_idx={forest.n_features - 1}', f'objective={forest.objective or "lambdarank"}',
+            'feature_names=' + ' '.join(str(s) for s in names), 'tree_sizes=' + ' '.join(str(len(b)) for b in blocks)]
+    return '\n'.join(head) + '\n\n' + ''.join(blocks) + 'end of trees\n'
