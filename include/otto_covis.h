@@ -117,9 +117,8 @@ int otto_covis_stats(otto_covis_ctx* ctx, int64_t* out /* [OTTO_COVIS_STAT_COUNT
  *   "l_cap": expanded pairs per hash partition of a heavy aid_x in the wide table layout (default 6144; the packed
  *            2^14-slot layout takes twice as many);
  *   "partition": 1 (default) bucket heavy aids' pairs by partition once, 0 re-read and filter per partition;
- *   "fused": pair-expand kernel when no filter kind is configured: 2 (default) component lists (k_expand_lists), 1 one record per
- *            pair from registers (k_expand_fused), 0 class-sorted kernels;
- *   "fast_path": 1 (default) gap-free window shortcut in the pair-expand kernels;
+ *   "lists": 1 (default) component lists (k_expand_lists) when no filter kind is configured, 0 the class-sorted k_expand kernels
+ *            for every kind (the independent pair-expand that the cross-check tests compare against);
  *   "bucket_index": 1 (default) group the runs by aid_x with LDS atomics per 1024-aid bucket, 0 one global atomic per run;
  *   "packed_heavy": packed 12-bit-counter tables for heavy aids with fewer than 4096 runs: 2 (default) 2^14 slots for aids that
  *                   fit one table, 2^13-slot partitions beyond; 1: 2^14-slot partitions of twice the size; 0: wide tables only;

@@ -6,11 +6,12 @@
 //
 // Pipeline:
 //   winscan  : per session n = min(len, W); exclusive scans of n(n-1) (record slots) and n (run slots)
-//   K1 expand: no filter kinds -> k_expand_fused: one launch over the sessions in memory order, windows of 8 / 16 / 32
-//              lanes held in registers, row loop with wave-mask predicates, gap-free shortcut; filter kinds ->
-//              class-sorted k_expand / k_expand_fast with the LDS ds_min matrix M[class_x][class_y] and filter bits.
-//              Either way: one 4-byte record per deduped pair, grouped by aid_x inside the window (a "run"), plus
-//              one run descriptor per window event
+//   K1 expand: no filter kinds -> k_expand_lists: one launch over the sessions in memory order, windows of 8 / 16 / 32
+//              lanes held in registers, one shared list of distinct aids per time-connected component (row loop with
+//              wave-mask predicates for the windows that are no cliques); filter kinds -> class-sorted k_expand with
+//              the LDS ds_min matrix M[class_x][class_y] and filter bits, one 4-byte record per deduped pair.
+//              Either way: records grouped by aid_x inside the window (a "run"), plus one run descriptor per window
+//              event
 //   index    : runs split into buckets of 1024 consecutive aids, then counted and placed per bucket with LDS atomics
 //              (k_bkt_*; fallback: one 64-bit memory-side atomic per run, k_hist_runs / k_scatter_runs); work-item
 //              lists in three size bins (S/M/L; L items are hash partitions of one heavy aid_x, three table layouts)
@@ -68,23 +69,15 @@ constexpr uint32_t M_EMPTY = 0xFFFFFFFFu;
 constexpr int REC_AID_BITS = 26;
 constexpr uint32_t REC_AID_MASK = (1u << REC_AID_BITS) - 1;
 
-// window classes: size (n <= 8 / 16 / 32 events -> G = 8 / 16 / 32 lanes, 8 / 4 / 2 windows per wave) x
-// "gap-free" (time span of the whole window <= max_gap: every pair of distinct aids is valid, so the first
-// valid pair of (x, y) is (first x, first y) and neither the n^2 ds_min phase nor the M matrix is needed).
-constexpr int N_WIN_CLASSES = 6;
-__global__ void k_classify(const int64_t* off, const int32_t* ts, int W, int max_gap, int use_fast, int64_t n_sess,
-                           uint8_t* cls_out) {
+// window classes of k_expand: size (n <= 8 / 16 / 32 events -> G = 8 / 16 / 32 lanes, 8 / 4 / 2 windows per wave)
+constexpr int N_WIN_CLASSES = 3;
+__global__ void k_classify(const int64_t* off, int W, int64_t n_sess, uint8_t* cls_out) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_sess) return;
     const int64_t lo = off[s], hi = off[s + 1];
     int64_t n = hi - lo;
     n = n < W ? n : W;
-    uint8_t c = 255;
-    if (n >= 2) {
-        c = n <= 8 ? 0 : (n <= 16 ? 1 : 2);
-        if (use_fast && (int64_t)ts[hi - 1] - (int64_t)ts[hi - n] <= (int64_t)max_gap) c += 3;
-    }
-    cls_out[s] = c;
+    cls_out[s] = n >= 2 ? (n <= 8 ? 0 : (n <= 16 ? 1 : 2)) : 255;
 }
 struct WinClass {   // 1 if session i falls in class `cls`
     const uint8_t* c;
@@ -293,107 +286,7 @@ __global__ __launch_bounds__(256) void k_expand(ExpandArgs a) {
     }
 }
 
-// Gap-free windows (no filter kinds): class ids, then per class row r the columns are simply the other class
-// representatives -- record = aid_y | type(first y) << 26, time extra of the first x. No M, no LDS atomics.
-template <int G, bool TIME>
-__global__ __launch_bounds__(256) void k_expand_fast(ExpandArgs a) {
-    constexpr int WPW = 64 / G;
-    __shared__ uint32_t s_aid[4][WPW][G];
-    const int wv = threadIdx.x >> 6;
-    const unsigned lane = lane_id();
-    const int grp = lane / G, g = lane % G;
-    const unsigned grp_shift = grp * G;
-    const uint64_t gmask = (1ull << G) - 1ull;
-    uint32_t* av = s_aid[wv][grp];
-    const int64_t wave_global = (int64_t)blockIdx.x * 4 + wv;
-    const int64_t wave_stride = (int64_t)gridDim.x * 4;
-    for (int64_t w0 = wave_global * WPW; w0 < a.n_list; w0 += wave_stride * WPW) {
-        const int64_t li = w0 + grp;
-        int n = 0;
-        int64_t wstart = 0;
-        uint64_t pbase = 0, ebase = 0;
-        if (li < a.n_list) {
-            const int64_t s = a.sess_list[li];
-            const int64_t lo = a.sess_off[s], hi = a.sess_off[s + 1];
-            const int64_t len = hi - lo;
-            n = (int)(len < a.window ? len : a.window);
-            wstart = hi - n;
-            pbase = a.pair_base[s];
-            ebase = a.ev_base[s];
-        }
-        int nmax = 0;
-#pragma unroll
-        for (int q = 0; q < WPW; ++q) {
-            const int nq = __builtin_amdgcn_readlane(n, q * G);
-            nmax = nq > nmax ? nq : nmax;
-        }
-        const int nmax4 = (nmax + 3) & ~3;
-        uint32_t aid = 0xFFFFFFFFu, ty = 0, extra = 0;
-        if (g < n) {
-            aid = a.aid[wstart + g];
-            ty = a.type[wstart + g];
-            if (TIME) {
-                const int32_t t = a.ts[wstart + g];
-                extra = time_extra(a, t);
-            }
-        }
-        av[g] = aid;
-        wave_lds_sync();
-        int cls = g;
-        for (int j0 = nmax4 - 4; j0 >= 0; j0 -= 4) {
-            uint32_t ax[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ax[u] = av[(j0 + u) & (G - 1)];
-#pragma unroll
-            for (int u = 3; u >= 0; --u)
-                if (j0 + u < n && ax[u] == aid) cls = j0 + u;
-        }
-        const bool rep = g < n && cls == g;
-        const uint32_t repm = (uint32_t)((__ballot(rep) >> grp_shift) & gmask);     // class representatives of my window
-        const uint32_t d = __popc(repm);
-        const uint32_t below = __popc(repm & ((1u << g) - 1u));                      // representatives before me
-        const uint32_t rec_word = aid | (ty << REC_AID_BITS);
-        // row r (a representative) lists every other representative in position order: d - 1 records
-        for (int r = 0; r < nmax; ++r) {
-            const bool row = (repm >> r) & 1u;                // uniform inside the window
-            // time extra of the row's event: read with ALL lanes active (the source lane g == r sits out the branch)
-            const uint32_t xr = TIME ? (uint32_t)__shfl((int)extra, (int)(grp_shift + r), 64) : 0u;
-            if (row && rep && g != r) {
-                const uint32_t rowrank = __popc(repm & ((1u << r) - 1u));
-                const uint32_t rank = below - (g > r ? 1u : 0u);
-                const uint64_t slot = a.rec_base + pbase + (uint64_t)rowrank * (d - 1) + rank;
-                a.rec[slot] = rec_word;
-                if (TIME) a.tw[slot] = xr;
-            }
-        }
-        if (g < n) {
-            const bool has = rep && d > 1;
-            a.run_x[a.run_base + ebase + g] = has ? aid : RUN_X_EMPTY;
-            a.run_desc[a.run_base + ebase + g] = make_desc(a.rec_base + pbase + (uint64_t)below * (d - 1), has ? d - 1 : 0u);
-        }
-        wave_lds_sync();
-    }
-}
-
-// ---- fused, register-only expansion (no filter kinds) -------------------------------------------------
-// Sessions are taken in MEMORY ORDER, 64 per wave round: the wave reads their offsets / slot bases coalesced,
-// sorts them by window class (size n <= 8 / 16 / 32  x  gap-free or not) into a wave-private LDS task list
-// with ballots, then runs the six classes back to back with G = 8 / 16 / 32 lanes per window. Neighbouring
-// sessions are expanded by the same wave, so every event cache line is fetched once (the class-sorted launches
-// above fetch it up to 6x), and there is one launch instead of six.
-//
-// A window lives in registers: lane g = event j; `same` = lanes of my window holding my aid (my class),
-// class id = first such lane, reps = first lanes. Row class r owns slots [rank(r) * (d - 1), +d - 1) of the
-// window (d distinct aids). Masks are kept in WAVE bit space (lane numbers), so a ballot is used as it comes.
-//
-// gap-free windows (span <= max_gap: every pair of distinct aids is valid, first pair = (first x, first y)):
-//   loop over row ranks k: every rep lane stores its own word into row k (skipping its own row).
-// general windows: row loop over i (uniform): pair (i, g) valid if aids differ and |dt| <= max_gap. The class
-//   pair (class(i), my class) is taken by the FIRST valid (i, j) in lexicographic order = first row whose valid
-//   mask meets my class (`done` bit per x class: identical in all lanes of a class because it only depends on
-//   ballot & same), lowest valid lane of the class. The row's fill level = number of column classes that
-//   already took the pair. Run length of class r = popc(done of r): the relation "x and y have a valid pair" is
-//   symmetric (no filter masks here). No M matrix, no LDS atomics: LDS only broadcasts one uint4 per row.
+// ---- no filter kinds: sessions in memory order, windows held in registers (k_expand_lists) ------------------------
 struct TaskPre {            // one task of a lane's window, its event already requested from memory
     int n;
     uint64_t pb, eb;
@@ -403,7 +296,7 @@ struct TaskPre {            // one task of a lane's window, its event already re
 
 // task `t0 + lane / G` of the list segment [b0, b0 + c): window descriptor from LDS, then the lane's event loads
 // are ISSUED here -- the caller runs the previous task's row loop before touching the values.
-template <int G, bool NEED_TS>
+template <int G>
 __device__ __forceinline__ TaskPre fetch_task(const ExpandArgs& a, const uint4* ta, const uint2* tb, int b0, int c, int t0,
                                               unsigned lane) {
     TaskPre p;
@@ -422,208 +315,9 @@ __device__ __forceinline__ TaskPre fetch_task(const ExpandArgs& a, const uint4* 
     if (g < p.n) {
         p.aid = a.aid[ws + g];
         p.ty = a.type[ws + g];
-        if (NEED_TS) p.t = a.ts[ws + g];
+        p.t = a.ts[ws + g];
     }
     return p;
-}
-
-template <int G, bool TIME, bool FAST, bool DBG>
-__device__ __forceinline__ void expand_task_reg(const ExpandArgs& a, uint4* ev, uint32_t* xs, unsigned lane, const TaskPre& tp) {
-    constexpr int WPW = 64 / G;
-    const int n = tp.n;
-    const uint64_t pbase = tp.pb, ebase = tp.eb;
-    const int g = (int)(lane & (G - 1));
-    const unsigned w0 = lane - g;                               // first lane of my window
-    uint4* evw = ev + w0;
-    int nmax = 0;
-#pragma unroll
-    for (int q = 0; q < WPW; ++q) {
-        const int nq = __builtin_amdgcn_readlane(n, q * G);
-        nmax = nq > nmax ? nq : nmax;
-    }
-    const int nmax4 = (nmax + 3) & ~3;
-    const bool act = g < n;
-    const uint32_t aid = tp.aid, ty = tp.ty;
-    const int32_t t = tp.t;
-    uint32_t extra = 0;
-    if (TIME && act) extra = time_extra(a, t);
-    ev[lane] = make_uint4(aid, (uint32_t)t, 0u, extra);
-    wave_lds_sync();
-    uint32_t same = 0;                                          // window-relative bits
-    for (int j0 = 0; j0 < nmax4; j0 += 4) {
-        uint32_t ax[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) ax[u] = evw[(j0 + u) & (G - 1)].x;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) same |= (ax[u] == aid ? 1u : 0u) << ((j0 + u) & 31);
-    }
-    same &= n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
-    const int cls = act ? (int)__builtin_ctz(same) : g;
-    const bool rep = act && cls == g;
-    // wave-space 64-bit masks of my window / the lanes of my window below me
-    const uint64_t win64 = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << w0;
-    const uint64_t lw64 = win64 & ((1ull << lane) - 1ull);
-    const uint64_t rep64 = __ballot(rep);
-    const uint32_t d1 = (uint32_t)__popcll(rep64 & win64) - 1u;                  // records a full row holds
-    uint32_t* recp = a.rec + (a.rec_base + pbase);
-    uint32_t* twp = TIME ? a.tw + (a.rec_base + pbase) : nullptr;
-    const uint32_t word = aid | (ty << REC_AID_BITS);
-    if (FAST) {
-        const uint32_t below = (uint32_t)__popcll(rep64 & lw64);                 // my rank among the reps
-        if (TIME) {
-            if (rep) xs[w0 + below] = extra;
-            wave_lds_sync();
-        }
-        int dmax = 0;
-#pragma unroll
-        for (int q = 0; q < WPW; ++q) {
-            const int dq = __builtin_amdgcn_readlane((int)d1, q * G) + 1;
-            dmax = dq > dmax ? dq : dmax;
-        }
-        if (DBG && (a.debug & 2)) dmax = 0;
-        for (int k = 0; k < dmax; ++k) {
-            if (!(DBG && (a.debug & 1)) && rep && (uint32_t)k <= d1 && (uint32_t)k != below) {
-                const uint32_t o = (uint32_t)k * d1 + below - (below > (uint32_t)k ? 1u : 0u);
-                recp[o] = word;
-                if (TIME) twp[o] = xs[w0 + k];
-            }
-        }
-        if (act) {
-            a.run_x[a.run_base + ebase + g] = (rep && d1) ? aid : RUN_X_EMPTY;
-            a.run_desc[a.run_base + ebase + g] = make_desc(a.rec_base + pbase + (uint64_t)below * d1, rep ? d1 : 0u);
-        }
-        wave_lds_sync();
-        return;
-    }
-    const uint32_t rb = (uint32_t)__popcll(rep64 & win64 & ((1ull << (w0 + cls)) - 1ull)) * d1;   // first slot of my class's row
-    reinterpret_cast<uint32_t*>(&ev[lane])[2] = (uint32_t)cls | (rb << 5);
-    wave_lds_sync();
-    const uint64_t same64 = (uint64_t)same << w0;
-    const uint64_t samelow64 = same64 & lw64;
-    const uint32_t nlim = act ? (uint32_t)n : 0u;
-    uint32_t done = 0;
-    uint4 e = evw[0];
-    if (DBG && (a.debug & 2)) nmax = 0;
-    // Predicates are kept as wave masks (v_cmp writes them, s_and combines them, exec takes them): the whole wave is
-    // active here, so a mask IS the ballot -- no select/compare round trip per ballot.
-    constexpr int NE = 33, EQ = 32, ULT = 36, ULE = 37;
-    for (int i = 0; i < nmax; ++i) {
-        const uint4 en = evw[(i + 1) & (G - 1)];                // next row in flight
-        const uint32_t dA = e.y - (uint32_t)t, dB = (uint32_t)t - e.y;
-        const uint32_t ad = dA < dB ? dA : dB;                    // |dt| (|dt| < 2^31)
-        const uint64_t V = __builtin_amdgcn_uicmp((uint32_t)i, nlim, ULT) & __builtin_amdgcn_uicmp(e.x, aid, NE) &
-                           __builtin_amdgcn_uicmp(ad, (uint32_t)a.max_gap, ULE);        // valid pairs (i, lane)
-        if (V != 0) {                                             // uniform: rows without any valid pair cost nothing more
-            const uint32_t bit = 1u << (e.z & 31u);               // x class of this row
-            const uint64_t S = __builtin_amdgcn_uicmp(done & bit, 0u, NE);              // my class already took (x class, me)
-            const uint64_t M = __builtin_amdgcn_uicmpl(V & same64, 0ull, NE);           // my class meets this row
-            const uint64_t F = __builtin_amdgcn_uicmpl(V & samelow64, 0ull, EQ);        // no lower lane of my class is valid
-            const uint64_t E = V & ~S & F;                                              // lanes that emit
-            const uint64_t D = rep64 & S;                                               // column classes already in the row
-            if (__builtin_amdgcn_inverse_ballot_w64(M)) done |= bit;
-            if (__builtin_amdgcn_inverse_ballot_w64(E) && !(DBG && (a.debug & 1))) {
-                const uint32_t o = (e.z >> 5) + (uint32_t)__popcll(D & win64) + (uint32_t)__popcll(E & lw64);
-                recp[o] = word;
-                if (TIME) twp[o] = e.w;
-            }
-        }
-        e = en;
-    }
-    if (act) {
-        const uint32_t len = rep ? __popc(done) : 0u;
-        a.run_x[a.run_base + ebase + g] = len ? aid : RUN_X_EMPTY;
-        a.run_desc[a.run_base + ebase + g] = make_desc(a.rec_base + pbase + rb, len);
-    }
-    wave_lds_sync();
-}
-
-// DBG: the timing diagnostics of ExpandArgs::debug are compiled into a second instantiation only
-template <bool TIME, bool DBG>
-__global__ __launch_bounds__(256) void k_expand_fused(ExpandArgs a, int64_t n_sess, int use_fast) {
-    __shared__ uint4 s_ev[4][64];
-    __shared__ uint32_t s_xs[4][TIME ? 64 : 1];
-    __shared__ uint4 s_ta[4][64];       // task: wstart lo, wstart hi | n << 16, pair_base lo, hi
-    __shared__ uint2 s_tb[4][64];       //       ev_base lo, hi
-    const int wv = threadIdx.x >> 6;
-    const unsigned lane = lane_id();
-    uint4* ev = s_ev[wv];
-    uint32_t* xs = s_xs[wv];
-    uint4* ta = s_ta[wv];
-    uint2* tb = s_tb[wv];
-    const int64_t n_tiles = (n_sess + 63) / 64;
-    const int64_t tile_stride = (int64_t)gridDim.x * 4;
-    // session metadata of a tile (one session per lane), requested one tile ahead
-    struct TilePre { int64_t lo, hi; uint64_t pb, eb; };
-    auto fetch_tile = [&](int64_t tile) {
-        TilePre q;
-        q.lo = q.hi = 0; q.pb = q.eb = 0;
-        const int64_t s = tile * 64 + lane;
-        if (tile < n_tiles && s < n_sess) {
-            q.lo = a.sess_off[s]; q.hi = a.sess_off[s + 1];
-            q.pb = a.pair_base[s]; q.eb = a.ev_base[s];
-        }
-        return q;
-    };
-    int64_t tile = (int64_t)blockIdx.x * 4 + wv;
-    TilePre cur = fetch_tile(tile);
-    for (; tile < n_tiles; tile += tile_stride) {
-        const TilePre nxt = fetch_tile(tile + tile_stride);
-        const int64_t len = cur.hi - cur.lo;
-        const int n = (int)(len < a.window ? len : a.window);
-        const int64_t wstart = cur.hi - n;
-        int c6 = 6;
-        if (n >= 2) {
-            c6 = n <= 8 ? 0 : (n <= 16 ? 1 : 2);
-            if (use_fast && (int64_t)a.ts[cur.hi - 1] - (int64_t)a.ts[wstart] <= (int64_t)a.max_gap) c6 += 3;
-        }
-        int cnt[6], base[6];
-        int below = 0, acc = 0;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            const uint64_t m = __ballot(c6 == q);
-            cnt[q] = __popcll(m);
-            base[q] = acc;
-            if (c6 == q) below = acc + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            acc += cnt[q];
-        }
-        if (c6 < 6) {
-            ta[below] = make_uint4((uint32_t)wstart, (uint32_t)((uint64_t)wstart >> 32) | ((uint32_t)n << 16), (uint32_t)cur.pb, (uint32_t)(cur.pb >> 32));
-            tb[below] = make_uint2((uint32_t)cur.eb, (uint32_t)(cur.eb >> 32));
-        }
-        wave_lds_sync();
-        // classes run back to back; the events of the NEXT task (same class, or the first task of the next class)
-        // are requested before the current task's row loop
-        auto run_class = [&](auto gtag, auto ftag, auto gntag, auto fntag, int q, const TaskPre& first) {
-            constexpr int G = decltype(gtag)::value;
-            constexpr bool FAST = decltype(ftag)::value;
-            constexpr int GN = decltype(gntag)::value;
-            constexpr bool FASTN = decltype(fntag)::value;
-            constexpr int WPW = 64 / G;
-            const int b0 = base[q], c = cnt[q];
-            const int bn = q < 5 ? base[q < 5 ? q + 1 : 5] : 0, cn = q < 5 ? cnt[q < 5 ? q + 1 : 5] : 0;
-            TaskPre tp = first;
-            for (int t0 = 0; t0 < c; t0 += WPW) {
-                TaskPre nx;
-                if (t0 + WPW < c) nx = fetch_task<G, !FAST || TIME>(a, ta, tb, b0, c, t0 + WPW, lane);
-                else nx = fetch_task<GN, !FASTN || TIME>(a, ta, tb, bn, cn, 0, lane);
-                expand_task_reg<G, TIME, FAST, DBG>(a, ev, xs, lane, tp);
-                tp = nx;
-            }
-            if (c == 0) tp = fetch_task<GN, !FASTN || TIME>(a, ta, tb, bn, cn, 0, lane);
-            return tp;
-        };
-        using I8 = std::integral_constant<int, 8>;
-        using I16 = std::integral_constant<int, 16>;
-        using I32 = std::integral_constant<int, 32>;
-        TaskPre tp = fetch_task<8, true>(a, ta, tb, base[0], cnt[0], 0, lane);
-        tp = run_class(I8{}, std::false_type{}, I16{}, std::false_type{}, 0, tp);
-        tp = run_class(I16{}, std::false_type{}, I32{}, std::false_type{}, 1, tp);
-        tp = run_class(I32{}, std::false_type{}, I8{}, std::true_type{}, 2, tp);
-        tp = run_class(I8{}, std::true_type{}, I16{}, std::true_type{}, 3, tp);
-        tp = run_class(I16{}, std::true_type{}, I32{}, std::true_type{}, 4, tp);
-        tp = run_class(I32{}, std::true_type{}, I32{}, std::true_type{}, 5, tp);
-        cur = nxt;
-    }
 }
 
 // ---- component lists (no filter kinds): a window's pairs WITHOUT writing one record per pair ---------------------
@@ -639,11 +333,23 @@ __global__ __launch_bounds__(256) void k_expand_fused(ExpandArgs a, int64_t n_se
 // and the run descriptor of every aid in it points at the shared list with the position of its own entry (sp), which
 // the gather skips. Only an aid with a repeated partner (x and y together in two components: 2.4 % of the runs of
 // multi-component windows) gets a private row, written by the component's lanes in one step. Windows with a component
-// that is not a clique, or with unsorted timestamps (1 % of the windows), take the general row loop of
-// expand_task_reg into private rows. The time extra of a shared run is ONE value (the first event of x in the
-// component): tw[list slot of x's own entry].
+// that is not a clique, or with unsorted timestamps (1 % of the windows), take the general row loop below into
+// private rows. The time extra of a shared run is ONE value (the first event of x in the component): tw[list slot
+// of x's own entry].
 // Slots: lists live behind the chunk's pair slots at list_base + ev_base[s] (n per window, dense: neighbouring
 // windows share cache lines); private rows keep the window's old region [pair_base[s], +n(n-1)).
+//
+// A window lives in registers: lane g = event j; `same` = lanes of my window holding my aid (my class),
+// class id = first such lane, reps = first lanes. Masks of the general row loop are kept in WAVE bit space (lane
+// numbers), so a ballot is used as it comes.
+// general windows: row class r owns slots [rank(r) * (d - 1), +d - 1) of the window (d distinct aids). Row loop over
+//   i (uniform): pair (i, g) valid if aids differ and |dt| <= max_gap. The class pair (class(i), my class) is taken
+//   by the FIRST valid (i, j) in lexicographic order = first row whose valid mask meets my class (`done` bit per x
+//   class: identical in all lanes of a class because it only depends on ballot & same), lowest valid lane of the
+//   class. The row's fill level = number of column classes that already took the pair. Run length of class r =
+//   popc(done of r): the relation "x and y have a valid pair" is symmetric (no filter masks here). No M matrix, no
+//   LDS atomics: LDS only broadcasts one uint4 per row. Predicates are kept as wave masks (v_cmp writes them, s_and
+//   combines them, exec takes them): the whole wave is active there, so a mask IS the ballot.
 template <int G, bool TIME, bool DBG>
 __device__ __forceinline__ void expand_task_lists(const ExpandArgs& a, uint4* ev, unsigned lane, const TaskPre& tp) {
     constexpr int WPW = 64 / G;
@@ -749,7 +455,7 @@ __device__ __forceinline__ void expand_task_lists(const ExpandArgs& a, uint4* ev
             if ((lane ^ (unsigned)L) < (unsigned)G) poff += len;                            // lanes of x's window
         }
     }
-    // general windows: the row loop of expand_task_reg (first valid pair per (x class, y class), private rows)
+    // general windows: row loop, first valid pair per (x class, y class), private rows (scheme: comment above)
     uint32_t glen = 0, grb = 0;
     const bool gact = act && general;
     if (__ballot(gact) != 0) {
@@ -814,8 +520,12 @@ __device__ __forceinline__ void expand_task_lists(const ExpandArgs& a, uint4* ev
     wave_lds_sync();
 }
 
-// One launch over the sessions in memory order (as k_expand_fused): 64 sessions per wave round, sorted with ballots
-// into three window size classes (n <= 8 / 16 / 32 -> 8 / 16 / 32 lanes per window) in a wave-private LDS task list.
+// One launch over the sessions in memory order, 64 per wave round: the wave reads their offsets / slot bases
+// coalesced and sorts them with ballots into three window size classes (n <= 8 / 16 / 32 -> 8 / 16 / 32 lanes per
+// window) in a wave-private LDS task list, then runs the classes back to back. Neighbouring sessions are expanded by
+// the same wave, so every event cache line is fetched once (the class-sorted launches of k_expand fetch it up to 3x).
+// The events of the NEXT task (same class, or the first task of the next class) are requested before the current
+// task's row loop. DBG: the timing diagnostics of ExpandArgs::debug are compiled into a second instantiation only.
 template <bool TIME, bool DBG>
 __global__ __launch_bounds__(256, 4) void k_expand_lists(ExpandArgs a, int64_t n_sess) {
     __shared__ uint4 s_ev[4][64];
@@ -871,18 +581,18 @@ __global__ __launch_bounds__(256, 4) void k_expand_lists(ExpandArgs a, int64_t n
             TaskPre tp = first;
             for (int t0 = 0; t0 < c; t0 += WPW) {
                 TaskPre nx;
-                if (t0 + WPW < c) nx = fetch_task<G, true>(a, ta, tb, b0, c, t0 + WPW, lane);
-                else nx = fetch_task<GN, true>(a, ta, tb, bn, cn, 0, lane);
+                if (t0 + WPW < c) nx = fetch_task<G>(a, ta, tb, b0, c, t0 + WPW, lane);
+                else nx = fetch_task<GN>(a, ta, tb, bn, cn, 0, lane);
                 expand_task_lists<G, TIME, DBG>(a, ev, lane, tp);
                 tp = nx;
             }
-            if (c == 0) tp = fetch_task<GN, true>(a, ta, tb, bn, cn, 0, lane);
+            if (c == 0) tp = fetch_task<GN>(a, ta, tb, bn, cn, 0, lane);
             return tp;
         };
         using I8 = std::integral_constant<int, 8>;
         using I16 = std::integral_constant<int, 16>;
         using I32 = std::integral_constant<int, 32>;
-        TaskPre tp = fetch_task<8, true>(a, ta, tb, base[0], cnt[0], 0, lane);
+        TaskPre tp = fetch_task<8>(a, ta, tb, base[0], cnt[0], 0, lane);
         tp = run_class(I8{}, I16{}, 0, tp);
         tp = run_class(I16{}, I32{}, 1, tp);
         tp = run_class(I32{}, I32{}, 2, tp);
@@ -3534,8 +3244,7 @@ struct otto_covis_ctx {
     int64_t sessions = 0;
     // chunk scratch
     OwnedBuf pair_base, ev_base, partial, cls_pos[N_WIN_CLASSES], sess_list, cls_byte;
-    int fast_path = 1;
-    int fused = 2;                 // no filter kind configured: 2 = k_expand_lists (component lists), 1 = k_expand_fused, 0 = class-sorted kernels
+    int lists = 1;                 // option "lists": no filter kind configured: 1 = k_expand_lists (component lists), 0 = class-sorted k_expand
     // index
     bool index_valid = false;
     OwnedBuf cnt64, run_start, run_rank, sorted_desc, item_start, boost, flag, counters;
@@ -3670,16 +3379,13 @@ extern "C" int otto_covis_feed(otto_covis_ctx* c, const uint32_t* d_aid, const i
     OTTO_TRY(device_scan(WinPairs{d_sess_off, p.window}, n_sess, c->pair_base.as<uint64_t>(), c->partial.as<uint64_t>(), s));
     OTTO_TRY(device_scan(WinEvents{d_sess_off, p.window}, n_sess, c->ev_base.as<uint64_t>(), c->partial.as<uint64_t>(), s));
     OTTO_REQUIRE(n_sess < (1ll << 32), "more than 2^32 sessions in one chunk");
-    // no filter kind: one launch over the sessions in memory order (k_expand_lists / k_expand_fused), no class lists.
-    // Otherwise window classes (3 sizes x gap-free or not): one session list, six segments
-    const bool fused = p.n_filters == 0 && c->fused;
-    const bool lists = fused && c->fused == 2;             // component lists: n list slots per window behind the pair slots
-    if (!fused) {
-        const int use_fast = p.n_filters == 0 && c->fast_path;
+    // no filter kind: one launch over the sessions in memory order (k_expand_lists), no class lists, n list slots per
+    // window behind the pair slots. Otherwise window classes (3 sizes): one session list, three segments
+    const bool lists = p.n_filters == 0 && c->lists;
+    if (!lists) {
         OTTO_TRY(c->cls_byte.ensure((size_t)n_sess, 0, s));
         OTTO_TRY(c->sess_list.ensure((size_t)(n_sess + 1) * 4, 0, s));
-        k_classify<<<(unsigned)((n_sess + 255) / 256), 256, 0, s>>>(d_sess_off, d_ts, p.window, p.max_gap, use_fast, n_sess,
-                                                                     c->cls_byte.as<uint8_t>());
+        k_classify<<<(unsigned)((n_sess + 255) / 256), 256, 0, s>>>(d_sess_off, p.window, n_sess, c->cls_byte.as<uint8_t>());
         OTTO_HIP(hipGetLastError());
         for (int cl = 0; cl < N_WIN_CLASSES; ++cl) {
             OTTO_TRY(c->cls_pos[cl].ensure((size_t)(n_sess + 1) * 8, 0, s));
@@ -3690,7 +3396,7 @@ extern "C" int otto_covis_feed(otto_covis_ctx* c, const uint32_t* d_aid, const i
     uint64_t totals[2 + N_WIN_CLASSES];                    // pairs, events (, sessions per class)
     OTTO_HIP(hipMemcpyAsync(&totals[0], c->pair_base.as<uint64_t>() + n_sess, 8, hipMemcpyDeviceToHost, s));
     OTTO_HIP(hipMemcpyAsync(&totals[1], c->ev_base.as<uint64_t>() + n_sess, 8, hipMemcpyDeviceToHost, s));
-    for (int cl = 0; !fused && cl < N_WIN_CLASSES; ++cl)
+    for (int cl = 0; !lists && cl < N_WIN_CLASSES; ++cl)
         OTTO_HIP(hipMemcpyAsync(&totals[2 + cl], c->cls_pos[cl].as<uint64_t>() + n_sess, 8, hipMemcpyDeviceToHost, s));
     OTTO_HIP(hipStreamSynchronize(s));
     const uint64_t n_ev = totals[1];
@@ -3712,16 +3418,14 @@ extern "C" int otto_covis_feed(otto_covis_ctx* c, const uint32_t* d_aid, const i
     a.window = p.window; a.max_gap = p.max_gap;
     a.t0 = p.ts_min; a.tspan = (int64_t)p.ts_max - (int64_t)p.ts_min;
     const int timed = p.want_time ? 1 : 0;
-    if (fused) {
+    if (lists) {
         a.list_base = c->rec_used + totals[0];
         a.debug = c->debug_skip >> 4;
         const int dbg = a.debug ? 1 : 0;
-        static const void* const kernels[2][2][2] = {      // [lists][TIME][DBG]
-            {{(const void*)k_expand_fused<false, false>, (const void*)k_expand_fused<false, true>},
-             {(const void*)k_expand_fused<true, false>, (const void*)k_expand_fused<true, true>}},
-            {{(const void*)k_expand_lists<false, false>, (const void*)k_expand_lists<false, true>},
-             {(const void*)k_expand_lists<true, false>, (const void*)k_expand_lists<true, true>}}};
-        const void* kern = kernels[lists][timed][dbg];
+        static const void* const kernels[2][2] = {         // [TIME][DBG]
+            {(const void*)k_expand_lists<false, false>, (const void*)k_expand_lists<false, true>},
+            {(const void*)k_expand_lists<true, false>, (const void*)k_expand_lists<true, true>}};
+        const void* kern = kernels[timed][dbg];
         const int64_t tiles = (n_sess + 63) / 64;
         const int64_t blocks = (tiles + 3) / 4;
         int per_cu = 0, n_cu = 0, dev = 0;
@@ -3730,8 +3434,8 @@ extern "C" int otto_covis_feed(otto_covis_ctx* c, const uint32_t* d_aid, const i
         OTTO_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0));
         const int64_t resident = (int64_t)(per_cu > 0 ? per_cu : 4) * (n_cu > 0 ? n_cu : 256);   // one round of resident workgroups
         const int grid = (int)(blocks < resident ? blocks : resident);
-        kname(c, OTTO_COVIS_T_EXPAND, lists ? "k_expand_lists<%s, %s>" : "k_expand_fused<%s, %s>", timed ? "true" : "false", dbg ? "true" : "false");
-        void* args[] = {&a, &n_sess, &c->fast_path};       // (ExpandArgs, n_sess) for k_expand_lists, (ExpandArgs, n_sess, use_fast) for k_expand_fused
+        kname(c, OTTO_COVIS_T_EXPAND, "k_expand_lists<%s, %s>", timed ? "true" : "false", dbg ? "true" : "false");
+        void* args[] = {&a, &n_sess};
         OTTO_HIP(hipLaunchKernel(kern, dim3(grid), dim3(256), args, 0, s));
     } else {
         ClassFill cf;
@@ -3746,11 +3450,7 @@ extern "C" int otto_covis_feed(otto_covis_ctx* c, const uint32_t* d_aid, const i
         const int filt = p.n_filters > 0 ? 1 : 0;
         for (int f = 0; f < p.n_filters; ++f) a.fmask[f] = p.filter_mask[f];
         using ExpandFn = void (*)(ExpandArgs);
-        static const ExpandFn gap_free[3][2] = {           // [size class][TIME]
-            {k_expand_fast<8, false>, k_expand_fast<8, true>},
-            {k_expand_fast<16, false>, k_expand_fast<16, true>},
-            {k_expand_fast<32, false>, k_expand_fast<32, true>}};
-        static const ExpandFn general[3][2][2] = {         // [size class][TIME][FILT]
+        static const ExpandFn kernels[N_WIN_CLASSES][2][2] = {   // [size class][TIME][FILT]
             {{k_expand<8, false, false>, k_expand<8, false, true>}, {k_expand<8, true, false>, k_expand<8, true, true>}},
             {{k_expand<16, false, false>, k_expand<16, false, true>}, {k_expand<16, true, false>, k_expand<16, true, true>}},
             {{k_expand<32, false, false>, k_expand<32, false, true>}, {k_expand<32, true, false>, k_expand<32, true, true>}}};
@@ -3758,15 +3458,12 @@ extern "C" int otto_covis_feed(otto_covis_ctx* c, const uint32_t* d_aid, const i
             a.sess_list = c->sess_list.as<uint32_t>() + cf.base[cl];
             a.n_list = (int64_t)totals[2 + cl];
             if (a.n_list == 0) continue;
-            const int size_cl = cl % 3;                    // G = 8 / 16 / 32 lanes per window
-            const bool fast = cl >= 3;
-            const int wpw = size_cl == 0 ? 8 : (size_cl == 1 ? 4 : 2);
+            const int wpw = 8 >> cl;                       // G = 8 / 16 / 32 lanes per window
             const int64_t waves = (a.n_list + wpw - 1) / wpw;
             const int64_t blocks = (waves + 3) / 4;
             const int grid = (int)(blocks < 256 * 16 ? blocks : 256 * 16);
-            const ExpandFn kern = fast ? gap_free[size_cl][timed] : general[size_cl][timed][filt];
-            kname(c, OTTO_COVIS_T_EXPAND, fast ? "k_expand_fast<%d, %s>" : "k_expand<%d, %s, %s>", 8 << size_cl, timed ? "true" : "false", filt ? "true" : "false");
-            kern<<<grid, 256, 0, s>>>(a);
+            kname(c, OTTO_COVIS_T_EXPAND, "k_expand<%d, %s, %s>", 8 << cl, timed ? "true" : "false", filt ? "true" : "false");
+            kernels[cl][timed][filt]<<<grid, 256, 0, s>>>(a);
             OTTO_HIP(hipGetLastError());
         }
     }
@@ -4264,11 +3961,10 @@ extern "C" int otto_covis_set_option(otto_covis_ctx* c, const char* name, int64_
     if (strcmp(name, "packed_heavy") == 0) { c->packed_heavy = value == 2 ? 2 : (value != 0); c->index_valid = false; return 0; }
     if (strcmp(name, "bucket_index") == 0) { c->bucket_index = value != 0; return 0; }
     if (strcmp(name, "guess") == 0) { c->guess = value != 0; return 0; }           // threshold guessing on/off (A/B)
-    if (strcmp(name, "fused") == 0) { c->fused = value < 0 ? 0 : (value > 2 ? 2 : (int)value); return 0; }   // 2 component lists, 1 fused register rows, 0 class-sorted kernels (A/B)
+    if (strcmp(name, "lists") == 0) { c->lists = value != 0; return 0; }           // 0: class-sorted k_expand for every kind (cross-check path)
     if (strcmp(name, "s_wgs") == 0) { c->s_wgs = value < 1 ? 1 : (value > 32 ? 32 : (int)value); return 0; }
     if (strcmp(name, "bkt_sh") == 0) { c->bkt_sh = (int)value; c->index_valid = false; return 0; }
     if (strcmp(name, "hot") == 0) { c->hot = value < 0 ? 0 : (value > 2 ? 2 : (int)value); return 0; }
-    if (strcmp(name, "fast_path") == 0) { c->fast_path = value != 0; return 0; }   // gap-free window kernel on/off (A/B)
     if (strcmp(name, "part_sized") == 0) { c->part_sized = value != 0; return 0; }   // A/B: counted buckets only
     if (strcmp(name, "partition") == 0) {
         // 1 (default): bucket heavy aids' records by hash partition once; 0: every partition re-reads

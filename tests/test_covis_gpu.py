@@ -11,7 +11,7 @@ from otto_amd.covisitation import spec as cs
 
 pytestmark = pytest.mark.gpu
 
-# kind sets: with filter kinds K1 runs the class-sorted M-matrix kernels, without them the fused register kernel
+# kind sets: with filter kinds K1 runs the class-sorted M-matrix kernels, without them the component-list kernel
 NOFILT = ('time_weighted', 'click_weighted', 'cart_weighted', 'order_weighted')
 
 
@@ -67,8 +67,8 @@ def test_product_spec_matches_oracle_spec():
 
 
 @pytest.mark.parametrize('kinds,options', [(cs.ALL_KINDS, None), (('time_weighted', 'click_weighted'), None), (('cart_weighted',), None),
-                                           (('time_weighted', 'click_weighted'), {'fused': 1}), (('cart_weighted',), {'fused': 1})],
-                         ids=['filters-class-kernels', 'lists-time', 'lists', 'fused-rows-time', 'fused-rows'])
+                                           (('time_weighted', 'click_weighted'), {'lists': 0}), (('cart_weighted',), {'lists': 0})],
+                         ids=['filters-class-kernels', 'lists-time', 'lists', 'class-kernels-time', 'class-kernels'])
 def test_pair_expand_records_match_oracle(gpu_device, kinds, options):
     """K1 alone: every window's records equal the oracle's per-window expansion. A run is (aid_x, a list of records);
     a run descriptor with sp != 63 points at a SHARED component list that holds the run's own aid at position sp (not a
@@ -122,11 +122,11 @@ def test_pair_expand_records_match_oracle(gpu_device, kinds, options):
     assert (shared_runs > 0) == lists
 
 
-@pytest.mark.parametrize('kinds', [cs.ALL_KINDS, NOFILT], ids=['all-kinds', 'fused'])
+@pytest.mark.parametrize('kinds', [cs.ALL_KINDS, NOFILT], ids=['all-kinds', 'lists'])
 @pytest.mark.parametrize('n_sessions,n_aids,seed', [(3000, 2000, 11), (20000, 60, 12), (800, 1855603, 13)])
 def test_topk_all_kinds_match_oracle(gpu_device, n_sessions, n_aids, seed, kinds):
     """Full pipeline, k=20: small/medium/heavy aids (n_aids=60 makes every aid heavy); all 8 kinds (class-sorted
-    K1) and the four kinds without a filter mask (fused K1)."""
+    K1) and the four kinds without a filter mask (component-list K1)."""
     ev = generate_sessions(n_sessions, n_aids=n_aids, seed=seed)
     st = {}
     want = _oracle_rows(ev, kinds, stats=st)
@@ -187,11 +187,10 @@ def test_topk_type_weights_that_rank_a_single_click_above_other_keys(gpu_device,
     _assert_rows_equal(got, want, kinds)
 
 
-@pytest.mark.parametrize('options', [{'fused': 1}, {'fused': 1, 'fast_path': 0}, {'fused': 0}, {'fused': 0, 'fast_path': 0}],
-                         ids=['fused-rows', 'fused-rows-general-only', 'class-kernels', 'class-kernels-general-only'])
+@pytest.mark.parametrize('options', [{'lists': 0}], ids=['class-kernels'])
 def test_expand_variants_agree(gpu_device, options):
-    """The fused K1 with its gap-free shortcut switched off (every window through the general row loop), and the
-    class-sorted kernels forced for the same kinds, give the oracle's rows too."""
+    """The class-sorted kernels forced for kinds without a filter mask (the second pair-expand implementation) give
+    the oracle's rows too, over two session chunks."""
     ev = generate_sessions(4000, n_aids=700, seed=17)
     want = _oracle_rows(ev, NOFILT)
     _, got = _build(ev, gpu_device, kinds=NOFILT, options=options, chunks=2)
@@ -273,16 +272,35 @@ def test_context_reuse_across_streams_and_groups(gpu_device):
 
 
 def test_removed_options_are_unknown(gpu_device):
-    """`overlap_partition` (partition pass on a side stream) and `p_wgs` (workgroups of the partition scatter) were
-    removed: the library rejects them like any other unknown name, and still accepts a name it kept."""
+    """`overlap_partition` (partition pass on a side stream), `p_wgs` (workgroups of the partition scatter), `fused` and
+    `fast_path` (pair-expand kernels that are gone) were removed: the library rejects them like any other unknown name, and
+    still accepts a name it kept."""
     from otto_amd._lib import OttoError
     from otto_amd.covisitation.engine import CovisBuilder
     b = CovisBuilder(1000, kinds=NOFILT, ts_min=0, ts_max=1, device=gpu_device)
-    for name, value in (('overlap_partition', 1), ('p_wgs', 8)):
+    for name, value in (('overlap_partition', 1), ('p_wgs', 8), ('fused', 1), ('fast_path', 0)):
         with pytest.raises(OttoError, match=f"unknown option '{name}'"):
             b.set_option(name, value)
     b.set_option('s_wgs', 20)
     b.close()
+
+
+def test_lists_option_selects_the_expand_kernels(gpu_device):
+    """What `lists` selects, as `kernel_names()` reports it: by default the component-list kernel alone when no filter
+    kind is configured, with `lists` 0 only class-sorted `k_expand` instantiations, and with a filter kind configured
+    only the filter instantiations `k_expand<..., true>` whatever `lists` says."""
+    ev = generate_sessions(200, n_aids=300, seed=5)
+
+    def expand_names(kinds, options):
+        b, _ = _build(ev, gpu_device, kinds=kinds, options=options)
+        names = b.kernel_names()['expand'].split(' + ')
+        b.close()
+        assert names and all(names)
+        return names
+    assert all(n.startswith('k_expand_lists<') for n in expand_names(NOFILT, None))
+    assert all(n.startswith('k_expand<') for n in expand_names(NOFILT, {'lists': 0}))
+    for options in (None, {'lists': 0}, {'lists': 1}):
+        assert all(n.startswith('k_expand<') and n.endswith(', true>') for n in expand_names(NOFILT + ('click_click',), options))
 
 
 @pytest.mark.parametrize('n_sess', [4095, 4096, 9000])
@@ -324,13 +342,13 @@ def _hub_and_random_events(n_hub, seed):
 
 
 @pytest.mark.parametrize('packed_heavy', [1, 0], ids=['packed-heavy', 'wide-heavy'])
-@pytest.mark.parametrize('kinds,options', [(NOFILT, {'fused': 2}), (NOFILT, {'fused': 1}), (cs.ALL_KINDS, {})],
-                         ids=['lists', 'fused-rows', 'class-kernels'])
+@pytest.mark.parametrize('kinds,options', [(NOFILT, {}), (NOFILT, {'lists': 0}), (cs.ALL_KINDS, {})],
+                         ids=['lists', 'lists-off', 'class-kernels'])
 def test_time_weight_clamps_events_outside_ts_range(gpu_device, kinds, options, packed_heavy):
     """ts_min / ts_max come from the caller (SPEC-COVIS 6: global over all chunks and ranks), so an event may lie outside
     them: its time extra is clamped to [0, 3 * 65536]. Unclamped, t < t0 wrapped to ~2^32 and the packed heavy sums
-    (aid_y << 36 | sum) carried into the aid_y bits. Every expand kernel that computes the extra (component lists, fused
-    register rows, class-sorted kernels), packed and wide heavy layouts, with the aids 7 and 11 above the heavy threshold;
+    (aid_y << 36 | sum) carried into the aid_y bits. Every expand kernel that computes the extra (component lists, class-sorted
+    kernels without and with filter bits), packed and wide heavy layouts, with the aids 7 and 11 above the heavy threshold;
     a narrowed range (events before t0 and after t1) and an empty one (t0 == t1) against the clamping oracle."""
     ev = _hub_and_random_events(4095, seed=91)
     lo, hi = int(ev.ts.min()), int(ev.ts.max())
@@ -349,7 +367,7 @@ def test_time_weight_clamps_events_outside_ts_range(gpu_device, kinds, options, 
 
 
 @pytest.mark.parametrize('options', [{'bucket_index': 0}, {'packed_heavy': 0}, {'guess': 0}, {'partition': 0},
-                                     {'packed_heavy': 0, 'guess': 0, 'bucket_index': 0, 'fused': 0}],
+                                     {'packed_heavy': 0, 'guess': 0, 'bucket_index': 0, 'lists': 0}],
                          ids=['atomic-index', 'wide-heavy', 'no-guess', 'no-partition', 'all-fallbacks'])
 def test_pipeline_options_agree(gpu_device, options):
     """Every A/B switch of the pipeline (global-atomic index, wide layout for all heavy aids, no threshold guessing,
@@ -827,9 +845,8 @@ def test_full_otto_bench_path_bit_exact_and_sampled_oracle(gpu_device, full_otto
     layouts, threshold guessing. Checks:
 
     1. bit for bit against a run that shares none of those code paths: 7 session chunks, class-sorted pair-expand
-       kernels (`fused` 0, `fast_path` 0), global-atomic index (`bucket_index` 0), wide heavy-aid tables
-       (`packed_heavy` 0), two-pass top-k (`guess` 0); and against the register-row pair-expand of round 2 (`fused` 1,
-       one private row per aid and window: one run per distinct aid of a window);
+       kernels (`lists` 0: one private row per aid and window, so one run per distinct aid of a window),
+       global-atomic index (`bucket_index` 0), wide heavy-aid tables (`packed_heavy` 0), two-pass top-k (`guess` 0);
     2. a SAMPLED ORACLE check: ~2,000 `aid_x` stratified over the three size bins of the reduce (the five heaviest aids,
        100 of the heaviest 3 % ~ L bin, 500 of the next 26 % ~ M bin, 1,400 of the rest ~ S bin). The row of `aid_x`
        depends only on the sessions that hold `aid_x`, so the oracle run on exactly those sessions must reproduce the
@@ -840,15 +857,11 @@ def test_full_otto_bench_path_bit_exact_and_sampled_oracle(gpu_device, full_otto
     out1, st1 = _full_run(d, dev, BENCH_KINDS, k, 1, {})
     assert st1['pairs'] > 1_000_000_000 and st1['items_l'] > 0 and st1['items_m'] > 0 and st1['items_s'] > 0
     assert st1['retries'] == 0
-    out2, st2 = _full_run(d, dev, BENCH_KINDS, k, 7, {'fused': 0, 'fast_path': 0, 'bucket_index': 0, 'packed_heavy': 0, 'guess': 0})
+    out2, st2 = _full_run(d, dev, BENCH_KINDS, k, 7, {'lists': 0, 'bucket_index': 0, 'packed_heavy': 0, 'guess': 0})
     # an aid has one run per COMPONENT of a window with the lists, one per window with private rows
     assert st1['pairs'] == st2['pairs'] and st2['runs'] <= st1['runs'] <= 1.1 * st2['runs']
     _assert_outputs_identical(out1, out2, BENCH_KINDS, k, dev)
     del out2
-    out3, st3 = _full_run(d, dev, BENCH_KINDS, k, 1, {'fused': 1})
-    assert st3['pairs'] == st2['pairs'] and st3['runs'] == st2['runs'] and st3['pair_slots'] < st1['pair_slots']
-    _assert_outputs_identical(out1, out3, BENCH_KINDS, k, dev)
-    del out3
     _assert_list_properties(out1, BENCH_KINDS, k, dev, OTTO_N_AIDS)
     # cart_weighted (1,9,6) dominates click_weighted (1,6,3) pair by pair, so its best weight per aid is >= too
     some = out1['click_weighted'][2] > 0
@@ -1002,7 +1015,7 @@ def test_randomized_small_configurations_vs_python_oracle(gpu_device):
     threshold, window / k sweeps) against the literal pure-Python transcription of SPEC-COVIS."""
     rng = np.random.default_rng(2024)
     for trial in range(60):
-        kinds = cs.ALL_KINDS if trial % 3 == 0 else NOFILT      # class-sorted K1 / fused K1
+        kinds = cs.ALL_KINDS if trial % 3 == 0 else NOFILT      # class-sorted K1 / component-list K1
         n_aids = int(rng.choice([2, 3, 5, 9, 40]))
         S = int(rng.integers(1, 60))
         window = int(rng.choice([2, 3, 7, 16, 30, 32]))
@@ -1022,7 +1035,7 @@ def test_randomized_small_configurations_vs_python_oracle(gpu_device):
         sp = co.CovisSpec(window=window, max_gap=gap, kinds=kinds)
         want_pairs = co.covis_pairs_python(ev.aid, ev.ts, ev.type, ev.sess_off, sp)
         want = {kd: co.topk_rows(*co.pairs_dict_to_arrays(want_pairs[kd]), k=k) for kd in kinds}
-        options = {'fast_path': 0} if trial % 3 == 2 else None
+        options = {'lists': 0} if trial % 3 == 2 else None   # NOFILT through the class-sorted kernels
         _, got = _build(ev, gpu_device, kinds=kinds, k=k, window=window, max_gap=gap, chunks=int(rng.integers(1, 4)), options=options)
         try:
             _assert_rows_equal(got, want, kinds)
