@@ -1,0 +1,109 @@
+/*
+ * otto_folds.h -- C-ABI of the fold machinery of the ranker trainer (SPEC-FOLDS): GroupKFold over
+ * the sessions, the index sets of one fold with the negative down-sampling, and the gather of the binned matrix.
+ *
+ * What this replaces in the reference: src/ranker/lgb_trainer.py:81-128, the part of the fold loop in front of lgb.train
+ * (GroupKFold(n_splits=5) over the session ids, train_df.sample(frac=negative_sampling_ratio, random_state=42) over the
+ * negatives of the sessions that have a positive, and the np.unique(..., return_counts=True) that rebuilds the query
+ * sizes). otto_amd/ranker/folds.py drives it and joins it to otto_gbdt.h, otto_forest.h and otto_eval.h.
+ *
+ * Conventions of otto_gbdt.h: 0 or a negative OTTO_E* code plus otto_last_error; caller-owned buffers; all device work on
+ * the caller's stream; no buffer is allocated per call (the *_workspace functions size d_work; error words and counters
+ * live in a per-device scratch the library keeps). A call that can detect an error on the device synchronises the stream
+ * once to read its error words. The feature holds no floating-point arithmetic: every output is pinned bit for bit.
+ *
+ * SPEC-FOLDS.
+ * Inputs. query_off int64 [Q+1] on the device, the row_off of ranker_table: the rows of a session are contiguous and
+ * sessions ascend. label uint8 or int32 [n], n < 2^31: a row is positive iff label > 0 and negative iff label == 0 (a
+ * negative int32 label is refused: OTTO_EINVAL). 2 <= n_splits <= OTTO_FOLDS_MAX_SPLITS (16) and Q >= n_splits, checked
+ * on the host before any launch. A query of more than OTTO_GBDT_MAX_QUERY (1024) rows, or offsets that are not
+ * 0 <= off[q] <= off[q+1] <= n, are detected on the device: the call returns OTTO_EINVAL after the stream has drained
+ * and leaves the outputs unwritten (the trainer refuses such a query anyway, and the bound lets the ordering be a
+ * counting sort). Zero-row queries are legal.
+ *
+ * Fold assignment (otto_folds_group_kfold). c_q = off[q+1] - off[q]. Queries are ordered by c_q descending, and among
+ * equal sizes by q descending: np.argsort(c, kind='stable')[::-1]. Walk that order: each query goes to the fold with the
+ * smallest row total so far (ties: the lowest fold index), then its size is added to that fold. fold_of_query int32 [Q],
+ * fold_rows int64 [n_splits] = the totals at the end. This is scikit-learn's GroupKFold._iter_test_indices with the tie
+ * order pinned: scikit-learn's argsort is unstable, so for equal-sized groups it does not say which group sits at which
+ * position. The sequence of sizes is the same for any tie order, therefore the load trajectory, fold_rows and the
+ * per-fold multiset of group sizes equal scikit-learn's, and the per-group assignment equals scikit-learn's exactly when
+ * all sizes are distinct. (The totals are below 2^31 because n is; the walk may hold them in 32 bits.)
+ *
+ * Index sets of one fold (otto_folds_classify, then otto_folds_emit), 0 <= ratio <= 1, seed a uint64. A row r of query q
+ *   - is a validation row iff fold_of_query[q] == fold; all validation rows are kept;
+ *   - is a training positive iff fold_of_query[q] != fold and label[r] > 0; all training positives are kept;
+ *   - is an eligible negative iff fold_of_query[q] != fold, label[r] == 0 and query q has at least one positive row
+ *     (session_target_sum > 0 in the reference);
+ *   - a query with no positive contributes no training row at all; a row outside every query is in no set.
+ * N = the number of eligible negatives; m = int(round(ratio * N)) on the host (float64 product, half to even): the count
+ * pandas.Series.sample(frac=) returns. key(r) is splitmix64 of the global row index:
+ *     z = seed + (r + 1) * 0x9E3779B97F4A7C15   (mod 2^64)
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     key = z ^ (z >> 31)
+ * Every step is a bijection of the 64-bit values and r -> seed + (r+1)*odd is injective, so distinct rows have distinct
+ * keys and "the m eligible negatives with the smallest keys" is one well-defined set. That set is kept; it does not
+ * depend on the grid, the workgroup size or the order of atomics. pandas' own Mersenne-Twister permutation is
+ * deliberately NOT reproduced: the count, the eligibility rule and determinism under a seed are what the reference pins.
+ * Outputs: train_idx int32 [Mt] ascending (training positives and kept negatives), train_query_off int64 [Qt+1],
+ * train_query int32 [Qt] (the original query of each training query; a query left with no row is dropped, as
+ * np.unique(..., return_counts=True) drops it); val_idx int32 [Mv], val_query_off int64 [Qv+1], val_query int32 [Qv]
+ * (a zero-row query of the fold is dropped too). A training query that has a positive keeps it, so Qt does not depend
+ * on the sample: Mt = P + m with P the training positives.
+ *
+ * Gather (otto_folds_gather_u8). out[f, i] = bins[f, idx[i]]; bins uint8 [F, n] feature-major, idx int32 [m], out uint8
+ * [F, m]. Correct for any idx in range (ascending, descending, repeated); an index outside [0, n) is detected on the
+ * device (its byte is written as 0) and gives OTTO_EINVAL.
+ */
+#ifndef OTTO_FOLDS_H
+#define OTTO_FOLDS_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define OTTO_FOLDS_MAX_SPLITS 16
+#define OTTO_FOLDS_COUNT_WORDS 5
+/* the state byte of a row (d_state) */
+#define OTTO_FOLDS_OUT 0
+#define OTTO_FOLDS_VAL 1
+#define OTTO_FOLDS_POS 2
+#define OTTO_FOLDS_NEG 3
+
+/* bytes of d_work for otto_folds_group_kfold; 0 for refused arguments */
+int64_t otto_folds_kfold_workspace(int64_t Q);
+
+/* d_fold_of_query int32 [Q], d_fold_rows int64 [n_splits]. n: the bound of the offsets (2^31 - 1 when the row count is
+ * not at hand). h_walk_ms float [1] (HOST) or NULL: receives the device time of the sequential walk alone. */
+int otto_folds_group_kfold(const int64_t* d_query_off, int64_t Q, int64_t n, int32_t n_splits, int32_t* d_fold_of_query,
+                           int64_t* d_fold_rows, float* h_walk_ms, void* d_work, int64_t work_bytes, void* stream);
+
+/* bytes of d_state for n rows (n rounded up to whole 16-byte vectors) */
+int64_t otto_folds_state_bytes(int64_t n);
+
+/* The state byte of every row for the fold `fold`. label_bytes: 1 (uint8) or 4 (int32). h_counts int64
+ * [OTTO_FOLDS_COUNT_WORDS] (HOST) = { N eligible negatives, P training positives, Mv validation rows, Qt, Qv }. */
+int otto_folds_classify(const void* d_label, int32_t label_bytes, const int64_t* d_query_off, int64_t Q, int64_t n,
+                        const int32_t* d_fold_of_query, int32_t fold, uint8_t* d_state, int64_t* h_counts, void* stream);
+
+/* bytes of d_work for otto_folds_emit; 0 for refused arguments */
+int64_t otto_folds_emit_workspace(int64_t Q);
+
+/* Keeps the m of the n_eligible eligible negatives of d_state with the smallest keys and writes the six index arrays.
+ * Mt, Qt, Mv, Qv: the sizes the caller allocated (Mt = P + m); every write is checked against them and a d_state that
+ * does not give exactly these sizes returns OTTO_EINVAL. */
+int otto_folds_emit(const uint8_t* d_state, const int64_t* d_query_off, int64_t Q, int64_t n, int64_t n_eligible, int64_t m,
+                    uint64_t seed, int64_t Mt, int64_t Qt, int64_t Mv, int64_t Qv, int32_t* d_train_idx,
+                    int64_t* d_train_query_off, int32_t* d_train_query, int32_t* d_val_idx, int64_t* d_val_query_off,
+                    int32_t* d_val_query, void* d_work, int64_t work_bytes, void* stream);
+
+int otto_folds_gather_u8(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_idx, int64_t m, uint8_t* d_out,
+                         void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

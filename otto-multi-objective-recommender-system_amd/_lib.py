@@ -195,6 +195,15 @@ SIGNATURES = {
     'otto_gbdt_ap_at_k': (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'otto_gbdt_grow_tree': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, C.c_double, C.c_double, C.c_double, C.c_double,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # include/otto_folds.h
+    'otto_folds_kfold_workspace': (_i64, [_i64]),
+    'otto_folds_group_kfold': (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, C.POINTER(C.c_float), _vp, _i64, _vp]),
+    'otto_folds_state_bytes': (_i64, [_i64]),
+    'otto_folds_classify': (_i32, [_vp, _i32, _vp, _i64, _i64, _vp, _i32, _vp, _p_i64, _vp]),
+    'otto_folds_emit_workspace': (_i64, [_i64]),
+    'otto_folds_emit': (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, C.c_uint64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _i64, _vp]),
+    'otto_folds_gather_u8': (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None
