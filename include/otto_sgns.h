@@ -1,0 +1,136 @@
+/*
+ * otto_sgns.h -- C-ABI of the skip-gram negative-sampling (SGNS) aid embedding trainer (SPEC-SGNS):
+ * the negative-sampling table, the per-epoch plan (subsampling, compaction, shrunken windows) and the SGD step.
+ *
+ * What this replaces in the reference: src/gensim_fasttext/trainer.py, i.e. fasttext.train_unsupervised with
+ * models/fasttext/config.yaml (skipgram, loss ns, dim 32, ws 10, neg 40, epoch 5, t 1e-4, minn = maxn = 0: no sub-words,
+ * plain SGNS) and gensim Word2Vec(sg=1, negative>0) with models/word2vec/config.yaml. otto_amd/gensim_fasttext/ drives it.
+ * Neither library is part of this build, so the arithmetic below is build-defined and parity-unpinned, as BPR is; the
+ * NumPy restatement tests/sgns_restatement.py is the checker.
+ *
+ * Conventions of otto_folds.h: 0 or a negative OTTO_E* code plus otto_last_error; caller-owned buffers; all device work on
+ * the caller's stream; fixed grids with grid-stride loops; no buffer is allocated per call (the *_workspace functions size
+ * d_work; error words live in a per-device scratch the library keeps). A call that can detect an error on the device
+ * synchronises the stream once to read its error words.
+ *
+ * SPEC-SGNS.
+ * Inputs. aid int32 [E] sorted by (session, ts); sess_off int64 [S+1] with sess_off[0] = 0, ascending, sess_off[S] = E;
+ * a dense aid id space [0, n_aids). Departure: there is no string dictionary and no end-of-sentence token "</s>".
+ *
+ * Vocabulary tables (host, float64 and integers; otto_amd.gensim_fasttext.skipgram.vocab_tables).
+ *   count[a]   events of the aid. count < minCount: out of the vocabulary, keep_q = 0 and weight = 0.
+ *   keep_q[a]  uint32 = min(2^32 - 1, floor(p * 2^32)), p = sqrt(t/f) + t/f, f = count/E (fastText's pdiscard, gensim's
+ *              sample); t = 0: every in-vocabulary aid has keep_q = 2^32 - 1 (always kept).
+ *   weight[a]  uint32 = min(2^32 - 1, floor(count^e * 2^16)), e in {0, 0.5, 0.75, 1} (0.5 fastText, 0.75 gensim).
+ *   cum[a]     uint64 = weight[0] + ... + weight[a] (inclusive), built on the device; total = cum[n_aids - 1].
+ *
+ * Random numbers. mix64 is the splitmix64 finaliser of oracle/mf_oracle.py and csrc/common.h:
+ *     mix64(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *               z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)        (all mod 2^64)
+ *     base(seed, epoch) = mix64(seed ^ (epoch * 0xD1342543DE82EF95))
+ *     ev(e)             = mix64(base ^ (e * 0xA0761D6478BD642F))           e: GLOBAL event index (event0 + local index)
+ *     key(e, stream, w) = mix64(ev(e) ^ (((stream << 20) | w) * 0xE7037ED1A0B428DB))
+ *     key_keep(e)   = key(e, 1, 0)
+ *     key_radius(e) = key(e, 2, 0)
+ *     key_neg(e, k, j, att) = key(e, 3, (k << 10) | (j << 4) | att)   e: the centre's event, k: context slot 0..63 (the
+ *                     ordinal of the pair among the centre's pairs), j: negative slot 0..63, att: redraw attempt 0..15
+ * No draw depends on the grid, the workgroup size or how an epoch is cut into launches.
+ *
+ * Epoch plan (otto_sgns_plan).
+ *  1. event e is kept iff keep_q[aid[e]] != 0 and hi32(key_keep(e)) <= keep_q[aid[e]]   (hi32(x) = x >> 32).
+ *  2. the kept events of each session are compacted in order: tokens 0..T-1; tok_aid, tok_src (the global event index),
+ *     tok_off [S+1] (the token range of each session). The window runs over kept tokens, as in fastText.
+ *  3. token c draws r_c = 1 + ((hi32(key_radius(tok_src[c])) * ws) >> 32), uniform in 1..ws (the shrunken window).
+ *  4. its contexts are the tokens of its session at offsets -r_c..-1, +1..+r_c in that order, clipped at the session's
+ *     ends: left_c = min(r_c, c - lo), right_c = min(r_c, hi - 1 - c); pair_off is the exclusive scan of left + right.
+ *     Pair k of centre c has context token c - left_c + k for k < left_c, else c + 1 + (k - left_c).
+ *  5. an aid outside [0, n_aids), or offsets that break the rule above, are found here: the call returns OTTO_EINVAL
+ *     after the stream has drained and leaves its outputs unwritten. The step kernels never see a bad id.
+ *
+ * Targets of pair k of centre c (e = tok_src[c], ctx = the context token's aid): ctx with label 1, then neg negatives with
+ * label 0; negative j is draw(key_neg(e, k, j, att)) for the first att in 0..15 whose draw differs from ctx, else
+ * (ctx + 1) % n_aids (bpr_negative's rule). draw(key) = upper_bound(cum, mulhi64(key, total)): the first a with
+ * cum[a] > floor(key * total / 2^64). A zero-weight aid is never drawn.
+ *
+ * Update. In, Out float32 [n_aids, d]. For a centre, h = In[centre]; for each of its pairs in order: grad = 0; for each
+ * target t in order: x = <h, Out[t]>, g = lr * (label - sigmoid(x)), grad += g * Out[t], Out[t] += g * h; after the
+ * pair's targets h += grad. In[centre] = h is written once, after the centre's last pair (a centre without pairs writes
+ * nothing). loss = sum of -log sigmoid(x) for label 1 and -log sigmoid(-x) for label 0. Departure from fastText: exact
+ * expf / log1pf, no sigmoid or log lookup table.
+ *
+ * Modes.
+ *   OTTO_SGNS_HOGWILD  rows are read, updated and written in place with plain stores and no float atomics; centres run
+ *                      concurrently and race by design. Inside one centre the order above holds exactly (a target drawn
+ *                      twice in a pair sees its own first update). Without shared rows it equals the sequential loop.
+ *   OTTO_SGNS_BATCH    the parity mode, allowed to be slow: every x and g of the launch comes from the pre-launch tables
+ *                      (h = In[centre] stays fixed over the centre's pairs), the g * Out[t] and g * h contributions are
+ *                      summed per row into the caller's dense float64 gradient workspaces, and In += gIn, Out += gOut is
+ *                      applied once. The workspaces must be all zero on entry and are all zero again on return.
+ */
+#ifndef OTTO_SGNS_H
+#define OTTO_SGNS_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define OTTO_SGNS_HOGWILD 0
+#define OTTO_SGNS_BATCH 1
+#define OTTO_SGNS_MAX_DIM 128
+#define OTTO_SGNS_MAX_NEG 64
+#define OTTO_SGNS_MAX_WS 32
+
+/* The negative table of SPEC-SGNS plus its bucket index. d_cum uint64 [n_aids]; d_bucket uint32 [n_buckets + 1];
+ * shift = the smallest s with ((total - 1) >> s) + 1 <= n_buckets; bucket[b] = min(upper_bound(cum, b << shift),
+ * n_aids - 1) for b <= (total - 1) >> shift, n_aids - 1 behind. A draw looks up b = u >> shift and searches
+ * cum[bucket[b] .. bucket[b + 1]]: the same element as the full upper_bound for every 64-bit key. */
+typedef struct otto_sgns_table {
+    const uint64_t* d_cum;
+    const uint32_t* d_bucket;
+    int64_t n_aids;
+    int64_t n_buckets;
+    uint64_t total;
+    int32_t shift;
+} otto_sgns_table;
+
+/* bytes of d_work for otto_sgns_neg_table; 0 for refused arguments */
+int64_t otto_sgns_neg_table_workspace(int64_t n_aids);
+
+/* d_weight uint32 [n_aids] -> d_cum, d_bucket and *table (HOST; it keeps the two device pointers). 1 <= n_aids < 2^31,
+ * 1 <= n_buckets < 2^31. total = 0 is legal (no draw may then be asked for). Synchronises the stream once (total). */
+int otto_sgns_neg_table(const uint32_t* d_weight, int64_t n_aids, int64_t n_buckets, uint64_t* d_cum, uint32_t* d_bucket,
+                        otto_sgns_table* table, void* d_work, int64_t work_bytes, void* stream);
+
+/* d_out[i] = draw(d_keys[i]) of SPEC-SGNS, int32 [m]; table->total > 0. */
+int otto_sgns_draw(const otto_sgns_table* table, const uint64_t* d_keys, int64_t m, int32_t* d_out, void* stream);
+
+/* bytes of d_work for otto_sgns_plan over E events; 0 for refused arguments */
+int64_t otto_sgns_plan_workspace(int64_t E);
+
+/* The epoch plan. event0: the global index of d_aid[0]. Outputs, each with room for cap_tokens tokens (E always
+ * suffices): d_tok_aid int32 [T], d_tok_src int64 [T], d_tok_off int64 [S+1], d_radius uint8 [T], d_tok_left uint8 [T]
+ * (left_c, so that the step needs no session lookup), d_pair_off int64 [T+1]. h_counts int64 [2] (HOST) = { T, P }.
+ * 1 <= ws <= OTTO_SGNS_MAX_WS, 0 <= E < 2^31. T > cap_tokens is OTTO_EINVAL with the outputs unwritten.
+ * Synchronises the stream twice (error word and T; P). */
+int otto_sgns_plan(const int32_t* d_aid, int64_t E, const int64_t* d_sess_off, int64_t S, const uint32_t* d_keep_q,
+                   int64_t n_aids, uint64_t seed, uint64_t epoch, int64_t event0, int32_t ws, int64_t cap_tokens,
+                   int32_t* d_tok_aid, int64_t* d_tok_src, int64_t* d_tok_off, uint8_t* d_radius, uint8_t* d_tok_left,
+                   int64_t* d_pair_off, int64_t* h_counts, void* d_work, int64_t work_bytes, void* stream);
+
+/* One launch over the centres [t0, t1) of a plan of T tokens (0 <= t0 <= t1 <= T; t0 == t1 only writes the loss 0).
+ * d % 4 == 0, 4 <= d <= OTTO_SGNS_MAX_DIM, d/4 a power of two; 0 <= neg <= OTTO_SGNS_MAX_NEG (neg > 0 needs n_aids >= 2
+ * and table->total > 0). *d_loss_sum (device double) receives the loss sum of the launch. d_ctx_out int32 [out_pairs]
+ * and d_neg_out int32 [out_pairs, neg] (both nullable; the tests' window into the sampler) are indexed by
+ * pair - pair_off[t0]; pairs past out_pairs are not recorded. d_gin, d_gout double [n_aids, d]: the BATCH workspaces,
+ * ignored (nullable) in HOGWILD mode. */
+int otto_sgns_step(const int32_t* d_tok_aid, const int64_t* d_tok_src, const uint8_t* d_tok_left, const int64_t* d_pair_off,
+                   int64_t T, int64_t t0, int64_t t1, float* d_In, float* d_Out, int32_t d, int32_t neg, float lr,
+                   int32_t mode, uint64_t seed, uint64_t epoch, const otto_sgns_table* table, double* d_loss_sum,
+                   int32_t* d_ctx_out, int32_t* d_neg_out, int64_t out_pairs, double* d_gin, double* d_gout, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

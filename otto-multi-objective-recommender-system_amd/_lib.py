@@ -83,6 +83,18 @@ class CovisParams(C.Structure):
     ]
 
 
+class SgnsTable(C.Structure):
+    # mirrors otto_sgns_table (include/otto_sgns.h)
+    _fields_ = [
+        ('d_cum', C.c_void_p),
+        ('d_bucket', C.c_void_p),
+        ('n_aids', C.c_int64),
+        ('n_buckets', C.c_int64),
+        ('total', C.c_uint64),
+        ('shift', C.c_int32),
+    ]
+
+
 _vp, _i64, _i32, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_uint32
 _p_i64 = C.POINTER(C.c_int64)
 
@@ -204,6 +216,15 @@ SIGNATURES = {
     'otto_folds_emit': (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, C.c_uint64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                _vp, _i64, _vp]),
     'otto_folds_gather_u8': (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
+    # include/otto_sgns.h
+    'otto_sgns_neg_table_workspace': (_i64, [_i64]),
+    'otto_sgns_neg_table': (_i32, [_vp, _i64, _i64, _vp, _vp, C.POINTER(SgnsTable), _vp, _i64, _vp]),
+    'otto_sgns_draw': (_i32, [C.POINTER(SgnsTable), _vp, _i64, _vp, _vp]),
+    'otto_sgns_plan_workspace': (_i64, [_i64]),
+    'otto_sgns_plan': (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, C.c_uint64, C.c_uint64, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _p_i64, _vp, _i64, _vp]),
+    'otto_sgns_step': (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, C.c_float, _i32, C.c_uint64, C.c_uint64,
+                              C.POINTER(SgnsTable), _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
 }
 
 _lib = None

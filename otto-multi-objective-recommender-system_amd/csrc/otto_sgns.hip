@@ -1,0 +1,497 @@
+// Skip-gram negative-sampling aid embeddings (SPEC-SGNS; include/otto_sgns.h).
+//
+// Device, on the caller's stream:
+//   device_scan     (scan.h) over the weights: the exclusive sums; cum is their tail (cum[a] = excl[a + 1]).
+//   k_sgns_bucket        bucket[b] = min(upper_bound(cum, b << shift), n - 1): one full binary search per bucket.
+//   k_sgns_draw          the sampler alone (tests, and the definition the step kernels share: sgns_draw).
+//   k_sgns_plan_check    aid range and offset rule; one error word.
+//   device_scan     over the keep flags (recomputed from the event index, no flag array): the token position of every event.
+//   k_sgns_plan_tokens   one thread per event: session by binary search of sess_off, token record, radius, clipped window.
+//   k_sgns_plan_off      tok_off[s] = pos[sess_off[s]].
+//   device_scan     over the pair counts: pair_off.
+//   k_sgns_step<BATCH>   one lane group of d/4 lanes per centre, grid-stride. h and grad live in registers, rows move as float4.
+//                   The 1 + neg target ids of a pair are drawn by the group's lanes into LDS before any row is loaded, then
+//                   the rows are fetched four at a time. HOGWILD: plain stores in place. BATCH: float64 atomics into the
+//                   dense workspaces, no table is written.
+//   k_sgns_apply         BATCH: table += workspace, workspace = 0 (dense sweep).
+//   k_sgns_loss_final    sums the per-workgroup loss partials in a fixed order.
+#include "common.h"
+#include "scan.h"
+#include "../../include/otto_covis.h"
+#include "../../include/otto_sgns.h"
+
+#include <string.h>
+
+namespace otto {
+
+constexpr int SG_THREADS = 256;
+constexpr int SG_MAX_GROUPS = 64;         // lane groups per workgroup: the workgroup is min(256, 64 * d/4) threads
+constexpr int SG_GRID = 2048;            // 256 CUs x 8 workgroups
+constexpr int SG_MAX_TARGETS = OTTO_SGNS_MAX_NEG + 1;
+constexpr uint64_t SG_C_EPOCH = 0xD1342543DE82EF95ull, SG_C_EVENT = 0xA0761D6478BD642Full, SG_C_KEY = 0xE7037ED1A0B428DBull;
+
+static __host__ __device__ __forceinline__ uint64_t sg_base(uint64_t seed, uint64_t epoch) { return mix64(seed ^ (epoch * SG_C_EPOCH)); }
+static __host__ __device__ __forceinline__ uint64_t sg_ev(uint64_t base, uint64_t e) { return mix64(base ^ (e * SG_C_EVENT)); }
+static __host__ __device__ __forceinline__ uint64_t sg_key(uint64_t ev, uint64_t stream, uint64_t w) {
+    return mix64(ev ^ (((stream << 20) | w) * SG_C_KEY));
+}
+
+struct SgTable {
+    const uint64_t* cum;
+    const uint32_t* bucket;
+    int64_t n;
+    uint64_t total;
+    int shift;
+};
+
+// first a in [lo, hi] with cum[a] > u; the caller guarantees cum[hi] > u
+static __device__ __forceinline__ int64_t sg_upper(const uint64_t* cum, int64_t lo, int64_t hi, uint64_t u) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (cum[mid] > u) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+static __device__ __forceinline__ int32_t sgns_draw(const SgTable& t, uint64_t key) {
+    const uint64_t u = __umul64hi(key, t.total);          // < total
+    const uint64_t b = u >> t.shift;
+    return (int32_t)sg_upper(t.cum, t.bucket[b], t.bucket[b + 1], u);
+}
+
+__global__ __launch_bounds__(256) void k_sgns_bucket(const uint64_t* cum, int64_t n, uint64_t total, int shift, int64_t n_buckets,
+                                                uint32_t* bucket) {
+    const int64_t used = total ? (int64_t)((total - 1) >> shift) + 1 : 0;
+    for (int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x; b <= n_buckets; b += (int64_t)gridDim.x * 256) {
+        uint32_t v = (uint32_t)(n - 1);
+        if (b < used) {
+            const uint64_t u = (uint64_t)b << shift;       // <= total - 1
+            v = (uint32_t)sg_upper(cum, 0, n - 1, u);
+        }
+        bucket[b] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_sgns_draw(SgTable t, const uint64_t* keys, int64_t m, int32_t* out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) out[i] = sgns_draw(t, keys[i]);
+}
+
+// ---------------------------------------------------------------------------
+// plan
+// ---------------------------------------------------------------------------
+struct SgPlanArgs {
+    const int32_t* aid;
+    int64_t E;
+    const int64_t* sess_off;
+    int64_t S;
+    const uint32_t* keep_q;
+    int64_t n_aids;
+    uint64_t base;
+    int64_t event0;
+    int ws;
+    uint32_t* err;
+    const uint64_t* pos;      // [E + 1]
+    uint8_t* npairs;          // [T] (workspace)
+    int32_t* tok_aid;
+    int64_t* tok_src;
+    int64_t* tok_off;
+    uint8_t* radius;
+    uint8_t* tok_left;
+};
+
+struct SgKeepFn {
+    const int32_t* aid;
+    const uint32_t* keep_q;
+    int64_t n_aids;
+    uint64_t base;
+    int64_t event0;
+    __device__ __forceinline__ uint64_t operator()(int64_t e) const {
+        const uint32_t a = (uint32_t)aid[e];
+        if ((uint64_t)a >= (uint64_t)n_aids) return 0;
+        const uint32_t q = keep_q[a];
+        if (q == 0) return 0;
+        const uint64_t k = sg_key(sg_ev(base, (uint64_t)(event0 + e)), 1, 0);
+        return (uint32_t)(k >> 32) <= q ? 1 : 0;
+    }
+};
+
+struct SgPairFn {
+    const uint8_t* npairs;
+    __device__ __forceinline__ uint64_t operator()(int64_t t) const { return npairs[t]; }
+};
+
+struct SgWeightFn {
+    const uint32_t* w;
+    __device__ __forceinline__ uint64_t operator()(int64_t a) const { return w[a]; }
+};
+
+__global__ __launch_bounds__(256) void k_sgns_plan_check(SgPlanArgs a) {
+    bool bad = false;
+    const int64_t stride = (int64_t)gridDim.x * 256, i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (int64_t e = i0; e < a.E; e += stride) bad |= (uint64_t)(uint32_t)a.aid[e] >= (uint64_t)a.n_aids;
+    for (int64_t s = i0; s < a.S; s += stride) {
+        const int64_t lo = a.sess_off[s], hi = a.sess_off[s + 1];
+        bad |= lo < 0 || hi < lo || hi > a.E;
+    }
+    if (i0 == 0) bad |= a.sess_off[0] != 0 || a.sess_off[a.S] != a.E;
+    if (bad) atomicOr(a.err, 1u);
+}
+
+__global__ __launch_bounds__(256) void k_sgns_plan_tokens(SgPlanArgs a) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.E; e += (int64_t)gridDim.x * 256) {
+        const int64_t t = (int64_t)a.pos[e];
+        if ((int64_t)a.pos[e + 1] == t) continue;          // not kept
+        // session of e: the last s with sess_off[s] <= e (empty sessions share an offset; the last one holds e)
+        int64_t lo = 0, hi = a.S - 1;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (a.sess_off[mid] <= e) lo = mid; else hi = mid - 1;
+        }
+        const int64_t tlo = (int64_t)a.pos[a.sess_off[lo]], thi = (int64_t)a.pos[a.sess_off[lo + 1]];
+        const uint64_t ev = sg_ev(a.base, (uint64_t)(a.event0 + e));
+        const int64_t r = 1 + (int64_t)(((sg_key(ev, 2, 0) >> 32) * (uint64_t)a.ws) >> 32);
+        const int64_t left = min(r, t - tlo), right = min(r, thi - 1 - t);
+        a.tok_aid[t] = a.aid[e];
+        a.tok_src[t] = a.event0 + e;
+        a.radius[t] = (uint8_t)r;
+        a.tok_left[t] = (uint8_t)left;
+        a.npairs[t] = (uint8_t)(left + right);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_sgns_plan_off(SgPlanArgs a) {
+    for (int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x; s <= a.S; s += (int64_t)gridDim.x * 256)
+        a.tok_off[s] = (int64_t)a.pos[a.sess_off[s]];
+}
+
+// ---------------------------------------------------------------------------
+// step
+// ---------------------------------------------------------------------------
+struct SgStepArgs {
+    const int32_t* tok_aid;
+    const int64_t* tok_src;
+    const uint8_t* tok_left;
+    const int64_t* pair_off;
+    int64_t T, t0, t1;
+    float* In;
+    float* Out;
+    int d, G, neg;
+    float lr;
+    uint64_t base;
+    SgTable tab;
+    double* partial;          // [SG_GRID]
+    int32_t* ctx_out;
+    int32_t* neg_out;
+    int64_t out_pairs;
+    double* gin;
+    double* gout;
+};
+
+static __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+static __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+static __device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+static __device__ __forceinline__ float group_sum(float v, int G) {
+    for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+static __device__ __forceinline__ float sigmoidf_exact(float x) {
+    return x >= 0.0f ? 1.0f / (1.0f + expf(-x)) : expf(x) / (1.0f + expf(x));
+}
+static __device__ __forceinline__ float softplusf_exact(float z) {    // log(1 + exp(z))
+    return fmaxf(z, 0.0f) + log1pf(expf(-fabsf(z)));
+}
+
+// negative j of pair k of the centre whose event key is ev: redrawn while equal to the context aid
+static __device__ __forceinline__ int32_t sgns_negative(const SgTable& t, uint64_t ev, int k, int j, int32_t ctx) {
+    for (int att = 0; att < 16; ++att) {
+        const int32_t n = sgns_draw(t, sg_key(ev, 3, ((uint64_t)k << 10) | ((uint64_t)j << 4) | (uint64_t)att));
+        if (n != ctx) return n;
+    }
+    return (int32_t)(((int64_t)ctx + 1) % t.n);
+}
+
+template <bool BATCH>
+__global__ __launch_bounds__(SG_THREADS) void k_sgns_step(SgStepArgs a) {
+    // the target ids of the pair each lane group is working on
+    __shared__ int32_t s_ids[SG_MAX_GROUPS * SG_MAX_TARGETS];
+    __shared__ double s_red[SG_THREADS / 64];
+    const int G = a.G;
+    const int gl = threadIdx.x & (G - 1);
+    const int grp = threadIdx.x / G;
+    const int64_t gpb = blockDim.x / G;
+    int32_t* ids = s_ids + grp * SG_MAX_TARGETS;
+    const int nt = 1 + a.neg;
+    const float lr = a.lr;
+    double lsum = 0.0;
+    const int64_t p0 = a.pair_off[a.t0];
+    for (int64_t c = a.t0 + (int64_t)blockIdx.x * gpb + grp; c < a.t1; c += (int64_t)gridDim.x * gpb) {
+        const int32_t ca = a.tok_aid[c];
+        const int64_t pb = a.pair_off[c];
+        const int np = (int)(a.pair_off[c + 1] - pb);
+        const int left = a.tok_left[c];
+        if ((uint64_t)(uint32_t)ca >= (uint64_t)a.tab.n || np <= 0 || np > 2 * OTTO_SGNS_MAX_WS || left > np) continue;
+        const uint64_t ev = sg_ev(a.base, (uint64_t)a.tok_src[c]);
+        float* pin = a.In + (int64_t)ca * a.d + 4 * gl;
+        float4 h = ld4(pin);
+        float4 gsum = make_float4(0.f, 0.f, 0.f, 0.f);      // BATCH: the centre's whole gradient
+        for (int k = 0; k < np; ++k) {
+            const int64_t ct = k < left ? c - left + k : c + 1 + (k - left);
+            if (ct < 0 || ct >= a.T) continue;               // cannot happen for a plan of T tokens
+            const int32_t ctx = a.tok_aid[ct];
+            if ((uint64_t)(uint32_t)ctx >= (uint64_t)a.tab.n) continue;
+            // draw every target id of the pair before the first row load
+            wave_lds_sync();
+            for (int m = gl; m < nt; m += G) ids[m] = m == 0 ? ctx : sgns_negative(a.tab, ev, k, m - 1, ctx);
+            wave_lds_sync();
+            const int64_t po = pb + k - p0;
+            if (po < a.out_pairs) {
+                if (a.ctx_out && gl == 0) a.ctx_out[po] = ctx;
+                if (a.neg_out)
+                    for (int m = 1 + gl; m < nt; m += G) a.neg_out[po * a.neg + (m - 1)] = ids[m];
+            }
+            float4 grad = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int m0 = 0; m0 < nt; m0 += 4) {
+                int32_t id[4];
+                float4 row[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    id[q] = m0 + q < nt ? ids[m0 + q] : -1;
+                    if (id[q] >= 0) row[q] = ld4(a.Out + (int64_t)id[q] * a.d + 4 * gl);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (id[q] < 0) continue;
+                    float* po_ = a.Out + (int64_t)id[q] * a.d + 4 * gl;
+                    if (!BATCH) {
+                        // a target drawn twice in these four sees its own earlier update
+                        bool dup = false;
+#pragma unroll
+                        for (int w = 0; w < q; ++w) dup |= id[w] == id[q];
+                        if (dup) row[q] = ld4(po_);
+                    }
+                    const float4 o = row[q];
+                    const float x = group_sum(dot4(h, o), G);
+                    const bool pos = m0 + q == 0;
+                    const float g = lr * ((pos ? 1.0f : 0.0f) - sigmoidf_exact(x));
+                    if (gl == 0) lsum += (double)softplusf_exact(pos ? -x : x);
+                    grad.x += g * o.x; grad.y += g * o.y; grad.z += g * o.z; grad.w += g * o.w;
+                    if (BATCH) {
+                        double* go = a.gout + (int64_t)id[q] * a.d + 4 * gl;
+                        atomicAdd(go + 0, (double)(g * h.x)); atomicAdd(go + 1, (double)(g * h.y));
+                        atomicAdd(go + 2, (double)(g * h.z)); atomicAdd(go + 3, (double)(g * h.w));
+                    } else {
+                        st4(po_, make_float4(o.x + g * h.x, o.y + g * h.y, o.z + g * h.z, o.w + g * h.w));
+                    }
+                }
+            }
+            if (BATCH) {
+                gsum.x += grad.x; gsum.y += grad.y; gsum.z += grad.z; gsum.w += grad.w;
+            } else {
+                h.x += grad.x; h.y += grad.y; h.z += grad.z; h.w += grad.w;
+            }
+        }
+        if (BATCH) {
+            double* gi = a.gin + (int64_t)ca * a.d + 4 * gl;
+            atomicAdd(gi + 0, (double)gsum.x); atomicAdd(gi + 1, (double)gsum.y);
+            atomicAdd(gi + 2, (double)gsum.z); atomicAdd(gi + 3, (double)gsum.w);
+        } else {
+            st4(pin, h);
+        }
+    }
+    // per-workgroup loss partial, fixed order inside the workgroup
+    for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o, 64);
+    if (lane_id() == 0) s_red[threadIdx.x >> 6] = lsum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_red[w];
+        a.partial[blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_sgns_loss_final(const double* partial, int n, double* out) {
+    __shared__ double s[256];
+    double t = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) t += partial[i];
+    s[threadIdx.x] = t;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = s[0];
+}
+
+// table += workspace, workspace = 0
+__global__ __launch_bounds__(256) void k_sgns_apply(float* tab, double* g, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double v = g[i];
+        if (v != 0.0) {
+            tab[i] = (float)((double)tab[i] + v);
+            g[i] = 0.0;
+        }
+    }
+}
+
+static int grid_for(int64_t n, int per_block) {
+    int64_t g = (n + per_block - 1) / per_block;
+    if (g < 1) g = 1;
+    return (int)(g > SG_GRID ? SG_GRID : g);
+}
+
+static int table_from(const otto_sgns_table* t, SgTable* out) {
+    OTTO_REQUIRE(t && t->d_cum && t->d_bucket, "null negative table");
+    OTTO_REQUIRE(t->n_aids >= 1 && t->n_aids < (1ll << 31) && t->n_buckets >= 1, "negative table: bad sizes");
+    OTTO_REQUIRE(t->shift >= 0 && t->shift < 64, "negative table: bad shift");
+    OTTO_REQUIRE(t->total > 0, "negative table: total weight is 0, nothing can be drawn");
+    OTTO_REQUIRE((int64_t)((t->total - 1) >> t->shift) + 1 <= t->n_buckets, "negative table: shift does not fit n_buckets");
+    out->cum = t->d_cum; out->bucket = t->d_bucket; out->n = t->n_aids; out->total = t->total; out->shift = t->shift;
+    return 0;
+}
+
+}  // namespace otto
+
+using namespace otto;
+
+extern "C" int64_t otto_sgns_neg_table_workspace(int64_t n_aids) {
+    if (n_aids < 1 || n_aids >= (1ll << 31)) return 0;
+    return (int64_t)((size_t)(n_aids + 1) * 8 + scan_partial_bytes(n_aids));
+}
+
+extern "C" int otto_sgns_neg_table(const uint32_t* d_weight, int64_t n_aids, int64_t n_buckets, uint64_t* d_cum,
+                                   uint32_t* d_bucket, otto_sgns_table* table, void* d_work, int64_t work_bytes, void* stream) {
+    OTTO_REQUIRE(d_weight && d_cum && d_bucket && table && d_work, "null argument");
+    OTTO_REQUIRE(n_aids >= 1 && n_aids < (1ll << 31), "n_aids = %lld outside [1, 2^31)", (long long)n_aids);
+    OTTO_REQUIRE(n_buckets >= 1 && n_buckets < (1ll << 31), "n_buckets = %lld outside [1, 2^31)", (long long)n_buckets);
+    OTTO_REQUIRE(work_bytes >= otto_sgns_neg_table_workspace(n_aids), "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    uint64_t* excl = reinterpret_cast<uint64_t*>(d_work);
+    uint64_t* partial = excl + (n_aids + 1);
+    OTTO_TRY(device_scan(SgWeightFn{d_weight}, n_aids, excl, partial, s));
+    OTTO_HIP(hipMemcpyAsync(d_cum, excl + 1, (size_t)n_aids * 8, hipMemcpyDeviceToDevice, s));
+    uint64_t total = 0;
+    OTTO_HIP(hipMemcpyAsync(&total, excl + n_aids, 8, hipMemcpyDeviceToHost, s));
+    OTTO_HIP(hipStreamSynchronize(s));
+    int shift = 0;
+    while (total && (int64_t)((total - 1) >> shift) + 1 > n_buckets) ++shift;
+    k_sgns_bucket<<<grid_for(n_buckets + 1, 256), 256, 0, s>>>(d_cum, n_aids, total, shift, n_buckets, d_bucket);
+    OTTO_HIP(hipGetLastError());
+    table->d_cum = d_cum; table->d_bucket = d_bucket; table->n_aids = n_aids; table->n_buckets = n_buckets;
+    table->total = total; table->shift = shift;
+    return 0;
+}
+
+extern "C" int otto_sgns_draw(const otto_sgns_table* table, const uint64_t* d_keys, int64_t m, int32_t* d_out, void* stream) {
+    SgTable t;
+    OTTO_TRY(table_from(table, &t));
+    OTTO_REQUIRE(m >= 0 && (m == 0 || (d_keys && d_out)), "null argument");
+    if (m == 0) return 0;
+    k_sgns_draw<<<grid_for(m, 256), 256, 0, (hipStream_t)stream>>>(t, d_keys, m, d_out);
+    OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t otto_sgns_plan_workspace(int64_t E) {
+    if (E < 0 || E >= (1ll << 31)) return 0;
+    // pos [E + 1] and the scan partials (the pair scan reuses them: T <= E), then one pair count per token
+    return (int64_t)((size_t)(E + 1) * 8 + scan_partial_bytes(E) + (size_t)E + 256);
+}
+
+extern "C" int otto_sgns_plan(const int32_t* d_aid, int64_t E, const int64_t* d_sess_off, int64_t S, const uint32_t* d_keep_q,
+                              int64_t n_aids, uint64_t seed, uint64_t epoch, int64_t event0, int32_t ws, int64_t cap_tokens,
+                              int32_t* d_tok_aid, int64_t* d_tok_src, int64_t* d_tok_off, uint8_t* d_radius,
+                              uint8_t* d_tok_left, int64_t* d_pair_off, int64_t* h_counts, void* d_work, int64_t work_bytes,
+                              void* stream) {
+    OTTO_REQUIRE(E >= 0 && E < (1ll << 31), "E = %lld outside [0, 2^31)", (long long)E);
+    OTTO_REQUIRE(S >= 0 && S < (1ll << 31), "S = %lld outside [0, 2^31)", (long long)S);
+    OTTO_REQUIRE(n_aids >= 1 && n_aids < (1ll << 31), "n_aids = %lld outside [1, 2^31)", (long long)n_aids);
+    OTTO_REQUIRE(ws >= 1 && ws <= OTTO_SGNS_MAX_WS, "ws = %d outside [1, %d]", ws, OTTO_SGNS_MAX_WS);
+    OTTO_REQUIRE(event0 >= 0 && cap_tokens >= 0, "negative event0 or cap_tokens");
+    OTTO_REQUIRE(d_sess_off && d_keep_q && d_tok_off && d_pair_off && h_counts && d_work && (E == 0 || d_aid), "null argument");
+    OTTO_REQUIRE(cap_tokens == 0 || (d_tok_aid && d_tok_src && d_radius && d_tok_left), "null token output");
+    OTTO_REQUIRE(work_bytes >= otto_sgns_plan_workspace(E), "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    void* scratch = nullptr;
+    OTTO_TRY(device_scratch(SCRATCH_SGNS, 256, &scratch, s));
+    uint64_t* pos = reinterpret_cast<uint64_t*>(d_work);
+    uint64_t* partial = pos + (E + 1);
+    uint8_t* npairs = reinterpret_cast<uint8_t*>(partial) + scan_partial_bytes(E);
+    SgPlanArgs a;
+    memset(&a, 0, sizeof a);
+    a.aid = d_aid; a.E = E; a.sess_off = d_sess_off; a.S = S; a.keep_q = d_keep_q; a.n_aids = n_aids;
+    a.base = sg_base(seed, epoch); a.event0 = event0; a.ws = ws; a.err = reinterpret_cast<uint32_t*>(scratch);
+    a.pos = pos; a.npairs = npairs; a.tok_aid = d_tok_aid; a.tok_src = d_tok_src; a.tok_off = d_tok_off;
+    a.radius = d_radius; a.tok_left = d_tok_left;
+    OTTO_HIP(hipMemsetAsync(scratch, 0, 256, s));
+    k_sgns_plan_check<<<grid_for(E > S ? E : S, 256), 256, 0, s>>>(a);
+    OTTO_HIP(hipGetLastError());
+    OTTO_TRY(device_scan(SgKeepFn{d_aid, d_keep_q, n_aids, a.base, event0}, E, pos, partial, s));
+    uint32_t bad = 0;
+    uint64_t T = 0;
+    OTTO_HIP(hipMemcpyAsync(&bad, scratch, 4, hipMemcpyDeviceToHost, s));
+    OTTO_HIP(hipMemcpyAsync(&T, pos + E, 8, hipMemcpyDeviceToHost, s));
+    OTTO_HIP(hipStreamSynchronize(s));
+    OTTO_REQUIRE(!bad, "otto_sgns_plan: an aid outside [0, %lld) or session offsets that do not ascend from 0 to E",
+                 (long long)n_aids);
+    OTTO_REQUIRE((int64_t)T <= cap_tokens, "otto_sgns_plan: %lld kept tokens, room for %lld", (long long)T, (long long)cap_tokens);
+    if (E > 0 && S > 0) k_sgns_plan_tokens<<<grid_for(E, 256), 256, 0, s>>>(a);
+    k_sgns_plan_off<<<grid_for(S + 1, 256), 256, 0, s>>>(a);
+    OTTO_HIP(hipGetLastError());
+    OTTO_TRY(device_scan(SgPairFn{npairs}, (int64_t)T, reinterpret_cast<uint64_t*>(d_pair_off), partial, s));
+    uint64_t P = 0;
+    OTTO_HIP(hipMemcpyAsync(&P, d_pair_off + T, 8, hipMemcpyDeviceToHost, s));
+    OTTO_HIP(hipStreamSynchronize(s));
+    h_counts[0] = (int64_t)T;
+    h_counts[1] = (int64_t)P;
+    return 0;
+}
+
+extern "C" int otto_sgns_step(const int32_t* d_tok_aid, const int64_t* d_tok_src, const uint8_t* d_tok_left,
+                              const int64_t* d_pair_off, int64_t T, int64_t t0, int64_t t1, float* d_In, float* d_Out, int32_t d,
+                              int32_t neg, float lr, int32_t mode, uint64_t seed, uint64_t epoch, const otto_sgns_table* table,
+                              double* d_loss_sum, int32_t* d_ctx_out, int32_t* d_neg_out, int64_t out_pairs, double* d_gin,
+                              double* d_gout, void* stream) {
+    OTTO_REQUIRE(d >= 4 && d <= OTTO_SGNS_MAX_DIM && d % 4 == 0 && ((d / 4) & (d / 4 - 1)) == 0,
+                 "d = %d: need a multiple of 4 in [4, %d] with d/4 a power of two", d, OTTO_SGNS_MAX_DIM);
+    OTTO_REQUIRE(neg >= 0 && neg <= OTTO_SGNS_MAX_NEG, "neg = %d outside [0, %d]", neg, OTTO_SGNS_MAX_NEG);
+    OTTO_REQUIRE(mode == OTTO_SGNS_HOGWILD || mode == OTTO_SGNS_BATCH, "unknown SGNS mode %d", mode);
+    OTTO_REQUIRE(T >= 0 && T < (1ll << 31) && 0 <= t0 && t0 <= t1 && t1 <= T, "token range [%lld, %lld) outside the plan's %lld",
+                 (long long)t0, (long long)t1, (long long)T);
+    OTTO_REQUIRE(d_pair_off && d_In && d_Out && d_loss_sum && table, "null argument");
+    OTTO_REQUIRE(T == 0 || (d_tok_aid && d_tok_src && d_tok_left), "null plan array");
+    OTTO_REQUIRE(mode == OTTO_SGNS_HOGWILD || (d_gin && d_gout), "BATCH mode needs both gradient workspaces");
+    OTTO_REQUIRE(out_pairs >= 0 && (out_pairs > 0 || (!d_ctx_out && !d_neg_out)), "ctx_out / neg_out without out_pairs");
+    hipStream_t s = (hipStream_t)stream;
+    if (t0 == t1) {
+        OTTO_HIP(hipMemsetAsync(d_loss_sum, 0, sizeof(double), s));
+        return 0;
+    }
+    SgStepArgs a;
+    memset(&a, 0, sizeof a);
+    if (neg > 0) {
+        OTTO_TRY(table_from(table, &a.tab));
+        OTTO_REQUIRE(table->n_aids >= 2, "negative sampling needs at least 2 aids");
+    } else {
+        OTTO_REQUIRE(table->n_aids >= 1 && table->n_aids < (1ll << 31), "negative table: bad sizes");
+        a.tab.n = table->n_aids;
+    }
+    void* scratch = nullptr;
+    OTTO_TRY(device_scratch(SCRATCH_SGNS_STEP, (size_t)SG_GRID * sizeof(double), &scratch, s));
+    a.tok_aid = d_tok_aid; a.tok_src = d_tok_src; a.tok_left = d_tok_left; a.pair_off = d_pair_off;
+    a.T = T; a.t0 = t0; a.t1 = t1; a.In = d_In; a.Out = d_Out; a.d = d; a.G = d / 4; a.neg = neg; a.lr = lr;
+    a.base = sg_base(seed, epoch); a.partial = reinterpret_cast<double*>(scratch);
+    a.ctx_out = d_ctx_out; a.neg_out = neg > 0 ? d_neg_out : nullptr; a.out_pairs = out_pairs; a.gin = d_gin; a.gout = d_gout;
+    const int threads = a.G >= 4 ? SG_THREADS : 64 * a.G;
+    const int grid = grid_for(t1 - t0, threads / a.G);
+    if (mode == OTTO_SGNS_HOGWILD) {
+        k_sgns_step<false><<<grid, threads, 0, s>>>(a);
+    } else {
+        k_sgns_step<true><<<grid, threads, 0, s>>>(a);
+        const int64_t n = table->n_aids * (int64_t)d;
+        k_sgns_apply<<<grid_for(n, 256), 256, 0, s>>>(d_In, d_gin, n);
+        k_sgns_apply<<<grid_for(n, 256), 256, 0, s>>>(d_Out, d_gout, n);
+    }
+    k_sgns_loss_final<<<1, 256, 0, s>>>(a.partial, grid, d_loss_sum);
+    OTTO_HIP(hipGetLastError());
+    return 0;
+}

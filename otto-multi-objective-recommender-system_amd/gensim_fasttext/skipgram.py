@@ -1,0 +1,290 @@
+"""Skip-gram negative-sampling aid embeddings on the device (SPEC-SGNS): thin Python over
+``include/otto_sgns.h``.
+
+What this replaces in the reference: ``fasttext.train_unsupervised`` with ``models/fasttext/config.yaml`` (skipgram, loss
+ns, ``minn = maxn = 0``: no sub-words) and gensim's ``Word2Vec(sg=1, negative>0)`` of ``src/gensim_fasttext/trainer.py``.
+The vocabulary tables are computed here on the host in float64 and integers; subsampling, windows, negative draws and the
+SGD step run in HIP kernels. There is no CPU fallback.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .. import _lib
+
+HOGWILD, BATCH = 0, 1               # OTTO_SGNS_HOGWILD, OTTO_SGNS_BATCH
+MAX_DIM, MAX_NEG, MAX_WS = 128, 64, 32
+NS_EXPONENTS = (0.0, 0.5, 0.75, 1.0)
+_U32_MAX = (1 << 32) - 1
+_MAX_BUCKETS = 1 << 21
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _stream(dev):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _host_counts(aid, n_aids):
+    if hasattr(aid, 'device') and hasattr(aid, 'cpu'):            # a torch tensor: count where it lives
+        import torch
+        if aid.numel() and (int(aid.min()) < 0 or int(aid.max()) >= n_aids):
+            raise ValueError(f'aid outside [0, {n_aids})')
+        return torch.bincount(aid.to(torch.int64), minlength=n_aids).cpu().numpy().astype(np.int64)
+    aid = np.asarray(aid)
+    if aid.size and (aid.min() < 0 or aid.max() >= n_aids):
+        raise ValueError(f'aid outside [0, {n_aids})')
+    return np.bincount(aid.astype(np.int64), minlength=n_aids).astype(np.int64)
+
+
+def vocab_tables(aid, n_aids, min_count=1, t=1e-4, ns_exponent=0.5):
+    """``(count int64, keep_q uint32, weight uint32)`` NumPy arrays [n_aids] of SPEC-SGNS. ``aid``: the events (a NumPy
+    array, or a tensor on any device: the counts are taken where it lives). ``keep_q = min(2^32 - 1, floor(p * 2^32))``
+    with ``p = sqrt(t/f) + t/f``, ``f = count/E`` (``t = 0``: always kept); ``weight = min(2^32 - 1, floor(count^e *
+    2^16))`` with ``e`` in {0, 0.5, 0.75, 1}; an aid with ``count < min_count`` (or no event) has both 0."""
+    n_aids, min_count, t, e = int(n_aids), int(min_count), float(t), float(ns_exponent)
+    if n_aids < 1:
+        raise ValueError('n_aids must be positive')
+    if t < 0:
+        raise ValueError('t must be >= 0')
+    if e not in NS_EXPONENTS:
+        raise ValueError(f'ns_exponent must be one of {NS_EXPONENTS} (got {ns_exponent})')
+    count = _host_counts(aid, n_aids)
+    E = int(count.sum())
+    in_vocab = count >= max(min_count, 1)
+    c = count.astype(np.float64)
+    keep_q = np.zeros(n_aids, dtype=np.uint32)
+    if t == 0.0:
+        keep_q[in_vocab] = _U32_MAX
+    else:
+        f = c[in_vocab] / float(E)
+        p = np.sqrt(t / f) + t / f
+        keep_q[in_vocab] = np.minimum(np.floor(p * 4294967296.0), float(_U32_MAX)).astype(np.uint64).astype(np.uint32)
+    if e == 0.0:
+        w = np.ones_like(c)
+    elif e == 0.5:
+        w = np.sqrt(c)
+    elif e == 0.75:
+        r = np.sqrt(np.sqrt(c))          # exact on fourth powers, and so is r^3
+        w = r * r * r
+    else:
+        w = c
+    weight = np.zeros(n_aids, dtype=np.uint32)
+    weight[in_vocab] = np.minimum(np.floor(w[in_vocab] * 65536.0), float(_U32_MAX)).astype(np.uint64).astype(np.uint32)
+    return count, keep_q, weight
+
+
+def init_tables(n_aids, d, seed=0):
+    """``(In, Out)`` float32 NumPy [n_aids, d]: ``In`` uniform(-1/d, 1/d), ``Out`` zeros, as fastText initialises."""
+    rng = np.random.default_rng(int(seed))
+    In = rng.uniform(-1.0 / d, 1.0 / d, size=(int(n_aids), int(d))).astype(np.float32)
+    return In, np.zeros((int(n_aids), int(d)), dtype=np.float32)
+
+
+def learning_rate(lr, events_consumed, total_events):
+    """The rate of a launch: ``lr * max(1e-4, 1 - events_consumed / total_events)``; ``events_consumed`` counts events
+    before subsampling, as fastText's ``tokenCount`` does; ``total_events = epochs * E``."""
+    return float(lr) * max(1e-4, 1.0 - float(events_consumed) / float(max(int(total_events), 1)))
+
+
+class Plan:
+    """One epoch's plan on the device: ``tok_aid`` int32 [T], ``tok_src`` int64 [T], ``tok_off`` int64 [S+1], ``radius``
+    uint8 [T], ``tok_left`` uint8 [T], ``pair_off`` int64 [T+1]; ``T`` tokens, ``P`` pairs, ``epoch``."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _as_u32_tensor(a, dev):
+    import torch
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.uint32))
+    return torch.from_numpy(a.view(np.int32)).to(dev)
+
+
+class SkipGramEngine:
+    """Plan / step with persistent workspaces. ``keep_q`` / ``weight``: the uint32 tables of :func:`vocab_tables`."""
+
+    def __init__(self, n_aids, d, ws, neg, keep_q, weight, seed=0, device='cuda:0', n_buckets=None):
+        import torch
+        self.dev = torch.device(device)
+        if self.dev.type != 'cuda':
+            raise _lib.OttoError('SkipGramEngine needs a ROCm device (no CPU fallback)')
+        self.n_aids, self.d, self.ws, self.neg, self.seed = int(n_aids), int(d), int(ws), int(neg), int(seed)
+        if self.d % 4 or not 4 <= self.d <= MAX_DIM or (self.d // 4) & (self.d // 4 - 1):
+            raise ValueError(f'd must be a multiple of 4 in [4, {MAX_DIM}] with d/4 a power of two (got {d})')
+        if not 0 <= self.neg <= MAX_NEG:
+            raise ValueError(f'neg must be in [0, {MAX_NEG}] (got {neg})')
+        if not 1 <= self.ws <= MAX_WS:
+            raise ValueError(f'ws must be in [1, {MAX_WS}] (got {ws})')
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError('seed: expected a uint64')
+        if len(keep_q) != self.n_aids or len(weight) != self.n_aids:
+            raise ValueError('keep_q and weight must have n_aids entries')
+        self.lib = _lib.lib()
+        if n_buckets is None:
+            n_buckets = 1
+            while n_buckets < self.n_aids and n_buckets < _MAX_BUCKETS:
+                n_buckets *= 2
+        self.n_buckets = int(n_buckets)
+        with torch.cuda.device(self.dev):
+            self.keep_q = _as_u32_tensor(keep_q, self.dev)
+            self.weight = _as_u32_tensor(weight, self.dev)
+            self.cum = torch.empty(self.n_aids, dtype=torch.int64, device=self.dev)
+            self.bucket = torch.empty(self.n_buckets + 1, dtype=torch.int32, device=self.dev)
+            self.table = _lib.SgnsTable()
+            nb = self.lib.otto_sgns_neg_table_workspace(self.n_aids)
+            if nb <= 0:
+                raise _lib.OttoError('otto_sgns_neg_table_workspace refused its arguments')
+            work = torch.empty(int(nb), dtype=torch.uint8, device=self.dev)
+            _lib.check(self.lib.otto_sgns_neg_table(_ptr(self.weight), self.n_aids, self.n_buckets, _ptr(self.cum),
+                                                    _ptr(self.bucket), C.byref(self.table), _ptr(work), work.numel(),
+                                                    _stream(self.dev)), 'otto_sgns_neg_table')
+        self._work = None
+        self._bufs = None
+        self._grads = None
+        self._loss = torch.zeros(1, dtype=torch.float64, device=self.dev)
+
+    @property
+    def total(self):
+        return int(self.table.total)
+
+    def draw(self, keys):
+        """``upper_bound(cum, mulhi64(key, total))`` for every key: int64-viewed uint64 tensor [m] -> int32 [m]."""
+        import torch
+        out = torch.empty(keys.numel(), dtype=torch.int32, device=self.dev)
+        with torch.cuda.device(self.dev):
+            _lib.check(self.lib.otto_sgns_draw(C.byref(self.table), _ptr(keys), keys.numel(), _ptr(out), _stream(self.dev)),
+                       'otto_sgns_draw')
+        return out
+
+    def plan(self, aid, sess_off, epoch, event0=0, out=None):
+        """The :class:`Plan` of ``epoch`` over ``aid`` int32 [E] / ``sess_off`` int64 [S+1] on the device. ``out``: a
+        dict of pre-allocated output tensors (tests); by default the engine's persistent buffers are reused, so a plan is
+        valid until the next call. Raises ``OttoError`` for an aid outside ``[0, n_aids)`` or bad offsets."""
+        import torch
+        if aid.dtype != torch.int32 or sess_off.dtype != torch.int64 or not aid.is_contiguous() or not sess_off.is_contiguous():
+            raise ValueError('aid: contiguous int32 [E]; sess_off: contiguous int64 [S+1]')
+        if aid.device != self.dev or sess_off.device != self.dev:
+            raise ValueError(f'aid and sess_off must be on {self.dev}')
+        E, S = int(aid.numel()), int(sess_off.numel()) - 1
+        if S < 0:
+            raise ValueError('sess_off: expected int64 [S+1]')
+        with torch.cuda.device(self.dev):
+            nb = self.lib.otto_sgns_plan_workspace(E)
+            if nb <= 0:
+                raise _lib.OttoError('otto_sgns_plan_workspace refused its arguments')
+            if self._work is None or self._work.numel() < nb:
+                self._work = torch.empty(int(nb), dtype=torch.uint8, device=self.dev)
+            if out is None:
+                if self._bufs is None or self._bufs['tok_aid'].numel() < E or self._bufs['tok_off'].numel() < S + 1:
+                    self._bufs = dict(tok_aid=torch.empty(E, dtype=torch.int32, device=self.dev),
+                                      tok_src=torch.empty(E, dtype=torch.int64, device=self.dev),
+                                      tok_off=torch.empty(S + 1, dtype=torch.int64, device=self.dev),
+                                      radius=torch.empty(E, dtype=torch.uint8, device=self.dev),
+                                      tok_left=torch.empty(E, dtype=torch.uint8, device=self.dev),
+                                      pair_off=torch.empty(E + 1, dtype=torch.int64, device=self.dev))
+                out = self._bufs
+            cap = min(out['tok_aid'].numel(), out['tok_src'].numel(), out['radius'].numel(), out['tok_left'].numel(),
+                      out['pair_off'].numel() - 1)
+            if out['tok_off'].numel() < S + 1:
+                raise ValueError('tok_off: room for S + 1 entries needed')
+            counts = (C.c_int64 * 2)()
+            _lib.check(self.lib.otto_sgns_plan(_ptr(aid), E, _ptr(sess_off), S, _ptr(self.keep_q), self.n_aids, self.seed,
+                                               int(epoch), int(event0), self.ws, cap, _ptr(out['tok_aid']), _ptr(out['tok_src']),
+                                               _ptr(out['tok_off']), _ptr(out['radius']), _ptr(out['tok_left']),
+                                               _ptr(out['pair_off']), counts, _ptr(self._work), self._work.numel(),
+                                               _stream(self.dev)), 'otto_sgns_plan')
+        T, P = int(counts[0]), int(counts[1])
+        return Plan(tok_aid=out['tok_aid'][:T], tok_src=out['tok_src'][:T], tok_off=out['tok_off'][:S + 1],
+                    radius=out['radius'][:T], tok_left=out['tok_left'][:T], pair_off=out['pair_off'][:T + 1], T=T, P=P,
+                    epoch=int(epoch))
+
+    def step(self, plan, t0, t1, In, Out, lr, mode=HOGWILD, ctx_out=None, neg_out=None, loss=None):
+        """One launch over the centres ``[t0, t1)`` of ``plan``; updates ``In`` / ``Out`` (float32 [n_aids, d] on the
+        device) in place and returns the device float64 [1] loss sum. ``ctx_out`` int32 [pairs], ``neg_out`` int32
+        [pairs, neg]: the sampler's choices for the launch's pairs (tests)."""
+        import torch
+        for name, M in (('In', In), ('Out', Out)):
+            if M.dtype != torch.float32 or tuple(M.shape) != (self.n_aids, self.d) or not M.is_contiguous() or M.device != self.dev:
+                raise ValueError(f'{name}: expected contiguous float32 [{self.n_aids}, {self.d}] on {self.dev}')
+        if mode not in (HOGWILD, BATCH):
+            raise ValueError(f'unknown mode {mode}')
+        out_pairs = 0
+        if ctx_out is not None:
+            out_pairs = ctx_out.numel()
+        if neg_out is not None:
+            out_pairs = neg_out.numel() // max(self.neg, 1) if ctx_out is None else min(out_pairs, neg_out.numel() // max(self.neg, 1))
+        loss = self._loss if loss is None else loss
+        with torch.cuda.device(self.dev):
+            gin = gout = None
+            if mode == BATCH:
+                if self._grads is None:
+                    self._grads = (torch.zeros(self.n_aids, self.d, dtype=torch.float64, device=self.dev),
+                                   torch.zeros(self.n_aids, self.d, dtype=torch.float64, device=self.dev))
+                gin, gout = self._grads
+            _lib.check(self.lib.otto_sgns_step(_ptr(plan.tok_aid), _ptr(plan.tok_src), _ptr(plan.tok_left), _ptr(plan.pair_off),
+                                               plan.T, int(t0), int(t1), _ptr(In), _ptr(Out), self.d, self.neg, float(lr),
+                                               int(mode), self.seed, plan.epoch, C.byref(self.table), _ptr(loss), _ptr(ctx_out),
+                                               _ptr(neg_out), out_pairs, _ptr(gin), _ptr(gout), _stream(self.dev)),
+                       'otto_sgns_step')
+        return loss
+
+
+def train(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, t=1e-4, min_count=1, ns_exponent=0.5, seed=0,
+          mode=HOGWILD, tokens_per_launch=1 << 24, device=None):
+    """Train SGNS aid embeddings. ``aid`` int32 [E] sorted by (session, ts) and ``sess_off`` int64 [S+1], device tensors.
+    Returns ``(In, Out, losses)``: the float32 [n_aids, dim] tables on the device and the per-epoch mean loss per pair
+    target (loss sum / (pairs * (1 + neg))). The rate of a launch is :func:`learning_rate` at the source event of the
+    launch's first token."""
+    import torch
+    dev = aid.device if device is None else torch.device(device)
+    tokens_per_launch = int(tokens_per_launch)
+    if tokens_per_launch < 1:
+        raise ValueError('tokens_per_launch must be positive')
+    _, keep_q, weight = vocab_tables(aid, n_aids, min_count, t, ns_exponent)
+    eng = SkipGramEngine(n_aids, dim, ws, neg, keep_q, weight, seed=seed, device=dev)
+    In_h, Out_h = init_tables(n_aids, dim, seed)
+    In, Out = torch.from_numpy(In_h).to(dev), torch.from_numpy(Out_h).to(dev)
+    E = int(aid.numel())
+    losses = []
+    for ep in range(int(epochs)):
+        plan = eng.plan(aid, sess_off, ep)
+        starts = list(range(0, plan.T, tokens_per_launch))
+        first_src = plan.tok_src[torch.tensor(starts, dtype=torch.int64, device=dev)].cpu().tolist() if starts else []
+        total = torch.zeros(1, dtype=torch.float64, device=dev)
+        for t0, src in zip(starts, first_src):
+            rate = learning_rate(lr, ep * E + int(src), int(epochs) * E)
+            total += eng.step(plan, t0, min(t0 + tokens_per_launch, plan.T), In, Out, rate, mode)
+        losses.append(float(total.item()) / max(plan.P * (1 + int(neg)), 1))
+    return In, Out, losses
+
+
+def save_vec(path, In, count, fmt='%.9g'):
+    """word2vec text format of the input vectors: header ``<n_vocab> <dim>``, then one line per aid with ``count > 0`` (the caller
+    zeroes the counts below ``min_count``), ordered by count descending, then aid ascending: the aid and ``dim`` values.
+    Returns the aid order."""
+    In = np.asarray(In, dtype=np.float32)
+    count = np.asarray(count)
+    order = np.lexsort((np.arange(len(count)), -count.astype(np.int64)))
+    order = order[count[order] > 0]
+    with open(path, 'w') as fh:
+        fh.write(f'{len(order)} {In.shape[1]}\n')
+        for a in order:
+            fh.write(str(int(a)) + ' ' + ' '.join(fmt % float(v) for v in In[a]) + '\n')
+    return order
+
+
+def load_vec(path):
+    """``(aids int64 [n], vectors float32 [n, d])`` of a word2vec text file."""
+    with open(path) as fh:
+        n, d = (int(x) for x in fh.readline().split())
+        aids = np.empty(n, dtype=np.int64)
+        vec = np.empty((n, d), dtype=np.float32)
+        for i in range(n):
+            parts = fh.readline().split()
+            aids[i] = int(parts[0])
+            vec[i] = np.array(parts[1:], dtype=np.float64)
+    return aids, vec

@@ -1,0 +1,100 @@
+"""``python trainer.py <config_path relative to settings.MODELS>``: the reference's ``src/gensim_fasttext/trainer.py``.
+
+Reads the reference's ``models/fasttext/config.yaml`` (``model_name: FastText``) and ``models/word2vec/config.yaml``
+(``model_name: Word2Vec``) and trains skip-gram negative-sampling aid embeddings on the device (SPEC-SGNS, DESIGN.md
+section 3i). Sessions come from ``settings.DATA / 'train.pkl'`` and ``'test.pkl'`` through ``events.frame_to_events_device``
+(the reference's fastText branch reads a ``sentences.txt`` made of the same two frames). Writes
+``<model_directory>/aid_embeddings.npy`` (float32 [n_aids, dim], the input vectors) and ``aid_embeddings.vec`` (word2vec
+text format, in-vocabulary aids by count descending then aid ascending). ``fasttext.bin`` / ``word2vec.model`` are not
+written.
+
+Refused with ``ValueError``: ``model: cbow``, ``loss`` other than ``ns``, ``minn`` / ``maxn`` above 0 (fastText);
+``sg: 0`` or ``negative: 0`` (Word2Vec); ``Doc2Vec``. Hierarchical softmax is not built: ``hs: 1`` with ``negative > 0``
+(the reference's own file) trains the negative-sampling part alone and logs the departure once.
+"""
+import argparse
+import logging
+import pathlib
+
+import numpy as np
+import yaml
+
+from .. import settings
+from . import skipgram
+
+_HS_WARNED = False
+
+
+def fasttext_args(model_args):
+    """The :func:`skipgram.train` keywords of a fastText ``model_args`` mapping (fastText's defaults where absent)."""
+    a = dict(model_args)
+    if a.get('model', 'skipgram') != 'skipgram':
+        raise ValueError(f"model: {a.get('model')!r} is not built (only skipgram)")
+    if a.get('loss', 'ns') != 'ns':
+        raise ValueError(f"loss: {a.get('loss')!r} is not built (only ns)")
+    if int(a.get('minn', 0)) > 0 or int(a.get('maxn', 0)) > 0:
+        raise ValueError('sub-word n-grams (minn / maxn > 0) are not built')
+    return dict(dim=int(a.get('dim', 100)), ws=int(a.get('ws', 5)), neg=int(a.get('neg', 5)), epochs=int(a.get('epoch', 5)),
+                lr=float(a.get('lr', 0.05)), t=float(a.get('t', 1e-4)), min_count=int(a.get('minCount', 5)), ns_exponent=0.5,
+                seed=int(a.get('seed', 0)))
+
+
+def word2vec_args(model_args):
+    """The :func:`skipgram.train` keywords of a gensim ``Word2Vec`` ``model_args`` mapping (gensim's defaults where
+    absent)."""
+    global _HS_WARNED
+    a = dict(model_args)
+    if int(a.get('sg', 0)) != 1:
+        raise ValueError('sg: 0 (cbow) is not built (only skip-gram)')
+    if int(a.get('negative', 5)) <= 0:
+        raise ValueError('negative: 0 leaves hierarchical softmax alone, which is not built')
+    if int(a.get('hs', 0)) and not _HS_WARNED:
+        _HS_WARNED = True
+        logging.warning('hs: 1 -- hierarchical softmax is not built; training the negative-sampling part alone')
+    return dict(dim=int(a.get('vector_size', 100)), ws=int(a.get('window', 5)), neg=int(a['negative'] if 'negative' in a else 5),
+                epochs=int(a.get('epochs', 5)), lr=float(a.get('alpha', 0.025)), t=float(a.get('sample', 1e-3)),
+                min_count=int(a.get('min_count', 5)), ns_exponent=float(a.get('ns_exponent', 0.75)), seed=int(a.get('seed', 1)))
+
+
+def train_args(config):
+    """``config`` (the whole YAML mapping) -> the :func:`skipgram.train` keywords."""
+    name = config['model']['model_name']
+    if name == 'FastText':
+        return fasttext_args(config['model']['model_args'])
+    if name == 'Word2Vec':
+        return word2vec_args(config['model']['model_args'])
+    if name == 'Doc2Vec':
+        raise ValueError('Doc2Vec is not built')
+    raise ValueError('Invalid model_name')
+
+
+def run(config, df=None, device='cuda:0', n_aids=None, tokens_per_launch=1 << 24):
+    """Train and write both files; returns ``(In, losses, model_root_directory)``. ``df``: a frame or a list of frames
+    with ``session``, ``aid``, ``ts``, ``type`` (default: ``train.pkl`` + ``test.pkl`` under ``settings.DATA``)."""
+    kw = train_args(config)                               # refusals come before any file or device is touched
+    from ..events import frame_to_events_device
+    model_root_directory = pathlib.Path(settings.MODELS / config['persistence']['model_directory'])
+    model_root_directory.mkdir(parents=True, exist_ok=True)
+    if df is None:
+        import pandas as pd
+        df = [pd.read_pickle(settings.DATA / 'train.pkl'), pd.read_pickle(settings.DATA / 'test.pkl')]
+    ev = frame_to_events_device(df, device=device, n_aids=n_aids)
+    logging.info(f'Sentences Dataset - sentences: {ev.n_sessions} - tokens: {ev.n_events}')
+    In, _, losses = skipgram.train(ev.aid, ev.sess_off, ev.n_aids, tokens_per_launch=tokens_per_launch, **kw)
+    for ep, ls in enumerate(losses):
+        logging.info(f'epoch {ep}: mean loss {ls:.6f}')
+    In = In.cpu().numpy()
+    count, _, _ = skipgram.vocab_tables(ev.aid, ev.n_aids, kw['min_count'], kw['t'], kw['ns_exponent'])
+    count[count < max(kw['min_count'], 1)] = 0
+    np.save(model_root_directory / 'aid_embeddings.npy', In)
+    skipgram.save_vec(model_root_directory / 'aid_embeddings.vec', In, count)
+    logging.info(f"{config['model']['model_name']} aid embeddings finished training and saved to {model_root_directory}")
+    return In, losses, model_root_directory
+
+
+if __name__ == '__main__':
+    parser = argparse.ArgumentParser()
+    parser.add_argument('config_path', type=str)
+    args = parser.parse_args()
+    config = yaml.load(open(settings.MODELS / args.config_path, 'r'), Loader=yaml.FullLoader)
+    run(config)

@@ -1,0 +1,132 @@
+"""Time the skip-gram negative-sampling trainer (csrc/otto_sgns.hip) at OTTO shape and print one JSON line.
+
+Sessions from ``synth.generate_sessions`` (n_aids = 1,855,603), d = 32, ws = 10, neg = 40, t = 1e-4, the reference's
+``models/fasttext/config.yaml``. hipEvents around each call, 1 warm-up, 5 repeats, median with min and max:
+
+  plan     one epoch's plan over all events
+  hogwild  one launch of up to 2^24 kept tokens: tokens/s, target-row updates/s and the algorithmic bytes per second
+           against the 8 TB/s HBM peak. Per target 2 * 4d bytes of Out (read and written), per centre 2 * 4d bytes of In,
+           per kept token 4 bytes of token id and 1 byte of radius; the ids of the drawn negatives are not counted.
+
+Host baseline, same run: vectorised NumPy batch steps of 4,096 centres over 2^16 tokens (the restatement's sequential loop is far too
+slow to time). No fastText or gensim figure exists: neither library is installed where this project is built.
+Needs a GPU; there is no fallback.
+
+    python tools/perf_sgns.py [--sessions 2000000] [--tokens 16777216] [--out profiles/sgns/perf_sgns.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+HBM_PEAK = 8.0e12     # bytes / s, MI355X data sheet
+
+
+def _time(fn, warmup, repeats):
+    import torch
+    for _ in range(warmup):
+        fn()
+    ms = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return {'median_ms': round(statistics.median(ms), 3), 'min_ms': round(min(ms), 3), 'max_ms': round(max(ms), 3)}
+
+
+def _host_batch_step(tok_aid, left, pair_off, In, Out, neg, lr, rng, lo, hi):
+    """vectorised NumPy batch step over the centres [lo, hi); negatives uniform (the draw is not what is timed)"""
+    npair = (pair_off[lo + 1:hi + 1] - pair_off[lo:hi]).astype(np.int64)
+    centre = np.repeat(np.arange(lo, hi), npair)
+    k = np.arange(len(centre)) - np.repeat(pair_off[lo:hi] - pair_off[lo], npair)
+    lf = left[centre].astype(np.int64)
+    ct = np.where(k < lf, centre - lf + k, centre + 1 + (k - lf))
+    tgt = np.concatenate((tok_aid[ct][:, None], rng.integers(0, In.shape[0], (len(centre), neg))), axis=1)
+    h = In[tok_aid[centre]]
+    x = np.einsum('pd,ptd->pt', h, Out[tgt])
+    label = np.zeros_like(x)
+    label[:, 0] = 1.0
+    g = lr * (label - 1.0 / (1.0 + np.exp(-x)))
+    gin = np.einsum('pt,ptd->pd', g, Out[tgt])
+    np.add.at(In, tok_aid[centre], gin)
+    np.add.at(Out, tgt.reshape(-1), (g[:, :, None] * h[:, None, :]).reshape(-1, In.shape[1]))
+    return len(centre)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--sessions', type=int, default=2_000_000)
+    ap.add_argument('--tokens', type=int, default=1 << 24)
+    ap.add_argument('--dim', type=int, default=32)
+    ap.add_argument('--ws', type=int, default=10)
+    ap.add_argument('--neg', type=int, default=40)
+    ap.add_argument('--t', type=float, default=1e-4)
+    ap.add_argument('--host-tokens', type=int, default=1 << 16)
+    ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--out', default='')
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit('perf_sgns: no ROCm device visible (this tool does not fall back)')
+    from otto_amd.gensim_fasttext import skipgram as sg
+    from otto_amd.synth import generate_sessions
+    dev = torch.device('cuda:0')
+    ev = generate_sessions(args.sessions)
+    aid = torch.from_numpy(ev.aid.astype(np.int32)).to(dev)
+    sess_off = torch.from_numpy(ev.sess_off).to(dev)
+    n_aids, d, E = ev.n_aids, args.dim, int(aid.numel())
+    _, keep_q, weight = sg.vocab_tables(aid, n_aids, 1, args.t, 0.5)
+    eng = sg.SkipGramEngine(n_aids, d, args.ws, args.neg, keep_q, weight, seed=1, device=dev)
+    In_h, Out_h = sg.init_tables(n_aids, d, 1)
+    In, Out = torch.from_numpy(In_h).to(dev), torch.from_numpy(Out_h).to(dev)
+    out = {'tool': 'perf_sgns', 'device': torch.cuda.get_device_name(0), 'sessions': args.sessions, 'events': E, 'n_aids': n_aids,
+           'd': d, 'ws': args.ws, 'neg': args.neg, 't': args.t, 'warmup': args.warmup, 'repeats': args.repeats,
+           'table_bytes_each': n_aids * d * 4}
+    out['plan'] = _time(lambda: eng.plan(aid, sess_off, 0), args.warmup, args.repeats)
+    plan = eng.plan(aid, sess_off, 0)
+    n_tok = min(args.tokens, plan.T)
+    pairs = int(plan.pair_off[n_tok] - plan.pair_off[0])
+    out.update(kept_tokens=plan.T, pairs=plan.P, launch_tokens=n_tok, launch_pairs=pairs)
+    hw = _time(lambda: eng.step(plan, 0, n_tok, In, Out, 0.05, sg.HOGWILD), args.warmup, args.repeats)
+    sec = hw['median_ms'] * 1e-3
+    targets = pairs * (1 + args.neg)
+    n_bytes = targets * 2 * 4 * d + n_tok * 2 * 4 * d + n_tok * 5
+    hw.update(tokens_per_s=round(n_tok / sec), target_rows_per_s=round(targets / sec), algorithmic_bytes=n_bytes,
+              bytes_per_s=round(n_bytes / sec), share_of_hbm_peak=round(n_bytes / sec / HBM_PEAK, 4))
+    out['hogwild'] = hw
+    m = min(args.host_tokens, plan.T)
+    tok_aid, left = plan.tok_aid[:m + 64].cpu().numpy().astype(np.int64), plan.tok_left[:m + 64].cpu().numpy()
+    pair_off = plan.pair_off[:m + 65].cpu().numpy()
+    valid = m
+    while valid and (pair_off[valid] - pair_off[valid - 1]) - left[valid - 1] + valid - 1 >= len(tok_aid):
+        valid -= 1                                           # keep every context inside the copied head
+    rng = np.random.default_rng(0)
+    In_c, Out_c = In_h.copy(), Out_h.copy()
+    t0 = time.perf_counter()
+    host_pairs = 0
+    for lo in range(0, valid, 4096):                         # 4,096 centres per batch step bound the gathered rows' memory
+        host_pairs += _host_batch_step(tok_aid, left, pair_off, In_c, Out_c, args.neg, 0.05, rng, lo, min(lo + 4096, valid))
+    hs = time.perf_counter() - t0
+    out['host_numpy_batch_step'] = {'tokens': valid, 'pairs': host_pairs, 'seconds': round(hs, 3), 'tokens_per_s': round(valid / hs),
+                                    'what': 'one run, one process, vectorised NumPy batch step on the host of the GPU machine; '
+                                            'no fastText or gensim figure exists (neither is installed)'}
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as fh:
+            fh.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()
