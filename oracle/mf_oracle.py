@@ -90,6 +90,23 @@ def eval_batch(E1, E2, i1, i2, target, kind):
     return float(l.mean()), out
 
 
+def eval_sums(E1, E2, i1, i2, target, kind):
+    """What ``otto_mf_eval_sums`` adds to the running validation sums for one batch, in float64 from float64 dot
+    products: (sum |p - t|, sum (p - t)^2, hits, count). p is the raw output (MSE models) or its sigmoid (BCE models);
+    a hit is (p >= 0.5) == (t >= 0.5) (include/otto_mf.h). The forward is written out here because ``forward`` rounds
+    to float32."""
+    out = (E1[i1].astype(np.float64) * E2[i2].astype(np.float64)).sum(axis=-1)
+    t = np.asarray(target).astype(np.float64)
+    if kind == 'MSELoss':
+        p = out
+    elif kind == 'BCEWithLogitsLoss':
+        p = 1.0 / (1.0 + np.exp(-out))
+    else:
+        raise ValueError(kind)
+    e = p - t
+    return float(np.abs(e).sum()), float((e * e).sum()), float(((p >= 0.5) == (t >= 0.5)).sum()), float(len(t))
+
+
 # ---------------------------------------------------------------------------
 # BPR (SURVEY.md App. B.2)
 # ---------------------------------------------------------------------------
@@ -100,16 +117,19 @@ def mix64(z):
     return z ^ (z >> 31)
 
 
-def bpr_negative(seed, epoch, row, pos, n_items):
+def bpr_negative(seed, epoch, row, pos, n_items, attempts=False):
     """Counter-based negative for one global row (python ints): uniform by multiply-high of 32
-    random bits, redrawn (16 attempts) while equal to the positive."""
+    random bits, redrawn (16 attempts) while equal to the positive. ``attempts=True`` returns
+    ``(j, n)`` with n the number of draws that hit the positive: 16 means every attempt was used
+    up and j is the fallback ``(pos + 1) % n_items``."""
     base = mix64(seed ^ ((epoch * 0xD1342543DE82EF95) & MASK)) ^ ((row * 0xA0761D6478BD642F) & MASK)
     for att in range(16):
         r = mix64(base ^ ((att * 0xE7037ED1A0B428DB) & MASK))
         j = ((r >> 32) * n_items) >> 32
         if j != pos:
-            return j
-    return (pos + 1) % n_items
+            return (j, att) if attempts else j
+    j = (pos + 1) % n_items
+    return (j, 16) if attempts else j
 
 
 def bpr_negatives(seed, epoch, row0, pos, n_items):

@@ -127,3 +127,28 @@ def test_score_topk_pad_and_ties():
     ids, sc = mo.score_topk(U, V, k=3, pad_col=0)
     assert ids[0].tolist() == [1, 2, 4] and ids[1].tolist() == [2, 3, 4]     # ties -> smaller id first; PAD never
     assert sc[0].tolist() == [1, 1, 1]
+
+
+def test_eval_sums_on_a_hand_computed_batch():
+    E1 = np.array([[1.0, 2.0], [0.5, -1.0], [0.0, 0.25]], dtype=np.float32)
+    E2 = np.array([[1.0, 0.0], [0.5, 0.5]], dtype=np.float32)
+    i1, i2, t = np.array([0, 1, 2, 0]), np.array([0, 1, 1, 1]), np.array([1, 0, 2, 1])
+    # outputs 1, -0.25, 0.125, 1.5; MSE: p = out; hits: (p >= .5) == (t >= .5) -> T, T, F, T
+    assert mo.eval_sums(E1, E2, i1, i2, t, 'MSELoss') == (0 + 0.25 + 1.875 + 0.5, 0.0625 + 1.875 ** 2 + 0.25, 3.0, 4.0)
+    p = 1 / (1 + np.exp(-np.array([1.0, -0.25, 0.125, 1.5])))
+    got = mo.eval_sums(E1, E2, i1, i2, t, 'BCEWithLogitsLoss')
+    np.testing.assert_allclose(got[:2], (np.abs(p - t).sum(), ((p - t) ** 2).sum()), rtol=1e-15)
+    assert got[2:] == (4.0, 4.0)                           # p >= .5: T, F, T, T; t >= .5: T, F, T, T
+    # float64 dot products, not the float32 forward: 1 + 2^-30 is kept
+    A = np.array([[1.0, 2.0 ** -15]], dtype=np.float32)
+    assert mo.eval_sums(A, A, np.array([0]), np.array([0]), np.array([1]), 'MSELoss')[0] == 2.0 ** -30
+    with pytest.raises(ValueError):
+        mo.eval_sums(E1, E2, i1, i2, t, 'L1Loss')
+
+
+def test_negative_sampler_reports_its_attempts():
+    for row in range(300):
+        for pos in (0, 1, 2):
+            j, n = mo.bpr_negative(3, 1, row, pos, 3, attempts=True)
+            assert j == mo.bpr_negative(3, 1, row, pos, 3) and 0 <= n < 16 and j != pos
+    assert mo.bpr_negative(1, 0, 6543, 1, 2, attempts=True) == (0, 16)
