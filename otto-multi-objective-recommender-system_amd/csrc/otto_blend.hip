@@ -11,10 +11,9 @@
 //                    select reads 8 n, and needs 16 n bytes of workspace where the select needs 100 KB.
 //   k_blend_scale    (float)((x - center) / scale): a true float64 division, then one rounding.
 //   k_join_keys      (session << 32 | aid, score, model) rows of all models, concatenated in model order; negative ids
-//                    counted; OR of the keys and of their complements (which digits vary at all).
-//   k_js_hist / k_js_scatter  stable 8-bit LSD radix sort of those rows by key: the scatter of otto_events.hip (stable
-//                    in-wave ranks by ballots, tile reordered in LDS, then written in digit order) carrying two payload
-//                    columns. A digit that is constant over the input turns its pass into a plain copy, decided on the
+//                    counted; OR and AND of the keys (which digits vary at all).
+//   k_rs_hist / k_rs_scatter  the shared stable LSD radix sort (radix.h) of those rows by key, carrying the model as its
+//                    byte column. A digit that is constant over the input turns its pass into a plain copy, decided on the
 //                    device, so the host needs no read-back before the passes. The sort is stable and the input is in
 //                    model order, so the rows of one key come out in ascending model order.
 //   k_join_mark      group heads (first row of a key) that own an output row: some un-flagged model is present. Two
@@ -27,7 +26,7 @@
 // (#pragma clang fp contract(off) in its body) and the sum is written with plain * and +: HIP's __fmul_rn / __fadd_rn are
 // plain operators in the headers, and hipcc, which contracts a * b + c by default, fuses them like any other.
 #include "common.h"
-#include "scan.h"
+#include "radix.h"
 #include "../../include/otto_covis.h"
 #include "../../include/otto_blend.h"
 
@@ -63,15 +62,6 @@ struct SelState {
     SelResult res;
 };
 
-__device__ __forceinline__ uint64_t dkey(double x) {
-    const uint64_t b = x == 0.0 ? 0ull : (uint64_t)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dkey_inv(uint64_t k) {
-    const uint64_t b = (k >> 63) ? (k ^ 0x8000000000000000ull) : ~k;
-    return __longlong_as_double((long long)b);
-}
-
 template <bool FIRST>
 __global__ __launch_bounds__(SEL_THREADS) void k_sel_hist(const double* __restrict__ x, int64_t n, int pass, SelState* st) {
     __shared__ uint32_t s_h[SEL_RANKS * 256];
@@ -86,7 +76,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_sel_hist(const double* __restri
     for (int64_t i = (int64_t)blockIdx.x * SEL_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * SEL_THREADS) {
         const double v = x[i];
         if (v != v) { ++nan; continue; }
-        const uint64_t k = dkey(v);
+        const uint64_t k = ordered_key(v);
         if (FIRST) {
             inf |= (v == INFINITY || v == -INFINITY);
             atomicAdd(&s_h[k >> 56], 1u);
@@ -104,7 +94,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_sel_hist(const double* __restri
         if (c) atomicAdd(&st->hist[pass][i >> 8][i & 255], (unsigned long long)c);
     }
     if (FIRST) {
-        for (int o = 32; o > 0; o >>= 1) nan += __shfl_xor(nan, o, 64);
+        nan = wave_reduce<Sum>(nan);
         if (lane_id() == 0 && nan) atomicAdd(&st->res.n_nan, nan);
         if (inf) atomicOr(&st->res.has_inf, 1u);
     }
@@ -159,7 +149,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_sel_pick(SelState* st, int64_t 
             while (u < nuq && st->uprefix[u] != s_npref[q]) ++u;
             if (u == nuq) st->uprefix[nuq++] = s_npref[q];
             st->slot[q] = u;
-            if (pass == SEL_PASSES - 1) st->res.stats[q] = dkey_inv(s_npref[q]);
+            if (pass == SEL_PASSES - 1) st->res.stats[q] = ordered_key_inv((uint64_t)s_npref[q]);
         }
         st->nuniq = nuq;
     }
@@ -174,14 +164,6 @@ __global__ __launch_bounds__(256) void k_blend_scale(const double* __restrict__ 
 // ---------------------------------------------------------------------------------------------------------------------
 // join
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int JS_THREADS = 256;
-constexpr int JS_ITEMS = 16;
-constexpr int JS_TILE = JS_THREADS * JS_ITEMS;       // 4096 rows per workgroup and step
-constexpr int JS_WAVES = JS_THREADS / 64;
-constexpr int JS_SUB = 4;                            // tiles a workgroup takes one after the other
-constexpr int64_t JS_SPAN = (int64_t)JS_TILE * JS_SUB;
-int64_t js_blocks(int64_t n) { return (n + JS_SPAN - 1) / JS_SPAN; }
-
 struct JoinArgs {
     const int32_t* session[OTTO_BLEND_MAX_MODELS];
     const int32_t* aid[OTTO_BLEND_MAX_MODELS];
@@ -195,46 +177,17 @@ struct JoinArgs {
 // per-device scratch of the join: counts, error words, key bits
 struct JoinScratch {
     unsigned long long n_out, n_sessions;
-    unsigned long long key_or, nkey_or;              // OR of the keys, OR of their complements: a bit varies iff set in both
+    unsigned long long key_bits[2];                  // OR and AND of the keys (key_bits_fold)
     unsigned int n_negative, n_duplicate;
 };
 
-struct JoinWs {
-    uint64_t* key[2];
-    uint32_t* val[2];
-    uint8_t* mod[2];
-    uint32_t* counts;    // [256 * nb]
-    uint64_t* offs;      // [max(256 * nb, n) + 1]
-    uint64_t* partial;
-};
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-size_t join_ws_layout(int64_t n, char* base, JoinWs* w) {
-    const int64_t nb = js_blocks(n);
-    const size_t scan_n = (size_t)(256 * nb > n ? 256 * nb : n) + 1;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += align256(bytes); return p; };
-    char* k0 = take((size_t)n * 8); char* k1 = take((size_t)n * 8);
-    char* v0 = take((size_t)n * 4); char* v1 = take((size_t)n * 4);
-    char* m0 = take((size_t)n); char* m1 = take((size_t)n);
-    char* c = take((size_t)256 * nb * 4);
-    char* f = take(scan_n * 8);
-    char* p = take(scan_partial_bytes((int64_t)scan_n));
-    if (w) {
-        w->key[0] = (uint64_t*)k0; w->key[1] = (uint64_t*)k1; w->val[0] = (uint32_t*)v0; w->val[1] = (uint32_t*)v1;
-        w->mod[0] = (uint8_t*)m0; w->mod[1] = (uint8_t*)m1;
-        w->counts = (uint32_t*)c; w->offs = (uint64_t*)f; w->partial = (uint64_t*)p;
-    }
-    return o;
-}
-
 __global__ __launch_bounds__(256) void k_join_keys(JoinArgs a, uint64_t* key, uint32_t* val, uint8_t* mod, JoinScratch* sc) {
-    __shared__ unsigned long long s_or[4], s_nor[4];
     const int m = blockIdx.y;
     const int64_t nm = a.off[m + 1] - a.off[m];
     const int32_t* ses = a.session[m];
     const int32_t* aid = a.aid[m];
     const float* score = a.score[m];
-    unsigned long long vo = 0, vn = 0;
+    unsigned long long vo = 0, va = ~0ull;
     unsigned int neg = 0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nm; i += (int64_t)gridDim.x * 256) {
         const int32_t s = ses[i], d = aid[i];
@@ -245,148 +198,10 @@ __global__ __launch_bounds__(256) void k_join_keys(JoinArgs a, uint64_t* key, ui
         val[o] = __float_as_uint(score[i]);
         mod[o] = (uint8_t)m;
         vo |= k;
-        vn |= ~k;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        vo |= __shfl_xor(vo, o, 64);
-        vn |= __shfl_xor(vn, o, 64);
+        va &= k;
     }
     if (neg) atomicAdd(&sc->n_negative, neg);
-    if (lane_id() == 0) { s_or[threadIdx.x >> 6] = vo; s_nor[threadIdx.x >> 6] = vn; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicOr(&sc->key_or, s_or[0] | s_or[1] | s_or[2] | s_or[3]);
-        atomicOr(&sc->nkey_or, s_nor[0] | s_nor[1] | s_nor[2] | s_nor[3]);
-    }
-}
-
-__device__ __forceinline__ bool digit_varies(const JoinScratch* sc, int shift) {
-    return (((sc->key_or & sc->nkey_or) >> shift) & 255ull) != 0;
-}
-
-__global__ __launch_bounds__(JS_THREADS) void k_js_hist(const uint64_t* key, int64_t n, int shift, int64_t nb, uint32_t* counts,
-                                                        const JoinScratch* sc) {
-    __shared__ uint32_t s_h[256];
-    if (!digit_varies(sc, shift)) return;            // the scatter of this pass copies; the counts are not read
-    s_h[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * JS_SPAN;
-    for (int sub = 0; sub < JS_SUB; ++sub) {
-#pragma unroll
-        for (int c = 0; c < JS_ITEMS; ++c) {
-            const int64_t i = base + (int64_t)sub * JS_TILE + (int64_t)c * JS_THREADS + threadIdx.x;
-            if (i < n) atomicAdd(&s_h[(key[i] >> shift) & 255u], 1u);
-        }
-    }
-    __syncthreads();
-    counts[(int64_t)threadIdx.x * nb + blockIdx.x] = s_h[threadIdx.x];
-}
-
-struct CountAt {
-    const uint32_t* c;
-    __device__ uint64_t operator()(int64_t i) const { return c[i]; }
-};
-
-// One pass of the stable LSD sort over (key, val, mod): see k_rs_scatter of otto_events.hip for the ranking scheme.
-__global__ __launch_bounds__(JS_THREADS) void k_js_scatter(const uint64_t* key, const uint32_t* val, const uint8_t* mod, int64_t n,
-                                                           int shift, int64_t nb, const uint64_t* offs, uint64_t* key_out,
-                                                           uint32_t* val_out, uint8_t* mod_out, const JoinScratch* sc) {
-    __shared__ uint16_t s_wcnt[JS_WAVES][256];
-    __shared__ uint32_t s_scan[JS_THREADS / 64 + 1];
-    __shared__ long long s_delta[256];
-    __shared__ uint64_t s_k[JS_TILE];
-    __shared__ uint32_t s_v[JS_TILE];
-    __shared__ uint8_t s_m[JS_TILE];
-    if (!digit_varies(sc, shift)) {                  // constant digit: the pass is the identity
-        const int64_t base = (int64_t)blockIdx.x * JS_SPAN;
-        for (int64_t i = base + threadIdx.x; i < base + JS_SPAN && i < n; i += JS_THREADS) {
-            key_out[i] = key[i];
-            val_out[i] = val[i];
-            mod_out[i] = mod[i];
-        }
-        return;
-    }
-    const int w = threadIdx.x >> 6;
-    const unsigned lane = lane_id();
-    unsigned long long gbase = offs[(int64_t)threadIdx.x * nb + blockIdx.x];     // thread d: where the workgroup's next row of digit d goes
-    for (int sub = 0; sub < JS_SUB; ++sub) {
-        const int64_t tile_base = (int64_t)blockIdx.x * JS_SPAN + (int64_t)sub * JS_TILE;
-        if (tile_base >= n) break;
-        for (int q = 0; q < JS_WAVES; ++q) s_wcnt[q][threadIdx.x] = 0;
-        __syncthreads();
-        const int64_t wave_base = tile_base + (int64_t)w * (JS_TILE / JS_WAVES);
-        uint64_t k[JS_ITEMS];
-        uint32_t v[JS_ITEMS], lr[JS_ITEMS];
-        uint8_t md[JS_ITEMS];
-        const uint64_t lt = (1ull << lane) - 1ull;
-#pragma unroll
-        for (int c = 0; c < JS_ITEMS; ++c) {
-            const int64_t i = wave_base + (int64_t)c * 64 + lane;
-            const bool valid = i < n;
-            k[c] = valid ? key[i] : ~0ull;
-            v[c] = valid ? val[i] : 0u;
-            md[c] = valid ? mod[i] : (uint8_t)0;
-        }
-#pragma unroll
-        for (int c = 0; c < JS_ITEMS; ++c) {
-            const bool valid = wave_base + (int64_t)c * 64 + lane < n;
-            const uint32_t dig = (uint32_t)(k[c] >> shift) & 255u;
-            uint64_t m = __ballot(valid);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const bool bit = (dig >> b) & 1u;
-                const uint64_t bb = __ballot(bit);
-                m &= bit ? bb : ~bb;
-            }
-            const int leader = valid ? __ffsll((unsigned long long)m) - 1 : (int)lane;
-            uint32_t prev = 0;
-            if (valid && (int)lane == leader) {
-                prev = s_wcnt[w][dig];
-                s_wcnt[w][dig] = (uint16_t)(prev + (uint32_t)__popcll(m));
-            }
-            prev = (uint32_t)__shfl((int)prev, leader, 64);
-            lr[c] = prev + (uint32_t)__popcll(m & lt);
-            wave_lds_sync();                         // the next chunk's leaders read what this chunk's wrote
-        }
-        __syncthreads();
-        {
-            // digit threadIdx.x: position of its run in the tile (exclusive scan over the digits), every wave's share of it
-            uint32_t tot = 0, cnt[JS_WAVES];
-#pragma unroll
-            for (int q = 0; q < JS_WAVES; ++q) { cnt[q] = s_wcnt[q][threadIdx.x]; tot += cnt[q]; }
-            uint32_t all;
-            uint32_t run = block_excl_scan<uint32_t, JS_THREADS>(tot, s_scan, &all);
-            s_delta[threadIdx.x] = (long long)gbase - (long long)run;
-            gbase += tot;
-#pragma unroll
-            for (int q = 0; q < JS_WAVES; ++q) { s_wcnt[q][threadIdx.x] = (uint16_t)run; run += cnt[q]; }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < JS_ITEMS; ++c) {
-            if (wave_base + (int64_t)c * 64 + lane < n) {
-                const uint32_t p = s_wcnt[w][(uint32_t)(k[c] >> shift) & 255u] + lr[c];      // < JS_TILE
-                s_k[p] = k[c];
-                s_v[p] = v[c];
-                s_m[p] = md[c];
-            }
-        }
-        __syncthreads();
-        const int64_t left = n - tile_base;
-        const uint32_t tile_n = left < (int64_t)JS_TILE ? (uint32_t)left : (uint32_t)JS_TILE;
-#pragma unroll
-        for (int c = 0; c < JS_ITEMS; ++c) {
-            const uint32_t p = (uint32_t)c * JS_THREADS + threadIdx.x;
-            if (p < tile_n) {
-                const uint64_t kk = s_k[p];
-                const long long g = s_delta[(uint32_t)(kk >> shift) & 255u] + (long long)p;  // in [0, n): offs is the scan of the counts
-                key_out[g] = kk;
-                val_out[g] = s_v[p];
-                mod_out[g] = s_m[p];
-            }
-        }
-        __syncthreads();                             // the next tile reuses the staging arrays
-    }
+    key_bits_fold(vo, va, sc->key_bits);
 }
 
 // flag[i] = 1 where sorted row i is the first of its key and some un-flagged model holds the key
@@ -529,7 +344,7 @@ extern "C" int otto_blend_scale(const double* d_x, int64_t n, double center, dou
 extern "C" int64_t otto_blend_join_workspace(int64_t n_total, int32_t M) {
     (void)M;
     if (n_total <= 0) return 256;
-    return (int64_t)join_ws_layout(n_total, nullptr, nullptr);
+    return (int64_t)radix_ws_layout(n_total, true, nullptr, nullptr);
 }
 
 extern "C" int otto_blend_join(int32_t M, const int32_t* const* d_session, const int32_t* const* d_aid, const float* const* d_score,
@@ -567,34 +382,25 @@ extern "C" int otto_blend_join(int32_t M, const int32_t* const* d_session, const
     OTTO_REQUIRE(((uintptr_t)d_ws & 255) == 0, "otto_blend_join: the workspace must be 256-byte aligned");
     OTTO_REQUIRE(ws_bytes >= otto_blend_join_workspace(tot, M), "workspace too small (%lld < %lld)", (long long)ws_bytes,
                  (long long)otto_blend_join_workspace(tot, M));
-    JoinWs w;
-    join_ws_layout(tot, (char*)d_ws, &w);
+    RadixWs w;
+    radix_ws_layout(tot, true, (char*)d_ws, &w);
     void* scratch = nullptr;
     OTTO_TRY(device_scratch(SCRATCH_BLEND, 256, &scratch, s));
     JoinScratch* sc = (JoinScratch*)scratch;
     OTTO_HIP(hipMemsetAsync(sc, 0, sizeof(JoinScratch), s));
-    k_join_keys<<<dim3((unsigned)grid_for(n_max), (unsigned)M), 256, 0, s>>>(a, w.key[0], w.val[0], w.mod[0], sc);
+    OTTO_HIP(hipMemsetAsync(&sc->key_bits[1], 0xFF, 8, s));      // the AND of the keys starts at all ones
+    k_join_keys<<<dim3((unsigned)grid_for(n_max), (unsigned)M), 256, 0, s>>>(a, w.key[0], w.val[0], w.byt[0], sc);
     OTTO_HIP(hipGetLastError());
-    const int64_t nb = js_blocks(tot);
-    int cur = 0;
-    for (int pass = 0; pass < 8; ++pass) {           // an even number of passes: the sorted rows end in buffer 0
-        const int shift = 8 * pass;
-        k_js_hist<<<(unsigned)nb, JS_THREADS, 0, s>>>(w.key[cur], tot, shift, nb, w.counts, sc);
-        OTTO_HIP(hipGetLastError());
-        OTTO_TRY(device_scan(CountAt{w.counts}, 256 * nb, w.offs, w.partial, s));
-        k_js_scatter<<<(unsigned)nb, JS_THREADS, 0, s>>>(w.key[cur], w.val[cur], w.mod[cur], tot, shift, nb, w.offs, w.key[cur ^ 1],
-                                                         w.val[cur ^ 1], w.mod[cur ^ 1], sc);
-        OTTO_HIP(hipGetLastError());
-        cur ^= 1;
-    }
+    int cur = 0;                                     // all eight passes are launched, an even number: the sorted rows end in buffer 0
+    OTTO_TRY((radix_passes<true>(w, tot, ~0ull, SkipOnDevice{sc->key_bits}, &cur, s)));
     // buffers 1 are free now: the group flags and the output rows' sessions live there
-    uint8_t* flag = w.mod[1];
+    uint8_t* flag = w.byt[1];
     int32_t* out_sess = (int32_t*)w.key[1];
     const int grid = grid_for(tot);
-    k_join_mark<<<grid, 256, 0, s>>>(w.key[0], w.mod[0], tot, M, ~a.flagged & ((1u << M) - 1u), flag, sc);
+    k_join_mark<<<grid, 256, 0, s>>>(w.key[0], w.byt[0], tot, M, ~a.flagged & ((1u << M) - 1u), flag, sc);
     OTTO_HIP(hipGetLastError());
     OTTO_TRY(device_scan(FlagAt{flag}, tot, w.offs, w.partial, s));
-    k_join_emit<<<grid, 256, 0, s>>>(a, w.key[0], w.val[0], w.mod[0], tot, flag, w.offs, d_out_aid, d_out_pred, d_out_pred64, out_sess, sc);
+    k_join_emit<<<grid, 256, 0, s>>>(a, w.key[0], w.val[0], w.byt[0], tot, flag, w.offs, d_out_aid, d_out_pred, d_out_pred64, out_sess, sc);
     OTTO_HIP(hipGetLastError());
     OTTO_TRY(device_scan(SessHead{out_sess, sc}, tot, w.offs, w.partial, s));
     k_join_sessions<<<grid, 256, 0, s>>>(out_sess, tot, w.offs, d_out_session_id, d_out_row_off, sc);

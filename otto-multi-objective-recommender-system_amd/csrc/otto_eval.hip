@@ -18,6 +18,7 @@
 // Hits. Padded rows (k <= 64): an 8-lane group per label session, one lane per label, no cross-lane traffic inside the
 // loops. CSR rows: one wave per label session, lanes strided over the row, a ballot per label.
 #include "common.h"
+#include "wave.h"
 #include "scan.h"
 #include "../../include/otto_covis.h"
 #include "../../include/otto_eval.h"
@@ -329,8 +330,6 @@ struct CntAt {
     __device__ uint64_t operator()(int64_t i) const { return (uint64_t)(uint32_t)c[i]; }
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct SplitWs {
     int32_t* cnt[4];
     int32_t* list_med;
@@ -544,7 +543,7 @@ __global__ __launch_bounds__(256) void k_hits_totals(HitsArgs A) {
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        for (int d = 1; d < 64; d <<= 1) t[c] += __shfl_xor(t[c], d, 64);
+        t[c] = wave_reduce<Sum>(t[c]);
         if (lane_id() == 0) sm[c][threadIdx.x >> 6] = t[c];
     }
     __syncthreads();

@@ -10,6 +10,8 @@
 // Session table: one wave per session, the aid-table columns summed in event order.
 // Matrix: lanes run along the flattened (row, column) index of a tile, so every wave writes whole lines.
 #include "common.h"
+#include "sort.h"
+#include "wave.h"
 #include "../../include/otto_events.h"
 #include "../../include/otto_feat.h"
 
@@ -17,9 +19,6 @@
 
 #include <algorithm>
 #include <vector>
-
-int otto_sort_pairs_in_ws(uint64_t* d_keys, int64_t n, void* d_ws, uint64_t** d_keys_sorted, uint32_t** d_vals_sorted, hipStream_t s);
-void otto_sort_ws_buffers(int64_t n, void* d_ws, uint64_t** key0, uint32_t** val0, uint64_t** scan_out, uint64_t** scan_partial);
 
 namespace otto {
 
@@ -54,22 +53,6 @@ struct AidTot {
     uint32_t slot[OTTO_FEAT_MAX_WEEK_SLOTS][3];
 };
 
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_or64(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)v, o, 64); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)v, o, 64); v = t > v ? t : v; }
-    return v;
-}
 __device__ __forceinline__ uint32_t count_lanes(bool p) { return (uint32_t)__popcll(__ballot(p)); }
 
 // the session that owns event / row e: the largest s in [lo, hi] with off[s] <= e
@@ -192,13 +175,13 @@ __device__ void feat_scan(const uint32_t* order, const uint2* rec, const FeatCal
             }
         }
     }
-    t.hour = wave_sum64(hour); t.hour2 = wave_sum64(hour2); t.dow = wave_sum64(dow); t.dow2 = wave_sum64(dow2);
-    t.lw_dow = wave_sum64(lw_dow);
-    t.days = wave_or64(days);
+    t.hour = wave_reduce<Sum>(hour); t.hour2 = wave_reduce<Sum>(hour2); t.dow = wave_reduce<Sum>(dow); t.dow2 = wave_reduce<Sum>(dow2);
+    t.lw_dow = wave_reduce<Sum>(lw_dow);
+    t.days = wave_reduce<Or>(days);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) t.tdays[k] = wave_or64(tdays[k]);
-    t.ts_min = wave_min32(ts_min); t.ts_max = wave_max32(ts_max);
-    t.lw_ts_min = wave_min32(lw_ts_min); t.lw_ts_max = wave_max32(lw_ts_max);
+    for (int k = 0; k < 3; ++k) t.tdays[k] = wave_reduce<Or>(tdays[k]);
+    t.ts_min = wave_reduce<Min>(ts_min); t.ts_max = wave_reduce<Max>(ts_max);
+    t.lw_ts_min = wave_reduce<Min>(lw_ts_min); t.lw_ts_max = wave_reduce<Max>(lw_ts_max);
 }
 
 __device__ void feat_merge(AidTot& a, const AidTot& b) {
@@ -374,7 +357,7 @@ __global__ __launch_bounds__(256) void k_feat_session(const uint32_t* aid, const
             for (int j = 0; j < i; ++j) first = first && s_aid[w][j] != a;
             uniq += first ? 1u : 0u;
         }
-        uniq = (uint32_t)wave_sum64(uniq);
+        uniq = wave_reduce<Sum>(uniq);
         double sum[5] = {0, 0, 0, 0, 0};
         uint32_t cnt[5] = {0, 0, 0, 0, 0};
         float last[5] = {nanf_, nanf_, nanf_, nanf_, nanf_}, cmin = nanf_, cmax = nanf_;
@@ -474,7 +457,6 @@ __global__ __launch_bounds__(256) void k_feat_matrix(const int64_t* row_off, int
     }
 }
 
-static size_t feat_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct AidWs {
     uint32_t* err;          // [0] error word, [1] hot aids
@@ -489,7 +471,7 @@ struct AidWs {
 
 static size_t aid_ws_layout(int64_t n, uint32_t n_aids, char* base, AidWs* w) {
     size_t o = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += feat_align(bytes); return p; };
+    auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += align256(bytes); return p; };
     char* e = take(256); char* c = take(sizeof(FeatCal)); char* d = take(OTTO_FEAT_MAX_DAYS * 4);
     char* a = take(((size_t)n_aids + 1) * 4); char* r = take((size_t)n * 8); char* v = take((size_t)FEAT_RANKED * n_aids * 4);
     char* h = take(((size_t)n / FEAT_HOT + 1) * 4);
@@ -601,7 +583,7 @@ extern "C" int otto_feat_aid_table(const uint32_t* d_aid, const int32_t* d_ts, c
     return read_error(w.err, s, "otto_feat_aid_table");
 }
 
-extern "C" int64_t otto_feat_session_table_workspace(int64_t n_sess) { return n_sess < 0 ? 0 : 256 + (int64_t)feat_align(sizeof(FeatCal)); }
+extern "C" int64_t otto_feat_session_table_workspace(int64_t n_sess) { return n_sess < 0 ? 0 : 256 + (int64_t)align256(sizeof(FeatCal)); }
 
 extern "C" int otto_feat_session_table(const uint32_t* d_aid, const int32_t* d_ts, const uint8_t* d_type, const int64_t* d_sess_off,
                                        int64_t n_sess, const float* d_aid_table, uint32_t n_aids, int32_t day_min, int32_t n_days,
@@ -627,7 +609,7 @@ extern "C" int otto_feat_session_table(const uint32_t* d_aid, const int32_t* d_t
 }
 
 extern "C" int64_t otto_feat_matrix_workspace(int64_t n_rows) {
-    return n_rows < 0 ? 0 : 256 + (int64_t)feat_align(sizeof(FeatProgram) * OTTO_FEAT_MAX_COLUMNS);
+    return n_rows < 0 ? 0 : 256 + (int64_t)align256(sizeof(FeatProgram) * OTTO_FEAT_MAX_COLUMNS);
 }
 
 extern "C" int otto_feat_matrix(const int64_t* d_row_off, int64_t n_sess, const int32_t* d_cand, const float* d_score, int64_t n_rows,

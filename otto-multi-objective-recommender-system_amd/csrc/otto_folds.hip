@@ -28,6 +28,7 @@
 //                  aligned dword; the bytes in front of the first aligned address and behind the last whole dword are
 //                  single byte stores.
 #include "common.h"
+#include "wave.h"
 #include "scan.h"
 #include "../../include/otto_covis.h"
 #include "../../include/otto_forest.h"
@@ -451,7 +452,6 @@ int err_end(uint32_t* err, hipStream_t s) {
     return err_code(bad);
 }
 
-int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 
 struct KfPlan {
     int nb;

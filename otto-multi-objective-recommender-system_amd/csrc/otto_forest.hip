@@ -15,6 +15,7 @@
 //   k_session_topk   one wave per session: its rows stream 64 at a time against the sorted list that topk.h keeps one
 //                    entry per lane (key = order-preserving image of the float64 score, then the row position).
 #include "common.h"
+#include "wave.h"
 #include "topk.h"
 #include "../../include/otto_covis.h"
 #include "../../include/otto_forest.h"
@@ -208,13 +209,6 @@ __global__ __launch_bounds__(256) void k_forest(ForestArgs a) {
         if (a.raw) a.raw[row0 + tid] = sum;
         if (a.acc) a.acc[row0 + tid] += (double)(float)sum / a.divisor;
     }
-}
-
-// order-preserving image of a score: larger = better, never 0 (0 = empty slot); every NaN -> 1, below -inf; -0.0 = +0.0
-__device__ __forceinline__ uint64_t score_key(double x) {
-    if (x != x) return 1ull;
-    const uint64_t b = x == 0.0 ? 0ull : (uint64_t)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 __global__ __launch_bounds__(256) void k_session_topk(const double* score, const int32_t* aid, const int64_t* row_off, int64_t S,

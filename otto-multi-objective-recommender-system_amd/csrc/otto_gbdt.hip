@@ -22,6 +22,7 @@
 //   k_add_tree     one lane per row walks the tree over the bins; bounded, range-checked.
 // Host: otto_gbdt_grow_tree drives the leaf-wise loop: one small device-to-host copy per split.
 #include "common.h"
+#include "wave.h"
 #include "../../include/otto_covis.h"
 #include "../../include/otto_forest.h"
 #include "../../include/otto_gbdt.h"
@@ -42,13 +43,6 @@ constexpr int PART_ROWS = 2048;     // rows per partition workgroup
 constexpr int SW = OTTO_GBDT_SPLIT_WORDS;
 // error words of a call
 constexpr int ERR_QUERY = 0, ERR_LABEL = 1, ERR_ROW = 2, ERR_WALK = 3, ERR_WORDS = 4;
-
-// order-preserving image of a score: larger = better; every NaN -> 1, below -inf; -0.0 = +0.0 (as otto_forest.hip)
-__device__ __forceinline__ uint64_t score_key(double x) {
-    if (x != x) return 1ull;
-    const uint64_t b = x == 0.0 ? 0ull : (uint64_t)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // binning
@@ -212,7 +206,7 @@ __global__ __launch_bounds__(256) void k_lambdarank(LambdaArgs a) {
         a.hess[row] = h;
     }
     if (!a.norm) return;
-    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);   // S in any order: the spec does not pin it
+    part = wave_reduce<Sum>(part);                  // S in any order: the spec does not pin it
     if ((tid & 63) == 0) s.red[tid >> 6] = part;
     __syncthreads();
     if (tid == 0) {
@@ -267,11 +261,8 @@ __global__ __launch_bounds__(256) void k_absmax(const double* grad, const double
         mg = g > mg ? g : mg;                           // NaN never wins
         mh = h > mh ? h : mh;
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double og = __shfl_xor(mg, d, 64), oh = __shfl_xor(mh, d, 64);
-        mg = og > mg ? og : mg;
-        mh = oh > mh ? oh : mh;
-    }
+    mg = wave_reduce<Max>(mg);
+    mh = wave_reduce<Max>(mh);
     if (lane_id() == 0) {                               // the bits of non-negative doubles order like the values
         atomicMax(mx + 0, (unsigned long long)__double_as_longlong(mg));
         atomicMax(mx + 1, (unsigned long long)__double_as_longlong(mh));
@@ -426,11 +417,9 @@ __global__ __launch_bounds__(256) void k_best_split(SplitJobs jobs, int F, const
         hP += hist[plane + l * 4 + e];
         cP += hist[2 * plane + l * 4 + e];
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-        gP += (int64_t)__shfl_xor((long long)gP, d, 64);
-        hP += (int64_t)__shfl_xor((long long)hP, d, 64);
-        cP += (int64_t)__shfl_xor((long long)cP, d, 64);
-    }
+    gP = wave_reduce<Sum>(gP);
+    hP = wave_reduce<Sum>(hP);
+    cP = wave_reduce<Sum>(cP);
     Cand best;
     best.found = 0; best.gain = 0.0; best.f = best.b = best.dl = 0; best.cntL = best.gL = best.hL = 0;
     for (int f = w; f < F; f += 4) {
@@ -515,7 +504,7 @@ __global__ __launch_bounds__(256) void k_part_count(const uint8_t* col, int64_t 
             else mine += goes_left(col[rid], split_bin, default_left) ? 1u : 0u;
         }
     }
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
+    mine = wave_reduce<Sum>(mine);
     if (lane_id() == 0) atomicAdd(&s_n, mine);
     __syncthreads();
     if (threadIdx.x == 0) block_left[blockIdx.x] = s_n;
@@ -653,7 +642,6 @@ int check_query_args(const double* d_score, const int32_t* d_label, const int64_
     return 0;
 }
 
-int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 
 struct WorkLayout {
     int64_t rows_a, rows_b, block_left, n_left, split, hist, total;

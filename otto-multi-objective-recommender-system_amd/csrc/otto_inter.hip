@@ -3,6 +3,7 @@
 // owns up to two candidates and walks the events once; session aggregates are wave reductions, per-aid aggregates go
 // through global atomics into a [n_aids] accumulator array that a second kernel turns into the nine aid features.
 #include "common.h"
+#include "wave.h"
 #include "../../include/otto_inter.h"
 
 #include <math.h>
@@ -16,27 +17,6 @@ struct AidAcc {              // per candidate aid, over all sessions
     uint32_t score_max_bits;  // order-preserving image of the float
     uint32_t shift_bits;      // order-preserving image of the aid's shift K (0 = not chosen yet): score_sum / score_sq are over f - K
 };
-
-__device__ __forceinline__ uint32_t float_order(float f) {       // monotone float -> uint32
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float float_unorder(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)v, o, 64); v = t > v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_min_u(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = (uint32_t)__shfl_xor((int)v, o, 64); v = t < v ? t : v; }
-    return v;
-}
 
 // cand_off == nullptr: dense rows, session s owns cand[s * C, +C) (-1 padded); else the CSR rows of the ranker's candidate
 // table, session s owns cand[cand_off[s], cand_off[s + 1]) (any length: the session's own aids + up to 100 candidates)
@@ -99,7 +79,7 @@ __global__ __launch_bounds__(256) void k_inter_rows(const uint32_t* aid, const u
                 uint16_t* r = row + ((size_t)cb + c) * OTTO_INTER_ROW_FEATURES;
                 r[0] = (uint16_t)occ; r[1] = (uint16_t)last; r[2] = (uint16_t)cnt[0]; r[3] = (uint16_t)cnt[1]; r[4] = (uint16_t)cnt[2];
                 const float f = score[cb + c];
-                const uint32_t fo = float_order(f);
+                const uint32_t fo = ordered_key(f);
                 const double fk = (double)f - (double)K;
                 sc_sum += fk; sc_sq += fk * fk;
                 sc_max = fo > sc_max ? fo : sc_max; sc_min = fo < sc_min ? fo : sc_min;
@@ -110,7 +90,7 @@ __global__ __launch_bounds__(256) void k_inter_rows(const uint32_t* aid, const u
                     AidAcc* a = acc + y;
                     atomicAdd(&a->rows, 1u);
                     const uint32_t k0 = atomicCAS(&a->shift_bits, 0u, fo);       // the first row of the aid sets its shift
-                    const double fa = (double)f - (double)float_unorder(k0 ? k0 : fo);
+                    const double fa = (double)f - (double)ordered_key_inv(k0 ? k0 : fo);
                     atomicAdd(&a->score_sum, fa);
                     atomicAdd(&a->score_sq, fa * fa);
                     atomicMax(&a->score_max_bits, fo);
@@ -125,17 +105,17 @@ __global__ __launch_bounds__(256) void k_inter_rows(const uint32_t* aid, const u
             }
         }
         // session features over the candidate rows (:87-98)
-        const double t_sc = wave_sum(sc_sum), t_sq = wave_sum(sc_sq), t_occ = wave_sum(occ_sum), t_last = wave_sum(last_sum);
-        const double nr = wave_sum((double)rows), nl = wave_sum((double)last_rows);
-        const uint32_t m_sc = wave_max_u(sc_max), n_sc = wave_min_u(sc_min), m_occ = wave_max_u(occ_max), m_last = wave_max_u(last_max);
+        const double t_sc = wave_reduce<Sum>(sc_sum), t_sq = wave_reduce<Sum>(sc_sq), t_occ = wave_reduce<Sum>(occ_sum), t_last = wave_reduce<Sum>(last_sum);
+        const double nr = wave_reduce<Sum>((double)rows), nl = wave_reduce<Sum>((double)last_rows);
+        const uint32_t m_sc = wave_reduce<Max>(sc_max), n_sc = wave_reduce<Min>(sc_min), m_occ = wave_reduce<Max>(occ_max), m_last = wave_reduce<Max>(last_max);
         if (lane == 0) {
             float* o = sess_feat + (size_t)s * OTTO_INTER_SESSION_FEATURES;
             if (nr > 0) {
                 const double mean = t_sc / nr;                // of f - K
                 o[0] = (float)((double)K + mean);
                 o[1] = nr > 1 ? (float)sqrt(fmax((t_sq - nr * mean * mean) / (nr - 1), 0.0)) : nanf_;
-                o[2] = float_unorder(n_sc);
-                o[3] = float_unorder(m_sc);
+                o[2] = ordered_key_inv(n_sc);
+                o[3] = ordered_key_inv(m_sc);
                 o[4] = (float)(t_occ / nr);
                 o[5] = (float)t_occ;
                 o[6] = (float)m_occ;
@@ -161,9 +141,9 @@ __global__ void k_inter_aids(const AidAcc* acc, uint32_t n_aids, float* out) {
         return;
     }
     const double nr = (double)a.rows, mean = a.score_sum / nr;       // of f - K
-    o[0] = (float)((double)float_unorder(a.shift_bits) + mean);
+    o[0] = (float)((double)ordered_key_inv(a.shift_bits) + mean);
     o[1] = a.rows > 1 ? (float)sqrt(fmax((a.score_sq - nr * mean * mean) / (nr - 1), 0.0)) : nanf_;
-    o[2] = float_unorder(a.score_max_bits);
+    o[2] = ordered_key_inv(a.score_max_bits);
     o[3] = (float)((double)a.occ_sum / nr);
     o[4] = (float)a.occ_sum;
     o[5] = (float)a.occ_max;

@@ -16,6 +16,7 @@
 //                 (the row's aid sits in LDS), which costs no register in the tile loop.
 //   k_knn_merge   one wave per row: exact merge of the item-range splits (sclist.h), score -> dist, padding, n.
 #include "common.h"
+#include "wave.h"
 #include "sclist.h"
 #include "../../include/otto_covis.h"
 #include "../../include/otto_knn.h"
@@ -31,8 +32,6 @@ constexpr int KN_BM = 128;      // rows per workgroup (4 waves x 32)
 constexpr int KN_BN = 32;       // items per tile
 constexpr int64_t KN_HDR = 256; // workspace header: the error word
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
 struct KnnArgs {
     const float* E;
@@ -226,7 +225,6 @@ int knn_nsplit(int64_t R, int64_t N) {
 
 bool knn_d_ok(int d) { return d == 8 || d == 16 || d == 32 || d == 64 || d == 128; }
 
-int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 
 template <int D>
 int launch(const KnnArgs& a, const uint8_t* valid, float2* item, dim3 grid, size_t lds, hipStream_t s) {

@@ -1,13 +1,11 @@
 // Aid-pair dataset builders of the collaborative-filtering trainer on the device (include/otto_pairs.h, SURVEY.md section
 // 8 a6; reference: src/matrix_factorization/torch_trainer.py:190-255). Records (x1 << 32 | x2, label) are emitted per
-// session, sorted by pair with the LSD radix sort of otto_events.hip and aggregated per run of equal pairs.
+// session, sorted by pair with the shared LSD radix sort (sort.h) and aggregated per run of equal pairs.
 #include "common.h"
 #include "scan.h"
+#include "sort.h"
 #include "../../include/otto_pairs.h"
 #include "../../include/otto_events.h"
-
-int otto_sort_pairs_in_ws(uint64_t* d_keys, int64_t n, void* d_ws, uint64_t** d_keys_sorted, uint32_t** d_vals_sorted, hipStream_t s);
-void otto_sort_ws_buffers(int64_t n, void* d_ws, uint64_t** key0, uint32_t** val0, uint64_t** scan_out, uint64_t** scan_partial);
 
 namespace otto {
 

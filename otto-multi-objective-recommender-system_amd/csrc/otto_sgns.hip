@@ -16,6 +16,7 @@
 //   k_sgns_apply         BATCH: table += workspace, workspace = 0 (dense sweep).
 //   k_sgns_loss_final    sums the per-workgroup loss partials in a fixed order.
 #include "common.h"
+#include "wave.h"
 #include "scan.h"
 #include "../../include/otto_covis.h"
 #include "../../include/otto_sgns.h"
@@ -187,8 +188,6 @@ struct SgStepArgs {
     double* gout;
 };
 
-static __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-static __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 static __device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 static __device__ __forceinline__ float group_sum(float v, int G) {
     for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -299,7 +298,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgns_step(SgStepArgs a) {
         }
     }
     // per-workgroup loss partial, fixed order inside the workgroup
-    for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o, 64);
+    lsum = wave_reduce<Sum>(lsum);
     if (lane_id() == 0) s_red[threadIdx.x >> 6] = lsum;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -61,7 +61,9 @@ def join_cases():
     m = _models(6, 3, 500, 0.8, 40)
     m[0] = tuple(x[:0] for x in m[0])
     c['empty_base'] = (m, (0.5, 0.25, 0.25), (0, 1, 0))
-    for tot in (1, 63, 64, 65, 257):
+    # concatenated totals around the wave (64), the sort's tile (4096) and its workgroup span (16384); the keys of the two
+    # models overlap, so equal keys of different models meet across the edge
+    for tot in (1, 63, 64, 65, 257, 4095, 4096, 4097, 16383, 16384, 16385):
         m = _models(10 + tot, 2, tot, 1.0, 5)
         cut = tot // 3
         c[f'total_{tot}'] = ([tuple(x[:tot - cut] for x in m[0]), tuple(x[:cut] for x in m[1])], (0.6, 0.4), None)
@@ -69,7 +71,34 @@ def join_cases():
     c['one_session'] = (_models(8, 3, 2000, 0.7, 1), (0.2, 0.3, 0.5), None)
     c['single_row_sessions'] = (_models(9, 3, 2000, 0.7, 2000), (0.2, 0.3, 0.5), (0, 0, 1))
     c['ids_to_int32_max'] = (_models(10, 3, 1500, 0.7, 50, hi_ids=True), (0.2, 0.3, 0.5), None)
+    c['every_digit_varies'] = (_wide_models(11, 3, 500, 10), (0.2, 0.3, 0.5), (0, 0, 1))      # no pass of the sort is a copy
+    one = (np.array([12345], np.int32), np.array([678], np.int32))
+    c['single_key'] = ([one + (np.array([v], np.float32),) for v in (0.5, -1.25, 2.0)], (0.2, 0.3, 0.5), None)   # every pass is a copy
     return c
+
+
+def _wide_models(seed, M, n_sessions, per):
+    """M models over n_sessions * per keys whose sessions and aids spread over all of [0, 2^31): every byte of the
+    (session << 32 | aid) key varies. Each model holds about 0.7 of the keys."""
+    rng = np.random.default_rng(seed)
+    top = (1 << 31) - 1
+    ses = np.unique(np.concatenate([[0, top], rng.integers(0, 1 << 31, n_sessions - 2)]))
+    keys = []
+    for s in ses:
+        aids = np.unique(np.concatenate([[0, top], rng.integers(0, 1 << 31, per - 2)]))
+        keys += [(int(s), int(a)) for a in aids]
+    keys = np.array(keys, dtype=np.int64)
+    out = []
+    for m in range(M):
+        take = rng.permutation(len(keys))[:int(round(0.7 * len(keys)))]
+        out.append((keys[take, 0].astype(np.int32), keys[take, 1].astype(np.int32), rng.standard_normal(take.size).astype(np.float32)))
+    return out
+
+
+def key_bits(models):
+    """(OR, AND) of the (session << 32 | aid) keys of all models"""
+    k = np.concatenate([(m[0].astype(np.int64) << 32) | m[1].astype(np.int64) for m in models])
+    return int(np.bitwise_or.reduce(k)), int(np.bitwise_and.reduce(k))
 
 
 def duplicate_cases():

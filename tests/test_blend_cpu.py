@@ -126,6 +126,27 @@ def test_inputs_contain_what_they_claim():
     assert tied
 
 
+def test_join_sort_edge_cases_contain_what_they_claim():
+    cases = bi.join_cases()
+    for tot in (4095, 4096, 4097, 16383, 16384, 16385):
+        models, weights, left = cases[f'total_{tot}']
+        assert [m[0].size for m in models] == [tot - tot // 3, tot // 3]
+        keys = [set(zip(m[0].tolist(), m[1].tolist())) for m in models]
+        assert keys[0] & keys[1] and keys[1] - keys[0], tot          # keys in both models, and keys of model 1 alone
+        sid, off, aid, pred = br.blend(models, weights, left)        # valid for the restatement: no duplicate, no negative id
+        assert aid.size == len(keys[0] | keys[1])
+    models, weights, left = cases['every_digit_varies']
+    o, a = bi.key_bits(models)
+    assert all(((o ^ a) >> (8 * d)) & 255 for d in range(8)) and sum(m[0].size for m in models) > 5000
+    assert min(int(c.min()) for m in models for c in m[:2]) == 0 and max(int(c.max()) for m in models for c in m[:2]) == 2 ** 31 - 1
+    br.blend(models, weights, left)
+    models, weights, left = cases['single_key']
+    o, a = bi.key_bits(models)
+    assert o == a and len(models) == 3 and all(m[0].size == 1 for m in models)
+    sid, off, aid, pred = br.blend(models, weights, left)
+    assert aid.size == 1 and off.tolist() == [0, 1]
+
+
 def test_every_size_residue_and_parity_is_covered():
     nvs = {n for n in bi.SCALE_SIZES}
     assert {(n - 1) % 4 for n in nvs if n >= 1000} == {0, 1, 2, 3} and {n % 2 for n in nvs} == {0, 1}
