@@ -35,7 +35,8 @@ def matrix_to_dict(y, n):
     return {int(x): y[x, :n[x]].tolist() for x in np.flatnonzero(n > 0)}
 
 
-def session_candidates(session_aids, session_event_types, top, recipe, n_common=100):
+def session_concatenation(session_aids, session_event_types, top, recipe):
+    """The list the reference counts (:119-127) and the session's unique aids, most recent first (:112)."""
     session_aids = list(map(int, session_aids))
     aids = np.array(session_aids)
     types = np.array(session_event_types)
@@ -45,13 +46,30 @@ def session_candidates(session_aids, session_event_types, top, recipe, n_common=
         'CC': np.unique(aids[types <= 1]).tolist(),
         'CO': np.unique(aids[types >= 1]).tolist(),
         'LAST': session_aids[-1:],
+        'C': np.unique(aids[types == 0]).tolist(),              # OTTO_CAND_SRC_C (covisitation/inference.py:147)
     }
     covisited = []
     for kind, src in recipe:
         d = top[kind]
         covisited += list(itertools.chain(*[d[aid] for aid in sources[src] if aid in d]))
+    return covisited, session_unique_aids
+
+
+def session_candidates(session_aids, session_event_types, top, recipe, n_common=100):
+    covisited, session_unique_aids = session_concatenation(session_aids, session_event_types, top, recipe)
     out = [(aid, count) for aid, count in Counter(covisited).most_common(n_common) if aid not in session_unique_aids]
     return [a for a, _ in out], [c for _, c in out]
+
+
+def session_candidates_self(session_aids, session_event_types, top, recipe, n_common=100):
+    """``otto_cand_lookup_self`` (include/otto_cand.h): the Counter over the same concatenation; ``own[i]`` = its count of
+    event i's aid, and the session's aids leave BEFORE the cut at ``n_common``. Returns (candidates, counts, own)."""
+    covisited, session_unique_aids = session_concatenation(session_aids, session_event_types, top, recipe)
+    counter = Counter(covisited)
+    own = [counter[int(a)] for a in session_aids]
+    session = set(session_unique_aids)
+    out = [(a, c) for a, c in counter.most_common() if a not in session][:n_common]
+    return [a for a, _ in out], [c for _, c in out], own
 
 
 def all_candidates(aid, typ, sess_off, top, recipe, n_common=100):
