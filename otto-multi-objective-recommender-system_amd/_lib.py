@@ -233,6 +233,7 @@ _lib = None
 def register(signatures):
     """Let sibling modules (matrix_factorization) add their header's symbols."""
     SIGNATURES.update(signatures)
+    _POINTERS.clear()
     global _lib
     if _lib is not None:
         _bind(_lib, signatures)
@@ -269,3 +270,112 @@ def check(rc, what):
     if rc != 0:
         msg = lib().otto_last_error()
         raise OttoError(f'{what} failed (code {rc}): {msg.decode() if msg else "?"}')
+
+
+def ptr(t, dev=None, what='tensor'):
+    """The address of a tensor's first element as a ``c_void_p``, NULL for None. With ``dev`` the tensor must be
+    contiguous device memory on ``dev`` (``ValueError``): the rule of ``marshal``, for a pointer stored into a
+    ``Structure`` field. Without, nothing is checked: for a matrix that goes in as rows with a leading dimension."""
+    if t is None:
+        return C.c_void_p(0)
+    if dev is not None and (t.device != dev or not t.is_contiguous()):
+        raise ValueError(_not_on(dev, t, what))
+    return C.c_void_p(t.data_ptr())
+
+
+def _not_on(dev, t, what):
+    return f'{what}: expected a contiguous tensor on {dev}, got a{"" if t.is_contiguous() else " strided"} tensor on {t.device}'
+
+
+def stream(dev):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+_stream_of = stream             # ``call`` has a flag of that name
+
+
+_Tensor = _ndarray = None      # torch.Tensor and numpy.ndarray, imported at first use: marshal and need run once per launch
+
+
+_POINTERS = {}                 # name -> (number of parameters, positions of the void* ones): what marshal looks at
+
+
+def _load_types():
+    global _Tensor, _ndarray
+    from numpy import ndarray as _ndarray
+    from torch import Tensor as _Tensor
+
+
+def marshal(name, dev, args, stream=True):
+    """The ctypes values of ``args`` for entry point ``name`` (a list; the stream that ``call`` appends is not in it).
+
+    A torch tensor always means device memory on ``dev``: it must live there and be contiguous, and goes in as its
+    address. Anything else is host: ``None`` is NULL (ctypes' own rule for every pointer parameter), a NumPy array is a
+    C-contiguous host buffer passed as its address, ctypes values, ``byref(...)``, ctypes arrays, bytes, ints and floats
+    go to ctypes as they are. Raises ``ValueError`` before anything is launched, also when the number of arguments is
+    not the one ``SIGNATURES[name]`` declares -- ctypes takes surplus cdecl arguments silently."""
+    if _Tensor is None:
+        _load_types()
+    pointers = _POINTERS.get(name)
+    if pointers is None:
+        argtypes = SIGNATURES[name][1]
+        pointers = _POINTERS[name] = (len(argtypes), tuple(i for i, t in enumerate(argtypes) if t is C.c_void_p))
+    if len(args) + (1 if stream else 0) != pointers[0]:
+        raise ValueError(f'{name}: {len(args)} arguments{" + the stream" if stream else ""}, the header declares {pointers[0]}')
+    out = list(args)
+    for i in pointers[1][:-1] if stream else pointers[1]:
+        a = out[i]
+        if isinstance(a, _Tensor):
+            if a.device != dev or not a.is_contiguous():
+                raise ValueError(_not_on(dev, a, f'{name}: argument {i}'))
+            out[i] = C.c_void_p(a.data_ptr())
+        elif isinstance(a, _ndarray):
+            if not a.flags.c_contiguous:
+                raise ValueError(f'{name}: argument {i}: expected a C-contiguous host array')
+            out[i] = a.ctypes.data_as(C.c_void_p)
+    return out
+
+
+def call(name, dev, *args, stream=True):
+    """Run entry point ``name`` on ``dev``: ``marshal`` the arguments, enter the device, append its current stream
+    (``stream=False`` for the entry points that take none) and raise ``OttoError`` on a non-zero return code.
+    ``dev=None``: an entry point that works on host arrays alone; no device is entered."""
+    import torch
+    argv = marshal(name, dev, args, stream)
+    fn = getattr(lib(), name)
+    if dev is None:
+        return check(fn(*argv), name)
+    with torch.cuda.device(dev):
+        if stream:
+            argv.append(_stream_of(dev))
+        check(fn(*argv), name)
+
+
+def need(t, what, dtype, dim=None, device=None, numel=None, copy=False):
+    """The argument check of the wrappers; returns ``t``. ``ValueError`` unless ``t`` is a ``dtype`` tensor (of ``dim``
+    dimensions, of ``numel`` elements, where given) that is contiguous -- ``copy=True`` returns ``t.contiguous()``
+    instead of refusing a strided one. ``device``: where it must live (``ValueError``); None: on any ROCm device, and a
+    tensor elsewhere is an ``OttoError``, since there is no CPU fallback."""
+    if _Tensor is None:
+        _load_types()
+    if not isinstance(t, _Tensor) or t.dtype != dtype or (dim is not None and t.dim() != dim):
+        raise ValueError(f'{what}: expected a {"" if dim is None else f"{dim}-d "}{dtype} tensor')
+    if device is None:
+        if t.device.type != 'cuda':
+            raise OttoError(f'{what} needs a ROCm device (no CPU fallback)')
+    elif t.device != device:
+        raise ValueError(f'{what}: expected a tensor on {device}, got one on {t.device}')
+    if not t.is_contiguous():
+        if not copy:
+            raise ValueError(f'{what}: expected a contiguous tensor')
+        t = t.contiguous()
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f'{what}: expected {numel} elements, got {t.numel()}')
+    return t
+
+
+def workspace(n_bytes, dev):
+    """Scratch for one call: uint8, never below the 256 bytes ``device_scratch`` keeps on the C side."""
+    import torch
+    return torch.empty(max(int(n_bytes), 256), dtype=torch.uint8, device=dev)

@@ -17,15 +17,24 @@ INFERENCE_CART_RECIPE = CART_RECIPE + (('neighbours', 'LAST'),)
 INFERENCE_ORDER_RECIPE = INFERENCE_CART_RECIPE
 
 
+def _events(who, aid, typ, sess_off):
+    """The device of the event arrays ``aid`` int32 / ``typ`` uint8 / ``sess_off`` int64, checked."""
+    import torch
+    dev = aid.device
+    if dev.type != 'cuda':
+        raise _lib.OttoError(f'{who} needs a ROCm device (no CPU fallback)')
+    for name, x, dt in (('aid', aid, torch.int32), ('type', typ, torch.uint8), ('sess_off', sess_off, torch.int64)):
+        _lib.need(x, name, dt, device=dev)
+    return dev
+
+
 def candidate_lookup(aid, typ, sess_off, matrices, recipe, n_common=100, self_counts=False):
     """``matrices``: {kind: (aid_y int32 [n_aids,k], W, n int32 [n_aids])} as returned by ``CovisBuilder.finalize``.
     Returns (cand int32 [S, n_common] (-1 padded), count int32 [S, n_common], n int32 [S]) on the device.
     ``self_counts``: the session's own aids leave the selection BEFORE most_common and their Counter counts come back as a
     fourth tensor int32 [E] (one value per event; ``otto_cand_lookup_self``, used by :func:`recency_predictions`)."""
     import torch
-    dev = aid.device
-    if dev.type != 'cuda':
-        raise _lib.OttoError('candidate_lookup needs a ROCm device (no CPU fallback)')
+    dev = _events('candidate_lookup', aid, typ, sess_off)
     kinds = []
     for kind, _ in recipe:
         if kind not in kinds:
@@ -41,7 +50,7 @@ def candidate_lookup(aid, typ, sess_off, matrices, recipe, n_common=100, self_co
         if y.dtype != torch.int32 or n.dtype != torch.int32 or not y.is_contiguous() or not n.is_contiguous() or y.shape[0] != y0.shape[0]:
             raise ValueError(f'matrix {kind}: expected contiguous int32 [n_aids, k] / [n_aids]')
         keep.append((y, n))
-        p.d_mat_y[i], p.d_mat_n[i] = y.data_ptr(), n.data_ptr()
+        p.d_mat_y[i], p.d_mat_n[i] = _lib.ptr(y, dev, f'matrix {kind}'), _lib.ptr(n, dev, f'matrix {kind}')
         p.mat_k[i] = 0 if widths[i] == p.k else widths[i]
     p.n_terms = len(recipe)
     for t, (kind, src) in enumerate(recipe):
@@ -51,21 +60,11 @@ def candidate_lookup(aid, typ, sess_off, matrices, recipe, n_common=100, self_co
     cand = torch.empty((S, n_common), dtype=torch.int32, device=dev)
     count = torch.empty((S, n_common), dtype=torch.int32, device=dev)
     n_out = torch.empty(S, dtype=torch.int32, device=dev)
-    for name, x, dt in (('aid', aid, torch.int32), ('type', typ, torch.uint8), ('sess_off', sess_off, torch.int64)):
-        if x.dtype != dt or not x.is_contiguous():
-            raise ValueError(f'{name}: expected contiguous {dt}')
-    with torch.cuda.device(dev):
-        if self_counts:
-            own = torch.zeros(max(aid.numel(), 1), dtype=torch.int32, device=dev)
-            _lib.check(_lib.lib().otto_cand_lookup_self(C.byref(p), C.c_void_p(aid.data_ptr()), C.c_void_p(typ.data_ptr()),
-                                                        C.c_void_p(sess_off.data_ptr()), S, C.c_void_p(cand.data_ptr()),
-                                                        C.c_void_p(count.data_ptr()), C.c_void_p(n_out.data_ptr()), C.c_void_p(own.data_ptr()),
-                                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'otto_cand_lookup_self')
-            return cand, count, n_out, own[:aid.numel()]
-        _lib.check(_lib.lib().otto_cand_lookup(C.byref(p), C.c_void_p(aid.data_ptr()), C.c_void_p(typ.data_ptr()),
-                                               C.c_void_p(sess_off.data_ptr()), S, C.c_void_p(cand.data_ptr()),
-                                               C.c_void_p(count.data_ptr()), C.c_void_p(n_out.data_ptr()),
-                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'otto_cand_lookup')
+    if self_counts:
+        own = torch.zeros(max(aid.numel(), 1), dtype=torch.int32, device=dev)
+        _lib.call('otto_cand_lookup_self', dev, C.byref(p), aid, typ, sess_off, S, cand, count, n_out, own)
+        return cand, count, n_out, own[:aid.numel()]
+    _lib.call('otto_cand_lookup', dev, C.byref(p), aid, typ, sess_off, S, cand, count, n_out)
     return cand, count, n_out
 
 
@@ -82,12 +81,8 @@ def predictions(aid, sess_off, cand, n_cand, most_frequent, n_pred=20):
     freq = torch.as_tensor(list(most_frequent), dtype=torch.int32, device=dev).contiguous()
     pred = torch.empty((S, n_pred), dtype=torch.int32, device=dev)
     n_out = torch.empty(S, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().otto_cand_predictions(C.c_void_p(aid.data_ptr()), C.c_void_p(sess_off.data_ptr()), S,
-                                                    C.c_void_p(cand.data_ptr()), C.c_void_p(n_cand.data_ptr()), int(cand.shape[1]),
-                                                    C.c_void_p(freq.data_ptr() if freq.numel() else 0), int(freq.numel()), int(n_pred),
-                                                    C.c_void_p(pred.data_ptr()), C.c_void_p(n_out.data_ptr()),
-                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'otto_cand_predictions')
+    _lib.call('otto_cand_predictions', dev, aid, sess_off, S, cand, n_cand, int(cand.shape[1]), freq if freq.numel() else None,
+              int(freq.numel()), int(n_pred), pred, n_out)
     return pred, n_out
 
 
@@ -106,33 +101,28 @@ def ranker_table(aid, sess_off, cand, count, n_cand, labels=None, session_ids=No
         raise _lib.OttoError('ranker_table needs a ROCm device (no CPU fallback)')
     for name, x, dt in (('aid', aid, torch.int32), ('sess_off', sess_off, torch.int64), ('cand', cand, torch.int32),
                         ('count', count, torch.int32), ('n_cand', n_cand, torch.int32)):
-        if x.dtype != dt or not x.is_contiguous():
-            raise ValueError(f'{name}: expected contiguous {dt}')
+        _lib.need(x, name, dt, device=dev)
     S, n_common = sess_off.numel() - 1, int(cand.shape[1])
     if cand.shape != count.shape or cand.shape[0] != S or n_cand.numel() != S:
         raise ValueError('cand / count / n_cand shapes disagree with sess_off')
-    lib = _lib.lib()
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-    stream = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    with torch.cuda.device(dev):
-        ws_b = int(lib.otto_cand_ranker_workspace(S))
-        ws = torch.empty(max(ws_b, 8), dtype=torch.uint8, device=dev)
-        row_off = torch.empty(S + 1, dtype=torch.int64, device=dev)
-        n_rows = C.c_int64()
-        _lib.check(lib.otto_cand_ranker_rows(p(aid), p(sess_off), S, p(n_cand), n_common, p(row_off), C.byref(n_rows), p(ws), ws_b, stream()),
-                   'otto_cand_ranker_rows')
-        R = int(n_rows.value)
-        out = {'session': torch.empty(R, dtype=torch.int64, device=dev), 'candidates': torch.empty(R, dtype=torch.int32, device=dev),
-               'candidate_scores': torch.empty(R, dtype=torch.float32, device=dev),
-               'candidate_labels': torch.empty(R, dtype=torch.uint8, device=dev) if labels is not None else None, 'row_off': row_off}
-        l_off, l_aid = (None, None) if labels is None else labels
-        if labels is not None and (l_off.dtype != torch.int64 or l_aid.dtype != torch.int32 or l_off.numel() != S + 1):
-            raise ValueError('labels: expected (int64 [S+1], int32) CSR lists')
-        if session_ids is not None and (session_ids.dtype != torch.int64 or session_ids.numel() != S):
-            raise ValueError('session_ids: expected int64 [S]')
-        _lib.check(lib.otto_cand_ranker_table(p(aid), p(sess_off), S, p(cand), p(count), p(n_cand), n_common, p(row_off), p(l_off), p(l_aid),
-                                              p(session_ids), p(out['session']), p(out['candidates']), p(out['candidate_scores']),
-                                              p(out['candidate_labels']), stream()), 'otto_cand_ranker_table')
+    l_off, l_aid = (None, None) if labels is None else labels
+    if labels is not None:
+        _lib.need(l_off, 'labels: the offsets of the (int64 [S+1], int32) CSR lists', torch.int64, device=dev, numel=S + 1)
+        _lib.need(l_aid, 'labels: the aids of the (int64 [S+1], int32) CSR lists', torch.int32, device=dev)
+    if session_ids is not None:
+        _lib.need(session_ids, 'session_ids', torch.int64, device=dev, numel=S)
+    p = lambda t: t if t is not None and t.numel() else None        # an empty array goes in as NULL
+    ws_b = int(_lib.lib().otto_cand_ranker_workspace(S))
+    ws = _lib.workspace(ws_b, dev)
+    row_off = torch.empty(S + 1, dtype=torch.int64, device=dev)
+    n_rows = C.c_int64()
+    _lib.call('otto_cand_ranker_rows', dev, p(aid), p(sess_off), S, p(n_cand), n_common, row_off, C.byref(n_rows), ws, ws_b)
+    R = int(n_rows.value)
+    out = {'session': torch.empty(R, dtype=torch.int64, device=dev), 'candidates': torch.empty(R, dtype=torch.int32, device=dev),
+           'candidate_scores': torch.empty(R, dtype=torch.float32, device=dev),
+           'candidate_labels': torch.empty(R, dtype=torch.uint8, device=dev) if labels is not None else None, 'row_off': row_off}
+    _lib.call('otto_cand_ranker_table', dev, p(aid), p(sess_off), S, p(cand), p(count), p(n_cand), n_common, row_off, p(l_off), p(l_aid),
+              p(session_ids), p(out['session']), p(out['candidates']), p(out['candidate_scores']), p(out['candidate_labels']))
     return out
 
 
@@ -147,12 +137,7 @@ def recency_candidates(aid, typ, sess_off, curves=RECENCY_CURVES, type_coef=RECE
     [n_curves, E], n int32 [S]): session s owns ``[sess_off[s], sess_off[s] + n[s])`` of every curve's row, in
     ``Counter.most_common`` order."""
     import torch
-    dev = aid.device
-    if dev.type != 'cuda':
-        raise _lib.OttoError('recency_candidates needs a ROCm device (no CPU fallback)')
-    for name, x, dt in (('aid', aid, torch.int32), ('type', typ, torch.uint8), ('sess_off', sess_off, torch.int64)):
-        if x.dtype != dt or not x.is_contiguous():
-            raise ValueError(f'{name}: expected contiguous {dt}')
+    dev = _events('recency_candidates', aid, typ, sess_off)
     p = _lib.RecencyParams()
     p.n_curves = len(curves)
     for c, (a0, a1) in enumerate(curves):
@@ -163,12 +148,7 @@ def recency_candidates(aid, typ, sess_off, curves=RECENCY_CURVES, type_coef=RECE
     cand = torch.full((len(curves), E), -1, dtype=torch.int32, device=dev)
     w = torch.zeros((len(curves), E), dtype=torch.float64, device=dev)
     n_out = torch.zeros(S, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().otto_recency_candidates(C.byref(p), C.c_void_p(aid.data_ptr()), C.c_void_p(typ.data_ptr()),
-                                                      C.c_void_p(sess_off.data_ptr()), S, E, C.c_void_p(cand.data_ptr()),
-                                                      C.c_void_p(w.data_ptr()), C.c_void_p(n_out.data_ptr()),
-                                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                   'otto_recency_candidates')
+    _lib.call('otto_recency_candidates', dev, C.byref(p), aid, typ, sess_off, S, E, cand, w, n_out)
     return cand, w, n_out
 
 
@@ -208,14 +188,10 @@ def recency_predictions(aid, typ, sess_off, matrices, targets=INFERENCE_RECENCY_
         cand, count, n_c, own = candidate_lookup(aid, typ, sess_off, matrices, recipe, n_common=n_common, self_counts=True)
         keep.append((cand, count, n_c, own))
         p.start[t], p.stop[t], p.bump[t] = float(tg['curve'][0]), float(tg['curve'][1]), float(tg['bump'])
-        p.d_cand[t], p.d_count[t], p.d_n_cand[t], p.d_self_count[t] = cand.data_ptr(), count.data_ptr(), n_c.data_ptr(), own.data_ptr()
+        p.d_cand[t], p.d_count[t], p.d_n_cand[t], p.d_self_count[t] = (_lib.ptr(x, dev, f'target {t}') for x in (cand, count, n_c, own))
     T = len(targets)
     pred = torch.empty((T, S, n_pred), dtype=torch.int32, device=dev)
     weight = torch.empty((T, S, n_pred), dtype=torch.float64, device=dev)
     n_out = torch.empty((T, S), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().otto_recency_predictions(C.byref(p), C.c_void_p(aid.data_ptr()), C.c_void_p(typ.data_ptr()),
-                                                       C.c_void_p(sess_off.data_ptr()), S, C.c_void_p(pred.data_ptr()),
-                                                       C.c_void_p(weight.data_ptr()), C.c_void_p(n_out.data_ptr()),
-                                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'otto_recency_predictions')
+    _lib.call('otto_recency_predictions', dev, C.byref(p), aid, typ, sess_off, S, pred, weight, n_out)
     return pred, weight, n_out

@@ -10,10 +10,6 @@ from .. import _lib
 from .spec import TYPE_WEIGHTS, FILTER_MASKS, TIME_KIND, ALL_KINDS, mask_bits
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
 class CovisBuilder:
     """One context per device. ``feed`` session chunks, then ``finalize``.
 
@@ -46,10 +42,9 @@ class CovisBuilder:
         for i, k in enumerate(self.type_kinds):
             for t in range(3):
                 p.type_weight[i][t] = TYPE_WEIGHTS[k][t]
-        self._lib = _lib.lib()
+        self._lib = _lib.lib()                    # close() may run while the interpreter shuts down
         self._ctx = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.otto_covis_create(C.byref(self._ctx), C.byref(p)), 'otto_covis_create')
+        _lib.call('otto_covis_create', self.device, C.byref(self._ctx), C.byref(p), stream=False)
 
     def close(self):
         if getattr(self, '_ctx', None) is not None and self._ctx:
@@ -58,25 +53,21 @@ class CovisBuilder:
 
     __del__ = close
 
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+    def _call(self, name, *args, **kw):
+        _lib.call(name, self.device, self._ctx, *args, **kw)
 
     def reset(self):
-        _lib.check(self._lib.otto_covis_reset(self._ctx), 'otto_covis_reset')
+        self._call('otto_covis_reset', stream=False)
 
     def feed(self, aid, ts, typ, sess_off):
         """K1 pair-expand over one session chunk (device tensors: aid int32, ts int32,
         type uint8, sess_off int64 CSR with n_sess+1 entries)."""
         t = self.torch
         for name, x, dt in (('aid', aid, t.int32), ('ts', ts, t.int32), ('type', typ, t.uint8), ('sess_off', sess_off, t.int64)):
-            if x.dtype != dt or x.device != self.device or not x.is_contiguous():
-                raise ValueError(f'{name}: expected contiguous {dt} on {self.device}, got {x.dtype} on {x.device}')
-        n_sess = sess_off.numel() - 1
+            _lib.need(x, name, dt, device=self.device)
         if aid.numel() != ts.numel() or aid.numel() != typ.numel():
             raise ValueError('aid/ts/type length mismatch')
-        with t.cuda.device(self.device):
-            _lib.check(self._lib.otto_covis_feed(self._ctx, _ptr(aid), _ptr(ts), _ptr(typ), _ptr(sess_off),
-                                                 C.c_int64(n_sess), self._stream()), 'otto_covis_feed')
+        self._call('otto_covis_feed', aid, ts, typ, sess_off, sess_off.numel() - 1)
 
     def _finalize_group(self, group, n_kinds, k, out=None):
         t = self.torch
@@ -85,9 +76,7 @@ class CovisBuilder:
                    t.empty((n_kinds, self.n_aids, k), dtype=t.int64, device=self.device),
                    t.empty((n_kinds, self.n_aids), dtype=t.int32, device=self.device))
         y, w, n = out
-        with t.cuda.device(self.device):
-            _lib.check(self._lib.otto_covis_finalize(self._ctx, group, int(k), _ptr(y), _ptr(w), _ptr(n), self._stream()),
-                       'otto_covis_finalize')
+        self._call('otto_covis_finalize', group, int(k), y, w, n)
         return y, w, n
 
     def finalize(self, k=20, out=None):
@@ -107,17 +96,17 @@ class CovisBuilder:
         return res
 
     def set_option(self, name, value):
-        _lib.check(self._lib.otto_covis_set_option(self._ctx, name.encode(), C.c_int64(int(value))), 'otto_covis_set_option')
+        self._call('otto_covis_set_option', name.encode(), int(value), stream=False)
 
     def stats(self):
         buf = (C.c_int64 * len(_lib.STAT_NAMES))()
-        _lib.check(self._lib.otto_covis_stats(self._ctx, buf), 'otto_covis_stats')
+        self._call('otto_covis_stats', buf, stream=False)
         return dict(zip(_lib.STAT_NAMES, [int(v) for v in buf]))
 
     def timings(self):
         """Per-kernel device milliseconds (hipEvents on the stream) of the last feed/finalize."""
         buf = (C.c_float * len(_lib.TIMING_NAMES))()
-        self._lib.otto_covis_timings(self._ctx, buf)
+        self._lib.otto_covis_timings(self._ctx, buf)            # returns the slot count, not an error code
         return dict(zip(_lib.TIMING_NAMES, [float(v) for v in buf]))
 
     def kernel_names(self):
@@ -125,7 +114,7 @@ class CovisBuilder:
         out = {}
         for i, name in enumerate(_lib.TIMING_NAMES):
             buf = C.create_string_buffer(1024)
-            _lib.check(self._lib.otto_covis_kernel_names(self._ctx, i, buf, 1024), 'otto_covis_kernel_names')
+            self._call('otto_covis_kernel_names', i, buf, 1024, stream=False)
             out[name] = buf.value.decode()
         return out
 
@@ -136,10 +125,7 @@ class CovisBuilder:
         tw = np.empty(st['pair_slots'], dtype=np.uint32) if self.want_time else None
         run_x = np.empty(st['tail_events'], dtype=np.uint32)
         run_desc = np.empty(st['tail_events'], dtype=np.uint64)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else C.c_void_p(0)
-        with self.torch.cuda.device(self.device):
-            _lib.check(self._lib.otto_covis_copy_records(self._ctx, vp(rec), vp(tw), vp(run_x), vp(run_desc)),
-                       'otto_covis_copy_records')
+        self._call('otto_covis_copy_records', rec, tw, run_x, run_desc, stream=False)
         return rec, tw, run_x, run_desc
 
     # ---- multi-GPU exchange (SURVEY.md section 8 e) ------------------------------------------------
@@ -147,14 +133,11 @@ class CovisBuilder:
         """Runs with aid_x in [x_lo, x_hi) as device tensors (hdr int32 [n_runs,2], rec int32, tw int32|None)."""
         t = self.torch
         nr, nc = C.c_int64(), C.c_int64()
-        with t.cuda.device(self.device):
-            _lib.check(self._lib.otto_covis_export_count(self._ctx, int(x_lo), int(x_hi), C.byref(nr), C.byref(nc),
-                                                         self._stream()), 'otto_covis_export_count')
-            hdr = t.empty((nr.value, 2), dtype=t.int32, device=self.device)
-            rec = t.empty(nc.value, dtype=t.int32, device=self.device)
-            tw = t.empty(nc.value, dtype=t.int32, device=self.device) if self.want_time else None
-            _lib.check(self._lib.otto_covis_export_runs(self._ctx, int(x_lo), int(x_hi), _ptr(hdr), _ptr(rec), _ptr(tw),
-                                                        self._stream()), 'otto_covis_export_runs')
+        self._call('otto_covis_export_count', int(x_lo), int(x_hi), C.byref(nr), C.byref(nc))
+        hdr = t.empty((nr.value, 2), dtype=t.int32, device=self.device)
+        rec = t.empty(nc.value, dtype=t.int32, device=self.device)
+        tw = t.empty(nc.value, dtype=t.int32, device=self.device) if self.want_time else None
+        self._call('otto_covis_export_runs', int(x_lo), int(x_hi), hdr, rec, tw)
         return hdr, rec, tw
 
     def export_all(self, bounds):
@@ -165,14 +148,12 @@ class CovisBuilder:
         W = len(bounds) - 1
         hb = (C.c_uint32 * (W + 1))(*[int(b) for b in bounds])
         nr, nc = (C.c_int64 * W)(), (C.c_int64 * W)()
-        with t.cuda.device(self.device):
-            _lib.check(self._lib.otto_covis_export_plan(self._ctx, W, hb, nr, nc, self._stream()), 'otto_covis_export_plan')
-            runs, recs = [int(v) for v in nr], [int(v) for v in nc]
-            hdr = t.empty((sum(runs), 2), dtype=t.int32, device=self.device)
-            rec = t.empty(sum(recs), dtype=t.int32, device=self.device)
-            tw = t.empty(sum(recs), dtype=t.int32, device=self.device) if self.want_time else None
-            _lib.check(self._lib.otto_covis_export_fill(self._ctx, W, hb, _ptr(hdr), _ptr(rec), _ptr(tw), self._stream()),
-                       'otto_covis_export_fill')
+        self._call('otto_covis_export_plan', W, hb, nr, nc)
+        runs, recs = [int(v) for v in nr], [int(v) for v in nc]
+        hdr = t.empty((sum(runs), 2), dtype=t.int32, device=self.device)
+        rec = t.empty(sum(recs), dtype=t.int32, device=self.device)
+        tw = t.empty(sum(recs), dtype=t.int32, device=self.device) if self.want_time else None
+        self._call('otto_covis_export_fill', W, hb, hdr, rec, tw)
         return hdr, rec, tw, runs, recs
 
     def export_plan_range(self, bounds, slot_lo, slot_hi):
@@ -180,9 +161,7 @@ class CovisBuilder:
         W = len(bounds) - 1
         hb = (C.c_uint32 * (W + 1))(*[int(b) for b in bounds])
         nr, nc = (C.c_int64 * W)(), (C.c_int64 * W)()
-        with self.torch.cuda.device(self.device):
-            _lib.check(self._lib.otto_covis_export_plan_range(self._ctx, W, hb, C.c_int64(int(slot_lo)), C.c_int64(int(slot_hi)), nr, nc,
-                                                              self._stream()), 'otto_covis_export_plan_range')
+        self._call('otto_covis_export_plan_range', W, hb, int(slot_lo), int(slot_hi), nr, nc)
         return [int(v) for v in nr], [int(v) for v in nc]
 
     def export_fill_range(self, bounds, slot_lo, slot_hi, runs, recs, hdr, rec, tw=None):
@@ -191,9 +170,7 @@ class CovisBuilder:
         W = len(bounds) - 1
         hb = (C.c_uint32 * (W + 1))(*[int(b) for b in bounds])
         nr, nc = (C.c_int64 * W)(*runs), (C.c_int64 * W)(*recs)
-        with self.torch.cuda.device(self.device):
-            _lib.check(self._lib.otto_covis_export_fill_range(self._ctx, W, hb, C.c_int64(int(slot_lo)), C.c_int64(int(slot_hi)), nr, nc,
-                                                              _ptr(hdr), _ptr(rec), _ptr(tw), self._stream()), 'otto_covis_export_fill_range')
+        self._call('otto_covis_export_fill_range', W, hb, int(slot_lo), int(slot_hi), nr, nc, hdr, rec, tw)
 
     def run_slots(self):
         return self.stats()['tail_events']
@@ -203,9 +180,7 @@ class CovisBuilder:
         Fill them (e.g. as the output of the all-to-all-v) and hand them to ``import_runs``: no device copy is made."""
         t = self.torch
         pr, pt = C.c_void_p(), C.c_void_p()
-        with t.cuda.device(self.device):
-            _lib.check(self._lib.otto_covis_import_reserve(self._ctx, C.c_int64(int(n_recs)), C.byref(pr), C.byref(pt),
-                                                           self._stream()), 'otto_covis_import_reserve')
+        self._call('otto_covis_import_reserve', int(n_recs), C.byref(pr), C.byref(pt))
 
         def wrap(ptr):
             if not ptr or n_recs == 0:
@@ -216,10 +191,7 @@ class CovisBuilder:
         return wrap(pr.value), wrap(pt.value)
 
     def import_runs(self, hdr, rec, tw=None):
-        t = self.torch
-        with t.cuda.device(self.device):
-            _lib.check(self._lib.otto_covis_import_runs(self._ctx, _ptr(hdr), C.c_int64(hdr.shape[0]), _ptr(rec), _ptr(tw),
-                                                        C.c_int64(rec.numel()), self._stream()), 'otto_covis_import_runs')
+        self._call('otto_covis_import_runs', hdr, hdr.shape[0], rec, tw, rec.numel())
 
 
 def topk_to_rows(y, w, n):

@@ -108,6 +108,8 @@ def frame_to_events_device(frame, device='cuda:0', n_aids=None, ts_unit='auto'):
     dev = torch.device(device)
     if dev.type != 'cuda':
         raise _lib.OttoError('frame_to_events_device needs a ROCm device (the NumPy path is events.frame_to_events)')
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())     # the tensors' device carries its index
     lib = _lib.lib()
     frames = list(frame) if isinstance(frame, (list, tuple)) else [frame]
 
@@ -115,8 +117,6 @@ def frame_to_events_device(frame, device='cuda:0', n_aids=None, ts_unit='auto'):
         if hasattr(c, 'to_numpy') and not hasattr(c, 'iloc') and hasattr(c, 'type'):
             return c.to_numpy(zero_copy_only=False)
         return c.to_numpy() if hasattr(c, 'to_numpy') else np.asarray(c)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-    stream = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
         ts_parts = []
         for c in _column_chunks(frames, 'ts'):
@@ -156,13 +156,12 @@ def frame_to_events_device(frame, device='cuda:0', n_aids=None, ts_unit='auto'):
                 data = np.frombuffer(bufs[2], dtype=np.uint8)
                 d_off = _to_device(off, off.dtype, dev)
                 d_bytes = _to_device(data, np.uint8, dev)
-                _lib.check(lib.otto_events_type_from_strings(ptr(d_off), int(big), ptr(d_bytes), m, ptr(d_type[o:o + m]), stream()),
-                           'otto_events_type_from_strings')
+                _lib.call('otto_events_type_from_strings', dev, d_off, int(big), d_bytes, m, d_type[o:o + m])
             elif m:
                 d_type[o:o + m].copy_(_to_device(host(c), np.uint8, dev))
             o += m
-        ws_bytes = lib.otto_events_sort_workspace(n)
-        ws = torch.empty(max(int(ws_bytes), 8), dtype=torch.uint8, device=dev)
+        ws_bytes = int(lib.otto_events_sort_workspace(n))
+        ws = _lib.workspace(ws_bytes, dev)
         o_aid = torch.empty(n, dtype=torch.int32, device=dev)
         o_ts = torch.empty(n, dtype=torch.int32, device=dev)
         o_type = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -170,8 +169,7 @@ def frame_to_events_device(frame, device='cuda:0', n_aids=None, ts_unit='auto'):
         sess_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
         sess_id = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         ns = C.c_int64()
-        _lib.check(lib.otto_events_sort(ptr(d_sess), ptr(d_ts), ptr(d_aid), ptr(d_type), n, div, ptr(o_aid), ptr(o_ts), ptr(o_type),
-                                        ptr(o_order), C.c_void_p(sess_off.data_ptr()), ptr(sess_id), C.byref(ns), C.c_void_p(ws.data_ptr()),
-                                        int(ws_bytes), stream()), 'otto_events_sort')
+        _lib.call('otto_events_sort', dev, d_sess, d_ts, d_aid, d_type, n, div, o_aid, o_ts, o_type, o_order, sess_off, sess_id,
+                  C.byref(ns), ws, ws_bytes)
         S = int(ns.value)
         return DeviceEvents(o_aid, o_ts, o_type, sess_off[:S + 1].clone(), sess_id[:S].to(torch.int64) & 0xFFFFFFFF, o_order, int(n_aids))

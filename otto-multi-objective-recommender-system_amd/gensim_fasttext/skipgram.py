@@ -19,15 +19,6 @@ _U32_MAX = (1 << 32) - 1
 _MAX_BUCKETS = 1 << 21
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream(dev):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _host_counts(aid, n_aids):
     if hasattr(aid, 'device') and hasattr(aid, 'cpu'):            # a torch tensor: count where it lives
         import torch
@@ -112,6 +103,8 @@ class SkipGramEngine:
         self.dev = torch.device(device)
         if self.dev.type != 'cuda':
             raise _lib.OttoError('SkipGramEngine needs a ROCm device (no CPU fallback)')
+        if self.dev.index is None:
+            self.dev = torch.device('cuda', torch.cuda.current_device())     # the tensors' device carries its index
         self.n_aids, self.d, self.ws, self.neg, self.seed = int(n_aids), int(d), int(ws), int(neg), int(seed)
         if self.d % 4 or not 4 <= self.d <= MAX_DIM or (self.d // 4) & (self.d // 4 - 1):
             raise ValueError(f'd must be a multiple of 4 in [4, {MAX_DIM}] with d/4 a power of two (got {d})')
@@ -138,14 +131,16 @@ class SkipGramEngine:
             nb = self.lib.otto_sgns_neg_table_workspace(self.n_aids)
             if nb <= 0:
                 raise _lib.OttoError('otto_sgns_neg_table_workspace refused its arguments')
-            work = torch.empty(int(nb), dtype=torch.uint8, device=self.dev)
-            _lib.check(self.lib.otto_sgns_neg_table(_ptr(self.weight), self.n_aids, self.n_buckets, _ptr(self.cum),
-                                                    _ptr(self.bucket), C.byref(self.table), _ptr(work), work.numel(),
-                                                    _stream(self.dev)), 'otto_sgns_neg_table')
+            work = _lib.workspace(nb, self.dev)
+            self._call('otto_sgns_neg_table', self.weight, self.n_aids, self.n_buckets, self.cum, self.bucket, C.byref(self.table),
+                       work, work.numel())
         self._work = None
         self._bufs = None
         self._grads = None
         self._loss = torch.zeros(1, dtype=torch.float64, device=self.dev)
+
+    def _call(self, name, *args):
+        _lib.call(name, self.dev, *args)
 
     @property
     def total(self):
@@ -155,9 +150,7 @@ class SkipGramEngine:
         """``upper_bound(cum, mulhi64(key, total))`` for every key: int64-viewed uint64 tensor [m] -> int32 [m]."""
         import torch
         out = torch.empty(keys.numel(), dtype=torch.int32, device=self.dev)
-        with torch.cuda.device(self.dev):
-            _lib.check(self.lib.otto_sgns_draw(C.byref(self.table), _ptr(keys), keys.numel(), _ptr(out), _stream(self.dev)),
-                       'otto_sgns_draw')
+        self._call('otto_sgns_draw', C.byref(self.table), keys, keys.numel(), out)
         return out
 
     def plan(self, aid, sess_off, epoch, event0=0, out=None):
@@ -165,10 +158,8 @@ class SkipGramEngine:
         dict of pre-allocated output tensors (tests); by default the engine's persistent buffers are reused, so a plan is
         valid until the next call. Raises ``OttoError`` for an aid outside ``[0, n_aids)`` or bad offsets."""
         import torch
-        if aid.dtype != torch.int32 or sess_off.dtype != torch.int64 or not aid.is_contiguous() or not sess_off.is_contiguous():
-            raise ValueError('aid: contiguous int32 [E]; sess_off: contiguous int64 [S+1]')
-        if aid.device != self.dev or sess_off.device != self.dev:
-            raise ValueError(f'aid and sess_off must be on {self.dev}')
+        _lib.need(aid, 'aid', torch.int32, device=self.dev)
+        _lib.need(sess_off, 'sess_off', torch.int64, device=self.dev)
         E, S = int(aid.numel()), int(sess_off.numel()) - 1
         if S < 0:
             raise ValueError('sess_off: expected int64 [S+1]')
@@ -177,7 +168,7 @@ class SkipGramEngine:
             if nb <= 0:
                 raise _lib.OttoError('otto_sgns_plan_workspace refused its arguments')
             if self._work is None or self._work.numel() < nb:
-                self._work = torch.empty(int(nb), dtype=torch.uint8, device=self.dev)
+                self._work = _lib.workspace(nb, self.dev)
             if out is None:
                 if self._bufs is None or self._bufs['tok_aid'].numel() < E or self._bufs['tok_off'].numel() < S + 1:
                     self._bufs = dict(tok_aid=torch.empty(E, dtype=torch.int32, device=self.dev),
@@ -192,11 +183,9 @@ class SkipGramEngine:
             if out['tok_off'].numel() < S + 1:
                 raise ValueError('tok_off: room for S + 1 entries needed')
             counts = (C.c_int64 * 2)()
-            _lib.check(self.lib.otto_sgns_plan(_ptr(aid), E, _ptr(sess_off), S, _ptr(self.keep_q), self.n_aids, self.seed,
-                                               int(epoch), int(event0), self.ws, cap, _ptr(out['tok_aid']), _ptr(out['tok_src']),
-                                               _ptr(out['tok_off']), _ptr(out['radius']), _ptr(out['tok_left']),
-                                               _ptr(out['pair_off']), counts, _ptr(self._work), self._work.numel(),
-                                               _stream(self.dev)), 'otto_sgns_plan')
+            self._call('otto_sgns_plan', aid, E, sess_off, S, self.keep_q, self.n_aids, self.seed, int(epoch), int(event0), self.ws,
+                       cap, out['tok_aid'], out['tok_src'], out['tok_off'], out['radius'], out['tok_left'], out['pair_off'], counts,
+                       self._work, self._work.numel())
         T, P = int(counts[0]), int(counts[1])
         return Plan(tok_aid=out['tok_aid'][:T], tok_src=out['tok_src'][:T], tok_off=out['tok_off'][:S + 1],
                     radius=out['radius'][:T], tok_left=out['tok_left'][:T], pair_off=out['pair_off'][:T + 1], T=T, P=P,
@@ -225,11 +214,9 @@ class SkipGramEngine:
                     self._grads = (torch.zeros(self.n_aids, self.d, dtype=torch.float64, device=self.dev),
                                    torch.zeros(self.n_aids, self.d, dtype=torch.float64, device=self.dev))
                 gin, gout = self._grads
-            _lib.check(self.lib.otto_sgns_step(_ptr(plan.tok_aid), _ptr(plan.tok_src), _ptr(plan.tok_left), _ptr(plan.pair_off),
-                                               plan.T, int(t0), int(t1), _ptr(In), _ptr(Out), self.d, self.neg, float(lr),
-                                               int(mode), self.seed, plan.epoch, C.byref(self.table), _ptr(loss), _ptr(ctx_out),
-                                               _ptr(neg_out), out_pairs, _ptr(gin), _ptr(gout), _stream(self.dev)),
-                       'otto_sgns_step')
+            self._call('otto_sgns_step', plan.tok_aid, plan.tok_src, plan.tok_left, plan.pair_off, plan.T, int(t0), int(t1), In, Out,
+                       self.d, self.neg, float(lr), int(mode), self.seed, plan.epoch, C.byref(self.table), loss, ctx_out, neg_out,
+                       out_pairs, gin, gout)
         return loss
 
 

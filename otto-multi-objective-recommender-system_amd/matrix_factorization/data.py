@@ -117,8 +117,6 @@ def build_aid_pairs_device(ev, sampling_strategy='diff', hour_difference=1, targ
     if target_aggregation not in ('mean', 'max'):
         raise ValueError('Invalid target aggregation')
     lib = _lib.lib()
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-    stream = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed))
     aid, ts, off = ev.aid, ev.ts, ev.sess_off
@@ -138,34 +136,31 @@ def build_aid_pairs_device(ev, sampling_strategy='diff', hour_difference=1, targ
             keys = (torch.randint(0, 2 ** 31, (E,), device=dev, generator=gen, dtype=torch.int64) if shuffle_keys is None
                     else torch.as_tensor(np.asarray(shuffle_keys, dtype=np.int64), device=dev))
             sess = torch.repeat_interleave(torch.arange(S, device=dev, dtype=torch.int32), off[1:] - off[:-1], output_size=E)
-            ws_b = lib.otto_events_sort_workspace(E)
-            ws = torch.empty(max(int(ws_b), 8), dtype=torch.uint8, device=dev)
+            ws_b = int(lib.otto_events_sort_workspace(E))
+            ws = _lib.workspace(ws_b, dev)
             second = torch.empty(E, dtype=torch.int32, device=dev)
             tmp_ts = torch.empty(E, dtype=torch.int32, device=dev)
             tmp_ty = torch.empty(E, dtype=torch.uint8, device=dev)
             tmp_off = torch.empty(E + 1, dtype=torch.int64, device=dev)
             tmp_id = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
             ns = C.c_int64()
-            _lib.check(lib.otto_events_sort(ptr(sess), ptr(keys), ptr(aid), ptr(ev.type), E, 1, ptr(second), ptr(tmp_ts), ptr(tmp_ty),
-                                            C.c_void_p(0), C.c_void_p(tmp_off.data_ptr()), ptr(tmp_id), C.byref(ns),
-                                            C.c_void_p(ws.data_ptr()), int(ws_b), stream()), 'otto_events_sort')
+            _lib.call('otto_events_sort', dev, sess, keys, aid, ev.type, E, 1, second, tmp_ts, tmp_ty, None, tmp_off, tmp_id,
+                      C.byref(ns), ws, ws_b)
             del ws, tmp_ts, tmp_ty, tmp_off, tmp_id
         raw = C.c_int64()
-        _lib.check(lib.otto_pairs_raw_count(ptr(off), S, int(sampling_strategy == 'time'), C.byref(raw), stream()), 'otto_pairs_raw_count')
+        _lib.call('otto_pairs_raw_count', dev, off, S, int(sampling_strategy == 'time'), C.byref(raw))
         raw = int(raw.value)
         if raw >= 2 ** 32:
             raise ValueError(f'{raw} raw pair records exceed one call (2^32 - 1): lower sample_frac or split the sessions')
-        ws_b = lib.otto_pairs_workspace(raw)
-        ws = torch.empty(max(int(ws_b), 8), dtype=torch.uint8, device=dev)
+        ws_b = int(lib.otto_pairs_workspace(raw))
+        ws = _lib.workspace(ws_b, dev)
         x1 = torch.empty(max(raw, 1), dtype=torch.int64, device=dev)
         x2, tg = torch.empty_like(x1), torch.empty_like(x1)
         n_rows = C.c_int64()
         if sampling_strategy == 'time':
-            _lib.check(lib.otto_pairs_time(ptr(aid), ptr(ts), ptr(off), S, raw, int(round(float(hour_difference) * 3600)),
-                                           0 if target_aggregation == 'mean' else 1, ptr(x1), ptr(x2), ptr(tg), C.byref(n_rows),
-                                           C.c_void_p(ws.data_ptr()), int(ws_b), stream()), 'otto_pairs_time')
+            _lib.call('otto_pairs_time', dev, aid, ts, off, S, raw, int(round(float(hour_difference) * 3600)),
+                      0 if target_aggregation == 'mean' else 1, x1, x2, tg, C.byref(n_rows), ws, ws_b)
         else:
-            _lib.check(lib.otto_pairs_diff(ptr(aid), ptr(second), ptr(off), S, raw, ptr(x1), ptr(x2), ptr(tg), C.byref(n_rows),
-                                           C.c_void_p(ws.data_ptr()), int(ws_b), stream()), 'otto_pairs_diff')
+            _lib.call('otto_pairs_diff', dev, aid, second, off, S, raw, x1, x2, tg, C.byref(n_rows), ws, ws_b)
         n = int(n_rows.value)
         return x1[:n].clone(), x2[:n].clone(), tg[:n].clone()

@@ -7,8 +7,6 @@ The reference takes its neighbour lists from an Annoy index over fastText vector
 trains, built once; it closes the chain *train item embeddings -> neighbour table -> candidate recipes*. The lists are
 not expected to reproduce those of an approximate index over other vectors.
 """
-import ctypes as C
-
 from .. import _lib
 
 METRICS = {'euclidean': 0, 'angular': 1, 'dot': 2}
@@ -17,10 +15,6 @@ DIMS = (8, 16, 32, 64, 128)
 # state_dict keys of the item tables this package trains: CollaborativeFiltering, MatrixFactorization
 # (torch_modules.py), the BPR model (bpr.py)
 ITEM_TABLE_KEYS = ('embeddings.weight', 'aid_embeddings.weight', 'item_embedding.weight')
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def neighbour_table(E, k=45, metric='euclidean', valid=None, rows=None):
@@ -57,16 +51,12 @@ def neighbour_table(E, k=45, metric='euclidean', valid=None, rows=None):
     if dev.type != 'cuda':
         raise _lib.OttoError('neighbour_table needs a ROCm device (no CPU fallback)')
     R = N if rows is None else int(rows.numel())
-    lib = _lib.lib()
-    ws_bytes = int(lib.otto_knn_workspace(R, N, d, k, METRICS[metric]))
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    ws_bytes = int(_lib.lib().otto_knn_workspace(R, N, d, k, METRICS[metric]))
+    ws = _lib.workspace(ws_bytes, dev)
     ids = torch.empty((R, k), dtype=torch.int32, device=dev)
     dist = torch.empty((R, k), dtype=torch.float32, device=dev)
     n = torch.empty(R, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.otto_knn_table(_ptr(E), N, d, _ptr(valid), _ptr(rows), R, k, METRICS[metric], _ptr(ids), _ptr(dist),
-                                      _ptr(n), _ptr(ws), ws_bytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                   'otto_knn_table')
+    _lib.call('otto_knn_table', dev, E, N, d, valid, rows, R, k, METRICS[metric], ids, dist, n, ws, ws_bytes)
     return ids, dist, n
 
 

@@ -14,18 +14,18 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from .forest import MAX_K, _ptr, _stream, session_topk
+from .forest import MAX_K, session_topk
 
 MAX_MODELS = 8           # OTTO_BLEND_MAX_MODELS
 _TINY = 10 * np.finfo(np.float64).eps
 
 
-def _need_device(t, what):
+def _column(t, what):
+    """``t`` as a contiguous 1-d device tensor, of whatever dtype."""
     import torch
-    if not isinstance(t, torch.Tensor) or t.dim() != 1:
+    if not isinstance(t, torch.Tensor):
         raise ValueError(f'{what}: expected a 1-d tensor')
-    if t.device.type != 'cuda':
-        raise _lib.OttoError(f'{what}: the blend needs a ROCm device (no CPU fallback)')
+    return _lib.need(t, what, t.dtype, 1, copy=True)
 
 
 def center_scale(nv, stats):
@@ -55,18 +55,13 @@ def robust_stats(score):
     two neighbours of the 25th and of the 75th percentile. Raises ``OttoError`` for an empty or all-NaN column or an
     infinite value."""
     import torch
-    _need_device(score, 'score')
-    if score.dtype != torch.float64 or not score.is_contiguous():
-        raise ValueError('score: expected a contiguous float64 tensor')
-    lib = _lib.lib()
+    _lib.need(score, 'score', torch.float64, 1)
     n = score.numel()
-    ws_bytes = int(lib.otto_blend_select_workspace(n))
+    ws_bytes = int(_lib.lib().otto_blend_select_workspace(n))
     nv = C.c_int64(0)
     stats = (C.c_double * 6)()
-    with torch.cuda.device(score.device):
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=score.device)
-        _lib.check(lib.otto_blend_robust_stats(_ptr(score), n, C.byref(nv), stats, _ptr(ws), ws_bytes, _stream(score.device)),
-                   'otto_blend_robust_stats')
+    ws = _lib.workspace(ws_bytes, score.device)
+    _lib.call('otto_blend_robust_stats', score.device, score, n, C.byref(nv), stats, ws, ws_bytes)
     return int(nv.value), np.array(list(stats), dtype=np.float64)
 
 
@@ -74,29 +69,26 @@ def robust_scale(score):
     """``RobustScaler().fit_transform`` of one score column, cast to float32: (scaled float32 tensor, center, scale).
     NaN entries are ignored by the statistics and stay NaN."""
     import torch
-    _need_device(score, 'score')
+    score = _column(score, 'score')
     if score.dtype == torch.float32:
         score = score.double()
-    score = score.contiguous()
     nv, stats = robust_stats(score)
     center, scale = center_scale(nv, stats)
     out = torch.empty(score.numel(), dtype=torch.float32, device=score.device)
-    with torch.cuda.device(score.device):
-        _lib.check(_lib.lib().otto_blend_scale(_ptr(score), score.numel(), center, scale, _ptr(out), _stream(score.device)),
-                   'otto_blend_scale')
+    _lib.call('otto_blend_scale', score.device, score, score.numel(), center, scale, out)
     return out, center, scale
 
 
 def _ids(t, what):
     import torch
-    _need_device(t, what)
+    t = _column(t, what)
     if t.dtype == torch.int64:
         if t.numel() and (int(t.min()) < -(1 << 31) or int(t.max()) >= (1 << 31)):
             raise ValueError(f'{what}: values outside int32')
         t = t.to(torch.int32)
     if t.dtype != torch.int32:
         raise ValueError(f'{what}: expected an int32 (or int64) tensor')
-    return t.contiguous()
+    return t
 
 
 def _prepare(models, weights, left_of_base, scale):
@@ -114,7 +106,7 @@ def _prepare(models, weights, left_of_base, scale):
     cols = []
     for m, (session, aid, score) in enumerate(models):
         session, aid = _ids(session, f'session of model {m}'), _ids(aid, f'aid of model {m}')
-        _need_device(score, f'score of model {m}')
+        score = _column(score, f'score of model {m}')
         if not (session.numel() == aid.numel() == score.numel()):
             raise ValueError(f'model {m}: session, aid and score differ in length')
         if session.device != score.device or aid.device != score.device or score.device != models[0][2].device:
@@ -137,24 +129,22 @@ def blend_predictions(models, weights, left_of_base=None, scale=True, _want64=Fa
     cols, weights, left = _prepare(models, weights, left_of_base, scale)
     M = len(cols)
     dev = cols[0][2].device
-    lib = _lib.lib()
     ns = [c[0].numel() for c in cols]
     tot = sum(ns)
     if tot >= 1 << 31:
         raise ValueError('more than 2^31 - 1 rows in all')
-    arr = lambda i: (C.c_void_p * M)(*[c[i].data_ptr() if c[i].numel() else None for c in cols])
-    with torch.cuda.device(dev):
-        ws_bytes = int(lib.otto_blend_join_workspace(tot, M))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        sid = torch.empty(tot, dtype=torch.int32, device=dev)
-        off = torch.empty(tot + 1, dtype=torch.int64, device=dev)
-        aid = torch.empty(tot, dtype=torch.int32, device=dev)
-        pred = torch.empty(tot, dtype=torch.float32, device=dev)
-        pred64 = torch.empty(tot, dtype=torch.float64, device=dev) if _want64 else None
-        n_out, n_sess = C.c_int64(0), C.c_int64(0)
-        _lib.check(lib.otto_blend_join(M, arr(0), arr(1), arr(2), (C.c_int64 * M)(*ns), (C.c_double * M)(*weights),
-                                       (C.c_int32 * M)(*left), _ptr(sid), _ptr(off), _ptr(aid), _ptr(pred), _ptr(pred64),
-                                       C.byref(n_out), C.byref(n_sess), _ptr(ws), ws_bytes, _stream(dev)), 'otto_blend_join')
+    # one pointer per model and column (_prepare made the columns contiguous on dev); an empty column goes in as NULL
+    arr = lambda i: (C.c_void_p * M)(*[_lib.ptr(c[i], dev, f'model {m}') if c[i].numel() else None for m, c in enumerate(cols)])
+    ws_bytes = int(_lib.lib().otto_blend_join_workspace(tot, M))
+    ws = _lib.workspace(ws_bytes, dev)
+    sid = torch.empty(tot, dtype=torch.int32, device=dev)
+    off = torch.empty(tot + 1, dtype=torch.int64, device=dev)
+    aid = torch.empty(tot, dtype=torch.int32, device=dev)
+    pred = torch.empty(tot, dtype=torch.float32, device=dev)
+    pred64 = torch.empty(tot, dtype=torch.float64, device=dev) if _want64 else None
+    n_out, n_sess = C.c_int64(0), C.c_int64(0)
+    _lib.call('otto_blend_join', dev, M, arr(0), arr(1), arr(2), (C.c_int64 * M)(*ns), (C.c_double * M)(*weights),
+              (C.c_int32 * M)(*left), sid, off, aid, pred, pred64, C.byref(n_out), C.byref(n_sess), ws, ws_bytes)
     R, S = int(n_out.value), int(n_sess.value)
     out = (sid[:S], off[:S + 1], aid[:R], pred[:R])
     return out + (pred64[:R],) if _want64 else out

@@ -9,39 +9,28 @@ are padded (``[P, k]`` int32, or ``([P, k], n int32 [P])``: what ``session_topk`
 (``(off int64 [P+1], aid int32)``: a ranker table's ``row_off`` / ``candidates``). No CPU fallback.
 """
 import ctypes as C
+import functools
 import math
 
 from .. import _lib
 from ..events import DeviceEvents
 from ..metrics import weighted_recall
-from .forest import MAX_K, _ptr, _stream
+from .forest import MAX_K
 
 TYPES = ('clicks', 'carts', 'orders')
-
-
-def _need(t, what, dtype, dim=1):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dim() != dim or t.dtype != dtype:
-        raise ValueError(f'{what}: expected a {dim}-d {dtype} tensor')
-    if t.device.type != 'cuda':
-        raise _lib.OttoError(f'{what}: the evaluation needs a ROCm device (no CPU fallback)')
-    return t.contiguous()
+# the 1-d device tensor every argument here is; a strided one is copied, not refused
+_tensor = functools.partial(_lib.need, dim=1, copy=True)
 
 
 def _events(events):
     import torch
     if not isinstance(events, DeviceEvents):
         raise ValueError('events: expected a DeviceEvents')
-    aid, ts = _need(events.aid, 'events.aid', torch.int32), _need(events.ts, 'events.ts', torch.int32)
-    typ, off = _need(events.type, 'events.type', torch.uint8), _need(events.sess_off, 'events.sess_off', torch.int64)
+    aid, ts = _tensor(events.aid, 'events.aid', torch.int32), _tensor(events.ts, 'events.ts', torch.int32)
+    typ, off = _tensor(events.type, 'events.type', torch.uint8), _tensor(events.sess_off, 'events.sess_off', torch.int64)
     if off.numel() < 1 or not (aid.numel() == ts.numel() == typ.numel()):
         raise ValueError('events: columns differ in length or sess_off is empty')
     return aid, ts, typ, off
-
-
-def _ws(n_bytes, dev):
-    import torch
-    return torch.empty(max(int(n_bytes), 256), dtype=torch.uint8, device=dev)
 
 
 def last_click(events):
@@ -50,8 +39,7 @@ def last_click(events):
     _, _, typ, off = _events(events)
     S = off.numel() - 1
     out = torch.empty(S, dtype=torch.int32, device=typ.device)
-    with torch.cuda.device(typ.device):
-        _lib.check(_lib.lib().otto_eval_last_click(_ptr(typ), _ptr(off), S, _ptr(out), _stream(typ.device)), 'otto_eval_last_click')
+    _lib.call('otto_eval_last_click', typ.device, typ, off, S, out)
     return out
 
 
@@ -64,9 +52,7 @@ def cutoffs(events, seed):
     S = off.numel() - 1
     out = torch.empty(S, dtype=torch.int32, device=typ.device)
     n_wo = C.c_int64(0)
-    with torch.cuda.device(typ.device):
-        _lib.check(_lib.lib().otto_eval_cutoffs(_ptr(typ), _ptr(off), S, int(seed) & (2 ** 64 - 1), _ptr(out), C.byref(n_wo),
-                                                _stream(typ.device)), 'otto_eval_cutoffs')
+    _lib.call('otto_eval_cutoffs', typ.device, typ, off, S, int(seed) & (2 ** 64 - 1), out, C.byref(n_wo))
     return out, int(n_wo.value)
 
 
@@ -79,25 +65,19 @@ def split(events, cutoff):
     aid, ts, typ, off = _events(events)
     dev = aid.device
     S, E = off.numel() - 1, aid.numel()
-    cutoff = _need(cutoff, 'cutoff', torch.int32)
+    cutoff = _tensor(cutoff, 'cutoff', torch.int32)
     if cutoff.numel() != S or cutoff.device != dev:
         raise ValueError('cutoff: expected int32 [S] on the events\' device')
-    lib = _lib.lib()
-    with torch.cuda.device(dev):
-        ws_bytes = int(lib.otto_eval_split_workspace(S, E))
-        ws = _ws(ws_bytes, dev)
-        offs = [torch.empty(S + 1, dtype=torch.int64, device=dev) for _ in range(4)]
-        counts = (C.c_int64 * 4)()
-        _lib.check(lib.otto_eval_split_count(_ptr(aid), _ptr(typ), _ptr(off), S, E, _ptr(cutoff), *[_ptr(o) for o in offs], counts,
-                                             _ptr(ws), ws.numel(), _stream(dev)), 'otto_eval_split_count')
-        kept, n_lab = int(counts[0]), [int(c) for c in counts[1:]]
-        k_aid = torch.empty(kept, dtype=torch.int32, device=dev)
-        k_ts = torch.empty(kept, dtype=torch.int32, device=dev)
-        k_typ = torch.empty(kept, dtype=torch.uint8, device=dev)
-        labs = [torch.empty(n, dtype=torch.int32, device=dev) for n in n_lab]
-        _lib.check(lib.otto_eval_split(_ptr(aid), _ptr(ts), _ptr(typ), _ptr(off), S, E, _ptr(cutoff), *[_ptr(o) for o in offs],
-                                       _ptr(k_aid), _ptr(k_ts), _ptr(k_typ), *[_ptr(x) for x in labs], _ptr(ws), ws.numel(),
-                                       _stream(dev)), 'otto_eval_split')
+    ws = _lib.workspace(_lib.lib().otto_eval_split_workspace(S, E), dev)
+    offs = [torch.empty(S + 1, dtype=torch.int64, device=dev) for _ in range(4)]
+    counts = (C.c_int64 * 4)()
+    _lib.call('otto_eval_split_count', dev, aid, typ, off, S, E, cutoff, *offs, counts, ws, ws.numel())
+    kept, n_lab = int(counts[0]), [int(c) for c in counts[1:]]
+    k_aid = torch.empty(kept, dtype=torch.int32, device=dev)
+    k_ts = torch.empty(kept, dtype=torch.int32, device=dev)
+    k_typ = torch.empty(kept, dtype=torch.uint8, device=dev)
+    labs = [torch.empty(n, dtype=torch.int32, device=dev) for n in n_lab]
+    _lib.call('otto_eval_split', dev, aid, ts, typ, off, S, E, cutoff, *offs, k_aid, k_ts, k_typ, *labs, ws, ws.numel())
     kept_events = DeviceEvents(k_aid, k_ts, k_typ, offs[0], events.session_ids, None, events.n_aids)
     return kept_events, {name: (offs[1 + i], labs[i]) for i, name in enumerate(TYPES)}
 
@@ -117,18 +97,18 @@ def hits(labels, preds, label_session=None, pred_session=None, cap=20, mask=None
     (Python ints). Raises ``OttoError`` for a prediction session that is no label session."""
     import torch
     l_off, l_aid = labels
-    l_off, l_aid = _need(l_off, 'label off', torch.int64), _need(l_aid, 'label aid', torch.int32)
+    l_off, l_aid = _tensor(l_off, 'label off', torch.int64), _tensor(l_aid, 'label aid', torch.int32)
     dev = l_off.device
     S = l_off.numel() - 1
     p_n = p_off = None
     if isinstance(preds, (tuple, list)):
         first, second = preds
         if isinstance(first, torch.Tensor) and first.dim() == 2:
-            p_aid, p_n = _need(first, 'pred aid', torch.int32, 2), _need(second, 'pred n', torch.int32)
+            p_aid, p_n = _tensor(first, 'pred aid', torch.int32, dim=2), _tensor(second, 'pred n', torch.int32)
         else:
-            p_off, p_aid = _need(first, 'pred off', torch.int64), _need(second, 'pred aid', torch.int32)
+            p_off, p_aid = _tensor(first, 'pred off', torch.int64), _tensor(second, 'pred aid', torch.int32)
     else:
-        p_aid = _need(preds, 'pred aid', torch.int32, 2)
+        p_aid = _tensor(preds, 'pred aid', torch.int32, dim=2)
     if p_off is not None:
         P, k = p_off.numel() - 1, 0
     else:
@@ -140,11 +120,11 @@ def hits(labels, preds, label_session=None, pred_session=None, cap=20, mask=None
     if S < 0 or P < 0:
         raise ValueError('labels / preds: an offset array needs at least one entry')
     if label_session is not None:
-        label_session = _need(label_session, 'label_session', torch.int32)
+        label_session = _tensor(label_session, 'label_session', torch.int32)
         if label_session.numel() != S:
             raise ValueError('label_session: expected int32 [S]')
     if pred_session is not None:
-        pred_session = _need(pred_session, 'pred_session', torch.int32)
+        pred_session = _tensor(pred_session, 'pred_session', torch.int32)
         if pred_session.numel() != P:
             raise ValueError('pred_session: expected int32 [P]')
     elif P != S:
@@ -152,21 +132,18 @@ def hits(labels, preds, label_session=None, pred_session=None, cap=20, mask=None
     if mask is not None:
         if mask.dtype == torch.bool:
             mask = mask.to(torch.uint8)
-        mask = _need(mask, 'mask', torch.uint8)
+        mask = _tensor(mask, 'mask', torch.uint8)
         if mask.numel() != S:
             raise ValueError('mask: expected uint8 [S]')
     for t in (l_aid, p_aid, p_n, p_off, label_session, pred_session, mask):
         if t is not None and t.device != dev:
             raise ValueError('all tensors must be on one device')
-    lib = _lib.lib()
     out_h = torch.empty(S, dtype=torch.int32, device=dev)
     out_d = torch.empty(S, dtype=torch.int32, device=dev)
     tot = (C.c_int64 * 4)()
-    with torch.cuda.device(dev):
-        ws = _ws(lib.otto_eval_hits_workspace(S), dev)
-        _lib.check(lib.otto_eval_hits(_ptr(label_session), _ptr(l_off), _ptr(l_aid), S, _ptr(p_aid), _ptr(p_n), _ptr(p_off), k, P,
-                                      _ptr(pred_session), int(cap) if cap else 0, _ptr(mask), _ptr(out_h), _ptr(out_d), tot,
-                                      _ptr(ws), ws.numel(), _stream(dev)), 'otto_eval_hits')
+    ws = _lib.workspace(_lib.lib().otto_eval_hits_workspace(S), dev)
+    _lib.call('otto_eval_hits', dev, label_session, l_off, l_aid, S, p_aid, p_n, p_off, k, P, pred_session, int(cap) if cap else 0,
+              mask, out_h, out_d, tot, ws, ws.numel())
     return out_h, out_d, {'hits': int(tot[0]), 'denom': int(tot[1]), 'mask_hits': int(tot[2]), 'mask_denom': int(tot[3])}
 
 

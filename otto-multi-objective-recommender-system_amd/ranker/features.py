@@ -7,7 +7,6 @@ What this replaces in the reference: ``src/ranker/aid_feature_engineering.py`` a
 ``interaction_features_rows`` -> :func:`aid_feature_table` / :func:`session_feature_table` -> :func:`feature_matrix` ->
 ``ranker.forest``. There is no CPU fallback.
 """
-import ctypes as C
 import datetime
 
 import numpy as np
@@ -59,10 +58,7 @@ def _events(name, aid, ts, typ, sess_off):
     if dev.type != 'cuda':
         raise _lib.OttoError(f'{name} needs a ROCm device (no CPU fallback)')
     for what, x, dt in (('aid', aid, torch.int32), ('ts', ts, torch.int32), ('type', typ, torch.uint8), ('sess_off', sess_off, torch.int64)):
-        if x.dtype != dt or x.dim() != 1 or not x.is_contiguous():
-            raise ValueError(f'{what}: expected contiguous 1-d {dt}')
-        if x.device != dev:
-            raise ValueError('aid, ts, type and sess_off must be on one device')
+        _lib.need(x, what, dt, 1, device=dev)
     n = aid.numel()
     if ts.numel() != n or typ.numel() != n or sess_off.numel() < 1:
         raise ValueError('aid / ts / type / sess_off shapes disagree')
@@ -82,15 +78,6 @@ def _days(ts):
     return day_min, day_table(day_min, min(day_max, day_min + 4 * MAX_DAYS))
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-
-
-def _stream(dev):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def aid_feature_table(aid, ts, typ, sess_off, n_aids):
     """``aid`` int32 / ``ts`` int32 seconds / ``typ`` uint8 / ``sess_off`` int64: (session, ts)-sorted events on the device.
     Returns (table float32 [n_aids, 31] on the device, :data:`AID_COLUMNS`); the row of an aid with no event is NaN."""
@@ -100,14 +87,10 @@ def aid_feature_table(aid, ts, typ, sess_off, n_aids):
     if n_aids < 1:
         raise ValueError('n_aids must be positive')
     day_min, days = _days(ts)
-    lib = _lib.lib()
-    ws_b = int(lib.otto_feat_aid_table_workspace(n, n_aids))
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    ws_b = int(_lib.lib().otto_feat_aid_table_workspace(n, n_aids))
+    ws = _lib.workspace(ws_b, dev)
     out = torch.empty((n_aids, len(AID_COLUMNS)), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.otto_feat_aid_table(_ptr(aid), _ptr(ts), _ptr(typ), _ptr(sess_off), S, n, n_aids, day_min, len(days),
-                                           days.ctypes.data_as(C.c_void_p), _ptr(out), _ptr(ws), ws_b, _stream(dev)),
-                   'otto_feat_aid_table')
+    _lib.call('otto_feat_aid_table', dev, aid, ts, typ, sess_off, S, n, n_aids, day_min, len(days), days, out, ws, ws_b)
     return out, AID_COLUMNS
 
 
@@ -121,14 +104,11 @@ def session_feature_table(aid, ts, typ, sess_off, aid_table):
             or aid_table.shape[1] != len(AID_COLUMNS) or not aid_table.is_contiguous() or aid_table.device != dev):
         raise ValueError(f'aid_table: expected a contiguous float32 [n_aids, {len(AID_COLUMNS)}] tensor on the events\' device')
     day_min, days = _days(ts)
-    lib = _lib.lib()
-    ws_b = int(lib.otto_feat_session_table_workspace(S))
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    ws_b = int(_lib.lib().otto_feat_session_table_workspace(S))
+    ws = _lib.workspace(ws_b, dev)
     out = torch.empty((S, len(SESSION_COLUMNS)), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.otto_feat_session_table(_ptr(aid), _ptr(ts), _ptr(typ), _ptr(sess_off), S, _ptr(aid_table), int(aid_table.shape[0]),
-                                               day_min, len(days), days.ctypes.data_as(C.c_void_p), _ptr(out), _ptr(ws), ws_b,
-                                               _stream(dev)), 'otto_feat_session_table')
+    _lib.call('otto_feat_session_table', dev, aid, ts, typ, sess_off, S, aid_table, int(aid_table.shape[0]), day_min, len(days), days,
+              out, ws, ws_b)
     return out
 
 
@@ -167,14 +147,11 @@ def feature_matrix(table, inter_row, inter_sess, inter_aid, aid_table, sess_tabl
                                ('sess_table', sess_table, torch.float32, (S, len(SESSION_COLUMNS)))):
         if x.dtype != dt or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
             raise ValueError(f'{name}: expected a contiguous {dt} tensor of shape {shape} on {dev}')
-    lib = _lib.lib()
-    ws_b = int(lib.otto_feat_matrix_workspace(R))
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    ws_b = int(_lib.lib().otto_feat_matrix_workspace(R))
+    ws = _lib.workspace(ws_b, dev)
     out = torch.empty((R, len(program)), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.otto_feat_matrix(_ptr(row_off), S, _ptr(cand), _ptr(scores), R, _ptr(inter_row), _ptr(inter_sess), _ptr(inter_aid),
-                                        _ptr(aid_table), _ptr(sess_table), n_aids, program.ctypes.data_as(C.c_void_p), len(program),
-                                        _ptr(out), _ptr(ws), ws_b, _stream(dev)), 'otto_feat_matrix')
+    _lib.call('otto_feat_matrix', dev, row_off, S, cand, scores, R, inter_row, inter_sess, inter_aid, aid_table, sess_table, n_aids,
+              program, len(program), out, ws, ws_b)
     return out
 
 

@@ -16,7 +16,6 @@ import numpy as np
 from .. import _lib
 from . import gbdt
 from .forest import MAX_FEATURES
-from .gbdt import _check_1d, _check_bins, _need_device, _ptr, _stream
 
 MAX_SPLITS = 16             # OTTO_FOLDS_MAX_SPLITS
 BIN_SAMPLE_ROWS = 200000    # LightGBM's bin_construct_sample_cnt
@@ -25,18 +24,18 @@ _MAX_N = (1 << 31) - 1
 
 def _check_query_off(query_off):
     import torch
-    _check_1d('query_off', query_off, torch.int64)
-    _need_device(query_off, 'the fold machinery')
+    _lib.need(query_off, 'query_off', torch.int64, 1)
     if query_off.numel() < 1:
         raise ValueError('query_off: expected int64 [Q+1]')
     return query_off.numel() - 1
 
 
-def _work(n_bytes, dev, what):
-    import torch
+def _scratch(size_fn, dev, *args):
+    """The workspace of the size ``size_fn(*args)`` asks for; a size <= 0 is the library's refusal of ``args``."""
+    n_bytes = getattr(_lib.lib(), size_fn)(*args)
     if n_bytes <= 0:
-        raise _lib.OttoError(f'{what} refused its arguments')
-    return torch.empty(int(n_bytes), dtype=torch.uint8, device=dev)
+        raise _lib.OttoError(f'{size_fn} refused its arguments')
+    return _lib.workspace(n_bytes, dev)
 
 
 def group_kfold(query_off, n_splits=5, n=None, timing=None):
@@ -57,16 +56,13 @@ def group_kfold(query_off, n_splits=5, n=None, timing=None):
     if not 0 <= n <= _MAX_N:
         raise ValueError(f'n = {n} outside [0, 2^31)')
     dev = query_off.device
-    lib = _lib.lib()
     # the outputs are handed over only after the call succeeded: a refused call leaves nothing behind
     fold_of_query = torch.empty(Q, dtype=torch.int32, device=dev)
     fold_rows = torch.empty(n_splits, dtype=torch.int64, device=dev)
     walk_ms = C.c_float(0.0)
-    with torch.cuda.device(dev):
-        work = _work(lib.otto_folds_kfold_workspace(Q), dev, 'otto_folds_kfold_workspace')
-        _lib.check(lib.otto_folds_group_kfold(_ptr(query_off), Q, n, n_splits, _ptr(fold_of_query), _ptr(fold_rows),
-                                              C.byref(walk_ms) if timing is not None else None, _ptr(work), work.numel(),
-                                              _stream(dev)), 'otto_folds_group_kfold')
+    work = _scratch('otto_folds_kfold_workspace', dev, Q)
+    _lib.call('otto_folds_group_kfold', dev, query_off, Q, n, n_splits, fold_of_query, fold_rows,
+              C.byref(walk_ms) if timing is not None else None, work, work.numel())
     if timing is not None:
         timing['walk_ms'] = float(walk_ms.value)
     return fold_of_query, fold_rows
@@ -93,13 +89,12 @@ def fold_indices(label, query_off, fold_of_query, fold, ratio, seed=42):
     negatives with the smallest ``splitmix64(seed, row)`` keys. ``label`` uint8 or int32 [n], ``query_off`` int64 [Q+1],
     ``fold_of_query`` int32 [Q], on the device. The host reads back ``N`` and the output sizes, nothing else."""
     import torch
-    if not isinstance(label, torch.Tensor) or label.dtype not in (torch.uint8, torch.int32) or label.dim() != 1 \
-            or not label.is_contiguous():
+    if not isinstance(label, torch.Tensor) or label.dtype not in (torch.uint8, torch.int32):
         raise ValueError('label: expected a contiguous 1-d uint8 or int32 tensor')
-    _need_device(label, 'fold_indices')
+    _lib.need(label, 'label', label.dtype, 1)
     dev = label.device
     Q = _check_query_off(query_off)
-    _check_1d('fold_of_query', fold_of_query, torch.int32, dev)
+    _lib.need(fold_of_query, 'fold_of_query', torch.int32, 1, device=dev)
     if query_off.device != dev:
         raise ValueError(f'query_off must be on {dev}')
     if fold_of_query.numel() != Q:
@@ -114,24 +109,19 @@ def fold_indices(label, query_off, fold_of_query, fold, ratio, seed=42):
         raise ValueError(f'ratio must be in [0, 1] (got {ratio})')
     if not 0 <= seed < 1 << 64:
         raise ValueError('seed: expected a uint64')
-    lib = _lib.lib()
     counts = (C.c_int64 * 5)()
-    with torch.cuda.device(dev):
-        state = _work(lib.otto_folds_state_bytes(n), dev, 'otto_folds_state_bytes')
-        _lib.check(lib.otto_folds_classify(_ptr(label), label.element_size(), _ptr(query_off), Q, n, _ptr(fold_of_query), fold,
-                                           _ptr(state), counts, _stream(dev)), 'otto_folds_classify')
-        N, P, Mv, Qt, Qv = (int(c) for c in counts)
-        m = sample_size(ratio, N)
-        Mt = P + m
-        i32 = lambda k: torch.empty(k, dtype=torch.int32, device=dev)
-        i64 = lambda k: torch.empty(k, dtype=torch.int64, device=dev)
-        out = FoldIndices(train_idx=i32(Mt), train_query_off=i64(Qt + 1), train_query=i32(Qt), val_idx=i32(Mv),
-                          val_query_off=i64(Qv + 1), val_query=i32(Qv), n_eligible=N, n_kept=m, n_positive=P)
-        work = _work(lib.otto_folds_emit_workspace(Q), dev, 'otto_folds_emit_workspace')
-        _lib.check(lib.otto_folds_emit(_ptr(state), _ptr(query_off), Q, n, N, m, seed, Mt, Qt, Mv, Qv, _ptr(out.train_idx),
-                                       _ptr(out.train_query_off), _ptr(out.train_query), _ptr(out.val_idx),
-                                       _ptr(out.val_query_off), _ptr(out.val_query), _ptr(work), work.numel(), _stream(dev)),
-                   'otto_folds_emit')
+    state = _scratch('otto_folds_state_bytes', dev, n)
+    _lib.call('otto_folds_classify', dev, label, label.element_size(), query_off, Q, n, fold_of_query, fold, state, counts)
+    N, P, Mv, Qt, Qv = (int(c) for c in counts)
+    m = sample_size(ratio, N)
+    Mt = P + m
+    i32 = lambda k: torch.empty(k, dtype=torch.int32, device=dev)
+    i64 = lambda k: torch.empty(k, dtype=torch.int64, device=dev)
+    out = FoldIndices(train_idx=i32(Mt), train_query_off=i64(Qt + 1), train_query=i32(Qt), val_idx=i32(Mv),
+                      val_query_off=i64(Qv + 1), val_query=i32(Qv), n_eligible=N, n_kept=m, n_positive=P)
+    work = _scratch('otto_folds_emit_workspace', dev, Q)
+    _lib.call('otto_folds_emit', dev, state, query_off, Q, n, N, m, seed, Mt, Qt, Mv, Qv, out.train_idx, out.train_query_off,
+              out.train_query, out.val_idx, out.val_query_off, out.val_query, work, work.numel())
     return out
 
 
@@ -139,14 +129,12 @@ def gather_bins(bins, idx):
     """``out[f, i] = bins[f, idx[i]]``: uint8 [F, m] from ``bins`` uint8 [F, n] (``gbdt.bin_matrix``) and ``idx`` int32
     [m] on the device; any order, repeats allowed. Raises ``OttoError`` for an index outside ``[0, n)``."""
     import torch
-    F, n = _check_bins(bins)
-    _check_1d('idx', idx, torch.int32, bins.device)
+    F, n = gbdt.check_bins(bins)
+    _lib.need(idx, 'idx', torch.int32, 1, device=bins.device)
     if not 1 <= F <= MAX_FEATURES:
         raise ValueError(f'F must be in [1, {MAX_FEATURES}] (got {F})')
     out = torch.empty((F, idx.numel()), dtype=torch.uint8, device=bins.device)
-    with torch.cuda.device(bins.device):
-        _lib.check(_lib.lib().otto_folds_gather_u8(_ptr(bins), n, F, _ptr(idx), idx.numel(), _ptr(out), _stream(bins.device)),
-                   'otto_folds_gather_u8')
+    _lib.call('otto_folds_gather_u8', bins.device, bins, n, F, idx, idx.numel(), out)
     return out
 
 
@@ -193,7 +181,8 @@ def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ra
     from .forest import session_topk
     if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.dtype != torch.float32:
         raise ValueError('X: expected a float32 tensor [n, F]')
-    _need_device(X, 'cross_validate')
+    if X.device.type != 'cuda':
+        raise _lib.OttoError('cross_validate needs a ROCm device (no CPU fallback)')
     dev = X.device
     n, F = int(X.shape[0]), int(X.shape[1])
     if label.numel() != n:

@@ -6,7 +6,6 @@ What this replaces in the reference: ``lgb.Booster.predict`` over every (session
 (``lgb_trainer.py:183-189``, ``src/ranker/inference.py:175-176, 245-246, 314-315``). Numerical splits only; raw scores
 (no output transform). The caller supplies the float32 feature matrix and chunks its rows by whole sessions.
 """
-import ctypes as C
 
 import numpy as np
 
@@ -67,10 +66,8 @@ class Forest:
         if n <= 0:
             raise _lib.OttoError('otto_forest_packed_bytes refused the forest (tree, node and leaf counts disagree)')
         out = np.zeros(n, dtype=np.uint8)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        _lib.check(lib.otto_forest_pack(self.n_trees, self.n_features, p(self.node_off), p(self.leaf_off), p(self.split_feature),
-                                        p(self.threshold), p(self.decision_type), p(self.left_child), p(self.right_child),
-                                        p(self.leaf_value), p(out), n), 'otto_forest_pack')
+        _lib.call('otto_forest_pack', None, self.n_trees, self.n_features, self.node_off, self.leaf_off, self.split_feature,
+                  self.threshold, self.decision_type, self.left_child, self.right_child, self.leaf_value, out, n, stream=False)
         return out
 
     def to(self, device):
@@ -206,10 +203,6 @@ def load_lightgbm_model(path):
         return parse_lightgbm_model(f.read())
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
 def _check_X(forest, X):
     import torch
     if not isinstance(forest, Forest):
@@ -225,18 +218,11 @@ def _check_X(forest, X):
     return int(X.shape[0]), int(X.stride(0)) if X.shape[0] else max(int(X.shape[1]), 1)
 
 
-def _stream(dev):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _predict_into(forest, X, raw, acc, divisor):
-    import torch
     n, ld = _check_X(forest, X)
     img = forest.to(X.device)._packed[X.device]
-    with torch.cuda.device(X.device):
-        _lib.check(_lib.lib().otto_forest_predict(_ptr(img), img.numel(), _ptr(X), ld, n, forest.n_features, _ptr(raw), _ptr(acc),
-                                                  float(divisor), _stream(X.device)), 'otto_forest_predict')
+    # X goes in as rows with the leading dimension ld (_check_X): it may be a column slice of a wider matrix
+    _lib.call('otto_forest_predict', X.device, img, img.numel(), _lib.ptr(X), ld, n, forest.n_features, raw, acc, float(divisor))
 
 
 def forest_predict(forest, X):
@@ -255,9 +241,7 @@ def forest_leaves(forest, X):
     n, ld = _check_X(forest, X)
     img = forest.to(X.device)._packed[X.device]
     leaf = torch.empty((n, forest.n_trees), dtype=torch.int32, device=X.device)
-    with torch.cuda.device(X.device):
-        _lib.check(_lib.lib().otto_forest_leaves(_ptr(img), img.numel(), _ptr(X), ld, n, forest.n_features, forest.n_trees,
-                                                 _ptr(leaf), _stream(X.device)), 'otto_forest_leaves')
+    _lib.call('otto_forest_leaves', X.device, img, img.numel(), _lib.ptr(X), ld, n, forest.n_features, forest.n_trees, leaf)
     return leaf
 
 
@@ -282,14 +266,10 @@ def session_topk(score, aid, row_off, k=20):
     ``row_off`` int64 [S+1], all on the device. Returns (top_aid int32 [S, k] (-1 padded), top_score float64 [S, k]
     (-inf padded), n int32 [S])."""
     import torch
-    for name, t, dt in (('score', score, torch.float64), ('aid', aid, torch.int32), ('row_off', row_off, torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
-            raise ValueError(f'{name}: expected a contiguous 1-d {dt} tensor')
+    _lib.need(score, 'score', torch.float64, 1)
     dev = score.device
-    if dev.type != 'cuda':
-        raise _lib.OttoError('session_topk needs a ROCm device (no CPU fallback)')
-    if aid.device != dev or row_off.device != dev:
-        raise ValueError('score, aid and row_off must be on one device')
+    _lib.need(aid, 'aid', torch.int32, 1, device=dev)
+    _lib.need(row_off, 'row_off', torch.int64, 1, device=dev)
     if aid.numel() != score.numel():
         raise ValueError(f'aid has {aid.numel()} rows, score has {score.numel()}')
     if row_off.numel() < 1:
@@ -301,9 +281,7 @@ def session_topk(score, aid, row_off, k=20):
     top_aid = torch.empty((S, k), dtype=torch.int32, device=dev)
     top_score = torch.empty((S, k), dtype=torch.float64, device=dev)
     n = torch.empty(S, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().otto_forest_session_topk(_ptr(score), _ptr(aid), _ptr(row_off), S, score.numel(), k, _ptr(top_aid),
-                                                       _ptr(top_score), _ptr(n), _stream(dev)), 'otto_forest_session_topk')
+    _lib.call('otto_forest_session_topk', dev, score, aid, row_off, S, score.numel(), k, top_aid, top_score, n)
     return top_aid, top_score, n
 
 

@@ -100,38 +100,13 @@ def fit_bins(sample, max_bin=255):
     return BinMapper(edges, n_edges)
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _np_ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _stream(dev):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _need_device(t, what):
-    if t.device.type != 'cuda':
-        raise _lib.OttoError(f'{what} needs a ROCm device (no CPU fallback)')
-
-
-def _check_1d(name, t, dtype, dev=None):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
-        raise ValueError(f'{name}: expected a contiguous 1-d {dtype} tensor')
-    if dev is not None and t.device != dev:
-        raise ValueError(f'{name} must be on {dev}')
-
-
 def bin_matrix(X, mapper):
     """uint8 [F, n] (feature-major) bins of ``X`` float32 [n, >= F] on the device."""
     import torch
     if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.dtype != torch.float32:
         raise ValueError('X: expected a float32 tensor [n, >= F]')
-    _need_device(X, 'bin_matrix')
+    if X.device.type != 'cuda':
+        raise _lib.OttoError('bin_matrix needs a ROCm device (no CPU fallback)')
     F = mapper.n_features
     if X.shape[1] < F:
         raise ValueError(f'X has {X.shape[1]} columns, the mapper reads {F}')
@@ -141,9 +116,8 @@ def bin_matrix(X, mapper):
     ld = int(X.stride(0)) if n else max(int(X.shape[1]), 1)
     edges, n_edges = mapper.to(X.device)
     bins = torch.empty((F, n), dtype=torch.uint8, device=X.device)
-    with torch.cuda.device(X.device):
-        _lib.check(_lib.lib().otto_gbdt_bin(_ptr(X), ld, n, F, _ptr(edges), _ptr(n_edges), _ptr(bins), _stream(X.device)),
-                   'otto_gbdt_bin')
+    # X goes in as rows with the leading dimension ld (checked above): it may be a column slice of a wider matrix
+    _lib.call('otto_gbdt_bin', X.device, _lib.ptr(X), ld, n, F, edges, n_edges, bins)
     return bins
 
 
@@ -174,10 +148,9 @@ def _tables(sigma, dev):
 
 def _check_queries(score, label, query_off):
     import torch
-    _check_1d('score', score, torch.float64)
-    _need_device(score, 'the ranking objective')
-    _check_1d('label', label, torch.int32, score.device)
-    _check_1d('query_off', query_off, torch.int64, score.device)
+    _lib.need(score, 'score', torch.float64, 1)
+    _lib.need(label, 'label', torch.int32, 1, device=score.device)
+    _lib.need(query_off, 'query_off', torch.int64, 1, device=score.device)
     if label.numel() != score.numel():
         raise ValueError(f'label has {label.numel()} rows, score has {score.numel()}')
     if query_off.numel() < 1:
@@ -193,51 +166,41 @@ def lambdarank_gradients(score, label, query_off, sigma=1.0, truncation_level=30
     dev = score.device
     table, lo, factor, disc = _tables(sigma, dev)
     grad, hess = out if out is not None else (torch.empty_like(score), torch.empty_like(score))
-    _check_1d('grad', grad, torch.float64, dev)
-    _check_1d('hess', hess, torch.float64, dev)
+    _lib.need(grad, 'grad', torch.float64, 1, device=dev)
+    _lib.need(hess, 'hess', torch.float64, 1, device=dev)
     if grad.numel() != score.numel() or hess.numel() != score.numel():
         raise ValueError('out: expected two float64 tensors [n]')
-    with torch.cuda.device(dev):
-        rc = _lib.lib().otto_gbdt_lambdarank(_ptr(score), _ptr(label), _ptr(query_off), query_off.numel() - 1, score.numel(),
-                                             _ptr(table), lo, factor, _ptr(disc), float(sigma), int(truncation_level),
-                                             int(bool(norm)), _ptr(grad), _ptr(hess), _stream(dev))
-    _lib.check(rc, 'otto_gbdt_lambdarank')
+    _lib.call('otto_gbdt_lambdarank', dev, score, label, query_off, query_off.numel() - 1, score.numel(), table, lo, factor, disc,
+              float(sigma), int(truncation_level), int(bool(norm)), grad, hess)
     return grad, hess
 
 
 def quantize_gradients(grad, hess):
     """(gh int32 [n, 2], exp int32 [2]) of SPEC-GBDT's quantisation, on the device."""
     import torch
-    _check_1d('grad', grad, torch.float64)
-    _need_device(grad, 'quantize_gradients')
-    _check_1d('hess', hess, torch.float64, grad.device)
+    _lib.need(grad, 'grad', torch.float64, 1)
+    _lib.need(hess, 'hess', torch.float64, 1, device=grad.device)
     if hess.numel() != grad.numel():
         raise ValueError('grad and hess differ in length')
     gh = torch.empty((grad.numel(), 2), dtype=torch.int32, device=grad.device)
     exp = torch.empty(2, dtype=torch.int32, device=grad.device)
-    with torch.cuda.device(grad.device):
-        _lib.check(_lib.lib().otto_gbdt_quantize(_ptr(grad), _ptr(hess), grad.numel(), _ptr(gh), _ptr(exp), _stream(grad.device)),
-                   'otto_gbdt_quantize')
+    _lib.call('otto_gbdt_quantize', grad.device, grad, hess, grad.numel(), gh, exp)
     return gh, exp
 
 
-def _check_bins(bins):
+def check_bins(bins):
     import torch
-    if not isinstance(bins, torch.Tensor) or bins.dtype != torch.uint8 or bins.dim() != 2 or not bins.is_contiguous():
-        raise ValueError('bins: expected a contiguous uint8 tensor [F, n] (bin_matrix)')
-    _need_device(bins, 'the tree trainer')
+    _lib.need(bins, 'bins (bin_matrix)', torch.uint8, 2)
     return int(bins.shape[0]), int(bins.shape[1])
 
 
 def leaf_histogram(bins, gh, rows):
     """int64 [3, F, 256] = (sum qg, sum qh, rows) of the leaf whose row ids are ``rows`` int32."""
     import torch
-    F, n = _check_bins(bins)
-    _check_1d('rows', rows, torch.int32, bins.device)
+    F, n = check_bins(bins)
+    _lib.need(rows, 'rows', torch.int32, 1, device=bins.device)
     hist = torch.empty((3, F, 256), dtype=torch.int64, device=bins.device)
-    with torch.cuda.device(bins.device):
-        _lib.check(_lib.lib().otto_gbdt_hist(_ptr(bins), n, F, _ptr(gh), _ptr(rows), rows.numel(), _ptr(hist), _stream(bins.device)),
-                   'otto_gbdt_hist')
+    _lib.call('otto_gbdt_hist', bins.device, bins, n, F, gh, rows, rows.numel(), hist)
     return hist
 
 
@@ -248,10 +211,8 @@ def best_split(hist, mapper, exp, min_data_in_leaf, min_sum_hessian_in_leaf, lam
     dev = hist.device
     _, n_edges = mapper.to(dev)
     out = torch.empty(SPLIT_WORDS, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().otto_gbdt_best_split(_ptr(hist), int(hist.shape[1]), _ptr(n_edges), _ptr(exp), int(min_data_in_leaf),
-                                                   float(min_sum_hessian_in_leaf), float(lambda_l2), float(min_gain_to_split),
-                                                   _ptr(out), _stream(dev)), 'otto_gbdt_best_split')
+    _lib.call('otto_gbdt_best_split', dev, hist, int(hist.shape[1]), n_edges, exp, int(min_data_in_leaf),
+              float(min_sum_hessian_in_leaf), float(lambda_l2), float(min_gain_to_split), out)
     w = out.cpu().numpy()
     if not w[0]:
         return None
@@ -262,17 +223,15 @@ def best_split(hist, mapper, exp, min_data_in_leaf, min_sum_hessian_in_leaf, lam
 def partition_rows(bins, rows, feature, bin, default_left):
     """(out int32 like ``rows``: the left rows in their order, then the right rows in theirs; n_left)."""
     import torch
-    F, n = _check_bins(bins)
-    _check_1d('rows', rows, torch.int32, bins.device)
+    F, n = check_bins(bins)
+    _lib.need(rows, 'rows', torch.int32, 1, device=bins.device)
     if not 0 <= int(feature) < F:
         raise ValueError(f'feature {feature} outside [0, {F})')
     out = torch.empty_like(rows)
     n_left = torch.zeros(1, dtype=torch.int64, device=bins.device)
     work = torch.empty(max(rows.numel() // 2048 + 1, 64), dtype=torch.int32, device=bins.device)
-    with torch.cuda.device(bins.device):
-        _lib.check(_lib.lib().otto_gbdt_partition(_ptr(bins), n, int(feature), int(bin), int(bool(default_left)), _ptr(rows),
-                                                  rows.numel(), _ptr(out), _ptr(n_left), _ptr(work), work.numel() * 4,
-                                                  _stream(bins.device)), 'otto_gbdt_partition')
+    _lib.call('otto_gbdt_partition', bins.device, bins, n, int(feature), int(bin), int(bool(default_left)), rows, rows.numel(), out,
+              n_left, work, work.numel() * 4)
     return out, int(n_left.item())
 
 
@@ -305,7 +264,7 @@ def workspace_bytes(n, F, num_leaves):
 def grow_tree(bins, gh, exp, mapper, p, work=None):
     """One leaf-wise tree over all rows: a :class:`BinTree`. ``p``: the resolved parameters (:func:`resolve_params`)."""
     import torch
-    F, n = _check_bins(bins)
+    F, n = check_bins(bins)
     dev = bins.device
     L = int(p['num_leaves'])
     if work is None:
@@ -316,12 +275,10 @@ def grow_tree(bins, gh, exp, mapper, p, work=None):
     dt = np.zeros(L - 1, dtype=np.int8)
     lv, cnt = np.zeros(L, dtype=np.float64), np.zeros(L, dtype=np.int64)
     n_leaves, hist_rows = C.c_int32(0), C.c_int64(0)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().otto_gbdt_grow_tree(
-            _ptr(bins), n, F, _ptr(gh), _ptr(exp), _ptr(n_edges), _np_ptr(mapper.edges), L, int(p['min_data_in_leaf']),
-            float(p['min_sum_hessian_in_leaf']), float(p['lambda_l2']), float(p['min_gain_to_split']), float(p['learning_rate']),
-            C.byref(n_leaves), _np_ptr(sf), _np_ptr(sb), _np_ptr(thr), _np_ptr(dt), _np_ptr(lc), _np_ptr(rc), _np_ptr(gain),
-            _np_ptr(lv), _np_ptr(cnt), C.byref(hist_rows), _ptr(work), work.numel(), _stream(dev)), 'otto_gbdt_grow_tree')
+    # the NumPy arrays are host buffers: the edges the thresholds come from, and the tree the call writes
+    _lib.call('otto_gbdt_grow_tree', dev, bins, n, F, gh, exp, n_edges, mapper.edges, L, int(p['min_data_in_leaf']),
+              float(p['min_sum_hessian_in_leaf']), float(p['lambda_l2']), float(p['min_gain_to_split']), float(p['learning_rate']),
+              C.byref(n_leaves), sf, sb, thr, dt, lc, rc, gain, lv, cnt, C.byref(hist_rows), work, work.numel())
     k = n_leaves.value
     return BinTree(split_feature=sf[:k - 1], split_bin=sb[:k - 1], default_left=((dt[:k - 1] & 2) >> 1).astype(np.int32),
                    left_child=lc[:k - 1], right_child=rc[:k - 1], threshold=thr[:k - 1], decision_type=dt[:k - 1],
@@ -331,16 +288,14 @@ def grow_tree(bins, gh, exp, mapper, p, work=None):
 def add_tree(bins, tree, score, want_leaf=False):
     """``score[r] += leaf_value[leaf(r)]`` by routing the bins through ``tree``; returns leaf(r) int32 [n] if asked."""
     import torch
-    F, n = _check_bins(bins)
-    _check_1d('score', score, torch.float64, bins.device)
+    F, n = check_bins(bins)
+    _lib.need(score, 'score', torch.float64, 1, device=bins.device)
     if score.numel() != n:
         raise ValueError(f'score has {score.numel()} rows, bins has {n}')
     dev = bins.device
     sf, sb, dl, lc, rc, lv = tree.to(dev)
     leaf = torch.empty(n, dtype=torch.int32, device=dev) if want_leaf else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().otto_gbdt_add_tree(_ptr(bins), n, F, tree.n_leaves, _ptr(sf), _ptr(sb), _ptr(dl), _ptr(lc), _ptr(rc),
-                                                 _ptr(lv), _ptr(score), _ptr(leaf), _stream(dev)), 'otto_gbdt_add_tree')
+    _lib.call('otto_gbdt_add_tree', dev, bins, n, F, tree.n_leaves, sf, sb, dl, lc, rc, lv, score, leaf)
     return leaf
 
 
@@ -353,9 +308,7 @@ def ap_at_k(score, label, query_off, k=20):
         raise ValueError(f'k must be in [1, {MAX_QUERY}] (got {k})')
     dev = score.device
     ap = torch.empty(query_off.numel() - 1, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().otto_gbdt_ap_at_k(_ptr(score), _ptr(label), _ptr(query_off), query_off.numel() - 1, score.numel(), k,
-                                                _ptr(ap), _stream(dev)), 'otto_gbdt_ap_at_k')
+    _lib.call('otto_gbdt_ap_at_k', dev, score, label, query_off, query_off.numel() - 1, score.numel(), k, ap)
     return ap
 
 
@@ -454,7 +407,7 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
     also returns the leaf of every (row, tree). Raises ``OttoError`` if not a single tree could be grown."""
     import torch
     p = resolve_params(params)
-    F, n = _check_bins(bins)
+    F, n = check_bins(bins)
     dev = bins.device
     if mapper.n_features != F:
         raise ValueError(f'the mapper has {mapper.n_features} features, bins has {F}')
@@ -462,7 +415,7 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
     _check_queries(score, label, query_off)
     if valid is not None:
         vbins, vlabel, voff = valid
-        if _check_bins(vbins)[0] != F:
+        if check_bins(vbins)[0] != F:
             raise ValueError('the validation bins have another feature count')
         vscore = torch.zeros(vbins.shape[1], dtype=torch.float64, device=dev)
         _check_queries(vscore, vlabel, voff)

@@ -5,8 +5,6 @@ dense candidate arrays ``covisitation.candidates.candidate_lookup`` returns, wit
 ``interaction_features`` returns device tensors; ``to_frame`` lays them out as the reference's feature frame (same column
 names and order, :115-125) for ``DATA/feature_engineering/{train,test}_<type>_interaction_features.pkl``.
 """
-import ctypes as C
-
 import numpy as np
 
 from .. import _lib
@@ -33,22 +31,16 @@ def interaction_features(aid, typ, sess_off, cand, scores, n_aids):
         raise _lib.OttoError('interaction_features needs a ROCm device (no CPU fallback)')
     for name, x, dt in (('aid', aid, torch.int32), ('type', typ, torch.uint8), ('sess_off', sess_off, torch.int64),
                         ('cand', cand, torch.int32), ('scores', scores, torch.float32)):
-        if x.dtype != dt or not x.is_contiguous():
-            raise ValueError(f'{name}: expected contiguous {dt}')
+        _lib.need(x, name, dt, device=dev)
     S, Cn = cand.shape
     if scores.shape != cand.shape or sess_off.numel() != S + 1:
         raise ValueError('cand / scores / sess_off shapes disagree')
-    lib = _lib.lib()
-    ws_b = lib.otto_inter_workspace(int(n_aids))
-    ws = torch.empty(int(ws_b), dtype=torch.uint8, device=dev)
+    ws_b = int(_lib.lib().otto_inter_workspace(int(n_aids)))
+    ws = _lib.workspace(ws_b, dev)
     row = torch.empty((S, Cn, 5), dtype=torch.int16, device=dev)
     sf = torch.empty((S, 10), dtype=torch.float32, device=dev)
     af = torch.empty((int(n_aids), 9), dtype=torch.float32, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        _lib.check(lib.otto_inter_features(p(aid), p(typ), p(sess_off), S, p(cand), p(scores), int(Cn), int(n_aids), p(row), p(sf), p(af),
-                                           p(ws), int(ws_b), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                   'otto_inter_features')
+    _lib.call('otto_inter_features', dev, aid, typ, sess_off, S, cand, scores, int(Cn), int(n_aids), row, sf, af, ws, ws_b)
     return row, sf, af
 
 
@@ -64,21 +56,15 @@ def interaction_features_rows(aid, typ, sess_off, table, n_aids):
     S, R = sess_off.numel() - 1, cand.numel()
     for name, x, dt in (('aid', aid, torch.int32), ('type', typ, torch.uint8), ('sess_off', sess_off, torch.int64),
                         ('candidates', cand, torch.int32), ('candidate_scores', scores, torch.float32), ('row_off', row_off, torch.int64)):
-        if x.dtype != dt or not x.is_contiguous():
-            raise ValueError(f'{name}: expected contiguous {dt}')
+        _lib.need(x, name, dt, device=dev)
     if row_off.numel() != S + 1 or scores.numel() != R:
         raise ValueError('table / sess_off shapes disagree')
-    lib = _lib.lib()
-    ws_b = lib.otto_inter_workspace(int(n_aids))
-    ws = torch.empty(int(ws_b), dtype=torch.uint8, device=dev)
+    ws_b = int(_lib.lib().otto_inter_workspace(int(n_aids)))
+    ws = _lib.workspace(ws_b, dev)
     row = torch.empty((max(R, 1), 5), dtype=torch.int16, device=dev)
     sf = torch.empty((S, 10), dtype=torch.float32, device=dev)
     af = torch.empty((int(n_aids), 9), dtype=torch.float32, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else C.c_void_p(0)
-    with torch.cuda.device(dev):
-        _lib.check(lib.otto_inter_features_rows(p(aid), p(typ), p(sess_off), S, p(row_off), p(cand), p(scores), int(n_aids), C.c_void_p(row.data_ptr()),
-                                                p(sf), p(af), p(ws), int(ws_b), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                   'otto_inter_features_rows')
+    _lib.call('otto_inter_features_rows', dev, aid, typ, sess_off, S, row_off, cand, scores, int(n_aids), row, sf, af, ws, ws_b)
     return row[:R], sf, af
 
 

@@ -84,10 +84,7 @@ def main():
     center, scale = blend.center_scale(nv, stats)
     out = torch.empty(n, dtype=torch.float32, device=dev)
     from otto_amd import _lib
-    from otto_amd.ranker.forest import _ptr, _stream
-    lib = _lib.lib()
-    ms, all_ms = _time(lambda: _lib.check(lib.otto_blend_scale(_ptr(x), n, center, scale, _ptr(out), _stream(dev)), 'scale'),
-                       args.warmup, args.repeats)
+    ms, all_ms = _time(lambda: _lib.call('otto_blend_scale', dev, x, n, center, scale, out), args.warmup, args.repeats)
     res['scale'] = {'ms': ms, 'all_ms': all_ms, 'must_move_bytes': 12 * n, 'share_of_hbm_peak': 12 * n / (ms * 1e-3) / HBM_PEAK}
     del out
 
