@@ -1112,7 +1112,7 @@ struct ReduceArgs {
     int hot_ok;                    // GROUP_TYPE: every kind ranks a key made of ONE click record below every other key (see k_reduce)
     int debug_skip;                // diagnostics only (wrong results): 1 skip gather, 2 skip top-k, 4 skip table init, 8 skip inserts
 #ifdef OTTO_PHASE_PROF
-    unsigned long long* prof;      // [16] summed shader-clock ticks of thread 0 per phase + path counters
+    unsigned long long* prof;      // [24] summed shader-clock ticks of thread 0 per phase + path counters
 #endif
 };
 
@@ -1258,15 +1258,25 @@ __device__ __forceinline__ void for_each_record_batch(const uint64_t* sorted_des
 // d0p: the caller already holds the wave's first 64 descriptors (requested while it was busy with something else)
 template <int NW, int GATHER_U, bool NEED_SL, typename FB>
 __device__ __forceinline__ void for_each_record_seg(const uint64_t* sorted_desc, const uint32_t* rec, uint64_t r0, uint64_t r1,
-                                                    int wid, uint8_t* s_seg, FB fb, const uint64_t* d0p = nullptr) {
+                                                    int wid, uint8_t* s_seg, FB fb, const uint64_t* d0p = nullptr,
+                                                    unsigned long long* pw = nullptr) {
     const unsigned lane = lane_id();
     const uint32_t g = lane >> 3, gl4 = (lane & 7u) << 2;
     if (r0 >= r1) return;
+#ifdef OTTO_PHASE_PROF
+    unsigned long long pw_t = clock64();   // pw[0]: wait for the item's first descriptors, pw[1]: for its first records (both inside p2)
+#else
+    (void)pw;
+#endif
     auto load_desc = [&](uint64_t cb) {
         const uint64_t mine = cb + (uint64_t)lane * NW + wid;
         return mine < r1 ? sorted_desc[mine] : 0ull;
     };
     uint64_t d = d0p ? *d0p : load_desc(r0);
+#ifdef OTTO_PHASE_PROF
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (pw) { const unsigned long long _t = clock64(); pw[0] += _t - pw_t; }
+#endif
     for (uint64_t cb = r0; cb < r1; cb += (uint64_t)NW * 64) {
         const uint64_t cbn = cb + (uint64_t)NW * 64;
         const uint64_t dn = cbn < r1 ? load_desc(cbn) : 0ull;              // next descriptors in flight
@@ -1314,6 +1324,13 @@ __device__ __forceinline__ void for_each_record_seg(const uint64_t* sorted_desc,
             }
         };
         if (nstep > 0) issue(0, rcA, slA, okA);
+#ifdef OTTO_PHASE_PROF
+        if (pw && cb == r0) {
+            pw_t = clock64();
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            pw[1] += clock64() - pw_t;
+        }
+#endif
         for (int t = 0; t < nstep; t += 2 * GATHER_U) {
             const bool hasB = t + GATHER_U < nstep;
             if (hasB) issue(t + GATHER_U, rcB, slB, okB);
@@ -1815,7 +1832,11 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
     __shared__ uint16_t s_occ[OCAP];
     __shared__ uint32_t s_wcnt[NW];         // keys each wave entered into the table (published after the insert phase)
     __shared__ uint32_t s_hcnt[NW];         // of them, the "heavy" ones (more than one click record), moved to the front of the wave's region
-    __shared__ uint16_t s_lbi[NW > 1 ? PKD : 1][NW > 1 ? THREADS : 1];         // slot of every lane's best key per kind (0xFFFF: none)
+    // INWAVE: P1 forms the group bests of P2 inside the waves (packed layouts). The wide layout (one list entry per lane at most
+    // in the common case) keeps round 4's form: every lane publishes the SLOT of its best key and the wave of kind j builds the
+    // group bests across the waves -- in-wave groups of adjacent lanes left lower threshold guesses there (profiles/round5)
+    constexpr bool INWAVE = PACKED;
+    __shared__ uint16_t s_lbi[(NW > 1 && !INWAVE) ? PKD : 1][(NW > 1 && !INWAVE) ? THREADS : 1];   // !INWAVE: slot of every lane's best key per kind (0xFFFF: none)
     __shared__ uint64_t s_exw[(NW > 1 || BOUND) ? PKD : 1][(NW > 1 || BOUND) ? EXCAP : 1];   // candidates above the threshold / rank broadcast
     __shared__ uint16_t s_cand[BOUND ? CCAP : 1];                               // BOUND: slots of the candidates
     __shared__ uint32_t s_exy[1][(NW > 1 && WIDE) ? EXCAP : 1];
@@ -1832,8 +1853,21 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
 
     const int wid = threadIdx.x >> 6;
     const unsigned lane = lane_id();
+    // HAND-OVER WARM-UP (M bin). The single-wave selection phases (SH, P2) run on waves 0 .. nk - 1 (nk <= PKD <= 3 < NW) while
+    // the other waves wait at the barrier. In the M kernel, whose phase profile shows an exposed wait for the first descriptors
+    // and records of every item (profiles/round5), the LAST wave uses that time to touch the next item's lines (warm_next).
+    //   - the item pipeline (dequeue, item word, ranges, hand-over) lives in lane 0 of that wave, which never selects: the
+    //     next item's descriptor is in its registers, and the wait for the ranges is its own, not a selecting wave's;
+    //   - "am I a selecting wave" is tested on a SCALAR copy of the wave index, so the selecting and the other waves are two
+    //     separate control paths.
+    // The heavy kernels keep thread 0 and no warm-up: their gather waits are under 2 % of the kernel, the 1024-thread ones hold
+    // the next bucket round in registers (PREF), and touching the next bucket from the idle wave of the 512-thread kernel cost
+    // 30 - 60 bytes of scratch and 0.17 ms (profiles/round5/README.md).
+    constexpr bool HANDOVER = THREADS == M_THREADS;
+    const int swid = HANDOVER ? __builtin_amdgcn_readfirstlane(wid) : wid;
+    const bool pipe = threadIdx.x == (HANDOVER ? (NW - 1) * 64 : 0);
 #ifdef OTTO_PHASE_PROF
-    unsigned long long ph[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ph_t = clock64();
+    unsigned long long ph[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ph_t = clock64();
 #endif
 
     // ---- item pipeline: (index, item word, run range, bucket range) of the NEXT item are fetched while the
@@ -1860,7 +1894,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
         }
     };
     ItemDesc cur, nx;
-    uint32_t idx_next = 0, idx_far = 0;   // DYNAMIC, thread 0: dequeued indices of the next two items
+    uint32_t idx_next = 0, idx_far = 0;   // DYNAMIC, pipeline lane: dequeued indices of the next two items to fetch
     // Items are reserved DQ at a time (same-address atomics retire at ~90 M/s: one per item would cost 5 ms for the M
     // bin alone); the next chunk is requested when the current one is opened, so its latency is never waited for.
     constexpr uint32_t DQ = THREADS == S_THREADS ? 16 : 4;      // (1.1 M one-wave items: 70 k counter bumps)
@@ -1875,7 +1909,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
         return r;
     };
     if (DYNAMIC) {
-        if (threadIdx.x == 0) {
+        if (pipe) {
             pool = atomicAdd(a.work_counter, 2 * DQ);
             pool_end = pool + DQ;
             pool_next = pool + DQ;
@@ -1940,7 +1974,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
         const uint32_t it = cur.it;
         // stage 1 of the next item
         if (DYNAMIC) {
-            if (threadIdx.x == 0) fetch_item(idx_next, nx);
+            if (pipe) fetch_item(idx_next, nx);
 #ifdef OTTO_PHASE_PROF
             if (threadIdx.x == 0) { const unsigned long long _t = clock64(); ph[13] += _t - ph_t; }   // part of p1: next item's dependent index -> item loads
 #endif
@@ -2168,6 +2202,42 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
                 kstore(best, &a.part_w[o], &a.part_y[o]);
             }
         };
+        // NEXT-ITEM WARM-UP (HANDOVER kernels), run by the last wave (which never selects, and whose lane 0 holds the next item's
+        // descriptor in registers: no LDS, no barrier) while waves 0 .. nk - 1 run a single-wave selection phase. The next item
+        // starts with two dependent memory round trips: run descriptors, then records. This wave walks that chain now -- it also
+        // absorbs the wait for the next item's ranges -- and drops what it loads (a real load; the value is consumed by an
+        // empty asm), so the working waves' own loads, unchanged, find the lines in L2. It touches the item's first WARM_B * 64
+        // run descriptors, and of each of those runs the first and the last record (a run is at most 32 records: two 128-byte
+        // lines). Descriptors inside [rb, re) only, records inside their run only; tw is not touched. More runs than that:
+        // the rest is not warmed.
+        constexpr int WARM_B = 4;
+        auto warm_next = [&]() {
+            if (!HANDOVER) return;
+            // lane 0's value in every lane
+            auto bc = [&](uint64_t v) -> uint64_t {
+                return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
+                       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+            };
+            if ((uint32_t)__builtin_amdgcn_readfirstlane((int)nx.it) == 0xFFFFFFFFu) return;
+            const uint64_t rb = bc(nx.rb), re = bc(nx.re);
+            uint64_t d[WARM_B];
+#pragma unroll
+            for (int b = 0; b < WARM_B; ++b) {
+                const uint64_t r = rb + (uint64_t)(b * 64 + (int)lane);
+                d[b] = r < re ? a.sorted_desc[r] : 0ull;
+            }
+            uint32_t acc = 0;
+#pragma unroll
+            for (int b = 0; b < WARM_B; ++b) {
+                const uint32_t len = desc_len(d[b]);
+                if (len) {
+                    const uint64_t s0 = desc_slot(d[b]);
+                    acc |= a.rec[s0] | a.rec[s0 + len - 1u];
+                }
+            }
+            asm volatile("" :: "v"(acc));
+        };
+        const int nsel = a.nk < PKD ? a.nk : PKD;                 // waves 0 .. nsel - 1 select
         if (DBG && (a.debug_skip & 1)) {
         } else if (lgR > 0 && a.pstart) {
             // heavy aid, records already bucketed by hash partition: contiguous coalesced reads
@@ -2210,12 +2280,16 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
                     e[u] = (GROUP == OTTO_COVIS_GROUP_TIME && __builtin_amdgcn_inverse_ballot_w64(okb[u])) ? a.tw[sl[NEED_SL ? u : 0]] : 0u;
                 }
                 insert_batch(std::integral_constant<int, GU>{}, rc, okb, e);
-            });
+            }
+#ifdef OTTO_PHASE_PROF
+            , nullptr, threadIdx.x == 0 ? &ph[15] : nullptr
+#endif
+            );
         }
         if (NW > 1 && lane == 0) s_wcnt[NW > 1 ? wid : 0] = wc;
         pre_valid = false;                     // consumed (or not applicable); set again by prefetch_next below
         // stage 2 of the next item (its item word has long arrived)
-        if (!DYNAMIC || threadIdx.x == 0) fetch_ranges(nx);
+        if (!DYNAMIC || pipe) fetch_ranges(nx);
         OTTO_PH(2);
         __syncthreads();
         OTTO_PH(3);
@@ -2717,8 +2791,11 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
 #ifdef OTTO_PHASE_PROF
                     if (threadIdx.x == 0) ph[14]++;
 #endif
-                    if (wid < a.nk && wid < PKD) {
-                        const int j = wid;
+#ifdef OTTO_PHASE_PROF
+                    const unsigned long long sel_t = clock64();
+#endif
+                    if (swid < nsel) {
+                        const int j = swid;
                         const uint32_t c0 = a.coef[j][0], c1 = a.coef[j][1], c2 = a.coef[j][2];
                         K keys[SHR], lbk;
                         kclear(lbk);
@@ -2762,7 +2839,12 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
                         wave_lds_sync();
                         if (n > (uint32_t)EXCAP) wave_exact_topk(j);
                         else finish_list(j, n, false);
+                    } else if (swid == NW - 1) {
+                        warm_next();
                     }
+#ifdef OTTO_PHASE_PROF
+                    if (threadIdx.x == 0) ph[18] += clock64() - sel_t;   // inside p7: the single-wave selection
+#endif
                     fast_done = true;
                 }
             }
@@ -2772,7 +2854,8 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
                 if (j < a.nk && !kvalid(guess[j])) gv = false;
             if (gv) {                                    // uniform: every thread loaded the same words
                 if (threadIdx.x < PK) s_nex[threadIdx.x] = 0;
-                if (threadIdx.x == 0) { s_more = 0; if (WARM) s_nxt = nx; }
+                if (threadIdx.x == 0) s_more = 0;
+                if (WARM && pipe) s_nxt = nx;
                 __syncthreads();
                 // the next item's bucket is touched now, one 64-byte line per thread, so that the prefetch below (which must wait
                 // for the last walk over the table: it holds BU registers per lane) finds it in L2 instead of HBM -- the records
@@ -2803,19 +2886,29 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
                 if (threadIdx.x == 0) { ph[8]++; if (ok) ph[9]++; else if (s_more) ph[11]++; else ph[10]++; }
 #endif
                 if (ok) {
+#ifdef OTTO_PHASE_PROF
+                    const unsigned long long sel_t = clock64();
+#endif
                     if (wid < a.nk && wid < PKD) finish_list(wid, s_nex[wid], true);
+#ifdef OTTO_PHASE_PROF
+                    if (threadIdx.x == 0) ph[18] += clock64() - sel_t;   // inside p7: finish_list of the guess path
+#endif
                     fast_done = true;
                 }
                 __syncthreads();                         // lists are reused by the two-pass path / the next item
             }
             OTTO_PH(7);
             if (!fast_done) {
-                // ---- P1 every lane: its best key per kind -> the key's SLOT to LDS. P2 wave j: best of each group of NW
-                //      lanes, one 64-lane sort, k-th = threshold of kind j (a lower bound of the k-th best key: the group
-                //      bests are a subset). P3 every lane: keys at or above the threshold -> candidate list of the kind
-                //      (about k of them). P4 wave j: rank the list. ----
+                // ---- P1 every lane: its best key per kind; INWAVE: every wave reduces them over groups of NW adjacent lanes (cross-
+                //      lane maxima) and stores its 64 / NW group bests as KEYS: 64 per kind in all (else: the slot of every lane's
+                //      best goes to s_lbi and wave j forms the best of lane l of all waves). P2 wave j: the k-th best of the
+                //      64 group bests of kind j, by counting = threshold. The group bests are 64 keys of the table, and the
+                //      k-th best of ANY subset of the keys is at most the k-th best key, so the threshold (and the rank-31 key
+                //      left in tau) is a lower bound whatever lanes form a group: P3 collects every key at or above it, P4
+                //      ranks them, and the rows do not depend on the grouping. P3 every lane: keys at or above the threshold
+                //      -> candidate list of the kind (about k of them). P4 wave j: rank the list. ----
                 K lb[PKD];
-                int bi[PKD];
+                int bi[PKD];                             // !INWAVE: slot of lb
                 // the keys of the lane's first NCK entries stay in registers for P3 (the dense list gives a lane 2 - 4 entries
                 // in the common case: P3 then recomputes nothing)
                 constexpr int NCK = (PACKED && THREADS <= 512) ? 3 : 0;
@@ -2845,8 +2938,22 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
                         if (kbetter(kk[j], lb[j])) { lb[j] = kk[j]; bi[j] = sl; }
                 }
 #pragma unroll
-                for (int j = 0; j < PKD; ++j)
-                    if (j < a.nk) s_lbi[j][NW > 1 ? threadIdx.x : 0] = (uint16_t)bi[j];
+                for (int j = 0; j < PKD; ++j) {
+                    if (!INWAVE) {
+                        if (j < a.nk) s_lbi[!INWAVE ? j : 0][(NW > 1 && !INWAVE) ? threadIdx.x : 0] = (uint16_t)bi[j];
+                        continue;
+                    }
+                    K g = lb[j];
+#pragma unroll
+                    for (int m = 1; m < NW; m <<= 1) {
+                        const K o = kshfl_xor(g, m);
+                        if (kbetter(o, g)) g = o;
+                    }
+                    if (j < a.nk && (lane & (NW - 1)) == 0) {
+                        const int gi = wid * (64 / NW) + (int)(lane / NW);
+                        kstore(g, &s_exw[j][gi], &s_exy[0][WIDE ? gi : 0]);
+                    }
+                }
                 if (threadIdx.x < PK) s_nex[threadIdx.x] = 0;
                 if (threadIdx.x == 0) s_more = 0;
                 __syncthreads();
@@ -2864,36 +2971,43 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
                 break;
                 }
                 OTTO_PH(4);
-                if (wid < a.nk && wid < PKD) {
-                    K gb;
-                    kclear(gb);
-                    const uint32_t c0 = a.coef[wid][0], c1 = a.coef[wid][1], c2 = a.coef[wid][2];
-#pragma unroll
-                    for (int q = 0; q < NW; ++q) {
-                        const uint32_t sl = s_lbi[wid][NW > 1 ? q * 64 + lane : 0];
-                        if (sl != 0xFFFFu) {
-                            const K o = slot_key1((int)sl, c0, c1, c2);
-                            if (kbetter(o, gb)) gb = o;
-                        }
-                    }
+                if (swid >= nsel) {
+                    if (swid == NW - 1) warm_next();
+                } else {
+                    const int j = swid;
                     // k-th best of the 64 group bests by counting (rank = number of better keys, read back with uniform
                     // addresses: 64 independent iterations instead of the 21 dependent stages of a sorting network)
-                    kstore(gb, &s_exw[wid][lane], &s_exy[0][WIDE ? lane : 0]);
-                    wave_lds_sync();
+                    K gb;
+                    if (INWAVE) {
+                        kload(gb, s_exw[j][lane], s_exy[0][WIDE ? lane : 0]);
+                    } else {
+                        kclear(gb);
+                        const uint32_t c0 = a.coef[j][0], c1 = a.coef[j][1], c2 = a.coef[j][2];
+#pragma unroll
+                        for (int q = 0; q < NW; ++q) {
+                            const uint32_t sl = s_lbi[!INWAVE ? j : 0][(NW > 1 && !INWAVE) ? q * 64 + lane : 0];
+                            if (sl != 0xFFFFu) {
+                                const K o = slot_key1((int)sl, c0, c1, c2);
+                                if (kbetter(o, gb)) gb = o;
+                            }
+                        }
+                        kstore(gb, &s_exw[j][lane], &s_exy[0][WIDE ? lane : 0]);
+                        wave_lds_sync();
+                    }
                     uint32_t rank = 0;
 #pragma unroll 8
                     for (int i = 0; i < 64; ++i) {
                         K o;
-                        kload(o, s_exw[wid][i], s_exy[0][WIDE ? i : 0]);
+                        kload(o, s_exw[j][i], s_exy[0][WIDE ? i : 0]);
                         kcount_better(rank, o, gb);
                     }
                     const uint64_t mk = __ballot(kvalid(gb) && rank == (uint32_t)(a.k - 1));
                     K thr;
                     kclear(thr);
                     if (mk) thr = kshfl(gb, __ffsll((unsigned long long)mk) - 1);
-                    if (lane == 0) kstore(thr, &s_thrw[wid], &s_thry[wid]);
+                    if (lane == 0) kstore(thr, &s_thrw[j], &s_thry[j]);
                     // rank 31: a lower bound of the partition's 32nd best key = the guess for the aid's other partitions
-                    if (use_guess && kvalid(gb) && rank == 31u) ktau_store(gb, a.tau_w, a.tau_y, (size_t)wid * a.n_aids + x);
+                    if (use_guess && kvalid(gb) && rank == 31u) ktau_store(gb, a.tau_w, a.tau_y, (size_t)j * a.n_aids + x);
                     wave_lds_sync();
                 }
                 OTTO_PH(5);
@@ -2916,7 +3030,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
                     for (int j = 0; j < PKD; ++j)
                         if (j < a.nk && kvalid(kk[j]) && !kbetter(thr[j], kk[j])) append(j, kk[j]);
                 }
-                if (PREF && !pre_issued && threadIdx.x == 0) s_nxt = nx;
+                if (PREF && !pre_issued && pipe) s_nxt = nx;
                 __syncthreads();
                 if (!pre_issued) prefetch_next();
                 OTTO_PH(6);
@@ -2929,6 +3043,9 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
         }
         // ---- clear the table for the next item: through the list when it is complete ----
         __syncthreads();
+#ifdef OTTO_PHASE_PROF
+        const unsigned long long clr_t = clock64();
+#endif
         if (!(DBG && (a.debug_skip & 4))) {
             if (dense) {
                 for (uint32_t idx = lane; idx < nocc; idx += 64u) clear_slot((int)s_occ[NW > 1 ? wid * RCAP + idx : 0]);
@@ -2937,12 +3054,15 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
             }
         }
         if (threadIdx.x == 0) s_ovf = 0;
+#ifdef OTTO_PHASE_PROF
+        if (threadIdx.x == 0) ph[17] += clock64() - clr_t;                     // inside p0: the clear itself (the rest of p0: barriers + hand-over)
+#endif
         }   // multi-wave bins
 
         // ---- hand the prefetched next item over ----
         if (DYNAMIC) {
             __syncthreads();                       // every thread is done with s_cur's consumers and the table
-            if (threadIdx.x == 0) {
+            if (pipe) {
                 s_cur = nx;
                 idx_next = idx_far;                                   // dequeued one iteration ago
                 idx_far = take();                                     // consumed one iteration from now
@@ -2954,7 +3074,7 @@ __global__ __launch_bounds__(THREADS, MINW) void k_reduce(ReduceArgs a) {
     }
 #ifdef OTTO_PHASE_PROF
     if (threadIdx.x == 0 && a.prof)
-        for (int i = 0; i < 16; ++i) atomicAdd(&a.prof[i], ph[i]);
+        for (int i = 0; i < 24; ++i) atomicAdd(&a.prof[i], ph[i]);
 #endif
 }
 
@@ -3753,17 +3873,18 @@ static int launch_reduce(otto_covis_ctx* c, ReduceArgs a, int bin, hipStream_t s
     // diagnostic build only: per-launch phase shares (shader-clock ticks of thread 0 of every workgroup) + wall time
     static unsigned long long* d_prof = nullptr;
     static hipEvent_t pe0 = nullptr, pe1 = nullptr;
-    if (!d_prof) { OTTO_HIP(hipMalloc(&d_prof, 128)); OTTO_HIP(hipEventCreate(&pe0)); OTTO_HIP(hipEventCreate(&pe1)); }
+    if (!d_prof) { OTTO_HIP(hipMalloc(&d_prof, 192)); OTTO_HIP(hipEventCreate(&pe0)); OTTO_HIP(hipEventCreate(&pe1)); }
     a.prof = d_prof;
-    auto prof_begin = [&]() { (void)hipMemsetAsync(d_prof, 0, 128, s); (void)hipEventRecord(pe0, s); };
+    auto prof_begin = [&]() { (void)hipMemsetAsync(d_prof, 0, 192, s); (void)hipEventRecord(pe0, s); };
     auto prof_end = [&](const char* tag, uint32_t n_work) {
-        unsigned long long h[16];
-        (void)hipEventRecord(pe1, s); (void)hipStreamSynchronize(s); (void)hipMemcpy(h, d_prof, 128, hipMemcpyDeviceToHost);
+        unsigned long long h[24];
+        (void)hipEventRecord(pe1, s); (void)hipStreamSynchronize(s); (void)hipMemcpy(h, d_prof, 192, hipMemcpyDeviceToHost);
         float ms = 0.f; (void)hipEventElapsedTime(&ms, pe0, pe1);
         unsigned long long tot = 0; for (int i = 0; i < 8; ++i) tot += h[i];
         fprintf(stderr, "[phase-prof] %s items %u  %.3f ms:", tag, n_work, ms);
         for (int i = 0; i < 8; ++i) fprintf(stderr, " p%d %.1f%%", i, tot ? 100.0 * h[i] / tot : 0.0);
-        fprintf(stderr, "  (ticks %llu) guess: tried %llu ok %llu toofew %llu overflow %llu | record wait (not in p2): %.1f%%, next-item fetch (in p1): %.1f%% of the ticks | single-wave selection of few heavy keys: %llu items\n", tot, h[8], h[9], h[10], h[11], tot ? 100.0 * (double)h[12] / tot : 0.0, tot ? 100.0 * (double)h[13] / tot : 0.0, h[14]);
+        fprintf(stderr, "  (ticks %llu) guess: tried %llu ok %llu toofew %llu overflow %llu | record wait (not in p2): %.1f%%, next-item fetch (in p1): %.1f%% of the ticks | single-wave selection of few heavy keys: %llu items | gather: descriptor wait %.1f%%, first-record wait %.1f%% (both in p2) | clear %.1f%% (in p0) | single-wave select / finish_list %.1f%% (in p7)\n", tot, h[8], h[9], h[10], h[11], tot ? 100.0 * (double)h[12] / tot : 0.0, tot ? 100.0 * (double)h[13] / tot : 0.0, h[14],
+                tot ? 100.0 * (double)h[15] / tot : 0.0, tot ? 100.0 * (double)h[16] / tot : 0.0, tot ? 100.0 * (double)h[17] / tot : 0.0, tot ? 100.0 * (double)h[18] / tot : 0.0);
     };
 #else
     auto prof_begin = [&]() {};
