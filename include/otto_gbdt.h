@@ -59,6 +59,34 @@
  *
  * AP@k of a query, in the same order: sum_{r<k, label_r>0} hits_through_r/(r+1) / min(n_pos, k), float64 in rank
  * order; -1 for a query without a positive.
+ *
+ * Sampling (stochastic gradient boosting as LightGBM v3 defines it: bagging_fraction, bagging_freq, feature_fraction).
+ * The draws come from a pinned counter-based sampler, not from LightGBM's RNG: the counts, the redraw schedule and the
+ * determinism are LightGBM's, the sets are not.
+ *     mix(s, i):  z = s + (i + 1) * 0x9E3779B97F4A7C15      (mod 2^64)
+ *                 z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *                 z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *                 return z ^ (z >> 31)
+ * (the row key of otto_folds.h; a bijection in i for a fixed s).
+ * Row bag. Active iff bagging_freq = k > 0 and bagging_fraction = p < 1 (bagging_freq = 0: no bagging). At a 0-based
+ * iteration it with it % k == 0 a new bag is drawn with draw index d = it / k, otherwise the previous bag is kept.
+ * m = int(p * n): the float64 product, truncated (LightGBM's bag_data_cnt); m >= 1 is required, the host refuses
+ * anything else before a launch. key(r) = mix(mix(bagging_seed, 2*d), r), r in [0, n): distinct rows have distinct
+ * keys. The bag is the m rows with the smallest keys, as an ascending int32 row list: it depends on no grid, workgroup
+ * size or order of atomics. The objective and the quantisation run over all n rows, unchanged. The tree is grown on
+ * the bag only: the root's row list is the bag; every histogram sum, every count, min_data_in_leaf,
+ * min_sum_hessian_in_leaf, leaf_value and leaf_count are over in-bag rows; hist_rows counts in-bag rows. After the
+ * tree, score[r] += leaf_value[leaf(r)] for every row, out-of-bag rows included (otto_gbdt_add_tree routes all rows).
+ * Feature sample. Active iff feature_fraction = q < 1; drawn for every tree, over all F features (one without an edge
+ * counts too). n_used = max(min(2, F), floor(F*q + 0.5)). fkey(f) = mix(mix(feature_fraction_seed, 2*it + 1), f). The
+ * tree of iteration it may split only on the n_used features with the smallest keys, kept as an ascending int32 list
+ * (made on the host: F <= 128). The tie order of the split search ("smallest f") is over the listed features; the
+ * parent sums of d_split are those of the FIRST LISTED feature, not of feature 0; the histogram planes of the other
+ * features are zero.
+ * Seeds. bagging_seed defaults to 3, feature_fraction_seed to 2 (LightGBM's defaults). `seed` is ignored: LightGBM
+ * would derive the two seeds from it, and that derivation is not reproduced.
+ * Refused: feature_fraction_bynode < 1, pos_bagging_fraction / neg_bagging_fraction != 1, bagging_fraction or
+ * feature_fraction outside (0, 1], bagging_freq < 0.
  */
 #ifndef OTTO_GBDT_H
 #define OTTO_GBDT_H
@@ -101,6 +129,25 @@ int otto_gbdt_best_split(const int64_t* d_hist, int32_t F, const int32_t* d_n_ed
                          int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2, double min_gain_to_split,
                          int64_t* d_split, void* stream);
 
+/* The two calls above over a feature list: d_features int32 [n_used] on the device, strictly ascending inside [0, F),
+ * 1 <= n_used <= F (copied to the host and checked there: one synchronisation; OTTO_EINVAL otherwise). The histogram
+ * fills the listed features' planes and leaves the others zero; the split search walks the listed features only and takes
+ * the parent sums from the first of them. d_features == NULL (n_used ignored) is otto_gbdt_hist / otto_gbdt_best_split. */
+int otto_gbdt_hist_features(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_rows, int64_t n_rows,
+                            const int32_t* d_features, int32_t n_used, int64_t* d_hist, void* stream);
+int otto_gbdt_best_split_features(const int64_t* d_hist, int32_t F, const int32_t* d_n_edges, const int32_t* d_exp,
+                                  int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2,
+                                  double min_gain_to_split, const int32_t* d_features, int32_t n_used, int64_t* d_split,
+                                  void* stream);
+
+/* The row bag: d_rows_out int32 receives, ascending, the m rows of [0, n) with the smallest mix(seed, r); seed is the
+ * already mixed mix(bagging_seed, 2*d). 1 <= m <= n < 2^31. out_rows: the row ids d_rows_out has room for; out_rows < m
+ * or a d_work below otto_gbdt_bag_workspace_bytes(n) (0 for a refused n) returns OTTO_EINVAL before anything is launched.
+ * The device checks once more that exactly m rows pass and writes nothing at or behind d_rows_out[out_rows]. */
+int64_t otto_gbdt_bag_workspace_bytes(int64_t n);
+int otto_gbdt_bag(int64_t n, int64_t m, uint64_t seed, int32_t* d_rows_out, int64_t out_rows, void* d_work, int64_t work_bytes,
+                  void* stream);
+
 /* d_out int32 [n_rows]: the rows that go left (bin <= bin, or bin 255 when default_left) in their order, then the
  * others in theirs; d_n_left int64 [1]. d_out must not overlap d_rows. */
 int otto_gbdt_partition(const uint8_t* d_bins, int64_t n, int32_t feature, int32_t bin, int32_t default_left,
@@ -129,6 +176,21 @@ int otto_gbdt_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, const int32
                         int8_t* h_decision_type, int32_t* h_left_child, int32_t* h_right_child, double* h_split_gain,
                         double* h_leaf_value, int64_t* h_leaf_count, int64_t* h_hist_rows, void* d_work, int64_t work_bytes,
                         void* stream);
+
+/* The same tree grown on a row bag and a feature list (SPEC-GBDT, Sampling). d_bag int32 [n_bag] on the device,
+ * 1 <= n_bag <= n: the root's row list. Only the range of its entries is checked (one outside [0, n) is skipped and the
+ * call returns OTTO_EINVAL, as for d_rows). That the ids ascend and that none occurs twice is the caller's
+ * responsibility, as it is for d_rows of otto_gbdt_hist: otto_gbdt_bag writes such a list; a row listed twice is counted
+ * twice, and an order other than ascending only costs the histogram its coalesced loads. NULL: all n rows. d_features / n_used as for otto_gbdt_hist_features; NULL: every feature. NULL / NULL is
+ * otto_gbdt_grow_tree. h_leaf_count and *h_hist_rows count in-bag rows. d_work as for otto_gbdt_grow_tree. */
+int otto_gbdt_grow_tree_sampled(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_exp,
+                                const int32_t* d_n_edges, const float* h_edges, int32_t num_leaves, int64_t min_data_in_leaf,
+                                double min_sum_hessian_in_leaf, double lambda_l2, double min_gain_to_split, double learning_rate,
+                                const int32_t* d_bag, int64_t n_bag, const int32_t* d_features, int32_t n_used,
+                                int32_t* h_n_leaves, int32_t* h_split_feature, int32_t* h_split_bin, double* h_threshold,
+                                int8_t* h_decision_type, int32_t* h_left_child, int32_t* h_right_child, double* h_split_gain,
+                                double* h_leaf_value, int64_t* h_leaf_count, int64_t* h_hist_rows, void* d_work,
+                                int64_t work_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -207,6 +207,13 @@ SIGNATURES = {
     'otto_gbdt_ap_at_k': (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'otto_gbdt_grow_tree': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, C.c_double, C.c_double, C.c_double, C.c_double,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'otto_gbdt_hist_features': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp]),
+    'otto_gbdt_best_split_features': (_i32, [_vp, _i32, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, _vp, _i32, _vp, _vp]),
+    'otto_gbdt_bag_workspace_bytes': (_i64, [_i64]),
+    'otto_gbdt_bag': (_i32, [_i64, _i64, C.c_uint64, _vp, _i64, _vp, _i64, _vp]),
+    'otto_gbdt_grow_tree_sampled': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, C.c_double, C.c_double, C.c_double,
+                                           C.c_double, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _i64, _vp]),
     # include/otto_folds.h
     'otto_folds_kfold_workspace': (_i64, [_i64]),
     'otto_folds_group_kfold': (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, C.POINTER(C.c_float), _vp, _i64, _vp]),

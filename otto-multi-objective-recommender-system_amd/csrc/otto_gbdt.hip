@@ -20,9 +20,19 @@
 //   k_part_count, k_part_scan, k_part_scatter   stable partition of a leaf's row list: left rows per 2048-row block, one
 //                  workgroup's exclusive scan of those counts, then the scatter.
 //   k_add_tree     one lane per row walks the tree over the bins; bounded, range-checked.
+//   k_bag_hist, k_bag_pick   the row bag: radix select of the m-th smallest key among all n rows, 8 digits of 8 bits from
+//                  the top. A pass recomputes every key from its row index (no key array, nothing read from memory) and
+//                  counts the digit of the keys that carry the prefix found so far: wave-private LDS histograms, merged
+//                  once per workgroup, one integer global atomic per touched bin; one wave picks the digit.
+//   k_bag_count, device_scan (scan.h), k_bag_emit   every wave owns a contiguous run of rows: kept rows (key <= threshold)
+//                  per wave, an exclusive scan of the workgroups' sums, then the row ids by ballot rank behind the wave's
+//                  base: ascending ids, contiguous writes, every write checked against the caller's buffer.
+//   k_hist<true>, k_best_split<true>   the same kernels over an ascending feature list (the per-tree feature sample): a
+//                  workgroup's up to 8 list entries are wave-uniform; sums land at the original feature's planes.
 // Host: otto_gbdt_grow_tree drives the leaf-wise loop: one small device-to-host copy per split.
 #include "common.h"
 #include "wave.h"
+#include "scan.h"
 #include "../../include/otto_covis.h"
 #include "../../include/otto_forest.h"
 #include "../../include/otto_gbdt.h"
@@ -42,7 +52,8 @@ constexpr int HIST_THREADS = 256;
 constexpr int PART_ROWS = 2048;     // rows per partition workgroup
 constexpr int SW = OTTO_GBDT_SPLIT_WORDS;
 // error words of a call
-constexpr int ERR_QUERY = 0, ERR_LABEL = 1, ERR_ROW = 2, ERR_WALK = 3, ERR_WORDS = 4;
+constexpr int ERR_QUERY = 0, ERR_LABEL = 1, ERR_ROW = 2, ERR_WALK = 3, ERR_BAG = 4, ERR_WORDS = 5;
+constexpr int BAG_BLOCKS = 1024;    // fixed grid of the bag kernels (4 waves per workgroup)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // binning
@@ -292,20 +303,28 @@ __global__ __launch_bounds__(256) void k_quantize(const double* grad, const doub
 // ---------------------------------------------------------------------------------------------------------------------
 // histogram
 // ---------------------------------------------------------------------------------------------------------------------
-// rows == nullptr: the rows are 0 .. n_rows - 1 (the root)
+// rows == nullptr: the rows are 0 .. n_rows - 1 (the root). LIST: blockIdx.y counts groups of 8 entries of feats (n_list
+// ascending feature ids inside [0, F), checked by the host); the sums go to the listed feature's own planes.
+template <bool LIST>
 __global__ __launch_bounds__(HIST_THREADS) void k_hist(const uint8_t* bins, int64_t n, int F, const int2* gh, const int32_t* rows,
-                                                       int64_t n_rows, int64_t chunk, unsigned long long* hist, uint32_t* err) {
+                                                       int64_t n_rows, int64_t chunk, unsigned long long* hist, uint32_t* err,
+                                                       const int32_t* feats, int n_list) {
     __shared__ unsigned long long sg[HIST_FG * 256];
     __shared__ unsigned long long sh[HIST_FG * 256];
     __shared__ uint32_t sc[HIST_FG * 256];
     const int tid = threadIdx.x;
     const int f0 = blockIdx.y * HIST_FG;
-    const int nf = F - f0 < HIST_FG ? F - f0 : HIST_FG;
+    const int nf = LIST ? (n_list - f0 < HIST_FG ? n_list - f0 : HIST_FG) : (F - f0 < HIST_FG ? F - f0 : HIST_FG);
     for (int j = tid; j < HIST_FG * 256; j += HIST_THREADS) { sg[j] = 0; sh[j] = 0; sc[j] = 0; }
     __syncthreads();
     const int64_t i0 = (int64_t)blockIdx.x * chunk;
     const int64_t i1 = i0 + chunk < n_rows ? i0 + chunk : n_rows;
     const uint8_t* col = bins + (int64_t)f0 * n;
+    int fid[HIST_FG];                                   // LIST: the group's feature ids, the same in every lane
+    if constexpr (LIST) {
+#pragma unroll
+        for (int f = 0; f < HIST_FG; ++f) fid[f] = f < nf ? feats[f0 + f] : 0;
+    }
     bool bad = false;
     for (int64_t i = i0 + tid; i < i1; i += HIST_THREADS) {
         const int64_t rid = rows ? (int64_t)rows[i] : i;
@@ -313,7 +332,10 @@ __global__ __launch_bounds__(HIST_THREADS) void k_hist(const uint8_t* bins, int6
         const int2 q = gh[rid];
         uint32_t b[HIST_FG];
 #pragma unroll
-        for (int f = 0; f < HIST_FG; ++f) b[f] = f < nf ? col[(int64_t)f * n + rid] : 0u;
+        for (int f = 0; f < HIST_FG; ++f) {
+            if constexpr (LIST) b[f] = f < nf ? bins[(int64_t)fid[f] * n + rid] : 0u;
+            else b[f] = f < nf ? col[(int64_t)f * n + rid] : 0u;
+        }
         const unsigned long long qg = (unsigned long long)(long long)q.x, qh = (unsigned long long)(long long)q.y;
 #pragma unroll
         for (int f = 0; f < HIST_FG; ++f)
@@ -327,13 +349,25 @@ __global__ __launch_bounds__(HIST_THREADS) void k_hist(const uint8_t* bins, int6
     if (bad) atomicOr(err + ERR_ROW, 1u);
     __syncthreads();
     const int64_t plane = (int64_t)F * 256;
-    unsigned long long* out = hist + (int64_t)f0 * 256;
-    for (int j = tid; j < nf * 256; j += HIST_THREADS) {
-        const uint32_t c = sc[j];
-        if (c) {
-            atomicAdd(out + j, sg[j]);
-            atomicAdd(out + plane + j, sh[j]);
-            atomicAdd(out + 2 * plane + j, (unsigned long long)c);
+    if constexpr (LIST) {
+        for (int j = tid; j < nf * 256; j += HIST_THREADS) {
+            const uint32_t c = sc[j];
+            if (c) {
+                unsigned long long* out = hist + (int64_t)feats[f0 + (j >> 8)] * 256 + (j & 255);
+                atomicAdd(out, sg[j]);
+                atomicAdd(out + plane, sh[j]);
+                atomicAdd(out + 2 * plane, (unsigned long long)c);
+            }
+        }
+    } else {
+        unsigned long long* out = hist + (int64_t)f0 * 256;
+        for (int j = tid; j < nf * 256; j += HIST_THREADS) {
+            const uint32_t c = sc[j];
+            if (c) {
+                atomicAdd(out + j, sg[j]);
+                atomicAdd(out + plane + j, sh[j]);
+                atomicAdd(out + 2 * plane + j, (unsigned long long)c);
+            }
         }
     }
 }
@@ -343,16 +377,22 @@ __global__ __launch_bounds__(256) void k_hist_sub(int64_t* parent, const int64_t
     if (i < words) parent[i] -= small[i];
 }
 
+// feats == nullptr: every feature; otherwise the planes of the features outside the list stay zero
 int launch_hist(const uint8_t* bins, int64_t n, int F, const int32_t* gh, const int32_t* rows, int64_t n_rows, int64_t* hist,
-                uint32_t* err, hipStream_t s) {
+                uint32_t* err, const int32_t* feats, int n_list, hipStream_t s) {
     OTTO_HIP(hipMemsetAsync(hist, 0, (size_t)3 * F * 256 * 8, s));
     if (n_rows == 0) return 0;
     // about 512 chunks for a large leaf; never below 2048 rows, so that the 6144 merge atomics of a workgroup stay small
     // beside its LDS work
     int64_t chunk = (n_rows + 511) / 512;
     chunk = chunk < 2048 ? 2048 : (chunk + HIST_THREADS - 1) / HIST_THREADS * HIST_THREADS;
-    const dim3 grid((unsigned)((n_rows + chunk - 1) / chunk), (unsigned)((F + HIST_FG - 1) / HIST_FG));
-    k_hist<<<grid, HIST_THREADS, 0, s>>>(bins, n, F, (const int2*)gh, rows, n_rows, chunk, (unsigned long long*)hist, err);
+    const dim3 grid((unsigned)((n_rows + chunk - 1) / chunk), (unsigned)(((feats ? n_list : F) + HIST_FG - 1) / HIST_FG));
+    if (feats)
+        k_hist<true><<<grid, HIST_THREADS, 0, s>>>(bins, n, F, (const int2*)gh, rows, n_rows, chunk, (unsigned long long*)hist, err,
+                                                   feats, n_list);
+    else
+        k_hist<false><<<grid, HIST_THREADS, 0, s>>>(bins, n, F, (const int2*)gh, rows, n_rows, chunk, (unsigned long long*)hist, err,
+                                                    nullptr, 0);
     OTTO_HIP(hipGetLastError());
     return 0;
 }
@@ -403,26 +443,32 @@ __device__ __forceinline__ void cand_try(Cand& best, int f, int b, int dl, int64
 
 __device__ __forceinline__ int64_t shfl64(int64_t v, int src) { return (int64_t)__shfl((long long)v, src, 64); }
 
-__global__ __launch_bounds__(256) void k_best_split(SplitJobs jobs, int F, const int32_t* n_edges, const int32_t* exps, SplitParams p) {
+// LIST: the waves walk the n_list entries of feats (ascending, so "smallest f" is over the listed features) and the
+// parent's sums come from the first listed feature
+template <bool LIST>
+__global__ __launch_bounds__(256) void k_best_split(SplitJobs jobs, int F, const int32_t* n_edges, const int32_t* exps, SplitParams p,
+                                                    const int32_t* feats, int n_list) {
     __shared__ Cand s_best[4];
     const int64_t* hist = jobs.hist[blockIdx.x];
     int64_t* out = jobs.out[blockIdx.x];
     const int l = (int)lane_id(), w = threadIdx.x >> 6;
     const int64_t plane = (int64_t)F * 256;
     const int eg = exps[0], eh = exps[1];
-    // the parent's sums: all 256 bins of feature 0
+    // the parent's sums: all 256 bins of feature 0 (LIST: of the first listed feature)
+    const int64_t* h0 = LIST ? hist + (int64_t)feats[0] * 256 : hist;
     int64_t gP = 0, hP = 0, cP = 0;
     for (int e = 0; e < 4; ++e) {
-        gP += hist[l * 4 + e];
-        hP += hist[plane + l * 4 + e];
-        cP += hist[2 * plane + l * 4 + e];
+        gP += h0[l * 4 + e];
+        hP += h0[plane + l * 4 + e];
+        cP += h0[2 * plane + l * 4 + e];
     }
     gP = wave_reduce<Sum>(gP);
     hP = wave_reduce<Sum>(hP);
     cP = wave_reduce<Sum>(cP);
     Cand best;
     best.found = 0; best.gain = 0.0; best.f = best.b = best.dl = 0; best.cntL = best.gL = best.hL = 0;
-    for (int f = w; f < F; f += 4) {
+    for (int i = w; i < (LIST ? n_list : F); i += 4) {
+        const int f = LIST ? feats[i] : i;
         const int64_t* hf = hist + (int64_t)f * 256 + l * 4;
         int64_t g[4], h[4], c[4];
         for (int e = 0; e < 4; ++e) { g[e] = hf[e]; h[e] = hf[plane + e]; c[e] = hf[2 * plane + e]; }
@@ -471,6 +517,14 @@ __global__ __launch_bounds__(256) void k_best_split(SplitJobs jobs, int F, const
         out[10] = hP;
         out[11] = 0;
     }
+}
+
+int launch_best_split(const SplitJobs& jobs, int n_jobs, int F, const int32_t* n_edges, const int32_t* exps, const SplitParams& p,
+                      const int32_t* feats, int n_list, hipStream_t s) {
+    if (feats) k_best_split<true><<<n_jobs, 256, 0, s>>>(jobs, F, n_edges, exps, p, feats, n_list);
+    else k_best_split<false><<<n_jobs, 256, 0, s>>>(jobs, F, n_edges, exps, p, nullptr, 0);
+    OTTO_HIP(hipGetLastError());
+    return 0;
 }
 
 int check_split_params(int64_t min_data, double min_hess, double l2, double min_gain) {
@@ -592,6 +646,112 @@ __global__ __launch_bounds__(256) void k_add_tree(const uint8_t* bins, int64_t n
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// row bag
+// ---------------------------------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ uint64_t bag_key(uint64_t seed, uint64_t r) {      // mix(seed, r) of SPEC-GBDT
+    uint64_t z = seed + (r + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// sel = { prefix: the digits found so far, k: the rank (1-based) still wanted among the keys that carry the prefix }
+__global__ __launch_bounds__(256) void k_bag_hist(int64_t n, uint64_t seed, const uint64_t* sel, int pass, uint32_t* hist) {
+    __shared__ uint32_t h[4][256];
+    for (int i = threadIdx.x; i < 4 * 256; i += 256) (&h[0][0])[i] = 0;
+    __syncthreads();
+    const uint64_t prefix = pass == 0 ? 0ull : sel[0];
+    const int shift = 56 - 8 * pass;
+    uint32_t* mine = h[threadIdx.x >> 6];
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+        const uint64_t key = bag_key(seed, (uint64_t)r);
+        if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&mine[(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    const uint32_t t = h[0][threadIdx.x] + h[1][threadIdx.x] + h[2][threadIdx.x] + h[3][threadIdx.x];
+    if (t) atomicAdd(hist + threadIdx.x, t);
+}
+
+__global__ __launch_bounds__(64) void k_bag_pick(const uint32_t* hist, uint64_t* sel, int pass, uint64_t m) {
+    __shared__ uint32_t sm[256];
+    for (int i = threadIdx.x; i < 256; i += 64) sm[i] = hist[i];
+    wave_lds_sync();
+    if (threadIdx.x == 0) {
+        const uint64_t prefix = pass == 0 ? 0ull : sel[0];
+        uint64_t k = pass == 0 ? m : sel[1];
+        int d = 0;
+        for (; d < 255; ++d) {                         // the last digit takes what is left: no index past the table
+            if (sm[d] >= k) break;
+            k -= sm[d];
+        }
+        sel[0] = (prefix << 8) | (uint64_t)d;
+        sel[1] = k;
+    }
+}
+
+// wave w of the grid owns rows [w * per, (w + 1) * per), per a multiple of 64; wave_cnt[w] = its rows with key <= sel[0]
+__global__ __launch_bounds__(256) void k_bag_count(int64_t n, int64_t per, uint64_t seed, const uint64_t* sel, uint32_t* wave_cnt) {
+    const int lane = (int)lane_id();
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint64_t threshold = sel[0];
+    const int64_t lo = w * per, hi = lo + per < n ? lo + per : n;
+    uint32_t cnt = 0;
+    for (int64_t r0 = lo; r0 < hi; r0 += 64) {
+        const int64_t r = r0 + lane;
+        cnt += (uint32_t)__popcll(__ballot(r < hi && bag_key(seed, (uint64_t)r) <= threshold));
+    }
+    if (lane == 0) wave_cnt[w] = cnt;
+}
+
+struct BagBlockCount {
+    const uint32_t* wave_cnt;
+    __device__ uint64_t operator()(int64_t b) const {
+        return (uint64_t)wave_cnt[4 * b] + wave_cnt[4 * b + 1] + wave_cnt[4 * b + 2] + wave_cnt[4 * b + 3];
+    }
+};
+
+// scan [blocks + 1]: kept rows in front of every workgroup and in all. Nothing is written at or behind out[cap].
+__global__ __launch_bounds__(256) void k_bag_emit(int64_t n, int64_t per, uint64_t seed, const uint64_t* sel, const uint32_t* wave_cnt,
+                                                  const uint64_t* scan, int64_t m, int64_t cap, int32_t* out, uint32_t* err) {
+    const int lane = (int)lane_id(), wv = threadIdx.x >> 6;
+    const int64_t w = (int64_t)blockIdx.x * 4 + wv;
+    if (w == 0 && lane == 0 && ((int64_t)scan[gridDim.x] != m || m > cap)) atomicOr(err + ERR_BAG, 1u);
+    const uint64_t threshold = sel[0];
+    const uint64_t below = (1ull << lane) - 1ull;
+    int64_t at = (int64_t)scan[blockIdx.x];
+    for (int j = 0; j < wv; ++j) at += wave_cnt[4 * blockIdx.x + j];
+    const int64_t lo = w * per, hi = lo + per < n ? lo + per : n;
+    bool over = false;
+    for (int64_t r0 = lo; r0 < hi; r0 += 64) {
+        const int64_t r = r0 + lane;
+        const bool keep = r < hi && bag_key(seed, (uint64_t)r) <= threshold;
+        const uint64_t mask = __ballot(keep);
+        const int64_t pos = at + __popcll(mask & below);
+        if (keep) {
+            if (pos < cap && pos < m) out[pos] = (int32_t)r;
+            else over = true;
+        }
+        at += __popcll(mask);
+    }
+    if (over) atomicOr(err + ERR_BAG, 1u);
+}
+
+struct BagLayout {
+    int64_t hist, sel, wave_cnt, scan, partial, bytes;
+};
+BagLayout bag_layout() {
+    BagLayout w;
+    int64_t at = 0;
+    w.hist = at; at += align256((int64_t)8 * 256 * 4);
+    w.sel = at; at += 256;
+    w.wave_cnt = at; at += align256((int64_t)BAG_BLOCKS * 4 * 4);
+    w.scan = at; at += align256((int64_t)(BAG_BLOCKS + 1) * 8);
+    w.partial = at; at += align256((int64_t)scan_partial_bytes(BAG_BLOCKS));
+    w.bytes = at;
+    return w;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host helpers
 // ---------------------------------------------------------------------------------------------------------------------
 int err_begin(uint32_t** err, hipStream_t s) {
@@ -604,7 +764,7 @@ int err_begin(uint32_t** err, hipStream_t s) {
 
 // drains the stream and turns the error words into a return code
 int err_end(uint32_t* err, hipStream_t s) {
-    uint32_t bad[ERR_WORDS] = {0, 0, 0, 0};
+    uint32_t bad[ERR_WORDS] = {0, 0, 0, 0, 0};
     OTTO_HIP(hipMemcpyAsync(bad, err, sizeof(bad), hipMemcpyDeviceToHost, s));
     OTTO_HIP(hipStreamSynchronize(s));
     if (bad[ERR_QUERY]) {
@@ -624,6 +784,10 @@ int err_end(uint32_t* err, hipStream_t s) {
         set_error("a tree walk did not reach a leaf of its tree within n_leaves - 1 steps, or read a feature outside [0, F)");
         return OTTO_EINVAL;
     }
+    if (bad[ERR_BAG]) {
+        set_error("the bag did not come to exactly m rows inside d_rows_out");
+        return OTTO_EINVAL;
+    }
     return 0;
 }
 
@@ -631,6 +795,18 @@ int check_bins_args(const uint8_t* d_bins, int64_t n, int32_t F) {
     OTTO_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "n = %lld outside [0, 2^31)", (long long)n);
     OTTO_REQUIRE(F >= 1 && F <= OTTO_FOREST_MAX_FEATURES, "F must be in [1, %d] (got %d)", OTTO_FOREST_MAX_FEATURES, F);
     OTTO_REQUIRE(d_bins || n == 0, "null d_bins");
+    return 0;
+}
+
+// copies the list to the host (one synchronisation): n_used ascending feature ids inside [0, F)
+int check_feature_list(const int32_t* d_features, int32_t n_used, int32_t F, hipStream_t s) {
+    OTTO_REQUIRE(n_used >= 1 && n_used <= F, "n_used = %d outside [1, F = %d]", n_used, F);
+    int32_t h[OTTO_FOREST_MAX_FEATURES];
+    OTTO_HIP(hipMemcpyAsync(h, d_features, (size_t)n_used * 4, hipMemcpyDeviceToHost, s));
+    OTTO_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < n_used; ++i)
+        OTTO_REQUIRE(h[i] >= 0 && h[i] < F && (i == 0 || h[i] > h[i - 1]), "d_features[%d] = %d: the list must ascend strictly inside "
+                     "[0, F = %d)", i, h[i], F);
     return 0;
 }
 
@@ -725,30 +901,84 @@ extern "C" int otto_gbdt_quantize(const double* d_grad, const double* d_hess, in
     return 0;
 }
 
-extern "C" int otto_gbdt_hist(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_rows, int64_t n_rows,
-                              int64_t* d_hist, void* stream) {
+extern "C" int otto_gbdt_hist_features(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_rows,
+                                       int64_t n_rows, const int32_t* d_features, int32_t n_used, int64_t* d_hist, void* stream) {
     OTTO_TRY(check_bins_args(d_bins, n, F));
     OTTO_REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows = %lld outside [0, 2^31)", (long long)n_rows);
     OTTO_REQUIRE(d_hist, "null d_hist");
     OTTO_REQUIRE((d_gh && d_rows) || n_rows == 0, "null d_gh or d_rows");
     hipStream_t s = (hipStream_t)stream;
+    if (d_features) OTTO_TRY(check_feature_list(d_features, n_used, F, s));
     uint32_t* err = nullptr;
     OTTO_TRY(err_begin(&err, s));
-    OTTO_TRY(launch_hist(d_bins, n, F, d_gh, d_rows, n_rows, d_hist, err, s));
+    OTTO_TRY(launch_hist(d_bins, n, F, d_gh, d_rows, n_rows, d_hist, err, d_features, n_used, s));
     return err_end(err, s);
+}
+
+extern "C" int otto_gbdt_hist(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_rows, int64_t n_rows,
+                              int64_t* d_hist, void* stream) {
+    return otto_gbdt_hist_features(d_bins, n, F, d_gh, d_rows, n_rows, nullptr, 0, d_hist, stream);
+}
+
+extern "C" int otto_gbdt_best_split_features(const int64_t* d_hist, int32_t F, const int32_t* d_n_edges, const int32_t* d_exp,
+                                             int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2,
+                                             double min_gain_to_split, const int32_t* d_features, int32_t n_used, int64_t* d_split,
+                                             void* stream) {
+    OTTO_REQUIRE(F >= 1 && F <= OTTO_FOREST_MAX_FEATURES, "F must be in [1, %d] (got %d)", OTTO_FOREST_MAX_FEATURES, F);
+    OTTO_REQUIRE(d_hist && d_n_edges && d_exp && d_split, "null argument");
+    OTTO_TRY(check_split_params(min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split));
+    if (d_features) OTTO_TRY(check_feature_list(d_features, n_used, F, (hipStream_t)stream));
+    SplitJobs jobs{{d_hist, d_hist}, {d_split, d_split}};
+    SplitParams p{min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split};
+    return launch_best_split(jobs, 1, F, d_n_edges, d_exp, p, d_features, n_used, (hipStream_t)stream);
 }
 
 extern "C" int otto_gbdt_best_split(const int64_t* d_hist, int32_t F, const int32_t* d_n_edges, const int32_t* d_exp,
                                     int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2,
                                     double min_gain_to_split, int64_t* d_split, void* stream) {
-    OTTO_REQUIRE(F >= 1 && F <= OTTO_FOREST_MAX_FEATURES, "F must be in [1, %d] (got %d)", OTTO_FOREST_MAX_FEATURES, F);
-    OTTO_REQUIRE(d_hist && d_n_edges && d_exp && d_split, "null argument");
-    OTTO_TRY(check_split_params(min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split));
-    SplitJobs jobs{{d_hist, d_hist}, {d_split, d_split}};
-    SplitParams p{min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split};
-    k_best_split<<<1, 256, 0, (hipStream_t)stream>>>(jobs, F, d_n_edges, d_exp, p);
+    return otto_gbdt_best_split_features(d_hist, F, d_n_edges, d_exp, min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2,
+                                         min_gain_to_split, nullptr, 0, d_split, stream);
+}
+
+extern "C" int64_t otto_gbdt_bag_workspace_bytes(int64_t n) {
+    if (n < 1 || n >= ((int64_t)1 << 31)) return 0;
+    return bag_layout().bytes;
+}
+
+extern "C" int otto_gbdt_bag(int64_t n, int64_t m, uint64_t seed, int32_t* d_rows_out, int64_t out_rows, void* d_work,
+                             int64_t work_bytes, void* stream) {
+    OTTO_REQUIRE(n >= 1 && n < ((int64_t)1 << 31), "n = %lld outside [1, 2^31)", (long long)n);
+    OTTO_REQUIRE(m >= 1 && m <= n, "m = %lld outside [1, n = %lld]", (long long)m, (long long)n);
+    OTTO_REQUIRE(d_rows_out && out_rows >= m, "d_rows_out holds %lld row ids, the bag has %lld", (long long)(d_rows_out ? out_rows : 0),
+                 (long long)m);
+    const BagLayout w = bag_layout();
+    OTTO_REQUIRE(d_work && work_bytes >= w.bytes, "d_work holds %lld bytes, otto_gbdt_bag_workspace_bytes asks for %lld",
+                 (long long)(d_work ? work_bytes : 0), (long long)w.bytes);
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)d_work;
+    uint32_t* hist = (uint32_t*)(base + w.hist);
+    uint64_t* sel = (uint64_t*)(base + w.sel);
+    uint32_t* wave_cnt = (uint32_t*)(base + w.wave_cnt);
+    uint64_t* scan = (uint64_t*)(base + w.scan);
+    uint64_t* partial = (uint64_t*)(base + w.partial);
+    uint32_t* err = nullptr;
+    OTTO_TRY(err_begin(&err, s));
+    OTTO_HIP(hipMemsetAsync(hist, 0, 8 * 256 * 4, s));
+    const unsigned blocks = (unsigned)((n + 255) / 256 < BAG_BLOCKS ? (n + 255) / 256 : BAG_BLOCKS);
+    for (int pass = 0; pass < 8; ++pass) {
+        k_bag_hist<<<blocks, 256, 0, s>>>(n, seed, sel, pass, hist + pass * 256);
+        OTTO_HIP(hipGetLastError());
+        k_bag_pick<<<1, 64, 0, s>>>(hist + pass * 256, sel, pass, (uint64_t)m);
+        OTTO_HIP(hipGetLastError());
+    }
+    const int64_t waves = (int64_t)blocks * 4;
+    const int64_t per = ((n + waves - 1) / waves + 63) / 64 * 64;
+    k_bag_count<<<blocks, 256, 0, s>>>(n, per, seed, sel, wave_cnt);
     OTTO_HIP(hipGetLastError());
-    return 0;
+    OTTO_TRY(device_scan(BagBlockCount{wave_cnt}, (int64_t)blocks, scan, partial, s));
+    k_bag_emit<<<blocks, 256, 0, s>>>(n, per, seed, sel, wave_cnt, scan, m, out_rows, d_rows_out, err);
+    OTTO_HIP(hipGetLastError());
+    return err_end(err, s);
 }
 
 extern "C" int otto_gbdt_partition(const uint8_t* d_bins, int64_t n, int32_t feature, int32_t bin, int32_t default_left,
@@ -805,14 +1035,16 @@ extern "C" int otto_gbdt_ap_at_k(const double* d_score, const int32_t* d_label, 
     return err_end(err, s);
 }
 
-extern "C" int otto_gbdt_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_exp,
-                                   const int32_t* d_n_edges, const float* h_edges, int32_t num_leaves, int64_t min_data_in_leaf,
-                                   double min_sum_hessian_in_leaf, double lambda_l2, double min_gain_to_split, double learning_rate,
-                                   int32_t* h_n_leaves, int32_t* h_split_feature, int32_t* h_split_bin, double* h_threshold,
-                                   int8_t* h_decision_type, int32_t* h_left_child, int32_t* h_right_child, double* h_split_gain,
-                                   double* h_leaf_value, int64_t* h_leaf_count, int64_t* h_hist_rows, void* d_work,
-                                   int64_t work_bytes, void* stream) {
+extern "C" int otto_gbdt_grow_tree_sampled(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_exp,
+                                           const int32_t* d_n_edges, const float* h_edges, int32_t num_leaves,
+                                           int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2,
+                                           double min_gain_to_split, double learning_rate, const int32_t* d_bag, int64_t n_bag,
+                                           const int32_t* d_features, int32_t n_used, int32_t* h_n_leaves, int32_t* h_split_feature,
+                                           int32_t* h_split_bin, double* h_threshold, int8_t* h_decision_type, int32_t* h_left_child,
+                                           int32_t* h_right_child, double* h_split_gain, double* h_leaf_value, int64_t* h_leaf_count,
+                                           int64_t* h_hist_rows, void* d_work, int64_t work_bytes, void* stream) {
     OTTO_TRY(check_bins_args(d_bins, n, F));
+    OTTO_REQUIRE(!d_bag || (n_bag >= 1 && n_bag <= n), "n_bag = %lld outside [1, n = %lld]", (long long)n_bag, (long long)n);
     OTTO_REQUIRE(n >= 1, "n = 0: nothing to grow a tree on");
     OTTO_REQUIRE(num_leaves >= 2 && num_leaves <= OTTO_FOREST_MAX_LEAVES, "num_leaves = %d outside [2, %d]", num_leaves,
                  OTTO_FOREST_MAX_LEAVES);
@@ -823,6 +1055,7 @@ extern "C" int otto_gbdt_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, 
     OTTO_REQUIRE(d_work && work_bytes >= w.total, "d_work holds %lld bytes, otto_gbdt_workspace_bytes asks for %lld",
                  (long long)work_bytes, (long long)w.total);
     hipStream_t s = (hipStream_t)stream;
+    if (d_features) OTTO_TRY(check_feature_list(d_features, n_used, F, s));
     char* base = (char*)d_work;
     int32_t* rows_a = (int32_t*)(base + w.rows_a);
     int32_t* rows_b = (int32_t*)(base + w.rows_b);
@@ -845,15 +1078,18 @@ extern "C" int otto_gbdt_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, 
         int64_t split[SW];
     };
     std::vector<Leaf> leaves(1);
-    leaves[0] = Leaf{0, n, 0, 0, 0, -1, 0, false, {0}};
-    int64_t hist_rows = n;
-    OTTO_TRY(launch_hist(d_bins, n, F, d_gh, nullptr, n, hist0, err, s));
+    leaves[0] = Leaf{0, d_bag ? n_bag : n, 0, 0, 0, -1, 0, d_bag != nullptr, {0}};
+    int64_t hist_rows = leaves[0].cnt;
+    // the bag is the root's row list: every sum, count and partition below is over in-bag rows
+    if (d_bag) OTTO_HIP(hipMemcpyAsync(rows_a, d_bag, (size_t)n_bag * 4, hipMemcpyDeviceToDevice, s));
+    OTTO_TRY(launch_hist(d_bins, n, F, d_gh, d_bag ? rows_a : nullptr, leaves[0].cnt, hist0, err, d_features, n_used, s));
     {
         SplitJobs jobs{{hist0, hist0}, {d_split, d_split}};
-        k_best_split<<<1, 256, 0, s>>>(jobs, F, d_n_edges, d_exp, p);
-        OTTO_HIP(hipGetLastError());
+        OTTO_TRY(launch_best_split(jobs, 1, F, d_n_edges, d_exp, p, d_features, n_used, s));
         OTTO_HIP(hipMemcpyAsync(leaves[0].split, d_split, SW * 8, hipMemcpyDeviceToHost, s));
-        OTTO_HIP(hipStreamSynchronize(s));
+        // a bag is the caller's: an entry outside [0, n) is reported here, before the counts it spoils are compared
+        if (d_bag) OTTO_TRY(err_end(err, s));
+        else OTTO_HIP(hipStreamSynchronize(s));
         leaves[0].gq = leaves[0].split[9];
         leaves[0].hq = leaves[0].split[10];
     }
@@ -893,13 +1129,12 @@ extern "C" int otto_gbdt_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, 
             large.slot = P.slot;
             int64_t* hs = hist0 + (int64_t)small.slot * hist_words;
             int64_t* hl = hist0 + (int64_t)large.slot * hist_words;
-            OTTO_TRY(launch_hist(d_bins, n, F, d_gh, rows_a + small.begin, small.cnt, hs, err, s));
+            OTTO_TRY(launch_hist(d_bins, n, F, d_gh, rows_a + small.begin, small.cnt, hs, err, d_features, n_used, s));
             hist_rows += small.cnt;
             k_hist_sub<<<(unsigned)((hist_words + 255) / 256), 256, 0, s>>>(hl, hs, hist_words);
             OTTO_HIP(hipGetLastError());
             SplitJobs jobs{{hist0 + (int64_t)L.slot * hist_words, hist0 + (int64_t)R.slot * hist_words}, {d_split, d_split + SW}};
-            k_best_split<<<2, 256, 0, s>>>(jobs, F, d_n_edges, d_exp, p);
-            OTTO_HIP(hipGetLastError());
+            OTTO_TRY(launch_best_split(jobs, 2, F, d_n_edges, d_exp, p, d_features, n_used, s));
             int64_t both[2 * SW];
             OTTO_HIP(hipMemcpyAsync(both, d_split, sizeof(both), hipMemcpyDeviceToHost, s));
             OTTO_HIP(hipStreamSynchronize(s));
@@ -921,4 +1156,17 @@ extern "C" int otto_gbdt_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, 
     *h_n_leaves = (int32_t)leaves.size();
     if (h_hist_rows) *h_hist_rows = hist_rows;
     return 0;
+}
+
+extern "C" int otto_gbdt_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_exp,
+                                   const int32_t* d_n_edges, const float* h_edges, int32_t num_leaves, int64_t min_data_in_leaf,
+                                   double min_sum_hessian_in_leaf, double lambda_l2, double min_gain_to_split, double learning_rate,
+                                   int32_t* h_n_leaves, int32_t* h_split_feature, int32_t* h_split_bin, double* h_threshold,
+                                   int8_t* h_decision_type, int32_t* h_left_child, int32_t* h_right_child, double* h_split_gain,
+                                   double* h_leaf_value, int64_t* h_leaf_count, int64_t* h_hist_rows, void* d_work,
+                                   int64_t work_bytes, void* stream) {
+    return otto_gbdt_grow_tree_sampled(d_bins, n, F, d_gh, d_exp, d_n_edges, h_edges, num_leaves, min_data_in_leaf,
+                                       min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split, learning_rate, nullptr, 0, nullptr, 0,
+                                       h_n_leaves, h_split_feature, h_split_bin, h_threshold, h_decision_type, h_left_child,
+                                       h_right_child, h_split_gain, h_leaf_value, h_leaf_count, h_hist_rows, d_work, work_bytes, stream);
 }

@@ -6,5 +6,5 @@ from .blend import blend_predictions, blend_topk, robust_scale  # noqa: E402,F40
 from .features import (AID_COLUMNS, SESSION_COLUMNS, aid_feature_table, feature_matrix, session_feature_table,  # noqa: E402,F401
                        to_frames)
 from .folds import cross_validate, feature_importance, fold_indices, gather_bins, group_kfold  # noqa: E402,F401
-from .gbdt import (BinMapper, TrainResult, ap_at_k, bin_matrix, fit_bins, lambdarank_gradients, train,  # noqa: E402,F401
-                   write_lightgbm_model)
+from .gbdt import (BinMapper, Sampling, TrainResult, ap_at_k, bin_matrix, fit_bins, lambdarank_gradients,  # noqa: E402,F401
+                   sampling_from_params, train, write_lightgbm_model)

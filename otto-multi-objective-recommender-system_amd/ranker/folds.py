@@ -163,11 +163,12 @@ class CVResult:
 
 
 def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ratio=0.3, seed=42, num_boost_round=100,
-                   early_stopping_rounds=None, feature_names=None, aid=None, truth=None):
+                   early_stopping_rounds=None, feature_names=None, aid=None, truth=None, sampling=None):
     """The fold loop of ``lgb_trainer.py:81-198`` on the device: a :class:`CVResult`.
 
     ``X`` float32 [n, F] (``ranker.features.feature_matrix``), ``label`` uint8 or int32 [n], ``query_off`` int64 [Q+1]
-    (the ``row_off`` of ``ranker_table``), on the device; ``params`` as ``gbdt.train`` takes them. :func:`group_kfold`
+    (the ``row_off`` of ``ranker_table``), on the device; ``params`` and ``sampling`` as ``gbdt.train`` takes them
+    (``gbdt.sampling_from_params`` makes both from a section of the reference's config). :func:`group_kfold`
     once, then per fold: :func:`fold_indices`; a ``BinMapper`` from ``gbdt.fit_bins`` (host) over at most 200,000 evenly
     strided training rows, ``train_idx[::ceil(Mt / 200000)]``; ``gbdt.bin_matrix`` over all rows; :func:`gather_bins` of
     the training and validation rows; ``gbdt.train(..., valid=...)``; the validation score by ``gbdt.add_tree`` over the
@@ -206,7 +207,7 @@ def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ra
         train_label, val_label = label32[fi.train_idx.long()], label32[fi.val_idx.long()]
         res = gbdt.train(train_bins, train_label, fi.train_query_off, mapper, params,
                          valid=(val_bins, val_label, fi.val_query_off), num_boost_round=num_boost_round,
-                         early_stopping_rounds=early_stopping_rounds, feature_names=feature_names)
+                         early_stopping_rounds=early_stopping_rounds, feature_names=feature_names, sampling=sampling)
         score = torch.zeros(fi.val_idx.numel(), dtype=torch.float64, device=dev)
         for tree in res.trees:
             gbdt.add_tree(val_bins, tree, score)

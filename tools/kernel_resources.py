@@ -19,6 +19,6 @@ for line in r.splitlines():
         rows[cur][k.strip()] = v.strip()
 for name, d in rows.items():
     if flt in name:
-        short = re.sub(r'\(.*', '', name).replace('void otto::', '')
+        short = re.sub(r'\(.*', '', name.replace('(anonymous namespace)::', '')).replace('void otto::', '')
         print(f"{short[:60]:60s} VGPR {d.get('VGPRs','?'):>4} AGPR {d.get('AGPRs','?'):>3} SGPR {d.get('TotalSGPRs', d.get('SGPRs','?')):>4} "
               f"scratch {d.get('ScratchSize [bytes/lane]','?'):>4} occ {d.get('Occupancy [waves/SIMD]','?'):>2} LDS {d.get('LDS Size [bytes/block]','?'):>7}")

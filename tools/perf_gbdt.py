@@ -12,7 +12,14 @@ machine's host: the CPU baseline. ``--trees-only N`` grows N trees and nothing e
 ``rocprofv3 --kernel-trace --stats`` the total of ``k_hist`` is then those trees' histogram time, which over
 ``hist_algorithmic_bytes_per_tree`` gives the rate summed over the leaves actually built. Needs a GPU; there is no fallback.
 
+``--bagging-fraction p`` / ``--feature-fraction q`` (SPEC-GBDT, Sampling): the tree is grown on the bag of draw 0 and the
+feature list of iteration 0, ``bag_rows`` at n rows is timed as well, and ``--trees-only`` grows its trees with them.
+``--only-tree`` times nothing but one whole tree after the set-up. ``--root DIR`` imports the package from another checkout
+of this repository (built there): alternating ``--root <parent checkout> --only-tree`` with ``--only-tree`` in one job is how
+two commits are compared, since kernel times move by several per cent with the chip's power state.
+
     python tools/perf_gbdt.py [--rows 16777216] [--features 54] [--leaves 128] [--min-data 2000] [--cpu-rows 262144]
+                              [--bagging-fraction 0.9] [--feature-fraction 0.9] [--only-tree] [--root DIR]
 """
 import argparse
 import json
@@ -24,7 +31,6 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
 HBM_PEAK = 8.0e12     # bytes / s, MI355X data sheet
 
 
@@ -54,7 +60,15 @@ def main():
     ap.add_argument('--trees-only', type=int, default=0)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--bagging-fraction', type=float, default=1.0)
+    ap.add_argument('--feature-fraction', type=float, default=1.0)
+    ap.add_argument('--bagging-seed', type=int, default=3)
+    ap.add_argument('--feature-fraction-seed', type=int, default=2)
+    ap.add_argument('--only-tree', action='store_true')
+    ap.add_argument('--root', default=ROOT)
     args = ap.parse_args()
+    root = os.path.abspath(args.root)
+    sys.path[:0] = [root, os.path.join(root, 'tests')]
     import torch
     if not torch.cuda.is_available():
         sys.exit('perf_gbdt: no ROCm device visible (this tool does not fall back)')
@@ -71,27 +85,52 @@ def main():
     mapper = gbdt.fit_bins(X[:200000].cpu().numpy())
     out = {'tool': 'perf_gbdt', 'device': torch.cuda.get_device_name(0), 'n_rows': n, 'F': F, 'num_leaves': args.leaves,
            'min_data_in_leaf': args.min_data, 'query_rows': args.query_rows, 'warmup': args.warmup, 'repeats': args.repeats}
-    out['bin_ms'], out['bin_ms_all'] = _time(lambda: gbdt.bin_matrix(X, mapper), args.warmup, args.repeats)
+    if root != ROOT:
+        out['root'] = args.root
+    if not args.only_tree:
+        out['bin_ms'], out['bin_ms_all'] = _time(lambda: gbdt.bin_matrix(X, mapper), args.warmup, args.repeats)
     bins = gbdt.bin_matrix(X, mapper)
     p = gbdt.resolve_params({'num_leaves': args.leaves, 'min_data_in_leaf': args.min_data})
     score = torch.zeros(n, dtype=torch.float64, device=dev)
     grad, hess = torch.empty_like(score), torch.empty_like(score)
     obj = lambda: gbdt.lambdarank_gradients(score, label, query_off, p['sigmoid'], p['lambdarank_truncation_level'], True, out=(grad, hess))
-    out['objective_ms'], out['objective_ms_all'] = _time(obj, args.warmup, args.repeats)
-    out['quantize_ms'], out['quantize_ms_all'] = _time(lambda: gbdt.quantize_gradients(grad, hess), args.warmup, args.repeats)
+    if args.only_tree:
+        obj()
+    else:
+        out['objective_ms'], out['objective_ms_all'] = _time(obj, args.warmup, args.repeats)
+        out['quantize_ms'], out['quantize_ms_all'] = _time(lambda: gbdt.quantize_gradients(grad, hess), args.warmup, args.repeats)
     gh, exp = gbdt.quantize_gradients(grad, hess)
     work = torch.empty(gbdt.workspace_bytes(n, F, args.leaves), dtype=torch.uint8, device=dev)
+    sampled = {}
+    if args.bagging_fraction < 1.0 or args.feature_fraction < 1.0:
+        out['bagging_fraction'], out['feature_fraction'] = args.bagging_fraction, args.feature_fraction
+        if args.bagging_fraction < 1.0:
+            m, seed = gbdt.bag_size(args.bagging_fraction, n), gbdt.mix(args.bagging_seed, 0)
+            if not args.trees_only:
+                out['bag_rows_ms'], out['bag_rows_ms_all'] = _time(lambda: gbdt.bag_rows(n, m, seed, dev), args.warmup, args.repeats)
+            sampled['bag'] = gbdt.bag_rows(n, m, seed, dev)
+            out['bag_size'] = m
+        if args.feature_fraction < 1.0:
+            # the device list, made once: a tree of the boosting loop pays one small host-to-device copy for it
+            feats = gbdt.sample_features(F, args.feature_fraction, args.feature_fraction_seed, 0)
+            sampled['features'] = torch.from_numpy(feats).to(dev)
+            out['n_used'] = int(feats.size)
+    grow = lambda: gbdt.grow_tree(bins, gh, exp, mapper, p, work, **sampled)
     if args.trees_only:
         # for a kernel trace: nothing but this many trees launches k_hist, so its traced total is theirs
         for _ in range(args.trees_only):
-            tree = gbdt.grow_tree(bins, gh, exp, mapper, p, work)
+            tree = grow()
         torch.cuda.synchronize()
         print(json.dumps({'tool': 'perf_gbdt', 'trees_only': args.trees_only, 'n_rows': n, 'F': F, 'tree_leaves': tree.n_leaves,
+                          'bagging_fraction': args.bagging_fraction, 'feature_fraction': args.feature_fraction,
                           'hist_rows_per_tree': tree.hist_rows, 'hist_algorithmic_bytes_per_tree': tree.hist_rows * (F + 8 + 4)}))
         return
-    out['tree_ms'], out['tree_ms_all'] = _time(lambda: gbdt.grow_tree(bins, gh, exp, mapper, p, work), args.warmup, args.repeats)
-    tree = gbdt.grow_tree(bins, gh, exp, mapper, p, work)
+    out['tree_ms'], out['tree_ms_all'] = _time(grow, args.warmup, args.repeats)
+    tree = grow()
     out['tree_leaves'], out['hist_rows'] = tree.n_leaves, tree.hist_rows
+    if args.only_tree:
+        print(json.dumps(out))
+        return
     rows = torch.arange(n, dtype=torch.int32, device=dev)
     out['root_hist_ms'], out['root_hist_ms_all'] = _time(lambda: gbdt.leaf_histogram(bins, gh, rows), args.warmup, args.repeats)
     per_row = F + 8 + 4
