@@ -1632,6 +1632,91 @@ __global__ void k_fill_chunks(ChunkCount f, uint32_t n_aids, const uint64_t* chu
     for (uint64_t q = 0; q < c; ++q) chunks[s + q] = (uint64_t)x | (q << 26);
 }
 
+// ---- processing order of the partition chunks: by where their records lie ----
+// chunks[] is ordered by aid, then by chunk, and an aid's runs follow session order: the ~1000 resident workgroups hold
+// every chunk of some 50 - 100 aids, so together they read list lines from the whole record region at once and a line that
+// several aids share (popular aids share windows) has left the Infinity Cache before the next aid asks for it. Ordered by
+// record slot, the resident chunks of all aids read the same slice of the region at the same time.
+// The order is ONE stable counting sort of the chunk words by a binned key: key + histogram (k_chunk_keys), scan, stable
+// scatter (k_ord_scatter). Cells are [bin][block of ORD_BLOCK chunks].
+constexpr int ORD_BLOCK = 256;             // chunks per workgroup of k_ord_scatter
+constexpr int ORD_KEY_RUNS = 64;           // descriptors of a chunk looked at for its key (one per lane)
+constexpr int ORD_MAX_BITS = 11;           // bins <= 2^11
+
+struct OrdBin {
+    int shift; uint32_t nb;                // (keys past the range the host sized the bins for land in the last bin)
+    __device__ __forceinline__ uint32_t operator()(uint64_t key) const {
+        const uint64_t d = key >> shift;
+        return (uint32_t)(d < nb ? d : nb - 1u);
+    }
+};
+
+// key of chunk ci: record slot of its first run with a shared list among its first ORD_KEY_RUNS descriptors, else of its
+// first run. 16 lanes per chunk, 4 descriptors per lane (a wave per chunk measured 68 us on 185 k chunks: three dependent
+// round trips per wave; four chunks per wave need a quarter of the waves). Adds the chunk to the histogram cell of its
+// first digit.
+__global__ __launch_bounds__(256) void k_chunk_keys(const uint64_t* chunks, uint32_t n_chunks, const uint64_t* run_start,
+                                                    const uint64_t* sorted_desc, OrdBin dg, uint32_t n_blocks,
+                                                    uint64_t* keys, uint32_t* cells) {
+    constexpr int PER_LANE = ORD_KEY_RUNS / 16;
+    const unsigned lane = lane_id(), sub = lane & 15u;
+    const uint32_t ci = blockIdx.x * 16u + (threadIdx.x >> 4);
+    const bool valid = ci < n_chunks;
+    uint64_t rb = 0, re = 0;
+    if (valid) {
+        const uint64_t ch = chunks[ci];
+        const uint32_t x = (uint32_t)(ch & REC_AID_MASK);
+        rb = run_start[x] + (ch >> 26) * PART_CHUNK_RUNS;
+        const uint64_t rs1 = run_start[x + 1];
+        re = rb + ORD_KEY_RUNS < rs1 ? rb + ORD_KEY_RUNS : rs1;
+    }
+    uint64_t d[PER_LANE];
+    uint32_t best = ORD_KEY_RUNS;                                 // first of my descriptors with a shared list
+#pragma unroll
+    for (int j = PER_LANE - 1; j >= 0; --j) {
+        const uint64_t r = rb + (uint64_t)j * 16u + sub;
+        d[j] = r < re ? sorted_desc[r] : 0ull;
+        if (r < re && desc_sp(d[j]) != DESC_SP_NONE) best = (uint32_t)j * 16u + sub;
+    }
+#pragma unroll
+    for (int m = 8; m >= 1; m >>= 1) {                            // minimum over the chunk's 16 lanes
+        const uint32_t o = (uint32_t)__shfl_xor((int)best, m);
+        best = o < best ? o : best;
+    }
+    if (best == ORD_KEY_RUNS) best = 0;                           // no shared list: the first run (rb < re for every chunk)
+    uint64_t mine = d[0];
+#pragma unroll
+    for (int j = 1; j < PER_LANE; ++j)
+        if ((best >> 4) == (uint32_t)j) mine = d[j];
+    const uint64_t slot = desc_slot(mine);
+    const int src = (int)((lane & 48u) | (best & 15u));
+    const uint64_t key = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(slot >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)slot, src);
+    if (valid && sub == 0) {
+        keys[ci] = key;
+        atomicAdd(&cells[(size_t)dg(key) * n_blocks + ci / ORD_BLOCK], 1u);
+    }
+}
+
+struct OrdCell {
+    const uint32_t* cells;
+    __device__ uint64_t operator()(int64_t i) const { return cells[i]; }
+};
+
+// stable: chunk i of block b goes to its cell's start + the number of earlier chunks of the block in the same bin
+__global__ __launch_bounds__(ORD_BLOCK) void k_ord_scatter(const uint64_t* keys, const uint64_t* chunks, uint32_t n, OrdBin dg,
+                                                           uint32_t n_blocks, const uint64_t* cell_start, uint64_t* out) {
+    __shared__ uint32_t s_bin[ORD_BLOCK];
+    const uint32_t i = blockIdx.x * ORD_BLOCK + threadIdx.x;
+    const uint32_t bin = i < n ? dg(keys[i]) : 0xffffffffu;
+    s_bin[threadIdx.x] = bin;
+    __syncthreads();
+    if (i >= n) return;
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < threadIdx.x; ++j) rank += s_bin[j] == bin ? 1u : 0u;
+    const uint64_t pos = cell_start[(size_t)bin * n_blocks + blockIdx.x] + rank;
+    if (pos < n) out[pos] = chunks[i];                            // (always: the cells count exactly these chunks)
+}
+
 // Every total the index build needs on the host (buffer sizes, statistics) in ONE reduction over the aids, so the build
 // synchronises with the host once instead of after each of its scans:
 //   [0] records  [1] runs  [2..4] records per bin  [5..7] runs per bin  [8..10] work items per bin
@@ -3376,6 +3461,9 @@ struct otto_covis_ctx {
     // partition pass of heavy aids
     OwnedBuf litem_start, chunks, pcount, pcursor, pstart, prec, ptw, item_part;
     uint64_t n_chunks = 0;
+    OwnedBuf ord_keys, ord_chunks, ord_cells, ord_start;       // chunk processing order (order_chunks)
+    int part_order = 1;            // option "part_order": the partition pass takes its chunks ordered by record slot (0 = by aid, A/B)
+    int part_q = 1024;             // option "part_q": bins of that order over the record slots in use ("Round-6 measurements")
     int partition = 1;
     bool exact_round = false;      // set by finalize for the rounds that redo flagged aids
     int part_sized = 1;            // option "part_sized": capacity-sized buckets on the first attempt (no count pass); 0 = always counted
@@ -3809,6 +3897,35 @@ static void reduce_name(otto_covis_ctx* c, int slot, int log2t, int threads, int
             k_reduce<__VA_ARGS__, 1, false><<<grid, threads, 0, s>>>(args);                            \
     } while (0)
 
+// The partition chunks ordered by where their records lie (comment above k_chunk_keys): *out points at the ordered copy
+// of chunks[]. Inside a bin the chunks keep their order (by aid, then by chunk).
+static int order_chunks(otto_covis_ctx* c, hipStream_t s, const uint64_t** out) {
+    const uint32_t n = (uint32_t)c->n_chunks;
+    const uint32_t n_blocks = (n + ORD_BLOCK - 1) / ORD_BLOCK;
+    int key_bits = 1, lgq = 0;                            // record slots in use < 2^key_bits, part_q = 2^lgq bins over them
+    while (key_bits < 62 && (1ull << key_bits) < c->rec_used) ++key_bits;
+    while ((2 << lgq) <= c->part_q) ++lgq;
+    const OrdBin bin{key_bits > lgq ? key_bits - lgq : 0, 1u << lgq};
+    const size_t n_cells = (size_t)bin.nb * n_blocks;
+    OTTO_TRY(c->ord_cells.ensure(n_cells * 4, 0, s));
+    OTTO_TRY(c->ord_start.ensure((n_cells + 1) * 8, 0, s));
+    OTTO_TRY(c->partial.ensure(scan_partial_bytes((int64_t)n_cells), 0, s));
+    OTTO_TRY(c->ord_keys.ensure((size_t)n * 8, 0, s));
+    OTTO_TRY(c->ord_chunks.ensure((size_t)n * 8, 0, s));
+    kname(c, OTTO_COVIS_T_PARTITION, "k_chunk_keys + k_ord_scatter");
+    uint32_t* cells = c->ord_cells.as<uint32_t>();
+    OTTO_HIP(hipMemsetAsync(cells, 0, n_cells * 4, s));
+    k_chunk_keys<<<(n + 15) / 16, 256, 0, s>>>(c->chunks.as<uint64_t>(), n, c->run_start.as<uint64_t>(), c->sorted_desc.as<uint64_t>(), bin,
+                                             n_blocks, c->ord_keys.as<uint64_t>(), cells);
+    OTTO_HIP(hipGetLastError());
+    OTTO_TRY(device_scan(OrdCell{cells}, (int64_t)n_cells, c->ord_start.as<uint64_t>(), c->partial.as<uint64_t>(), s));
+    k_ord_scatter<<<n_blocks, ORD_BLOCK, 0, s>>>(c->ord_keys.as<uint64_t>(), c->chunks.as<uint64_t>(), n, bin, n_blocks,
+                                                c->ord_start.as<uint64_t>(), c->ord_chunks.as<uint64_t>());
+    OTTO_HIP(hipGetLastError());
+    *out = c->ord_chunks.as<uint64_t>();
+    return 0;
+}
+
 // bucket the records of the partitioned heavy aids by hash partition (a: the L item list of this pass). Leaves pstart / pcursor /
 // prec (/ ptw) in the context. Synchronises `s` once (bucket total -> allocation).
 static int run_partition(otto_covis_ctx* c, const ReduceArgs& a, bool time, hipStream_t s) {
@@ -3819,7 +3936,9 @@ static int run_partition(otto_covis_ctx* c, const ReduceArgs& a, bool time, hipS
     OTTO_TRY(c->pstart.ensure((size_t)(a.n_items + 1) * 8, 0, s));
     OTTO_TRY(c->partial.ensure(scan_partial_bytes((int64_t)a.n_items), 0, s));
     OTTO_HIP(hipMemsetAsync(c->pcursor.p, 0, (size_t)a.n_items * 4, s));
-    PartArgs pa{c->chunks.as<uint64_t>(), (uint32_t)c->n_chunks, c->cnt64.as<uint64_t>(), c->boost.as<uint8_t>(),
+    const uint64_t* chunks = c->chunks.as<uint64_t>();
+    if (c->part_order) OTTO_TRY(order_chunks(c, s, &chunks));   // both passes below take the chunks in this order
+    PartArgs pa{chunks, (uint32_t)c->n_chunks, c->cnt64.as<uint64_t>(), c->boost.as<uint8_t>(),
                 c->run_start.as<uint64_t>(), c->sorted_desc.as<uint64_t>(), c->rec.as<uint32_t>(), c->tw.as<uint32_t>(),
                 c->litem_start.as<uint64_t>(), c->pcount.as<uint32_t>(), c->pcursor.as<uint32_t>(),
                 c->pstart.as<uint64_t>(), nullptr, nullptr, c->l_cap, c->p.window, a.allow_packed, c->flag.as<uint32_t>(),
@@ -4087,6 +4206,14 @@ extern "C" int otto_covis_set_option(otto_covis_ctx* c, const char* name, int64_
     if (strcmp(name, "bkt_sh") == 0) { c->bkt_sh = (int)value; c->index_valid = false; return 0; }
     if (strcmp(name, "hot") == 0) { c->hot = value < 0 ? 0 : (value > 2 ? 2 : (int)value); return 0; }
     if (strcmp(name, "part_sized") == 0) { c->part_sized = value != 0; return 0; }   // A/B: counted buckets only
+    if (strcmp(name, "part_order") == 0) { c->part_order = value != 0; return 0; }   // 0: chunks by aid, then chunk (A/B)
+    if (strcmp(name, "part_q") == 0) {
+        // bins of the chunk order over the record slots in use (A/B)
+        OTTO_REQUIRE(value >= 2 && value <= (1 << ORD_MAX_BITS) && (value & (value - 1)) == 0, "part_q must be a power of two in [2, %d]",
+                     1 << ORD_MAX_BITS);
+        c->part_q = (int)value;
+        return 0;
+    }
     if (strcmp(name, "partition") == 0) {
         // 1 (default): bucket heavy aids' records by hash partition once; 0: every partition re-reads
         // all of its aid's records and filters (round-1 baseline, kept for A/B measurements)
