@@ -102,7 +102,6 @@ def frame_to_events_device(frame, device='cuda:0', n_aids=None, ts_unit='auto'):
     sort and the CSR session offsets all run in HIP kernels (``include/otto_events.h``): no ``pd.concat``, no host lexsort
     of 223 M rows. Same semantics as the NumPy path on the concatenated frame: ties keep their input order; ``ts_unit``
     's', 'ms' or 'auto'."""
-    import ctypes as C
     import torch
     from . import _lib
     dev = torch.device(device)
@@ -110,7 +109,7 @@ def frame_to_events_device(frame, device='cuda:0', n_aids=None, ts_unit='auto'):
         raise _lib.OttoError('frame_to_events_device needs a ROCm device (the NumPy path is events.frame_to_events)')
     if dev.index is None:
         dev = torch.device('cuda', torch.cuda.current_device())     # the tensors' device carries its index
-    lib = _lib.lib()
+    _lib.lib()                                             # a missing library is an error before anything is copied
     frames = list(frame) if isinstance(frame, (list, tuple)) else [frame]
 
     def host(c):                                          # one column chunk -> NumPy
@@ -160,7 +159,17 @@ def frame_to_events_device(frame, device='cuda:0', n_aids=None, ts_unit='auto'):
             elif m:
                 d_type[o:o + m].copy_(_to_device(host(c), np.uint8, dev))
             o += m
-        ws_bytes = int(lib.otto_events_sort_workspace(n))
+        return _sort_to_events(dev, d_sess, d_ts, d_aid, d_type, n, div, n_aids)
+
+
+def _sort_to_events(dev, d_sess, d_ts, d_aid, d_type, n, div, n_aids):
+    """The tail that the frame and the JSONL path share: the stable (session, ts // div) sort and the CSR of
+    ``otto_events_sort`` over the unsorted device columns -> :class:`DeviceEvents`."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    with torch.cuda.device(dev):
+        ws_bytes = int(_lib.lib().otto_events_sort_workspace(n))
         ws = _lib.workspace(ws_bytes, dev)
         o_aid = torch.empty(n, dtype=torch.int32, device=dev)
         o_ts = torch.empty(n, dtype=torch.int32, device=dev)
@@ -173,3 +182,27 @@ def frame_to_events_device(frame, device='cuda:0', n_aids=None, ts_unit='auto'):
                   C.byref(ns), ws, ws_bytes)
         S = int(ns.value)
         return DeviceEvents(o_aid, o_ts, o_type, sess_off[:S + 1].clone(), sess_id[:S].to(torch.int64) & 0xFFFFFFFF, o_order, int(n_aids))
+
+
+def jsonl_to_events_device(paths, device='cuda:0', n_aids=None, ts_unit='auto', chunk_bytes=256 << 20):
+    """The dataset's own files -> :class:`DeviceEvents`: ``train.jsonl`` / ``test.jsonl`` (one path or a list, read in order)
+    are parsed on the device (``jsonl.read_columns``, ``include/otto_jsonl.h``), then the same division rule, the same
+    ``otto_events_sort`` call and the same constructor arguments as :func:`frame_to_events_device` apply. The result is
+    bit-identical, ``order`` included, to ``frame_to_events_device`` of the frame the reference's ``create_dataframe``
+    (``src/utilities/dataset_writer_pickle.py:11-65``) builds from the same files; no frame and no pickle is made."""
+    import torch
+    from . import _lib, jsonl
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.OttoError('jsonl_to_events_device needs a ROCm device (no CPU fallback)')
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        d_sess, d_aid, d_ts, d_type = jsonl.read_columns(paths, dev, chunk_bytes)
+        n = int(d_ts.numel())
+        div = 1
+        if n and (ts_unit == 'ms' or (ts_unit == 'auto' and int(d_ts.max()) > 10 ** 11)):
+            div = 1000
+        if n_aids is None:
+            n_aids = (int((d_aid.to(torch.int64) & 0xFFFFFFFF).max()) if n else 0) + 1
+        return _sort_to_events(dev, d_sess, d_ts, d_aid, d_type, n, div, n_aids)
