@@ -1,6 +1,7 @@
 /*
  * otto_sgns.h -- C-ABI of the skip-gram negative-sampling (SGNS) aid embedding trainer (SPEC-SGNS):
- * the negative-sampling table, the per-epoch plan (subsampling, compaction, shrunken windows) and the SGD step.
+ * the negative-sampling table, the per-epoch plan (subsampling, compaction, shrunken windows), the SGD step, and the
+ * hierarchical-softmax half of gensim's hs: 1 (SPEC-SGNS-HS below: Huffman tree, path tables, a third table Syn1).
  *
  * What this replaces in the reference: src/gensim_fasttext/trainer.py, i.e. fasttext.train_unsupervised with
  * models/fasttext/config.yaml (skipgram, loss ns, dim 32, ws 10, neg 40, epoch 5, t 1e-4, minn = maxn = 0: no sub-words,
@@ -66,6 +67,33 @@
  *                      (h = In[centre] stays fixed over the centre's pairs), the g * Out[t] and g * h contributions are
  *                      summed per row into the caller's dense float64 gradient workspaces, and In += gIn, Out += gOut is
  *                      applied once. The workspaces must be all zero on entry and are all zero again on return.
+ *
+ * SPEC-SGNS-HS: hierarchical softmax next to the negatives (gensim Word2Vec(sg=1, hs=1, negative>0), the reference's
+ * models/word2vec/config.yaml; otto_sgns_hs_tree, otto_sgns_step_hs). gensim trains every (centre, context) pair twice
+ * against the same hidden vector: down the Huffman path of one word, then against the negative samples. gensim is not part
+ * of this build, so like SPEC-SGNS this is build-defined and parity-unpinned; tests/sgns_hs_restatement.py is the checker.
+ * Two departures are deliberate. (1) The tree is word2vec.c's CreateBinaryTree (fastText's buildTree), two cursors over
+ * the sorted counts, not gensim's heap, whose order among equal counts is not pinned. (2) gensim predicts the centre from
+ * the context's vector; SPEC-SGNS predicts the context from the centre's vector and the path follows that direction: it is
+ * the CONTEXT's path, walked against h = In[centre]. Over a session's symmetric windows the pair multiset is the same.
+ *
+ * Vocabulary. The aids with count >= max(min_count, 1), V of them; leaves 0..V-1 in (count descending, aid ascending)
+ * order, the order save_vec writes.
+ * Tree. cnt[0..V) = the leaf counts (int64), cnt[V..2V-1) = a sentinel above any sum; p1 = V-1, p2 = V. For a in 0..V-2
+ * choose min1 and then min2 by the same rule: the leaf p1-- if p1 >= 0 and cnt[p1] < cnt[p2], else the inner node p2++ (a
+ * tie takes the inner node). cnt[V+a] = cnt[min1] + cnt[min2]; parent[min1] = parent[min2] = V+a; bit[min2] = 1 (bit[min1]
+ * = 0). Inner node id = node - V in [0, V-1); the root is V-2.
+ * Paths. For an in-vocabulary aid t the path is the inner ids from the root down to the leaf's parent, L_t of them; bit j
+ * is the bit of the child taken below path node j. path_off int64 [n_aids+1] (CSR; an out-of-vocabulary aid has an empty
+ * row), path_node int32 [sum L], code uint64 [n_aids] with bit j in bit position j. L_t > 64: OTTO_EINVAL, nothing
+ * written. V < 2: no inner node, every path empty.
+ * Update. Syn1 float32 [max(V-1, 1), d], zero-initialised. For pair k of centre c with context aid ctx, h and grad as in
+ * SPEC-SGNS: first for j in 0..L-1, n = path_node[path_off[ctx] + j]: label = 1 - bit_j, x = <h, Syn1[n]>,
+ * g = lr * (label - sigmoid(x)), grad += g * Syn1[n], Syn1[n] += g * h, loss += softplus(label ? -x : x); then the
+ * 1 + neg targets of SPEC-SGNS on Out, unchanged (the same draws, the same keys); h += grad once after all targets of
+ * the pair.
+ * Modes. HOGWILD and BATCH as above; in BATCH every x and g comes from the pre-launch In / Out / Syn1, and a third dense
+ * float64 workspace gsyn1 [max(V-1, 1), d] is summed by atomics and applied once: zero on entry, zero again on return.
  */
 #ifndef OTTO_SGNS_H
 #define OTTO_SGNS_H
@@ -129,6 +157,28 @@ int otto_sgns_step(const int32_t* d_tok_aid, const int64_t* d_tok_src, const uin
                    int64_t T, int64_t t0, int64_t t1, float* d_In, float* d_Out, int32_t d, int32_t neg, float lr,
                    int32_t mode, uint64_t seed, uint64_t epoch, const otto_sgns_table* table, double* d_loss_sum,
                    int32_t* d_ctx_out, int32_t* d_neg_out, int64_t out_pairs, double* d_gin, double* d_gout, void* stream);
+
+/* SPEC-SGNS-HS: the Huffman tree over count int64 [n_aids] (HOST pointers, no device work, no stream).
+ * otto_sgns_hs_tree_sizes: sizes int64 [3] = { V, sum of the path lengths, the longest path }, so that the caller can size
+ * path_node; it reports a longest path above 64 without refusing it. otto_sgns_hs_tree fills path_off int64 [n_aids+1],
+ * path_node int32 [cap_nodes >= sum L] and code uint64 [n_aids]; a path longer than 64, or cap_nodes below sum L, is
+ * OTTO_EINVAL with the outputs unwritten. 1 <= n_aids < 2^31, counts >= 0 with a sum below 2^62. O(V log V) for the leaf
+ * order, O(V) for the merge, O(sum L) for the paths. */
+int otto_sgns_hs_tree_sizes(const int64_t* count, int64_t n_aids, int64_t min_count, int64_t* sizes);
+int otto_sgns_hs_tree(const int64_t* count, int64_t n_aids, int64_t min_count, int64_t* path_off, int32_t* path_node,
+                      int64_t cap_nodes, uint64_t* code);
+
+/* otto_sgns_step with the path half of SPEC-SGNS-HS in front of each pair's targets. d_path_off int64 [n_aids+1],
+ * d_path_node int32 [path_off[n_aids]], d_code uint64 [n_aids]: the tables of otto_sgns_hs_tree on the device;
+ * d_Syn1 float32 [n_inner, d], n_inner >= 1 (max(V-1, 1)); a path id outside [0, n_inner) is skipped, its row never
+ * touched. d_gsyn1 double [n_inner, d]: the third BATCH workspace, ignored (nullable) in HOGWILD mode. With every path
+ * empty the call equals otto_sgns_step. */
+int otto_sgns_step_hs(const int32_t* d_tok_aid, const int64_t* d_tok_src, const uint8_t* d_tok_left, const int64_t* d_pair_off,
+                      int64_t T, int64_t t0, int64_t t1, float* d_In, float* d_Out, int32_t d, int32_t neg, float lr,
+                      int32_t mode, uint64_t seed, uint64_t epoch, const otto_sgns_table* table, double* d_loss_sum,
+                      int32_t* d_ctx_out, int32_t* d_neg_out, int64_t out_pairs, double* d_gin, double* d_gout,
+                      const int64_t* d_path_off, const int32_t* d_path_node, const uint64_t* d_code, float* d_Syn1,
+                      int64_t n_inner, double* d_gsyn1, void* stream);
 
 #ifdef __cplusplus
 }

@@ -237,6 +237,11 @@ SIGNATURES = {
                               _vp, _p_i64, _vp, _i64, _vp]),
     'otto_sgns_step': (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, C.c_float, _i32, C.c_uint64, C.c_uint64,
                               C.POINTER(SgnsTable), _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    'otto_sgns_step_hs': (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, C.c_float, _i32, C.c_uint64,
+                                 C.c_uint64, C.POINTER(SgnsTable), _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
+                                 _vp]),
+    'otto_sgns_hs_tree_sizes': (_i32, [_vp, _i64, _i64, _p_i64]),
+    'otto_sgns_hs_tree': (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -9,12 +9,15 @@
 //   k_sgns_plan_tokens   one thread per event: session by binary search of sess_off, token record, radius, clipped window.
 //   k_sgns_plan_off      tok_off[s] = pos[sess_off[s]].
 //   device_scan     over the pair counts: pair_off.
-//   k_sgns_step<BATCH>   one lane group of d/4 lanes per centre, grid-stride. h and grad live in registers, rows move as float4.
-//                   The 1 + neg target ids of a pair are drawn by the group's lanes into LDS before any row is loaded, then
-//                   the rows are fetched four at a time. HOGWILD: plain stores in place. BATCH: float64 atomics into the
-//                   dense workspaces, no table is written.
+//   k_sgns_step<BATCH, HS>  one lane group of d/4 lanes per centre, grid-stride. h and grad live in registers, rows move as
+//                   float4. The 1 + neg target ids of a pair are drawn by the group's lanes into LDS before any row is loaded,
+//                   then the rows are fetched four at a time (sg_targets). HOGWILD: plain stores in place. BATCH: float64
+//                   atomics into the dense workspaces, no table is written. HS (SPEC-SGNS-HS): the Syn1 rows on the Huffman
+//                   path of the context go through sg_targets first; their ids are read from path_node (the same address in
+//                   every lane of the group), the pair's code word is one uint64.
 //   k_sgns_apply         BATCH: table += workspace, workspace = 0 (dense sweep).
 //   k_sgns_loss_final    sums the per-workgroup loss partials in a fixed order.
+// Host: otto_sgns_hs_tree_sizes / otto_sgns_hs_tree build the Huffman tree and the path tables of SPEC-SGNS-HS (no HIP call).
 #include "common.h"
 #include "wave.h"
 #include "scan.h"
@@ -22,6 +25,10 @@
 #include "../../include/otto_sgns.h"
 
 #include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
 
 namespace otto {
 
@@ -186,6 +193,13 @@ struct SgStepArgs {
     int64_t out_pairs;
     double* gin;
     double* gout;
+    // SPEC-SGNS-HS (read by the HS instantiations alone)
+    const int64_t* path_off;
+    const int32_t* path_node;
+    const uint64_t* code;
+    float* Syn1;
+    double* gsyn1;
+    uint32_t n_inner;
 };
 
 static __device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
@@ -209,7 +223,48 @@ static __device__ __forceinline__ int32_t sgns_negative(const SgTable& t, uint64
     return (int32_t)(((int64_t)ctx + 1) % t.n);
 }
 
-template <bool BATCH>
+// The rows idf(0) .. idf(n - 1) of `tab` against h, four at a time: the loads of a four go out before its first update.
+// idf(m) < 0: no row. labf(m): the label. DUP: a row named twice in a four sees its own earlier update (HOGWILD over drawn
+// targets; a Huffman path never repeats a node).
+template <bool BATCH, bool DUP, class IdFn, class LabelFn>
+static __device__ __forceinline__ void sg_targets(float* tab, double* gtab, int d, int G, int gl, int n, float lr, const float4& h,
+                                                  float4& grad, double& lsum, IdFn idf, LabelFn labf) {
+    for (int m0 = 0; m0 < n; m0 += 4) {
+        int32_t id[4];
+        float4 row[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            id[q] = m0 + q < n ? idf(m0 + q) : -1;
+            if (id[q] >= 0) row[q] = ld4(tab + (int64_t)id[q] * d + 4 * gl);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (id[q] < 0) continue;
+            float* po_ = tab + (int64_t)id[q] * d + 4 * gl;
+            if (!BATCH && DUP) {
+                bool dup = false;
+#pragma unroll
+                for (int w = 0; w < q; ++w) dup |= id[w] == id[q];
+                if (dup) row[q] = ld4(po_);
+            }
+            const float4 o = row[q];
+            const float x = group_sum(dot4(h, o), G);
+            const bool pos = labf(m0 + q);
+            const float g = lr * ((pos ? 1.0f : 0.0f) - sigmoidf_exact(x));
+            if (gl == 0) lsum += (double)softplusf_exact(pos ? -x : x);
+            grad.x += g * o.x; grad.y += g * o.y; grad.z += g * o.z; grad.w += g * o.w;
+            if (BATCH) {
+                double* go = gtab + (int64_t)id[q] * d + 4 * gl;
+                atomicAdd(go + 0, (double)(g * h.x)); atomicAdd(go + 1, (double)(g * h.y));
+                atomicAdd(go + 2, (double)(g * h.z)); atomicAdd(go + 3, (double)(g * h.w));
+            } else {
+                st4(po_, make_float4(o.x + g * h.x, o.y + g * h.y, o.z + g * h.z, o.w + g * h.w));
+            }
+        }
+    }
+}
+
+template <bool BATCH, bool HS>
 __global__ __launch_bounds__(SG_THREADS) void k_sgns_step(SgStepArgs a) {
     // the target ids of the pair each lane group is working on
     __shared__ int32_t s_ids[SG_MAX_GROUPS * SG_MAX_TARGETS];
@@ -249,40 +304,20 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgns_step(SgStepArgs a) {
                     for (int m = 1 + gl; m < nt; m += G) a.neg_out[po * a.neg + (m - 1)] = ids[m];
             }
             float4 grad = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int m0 = 0; m0 < nt; m0 += 4) {
-                int32_t id[4];
-                float4 row[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    id[q] = m0 + q < nt ? ids[m0 + q] : -1;
-                    if (id[q] >= 0) row[q] = ld4(a.Out + (int64_t)id[q] * a.d + 4 * gl);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (id[q] < 0) continue;
-                    float* po_ = a.Out + (int64_t)id[q] * a.d + 4 * gl;
-                    if (!BATCH) {
-                        // a target drawn twice in these four sees its own earlier update
-                        bool dup = false;
-#pragma unroll
-                        for (int w = 0; w < q; ++w) dup |= id[w] == id[q];
-                        if (dup) row[q] = ld4(po_);
-                    }
-                    const float4 o = row[q];
-                    const float x = group_sum(dot4(h, o), G);
-                    const bool pos = m0 + q == 0;
-                    const float g = lr * ((pos ? 1.0f : 0.0f) - sigmoidf_exact(x));
-                    if (gl == 0) lsum += (double)softplusf_exact(pos ? -x : x);
-                    grad.x += g * o.x; grad.y += g * o.y; grad.z += g * o.z; grad.w += g * o.w;
-                    if (BATCH) {
-                        double* go = a.gout + (int64_t)id[q] * a.d + 4 * gl;
-                        atomicAdd(go + 0, (double)(g * h.x)); atomicAdd(go + 1, (double)(g * h.y));
-                        atomicAdd(go + 2, (double)(g * h.z)); atomicAdd(go + 3, (double)(g * h.w));
-                    } else {
-                        st4(po_, make_float4(o.x + g * h.x, o.y + g * h.y, o.z + g * h.z, o.w + g * h.w));
-                    }
-                }
+            if (HS) {
+                // the path of ctx from the root: label 1 - bit; a row outside [0, n_inner) is skipped, never touched
+                const int64_t off = a.path_off[ctx];
+                const int64_t len = a.path_off[ctx + 1] - off;
+                const int L = off < 0 || len < 0 ? 0 : (int)(len > 64 ? 64 : len);
+                const uint64_t code = a.code[ctx];
+                const int32_t* pn = a.path_node + off;
+                const uint32_t n_inner = a.n_inner;
+                sg_targets<BATCH, false>(a.Syn1, a.gsyn1, a.d, G, gl, L, lr, h, grad, lsum,
+                                         [&](int m) { const uint32_t n = (uint32_t)pn[m]; return n < n_inner ? (int32_t)n : -1; },
+                                         [&](int m) { return ((code >> m) & 1ull) == 0; });
             }
+            sg_targets<BATCH, true>(a.Out, a.gout, a.d, G, gl, nt, lr, h, grad, lsum, [&](int m) { return ids[m]; },
+                                    [](int m) { return m == 0; });
             if (BATCH) {
                 gsum.x += grad.x; gsum.y += grad.y; gsum.z += grad.z; gsum.w += grad.w;
             } else {
@@ -445,11 +480,22 @@ extern "C" int otto_sgns_plan(const int32_t* d_aid, int64_t E, const int64_t* d_
     return 0;
 }
 
-extern "C" int otto_sgns_step(const int32_t* d_tok_aid, const int64_t* d_tok_src, const uint8_t* d_tok_left,
-                              const int64_t* d_pair_off, int64_t T, int64_t t0, int64_t t1, float* d_In, float* d_Out, int32_t d,
-                              int32_t neg, float lr, int32_t mode, uint64_t seed, uint64_t epoch, const otto_sgns_table* table,
-                              double* d_loss_sum, int32_t* d_ctx_out, int32_t* d_neg_out, int64_t out_pairs, double* d_gin,
-                              double* d_gout, void* stream) {
+namespace otto {
+
+// what otto_sgns_step_hs adds to otto_sgns_step
+struct SgHsTables {
+    const int64_t* path_off;
+    const int32_t* path_node;
+    const uint64_t* code;
+    float* Syn1;
+    int64_t n_inner;
+    double* gsyn1;
+};
+
+static int sgns_step(const int32_t* d_tok_aid, const int64_t* d_tok_src, const uint8_t* d_tok_left, const int64_t* d_pair_off,
+                     int64_t T, int64_t t0, int64_t t1, float* d_In, float* d_Out, int32_t d, int32_t neg, float lr, int32_t mode,
+                     uint64_t seed, uint64_t epoch, const otto_sgns_table* table, double* d_loss_sum, int32_t* d_ctx_out,
+                     int32_t* d_neg_out, int64_t out_pairs, double* d_gin, double* d_gout, const SgHsTables* hs, void* stream) {
     OTTO_REQUIRE(d >= 4 && d <= OTTO_SGNS_MAX_DIM && d % 4 == 0 && ((d / 4) & (d / 4 - 1)) == 0,
                  "d = %d: need a multiple of 4 in [4, %d] with d/4 a power of two", d, OTTO_SGNS_MAX_DIM);
     OTTO_REQUIRE(neg >= 0 && neg <= OTTO_SGNS_MAX_NEG, "neg = %d outside [0, %d]", neg, OTTO_SGNS_MAX_NEG);
@@ -460,6 +506,11 @@ extern "C" int otto_sgns_step(const int32_t* d_tok_aid, const int64_t* d_tok_src
     OTTO_REQUIRE(T == 0 || (d_tok_aid && d_tok_src && d_tok_left), "null plan array");
     OTTO_REQUIRE(mode == OTTO_SGNS_HOGWILD || (d_gin && d_gout), "BATCH mode needs both gradient workspaces");
     OTTO_REQUIRE(out_pairs >= 0 && (out_pairs > 0 || (!d_ctx_out && !d_neg_out)), "ctx_out / neg_out without out_pairs");
+    if (hs) {
+        OTTO_REQUIRE(hs->path_off && hs->path_node && hs->code && hs->Syn1, "null hierarchical-softmax table");
+        OTTO_REQUIRE(hs->n_inner >= 1 && hs->n_inner < (1ll << 31), "n_inner = %lld outside [1, 2^31)", (long long)hs->n_inner);
+        OTTO_REQUIRE(mode == OTTO_SGNS_HOGWILD || hs->gsyn1, "BATCH mode needs the Syn1 gradient workspace");
+    }
     hipStream_t s = (hipStream_t)stream;
     if (t0 == t1) {
         OTTO_HIP(hipMemsetAsync(d_loss_sum, 0, sizeof(double), s));
@@ -480,17 +531,137 @@ extern "C" int otto_sgns_step(const int32_t* d_tok_aid, const int64_t* d_tok_src
     a.T = T; a.t0 = t0; a.t1 = t1; a.In = d_In; a.Out = d_Out; a.d = d; a.G = d / 4; a.neg = neg; a.lr = lr;
     a.base = sg_base(seed, epoch); a.partial = reinterpret_cast<double*>(scratch);
     a.ctx_out = d_ctx_out; a.neg_out = neg > 0 ? d_neg_out : nullptr; a.out_pairs = out_pairs; a.gin = d_gin; a.gout = d_gout;
+    if (hs) {
+        a.path_off = hs->path_off; a.path_node = hs->path_node; a.code = hs->code; a.Syn1 = hs->Syn1; a.gsyn1 = hs->gsyn1;
+        a.n_inner = (uint32_t)hs->n_inner;
+    }
     const int threads = a.G >= 4 ? SG_THREADS : 64 * a.G;
     const int grid = grid_for(t1 - t0, threads / a.G);
     if (mode == OTTO_SGNS_HOGWILD) {
-        k_sgns_step<false><<<grid, threads, 0, s>>>(a);
+        if (hs) k_sgns_step<false, true><<<grid, threads, 0, s>>>(a);
+        else k_sgns_step<false, false><<<grid, threads, 0, s>>>(a);
     } else {
-        k_sgns_step<true><<<grid, threads, 0, s>>>(a);
+        if (hs) k_sgns_step<true, true><<<grid, threads, 0, s>>>(a);
+        else k_sgns_step<true, false><<<grid, threads, 0, s>>>(a);
         const int64_t n = table->n_aids * (int64_t)d;
         k_sgns_apply<<<grid_for(n, 256), 256, 0, s>>>(d_In, d_gin, n);
         k_sgns_apply<<<grid_for(n, 256), 256, 0, s>>>(d_Out, d_gout, n);
+        if (hs) k_sgns_apply<<<grid_for(hs->n_inner * (int64_t)d, 256), 256, 0, s>>>(hs->Syn1, hs->gsyn1, hs->n_inner * (int64_t)d);
     }
     k_sgns_loss_final<<<1, 256, 0, s>>>(a.partial, grid, d_loss_sum);
     OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
+// The tree of SPEC-SGNS-HS over the in-vocabulary aids: leaves 0..V-1 in (count desc, aid asc) order, inner nodes V..2V-2.
+struct SgTree {
+    std::vector<int32_t> leaf_aid;      // [V]
+    std::vector<int32_t> parent;        // [2V - 1]
+    std::vector<uint8_t> bit;           // [2V - 1]
+    std::vector<int32_t> depth;         // [2V - 1]: edges from the root
+    int64_t V = 0, sum_len = 0, max_len = 0;
+};
+
+static int sgns_hs_build(const int64_t* count, int64_t n_aids, int64_t min_count, SgTree* t) {
+    OTTO_REQUIRE(count, "null argument");
+    OTTO_REQUIRE(n_aids >= 1 && n_aids < (1ll << 31), "n_aids = %lld outside [1, 2^31)", (long long)n_aids);
+    const int64_t floor_count = min_count > 1 ? min_count : 1;
+    int64_t total = 0;
+    for (int64_t a = 0; a < n_aids; ++a) {
+        OTTO_REQUIRE(count[a] >= 0 && count[a] < (1ll << 62) - total, "count[%lld] is negative or the counts sum past 2^62",
+                     (long long)a);
+        total += count[a];
+        if (count[a] >= floor_count) t->leaf_aid.push_back((int32_t)a);
+    }
+    std::stable_sort(t->leaf_aid.begin(), t->leaf_aid.end(), [&](int32_t x, int32_t y) { return count[x] > count[y]; });
+    const int64_t V = t->V = (int64_t)t->leaf_aid.size();
+    if (V < 2) return 0;
+    std::vector<int64_t> cnt((size_t)(2 * V - 1), total + 1);       // the sentinel is above any sum
+    for (int64_t i = 0; i < V; ++i) cnt[i] = count[t->leaf_aid[i]];
+    t->parent.assign((size_t)(2 * V - 1), -1);
+    t->bit.assign((size_t)(2 * V - 1), 0);
+    int64_t p1 = V - 1, p2 = V;
+    for (int64_t a = 0; a < V - 1; ++a) {
+        int64_t mn[2];
+        for (int w = 0; w < 2; ++w) mn[w] = p1 >= 0 && cnt[p1] < cnt[p2] ? p1-- : p2++;    // a tie takes the inner node
+        cnt[V + a] = cnt[mn[0]] + cnt[mn[1]];
+        t->parent[mn[0]] = t->parent[mn[1]] = (int32_t)(V + a);
+        t->bit[mn[1]] = 1;
+    }
+    // a parent is made after its children, so it has the larger index: one sweep from the root down gives every depth
+    t->depth.assign((size_t)(2 * V - 1), 0);
+    for (int64_t n = 2 * V - 3; n >= 0; --n) t->depth[n] = t->depth[t->parent[n]] + 1;
+    for (int64_t i = 0; i < V; ++i) {
+        t->sum_len += t->depth[i];
+        if (t->depth[i] > t->max_len) t->max_len = t->depth[i];
+    }
+    return 0;
+}
+
+}  // namespace otto
+
+extern "C" int otto_sgns_step(const int32_t* d_tok_aid, const int64_t* d_tok_src, const uint8_t* d_tok_left,
+                              const int64_t* d_pair_off, int64_t T, int64_t t0, int64_t t1, float* d_In, float* d_Out, int32_t d,
+                              int32_t neg, float lr, int32_t mode, uint64_t seed, uint64_t epoch, const otto_sgns_table* table,
+                              double* d_loss_sum, int32_t* d_ctx_out, int32_t* d_neg_out, int64_t out_pairs, double* d_gin,
+                              double* d_gout, void* stream) {
+    return sgns_step(d_tok_aid, d_tok_src, d_tok_left, d_pair_off, T, t0, t1, d_In, d_Out, d, neg, lr, mode, seed, epoch, table,
+                     d_loss_sum, d_ctx_out, d_neg_out, out_pairs, d_gin, d_gout, nullptr, stream);
+}
+
+extern "C" int otto_sgns_step_hs(const int32_t* d_tok_aid, const int64_t* d_tok_src, const uint8_t* d_tok_left,
+                                 const int64_t* d_pair_off, int64_t T, int64_t t0, int64_t t1, float* d_In, float* d_Out, int32_t d,
+                                 int32_t neg, float lr, int32_t mode, uint64_t seed, uint64_t epoch, const otto_sgns_table* table,
+                                 double* d_loss_sum, int32_t* d_ctx_out, int32_t* d_neg_out, int64_t out_pairs, double* d_gin,
+                                 double* d_gout, const int64_t* d_path_off, const int32_t* d_path_node, const uint64_t* d_code,
+                                 float* d_Syn1, int64_t n_inner, double* d_gsyn1, void* stream) {
+    const SgHsTables hs = {d_path_off, d_path_node, d_code, d_Syn1, n_inner, d_gsyn1};
+    return sgns_step(d_tok_aid, d_tok_src, d_tok_left, d_pair_off, T, t0, t1, d_In, d_Out, d, neg, lr, mode, seed, epoch, table,
+                     d_loss_sum, d_ctx_out, d_neg_out, out_pairs, d_gin, d_gout, &hs, stream);
+}
+
+extern "C" int otto_sgns_hs_tree_sizes(const int64_t* count, int64_t n_aids, int64_t min_count, int64_t* sizes) {
+    OTTO_REQUIRE(sizes, "null argument");
+    try {
+        SgTree t;
+        OTTO_TRY(sgns_hs_build(count, n_aids, min_count, &t));
+        sizes[0] = t.V; sizes[1] = t.sum_len; sizes[2] = t.max_len;
+    } catch (const std::bad_alloc&) {
+        set_error("otto_sgns_hs_tree_sizes: out of host memory");
+        return OTTO_ENOMEM;
+    }
+    return 0;
+}
+
+extern "C" int otto_sgns_hs_tree(const int64_t* count, int64_t n_aids, int64_t min_count, int64_t* path_off, int32_t* path_node,
+                                 int64_t cap_nodes, uint64_t* code) {
+    OTTO_REQUIRE(path_off && code && cap_nodes >= 0 && (cap_nodes == 0 || path_node), "null argument");
+    try {
+        SgTree t;
+        OTTO_TRY(sgns_hs_build(count, n_aids, min_count, &t));
+        OTTO_REQUIRE(t.max_len <= 64, "the longest Huffman path has %lld nodes, a code word holds 64", (long long)t.max_len);
+        OTTO_REQUIRE(t.sum_len <= cap_nodes, "path_node: %lld ids, room for %lld", (long long)t.sum_len, (long long)cap_nodes);
+        const int64_t V = t.V;
+        for (int64_t a = 0; a <= n_aids; ++a) path_off[a] = 0;
+        for (int64_t a = 0; a < n_aids; ++a) code[a] = 0;
+        if (V < 2) return 0;
+        for (int64_t i = 0; i < V; ++i) path_off[t.leaf_aid[i] + 1] = t.depth[i];
+        for (int64_t a = 0; a < n_aids; ++a) path_off[a + 1] += path_off[a];
+        for (int64_t i = 0; i < V; ++i) {
+            // from the leaf up: the node at depth j - 1 is path node j - 1, the child below it carries bit j - 1
+            int32_t* row = path_node + path_off[t.leaf_aid[i]];
+            uint64_t cw = 0;
+            int64_t n = i;
+            for (int j = t.depth[i]; j > 0; --j) {
+                cw |= (uint64_t)t.bit[n] << (j - 1);
+                n = t.parent[n];
+                row[j - 1] = (int32_t)(n - V);
+            }
+            code[t.leaf_aid[i]] = cw;
+        }
+    } catch (const std::bad_alloc&) {
+        set_error("otto_sgns_hs_tree: out of host memory");
+        return OTTO_ENOMEM;
+    }
     return 0;
 }

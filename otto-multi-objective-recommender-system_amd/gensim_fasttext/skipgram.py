@@ -5,6 +5,10 @@ What this replaces in the reference: ``fasttext.train_unsupervised`` with ``mode
 ns, ``minn = maxn = 0``: no sub-words) and gensim's ``Word2Vec(sg=1, negative>0)`` of ``src/gensim_fasttext/trainer.py``.
 The vocabulary tables are computed here on the host in float64 and integers; subsampling, windows, negative draws and the
 SGD step run in HIP kernels. There is no CPU fallback.
+
+gensim's ``hs: 1`` next to ``negative > 0`` (SPEC-SGNS-HS) adds the Huffman path of every pair's context in front of its
+negative-sampling targets: :func:`huffman_tables` builds the tree and the path tables in the library (host C++), the
+engine takes them as ``hs=`` and trains a third table ``Syn1``.
 """
 import ctypes as C
 
@@ -68,6 +72,41 @@ def vocab_tables(aid, n_aids, min_count=1, t=1e-4, ns_exponent=0.5):
     return count, keep_q, weight
 
 
+class HuffmanTables:
+    """The path tables of SPEC-SGNS-HS (NumPy, host): ``V`` in-vocabulary aids, ``n_inner = max(V - 1, 1)`` rows of
+    ``Syn1``, ``path_off`` int64 [n_aids+1], ``path_node`` int32 [sum L], ``code`` uint64 [n_aids], ``max_len``."""
+
+    def __init__(self, V, path_off, path_node, code, max_len):
+        self.V, self.n_inner, self.max_len = int(V), max(int(V) - 1, 1), int(max_len)
+        self.path_off, self.path_node, self.code = path_off, path_node, code
+
+    @property
+    def n_aids(self):
+        return len(self.path_off) - 1
+
+    def lengths(self):
+        """int64 [n_aids]: the path length of every aid (0 outside the vocabulary)"""
+        return np.diff(self.path_off)
+
+
+def huffman_tables(count, min_count=1):
+    """:class:`HuffmanTables` over ``count`` int64 [n_aids] (:func:`vocab_tables`'s first result): the word2vec.c tree
+    over the aids with ``count >= max(min_count, 1)``, leaves by count descending then aid ascending. Built by
+    ``otto_sgns_hs_tree`` on the host; raises ``OttoError`` when a path is longer than the 64 bits of a code word."""
+    count = np.ascontiguousarray(np.asarray(count, dtype=np.int64))
+    if count.ndim != 1 or count.size < 1:
+        raise ValueError('count: expected int64 [n_aids], n_aids >= 1')
+    n = int(count.size)
+    sizes = np.zeros(3, dtype=np.int64)
+    _lib.call('otto_sgns_hs_tree_sizes', None, count, n, int(min_count), sizes.ctypes.data_as(C.POINTER(C.c_int64)), stream=False)
+    V, total, max_len = (int(x) for x in sizes)
+    path_off = np.zeros(n + 1, dtype=np.int64)
+    path_node = np.zeros(total, dtype=np.int32)
+    code = np.zeros(n, dtype=np.uint64)
+    _lib.call('otto_sgns_hs_tree', None, count, n, int(min_count), path_off, path_node, total, code, stream=False)
+    return HuffmanTables(V, path_off, path_node, code, max_len)
+
+
 def init_tables(n_aids, d, seed=0):
     """``(In, Out)`` float32 NumPy [n_aids, d]: ``In`` uniform(-1/d, 1/d), ``Out`` zeros, as fastText initialises."""
     rng = np.random.default_rng(int(seed))
@@ -96,9 +135,11 @@ def _as_u32_tensor(a, dev):
 
 
 class SkipGramEngine:
-    """Plan / step with persistent workspaces. ``keep_q`` / ``weight``: the uint32 tables of :func:`vocab_tables`."""
+    """Plan / step with persistent workspaces. ``keep_q`` / ``weight``: the uint32 tables of :func:`vocab_tables`.
+    ``hs``: the :class:`HuffmanTables` of :func:`huffman_tables` (or any object with its fields); they are uploaded, and
+    :meth:`step` then trains the path half of SPEC-SGNS-HS on a ``Syn1`` float32 [hs.n_inner, d] table."""
 
-    def __init__(self, n_aids, d, ws, neg, keep_q, weight, seed=0, device='cuda:0', n_buckets=None):
+    def __init__(self, n_aids, d, ws, neg, keep_q, weight, seed=0, device='cuda:0', n_buckets=None, hs=None):
         import torch
         self.dev = torch.device(device)
         if self.dev.type != 'cuda':
@@ -137,10 +178,50 @@ class SkipGramEngine:
         self._work = None
         self._bufs = None
         self._grads = None
+        self.hs = None
+        self.Syn1 = None                 # the table of the last HS step (train(hs=True) leaves its own here)
+        if hs is not None:
+            self._upload_hs(hs)
         self._loss = torch.zeros(1, dtype=torch.float64, device=self.dev)
 
     def _call(self, name, *args):
         _lib.call(name, self.dev, *args)
+
+    def _upload_hs(self, hs):
+        import torch
+        path_off = np.ascontiguousarray(np.asarray(hs.path_off, dtype=np.int64))
+        path_node = np.ascontiguousarray(np.asarray(hs.path_node, dtype=np.int32))
+        code = np.ascontiguousarray(np.asarray(hs.code, dtype=np.uint64))
+        n_inner = int(hs.n_inner)
+        if path_off.shape != (self.n_aids + 1,) or code.shape != (self.n_aids,):
+            raise ValueError(f'hs: path_off needs n_aids + 1 = {self.n_aids + 1} entries and code n_aids')
+        lens = np.diff(path_off)
+        if path_off[0] != 0 or (lens < 0).any() or (lens > 64).any() or path_off[-1] != path_node.size:
+            raise ValueError('hs: path_off must ascend from 0 to len(path_node) in rows of at most 64 ids')
+        if not 1 <= n_inner < 1 << 31 or (path_node.size and (path_node.min() < 0 or path_node.max() >= n_inner)):
+            raise ValueError('hs: n_inner must be positive and every path id below it')
+        self.hs = hs
+        self.n_inner = n_inner
+        self._path_off = torch.from_numpy(path_off).to(self.dev)
+        self._path_node = torch.from_numpy(path_node if path_node.size else np.zeros(1, dtype=np.int32)).to(self.dev)
+        self._code = torch.from_numpy(code.view(np.int64)).to(self.dev)
+        self._path_len = torch.from_numpy(lens.astype(np.int64)).to(self.dev)
+        self._gsyn1 = None
+
+    def path_targets(self, plan, t0=0, t1=None):
+        """The sum of the path lengths of the contexts of all pairs of the centres ``[t0, t1)`` of ``plan`` (an int),
+        computed on the device: the contexts of centre c are the tokens c - left .. c - 1 and c + 1 .. c + right, two
+        ranges of a prefix sum over the tokens' path lengths."""
+        import torch
+        t1 = plan.T if t1 is None else int(t1)
+        if self.hs is None or t1 <= t0:
+            return 0
+        cs = torch.zeros(plan.T + 1, dtype=torch.int64, device=self.dev)
+        cs[1:] = torch.cumsum(self._path_len[plan.tok_aid.to(torch.int64)], 0)
+        c = torch.arange(int(t0), t1, dtype=torch.int64, device=self.dev)
+        left = plan.tok_left[t0:t1].to(torch.int64)
+        right = plan.pair_off[t0 + 1:t1 + 1] - plan.pair_off[t0:t1] - left
+        return int((cs[c] - cs[c - left] + cs[c + 1 + right] - cs[c + 1]).sum().item())
 
     @property
     def total(self):
@@ -191,14 +272,21 @@ class SkipGramEngine:
                     radius=out['radius'][:T], tok_left=out['tok_left'][:T], pair_off=out['pair_off'][:T + 1], T=T, P=P,
                     epoch=int(epoch))
 
-    def step(self, plan, t0, t1, In, Out, lr, mode=HOGWILD, ctx_out=None, neg_out=None, loss=None):
+    def step(self, plan, t0, t1, In, Out, lr, mode=HOGWILD, ctx_out=None, neg_out=None, loss=None, Syn1=None):
         """One launch over the centres ``[t0, t1)`` of ``plan``; updates ``In`` / ``Out`` (float32 [n_aids, d] on the
         device) in place and returns the device float64 [1] loss sum. ``ctx_out`` int32 [pairs], ``neg_out`` int32
-        [pairs, neg]: the sampler's choices for the launch's pairs (tests)."""
+        [pairs, neg]: the sampler's choices for the launch's pairs (tests). An engine built with ``hs=`` takes the
+        SPEC-SGNS-HS entry point and needs ``Syn1`` float32 [hs.n_inner, d], updated in place as well; without tables
+        ``Syn1`` must stay None."""
         import torch
         for name, M in (('In', In), ('Out', Out)):
             if M.dtype != torch.float32 or tuple(M.shape) != (self.n_aids, self.d) or not M.is_contiguous() or M.device != self.dev:
                 raise ValueError(f'{name}: expected contiguous float32 [{self.n_aids}, {self.d}] on {self.dev}')
+        if self.hs is None and Syn1 is not None:
+            raise ValueError('Syn1 given to an engine without hierarchical-softmax tables')
+        if Syn1 is not None and (Syn1.dtype != torch.float32 or tuple(Syn1.shape) != (self.n_inner, self.d)
+                                 or not Syn1.is_contiguous() or Syn1.device != self.dev):
+            raise ValueError(f'Syn1: expected contiguous float32 [{self.n_inner}, {self.d}] on {self.dev}')
         if mode not in (HOGWILD, BATCH):
             raise ValueError(f'unknown mode {mode}')
         out_pairs = 0
@@ -214,6 +302,18 @@ class SkipGramEngine:
                     self._grads = (torch.zeros(self.n_aids, self.d, dtype=torch.float64, device=self.dev),
                                    torch.zeros(self.n_aids, self.d, dtype=torch.float64, device=self.dev))
                 gin, gout = self._grads
+            if self.hs is not None:
+                gsyn1 = None
+                if mode == BATCH:
+                    if self._gsyn1 is None:
+                        self._gsyn1 = torch.zeros(self.n_inner, self.d, dtype=torch.float64, device=self.dev)
+                    gsyn1 = self._gsyn1
+                self._call('otto_sgns_step_hs', plan.tok_aid, plan.tok_src, plan.tok_left, plan.pair_off, plan.T, int(t0), int(t1),
+                           In, Out, self.d, self.neg, float(lr), int(mode), self.seed, plan.epoch, C.byref(self.table), loss,
+                           ctx_out, neg_out, out_pairs, gin, gout, self._path_off, self._path_node, self._code, Syn1,
+                           self.n_inner, gsyn1)
+                self.Syn1 = Syn1
+                return loss
             self._call('otto_sgns_step', plan.tok_aid, plan.tok_src, plan.tok_left, plan.pair_off, plan.T, int(t0), int(t1), In, Out,
                        self.d, self.neg, float(lr), int(mode), self.seed, plan.epoch, C.byref(self.table), loss, ctx_out, neg_out,
                        out_pairs, gin, gout)
@@ -221,20 +321,27 @@ class SkipGramEngine:
 
 
 def train(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, t=1e-4, min_count=1, ns_exponent=0.5, seed=0,
-          mode=HOGWILD, tokens_per_launch=1 << 24, device=None):
+          mode=HOGWILD, tokens_per_launch=1 << 24, device=None, hs=False):
     """Train SGNS aid embeddings. ``aid`` int32 [E] sorted by (session, ts) and ``sess_off`` int64 [S+1], device tensors.
     Returns ``(In, Out, losses)``: the float32 [n_aids, dim] tables on the device and the per-epoch mean loss per pair
     target (loss sum / (pairs * (1 + neg))). The rate of a launch is :func:`learning_rate` at the source event of the
-    launch's first token."""
+    launch's first token.
+
+    ``hs=True`` (SPEC-SGNS-HS): every pair also walks the Huffman path of its context on a third table ``Syn1``
+    float32 [max(V - 1, 1), dim], zero-initialised. The mean loss then divides by ``pairs * (1 + neg)`` plus the sum of
+    the path lengths of the pairs' contexts (computed on the device from the plan), so it stays a mean per target.
+    The return value becomes ``(In, Out, losses, Syn1)``: the fourth entry exists only with ``hs=True``."""
     import torch
     dev = aid.device if device is None else torch.device(device)
     tokens_per_launch = int(tokens_per_launch)
     if tokens_per_launch < 1:
         raise ValueError('tokens_per_launch must be positive')
-    _, keep_q, weight = vocab_tables(aid, n_aids, min_count, t, ns_exponent)
-    eng = SkipGramEngine(n_aids, dim, ws, neg, keep_q, weight, seed=seed, device=dev)
+    count, keep_q, weight = vocab_tables(aid, n_aids, min_count, t, ns_exponent)
+    tables = huffman_tables(count, min_count) if hs else None
+    eng = SkipGramEngine(n_aids, dim, ws, neg, keep_q, weight, seed=seed, device=dev, hs=tables)
     In_h, Out_h = init_tables(n_aids, dim, seed)
     In, Out = torch.from_numpy(In_h).to(dev), torch.from_numpy(Out_h).to(dev)
+    Syn1 = torch.zeros(tables.n_inner, int(dim), dtype=torch.float32, device=eng.dev) if hs else None
     E = int(aid.numel())
     losses = []
     for ep in range(int(epochs)):
@@ -244,9 +351,9 @@ def train(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, t=1e-
         total = torch.zeros(1, dtype=torch.float64, device=dev)
         for t0, src in zip(starts, first_src):
             rate = learning_rate(lr, ep * E + int(src), int(epochs) * E)
-            total += eng.step(plan, t0, min(t0 + tokens_per_launch, plan.T), In, Out, rate, mode)
-        losses.append(float(total.item()) / max(plan.P * (1 + int(neg)), 1))
-    return In, Out, losses
+            total += eng.step(plan, t0, min(t0 + tokens_per_launch, plan.T), In, Out, rate, mode, Syn1=Syn1)
+        losses.append(float(total.item()) / max(plan.P * (1 + int(neg)) + eng.path_targets(plan), 1))
+    return (In, Out, losses, Syn1) if hs else (In, Out, losses)
 
 
 def save_vec(path, In, count, fmt='%.9g'):

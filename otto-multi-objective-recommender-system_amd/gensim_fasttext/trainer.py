@@ -9,8 +9,9 @@ text format, in-vocabulary aids by count descending then aid ascending). ``fastt
 written.
 
 Refused with ``ValueError``: ``model: cbow``, ``loss`` other than ``ns``, ``minn`` / ``maxn`` above 0 (fastText);
-``sg: 0`` or ``negative: 0`` (Word2Vec); ``Doc2Vec``. Hierarchical softmax is not built: ``hs: 1`` with ``negative > 0``
-(the reference's own file) trains the negative-sampling part alone and logs the departure once.
+``sg: 0`` or ``negative: 0`` (Word2Vec, with or without ``hs: 1``: hierarchical softmax alone is not built);
+``Doc2Vec``. ``hs: 1`` with ``negative > 0`` (the reference's own Word2Vec file) trains hierarchical softmax next to the
+negative-sampling part (SPEC-SGNS-HS), over the word2vec.c tree rather than gensim's heap; that departure is logged once.
 """
 import argparse
 import logging
@@ -50,10 +51,17 @@ def word2vec_args(model_args):
         raise ValueError('negative: 0 leaves hierarchical softmax alone, which is not built')
     if int(a.get('hs', 0)) and not _HS_WARNED:
         _HS_WARNED = True
-        logging.warning('hs: 1 -- hierarchical softmax is not built; training the negative-sampling part alone')
+        logging.warning('hs: 1 -- hierarchical softmax is trained next to the negative-sampling part, over the word2vec.c '
+                        "tree (two cursors over the sorted counts) rather than gensim's heap")
     return dict(dim=int(a.get('vector_size', 100)), ws=int(a.get('window', 5)), neg=int(a['negative'] if 'negative' in a else 5),
                 epochs=int(a.get('epochs', 5)), lr=float(a.get('alpha', 0.025)), t=float(a.get('sample', 1e-3)),
                 min_count=int(a.get('min_count', 5)), ns_exponent=float(a.get('ns_exponent', 0.75)), seed=int(a.get('seed', 1)))
+
+
+def hs_requested(config):
+    """True when ``config`` (the whole YAML mapping) asks for hierarchical softmax: ``Word2Vec`` with ``hs: 1``."""
+    model = config['model']
+    return model['model_name'] == 'Word2Vec' and bool(int(dict(model.get('model_args') or {}).get('hs', 0)))
 
 
 def train_args(config):
@@ -80,7 +88,8 @@ def run(config, df=None, device='cuda:0', n_aids=None, tokens_per_launch=1 << 24
         df = [pd.read_pickle(settings.DATA / 'train.pkl'), pd.read_pickle(settings.DATA / 'test.pkl')]
     ev = frame_to_events_device(df, device=device, n_aids=n_aids)
     logging.info(f'Sentences Dataset - sentences: {ev.n_sessions} - tokens: {ev.n_events}')
-    In, _, losses = skipgram.train(ev.aid, ev.sess_off, ev.n_aids, tokens_per_launch=tokens_per_launch, **kw)
+    In, _, losses = skipgram.train(ev.aid, ev.sess_off, ev.n_aids, tokens_per_launch=tokens_per_launch,
+                                   hs=hs_requested(config), **kw)[:3]
     for ep, ls in enumerate(losses):
         logging.info(f'epoch {ep}: mean loss {ls:.6f}')
     In = In.cpu().numpy()

@@ -8,11 +8,17 @@ Sessions from ``synth.generate_sessions`` (n_aids = 1,855,603), d = 32, ws = 10,
            against the 8 TB/s HBM peak. Per target 2 * 4d bytes of Out (read and written), per centre 2 * 4d bytes of In,
            per kept token 4 bytes of token id and 1 byte of radius; the ids of the drawn negatives are not counted.
 
+``--hs`` times the same launch through ``otto_sgns_step_hs`` (SPEC-SGNS-HS: the Huffman path of every pair's context on
+``Syn1`` in front of its 1 + neg targets; the reference's ``models/word2vec/config.yaml`` has ``window: 12``, so pass
+``--ws 12``). It adds the mean path length per pair and, to the algorithmic bytes, 2 * 4d bytes of ``Syn1`` plus 4 bytes of
+node id per path node per pair. Compare it with a run without ``--hs`` by alternating the two in one job, several processes
+each; ``--skip-host`` leaves the host baseline out of such runs.
+
 Host baseline, same run: vectorised NumPy batch steps of 4,096 centres over 2^16 tokens (the restatement's sequential loop is far too
 slow to time). No fastText or gensim figure exists: neither library is installed where this project is built.
 Needs a GPU; there is no fallback.
 
-    python tools/perf_sgns.py [--sessions 2000000] [--tokens 16777216] [--out profiles/sgns/perf_sgns.json]
+    python tools/perf_sgns.py [--sessions 2000000] [--tokens 16777216] [--hs] [--skip-host] [--out profiles/sgns/perf_sgns.json]
 """
 import argparse
 import json
@@ -73,6 +79,8 @@ def main():
     ap.add_argument('--host-tokens', type=int, default=1 << 16)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--hs', action='store_true', help='time otto_sgns_step_hs: the Huffman path half next to the negatives')
+    ap.add_argument('--skip-host', action='store_true', help='leave the NumPy host baseline out')
     ap.add_argument('--out', default='')
     args = ap.parse_args()
     import torch
@@ -85,25 +93,43 @@ def main():
     aid = torch.from_numpy(ev.aid.astype(np.int32)).to(dev)
     sess_off = torch.from_numpy(ev.sess_off).to(dev)
     n_aids, d, E = ev.n_aids, args.dim, int(aid.numel())
-    _, keep_q, weight = sg.vocab_tables(aid, n_aids, 1, args.t, 0.5)
-    eng = sg.SkipGramEngine(n_aids, d, args.ws, args.neg, keep_q, weight, seed=1, device=dev)
+    count, keep_q, weight = sg.vocab_tables(aid, n_aids, 1, args.t, 0.5)
+    tables = None
+    if args.hs:
+        t0 = time.perf_counter()
+        tables = sg.huffman_tables(count, 1)
+        tree_s = time.perf_counter() - t0
+    eng = sg.SkipGramEngine(n_aids, d, args.ws, args.neg, keep_q, weight, seed=1, device=dev, hs=tables)
     In_h, Out_h = sg.init_tables(n_aids, d, 1)
     In, Out = torch.from_numpy(In_h).to(dev), torch.from_numpy(Out_h).to(dev)
+    # hs: Syn1 starts at zero in training; a launch over zeros would time rows that never change, so it starts as In does
+    step_kw = {}
+    if args.hs:
+        step_kw['Syn1'] = torch.from_numpy(sg.init_tables(tables.n_inner, d, 2)[0]).to(dev)
     out = {'tool': 'perf_sgns', 'device': torch.cuda.get_device_name(0), 'sessions': args.sessions, 'events': E, 'n_aids': n_aids,
            'd': d, 'ws': args.ws, 'neg': args.neg, 't': args.t, 'warmup': args.warmup, 'repeats': args.repeats,
-           'table_bytes_each': n_aids * d * 4}
+           'table_bytes_each': n_aids * d * 4, 'hs': bool(args.hs)}
+    if args.hs:
+        out['huffman'] = {'V': tables.V, 'n_inner': tables.n_inner, 'max_len': tables.max_len, 'path_nodes': int(tables.path_node.size),
+                          'host_tree_seconds': round(tree_s, 3)}
     out['plan'] = _time(lambda: eng.plan(aid, sess_off, 0), args.warmup, args.repeats)
     plan = eng.plan(aid, sess_off, 0)
     n_tok = min(args.tokens, plan.T)
     pairs = int(plan.pair_off[n_tok] - plan.pair_off[0])
     out.update(kept_tokens=plan.T, pairs=plan.P, launch_tokens=n_tok, launch_pairs=pairs)
-    hw = _time(lambda: eng.step(plan, 0, n_tok, In, Out, 0.05, sg.HOGWILD), args.warmup, args.repeats)
+    hw = _time(lambda: eng.step(plan, 0, n_tok, In, Out, 0.05, sg.HOGWILD, **step_kw), args.warmup, args.repeats)
     sec = hw['median_ms'] * 1e-3
-    targets = pairs * (1 + args.neg)
-    n_bytes = targets * 2 * 4 * d + n_tok * 2 * 4 * d + n_tok * 5
+    path_rows = eng.path_targets(plan, 0, n_tok)
+    targets = pairs * (1 + args.neg) + path_rows
+    n_bytes = targets * 2 * 4 * d + n_tok * 2 * 4 * d + n_tok * 5 + path_rows * 4
+    if args.hs:
+        hw.update(path_rows=path_rows, mean_path_length_per_pair=round(path_rows / max(pairs, 1), 3))
     hw.update(tokens_per_s=round(n_tok / sec), target_rows_per_s=round(targets / sec), algorithmic_bytes=n_bytes,
               bytes_per_s=round(n_bytes / sec), share_of_hbm_peak=round(n_bytes / sec / HBM_PEAK, 4))
     out['hogwild'] = hw
+    if args.skip_host:
+        _emit(out, args.out)
+        return
     m = min(args.host_tokens, plan.T)
     tok_aid, left = plan.tok_aid[:m + 64].cpu().numpy().astype(np.int64), plan.tok_left[:m + 64].cpu().numpy()
     pair_off = plan.pair_off[:m + 65].cpu().numpy()
@@ -120,11 +146,15 @@ def main():
     out['host_numpy_batch_step'] = {'tokens': valid, 'pairs': host_pairs, 'seconds': round(hs, 3), 'tokens_per_s': round(valid / hs),
                                     'what': 'one run, one process, vectorised NumPy batch step on the host of the GPU machine; '
                                             'no fastText or gensim figure exists (neither is installed)'}
+    _emit(out, args.out)
+
+
+def _emit(out, path):
     line = json.dumps(out)
     print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as fh:
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, 'w') as fh:
             fh.write(line + '\n')
 
 
