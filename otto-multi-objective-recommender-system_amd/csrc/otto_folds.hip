@@ -15,10 +15,8 @@
 //   k_kf_scatter   fold_of_query[q] = fold_at[pos_of_q[q]].
 //   k_classify     one wave per query (grid-stride): positives of the query by ballot, then the state byte of every row;
 //                  N, P, Mv, Qt, Qv as per-wave sums and one integer atomic per wave and counter.
-//   k_sel_hist, k_sel_pick   radix select of the m-th smallest key among the eligible negatives, 8 digits of 8 bits from
-//                  the top. A pass reads the state bytes (4 per load), recomputes the key from the row index, and counts
-//                  the digit of the keys that carry the prefix found so far: wave-private LDS histograms, merged once per
-//                  workgroup, one integer global atomic per touched bin. No key array is stored.
+//   device_select  (select.h) radix select of the m-th smallest key among the eligible negatives; NegRows reads the state
+//                  bytes, 4 per load.
 //   k_query_counts one wave per query: kept rows of the query (validation rows, or positives + negatives with
 //                  key <= threshold).
 //   device_scan    (scan.h) twice over the queries: (kept queries << 32 | kept rows) of the training and validation side.
@@ -30,6 +28,7 @@
 #include "common.h"
 #include "wave.h"
 #include "scan.h"
+#include "select.h"
 #include "../../include/otto_covis.h"
 #include "../../include/otto_forest.h"
 #include "../../include/otto_gbdt.h"
@@ -43,20 +42,12 @@ constexpr int KF_BINS = MAXQ + 1;           // sizes 0 .. 1024
 constexpr int KF_CHUNK = 1024;              // queries per chunk until the chunk count reaches KF_MAX_CHUNKS
 constexpr int KF_MAX_CHUNKS = 1024;
 constexpr int GRID_WAVES_BLOCKS = 2048;     // fixed grid of the wave-per-query kernels (4 waves per workgroup)
-constexpr int SEL_BLOCKS = 1024;
 constexpr int ST_OUT = OTTO_FOLDS_OUT, ST_VAL = OTTO_FOLDS_VAL, ST_POS = OTTO_FOLDS_POS, ST_NEG = OTTO_FOLDS_NEG;
 constexpr int MODE_NONE = 0, MODE_THRESHOLD = 1, MODE_ALL = 2;
 // error words of a call
 constexpr int ERR_QUERY = 0, ERR_LABEL = 1, ERR_INDEX = 2, ERR_SIZE = 3, ERR_WORDS = 4;
 constexpr int COUNT_WORDS = OTTO_FOLDS_COUNT_WORDS;
 constexpr int CNT_N = 0, CNT_P = 1, CNT_MV = 2, CNT_QT = 3, CNT_QV = 4;
-
-__host__ __device__ __forceinline__ uint64_t row_key(uint64_t seed, uint64_t r) {
-    uint64_t z = seed + (r + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ bool query_ok(int64_t a, int64_t b, int64_t n) { return a >= 0 && a <= b && b <= n && b - a <= MAXQ; }
 
@@ -243,45 +234,17 @@ __global__ __launch_bounds__(256) void k_classify(const L* label, const int64_t*
     }
 }
 
-// sel = { prefix: the digits found so far, k: the rank (1-based) still wanted among the keys that carry the prefix }
-__global__ __launch_bounds__(256) void k_sel_hist(const uint32_t* state4, int64_t n4, uint64_t seed, const uint64_t* sel, int pass,
-                                                  uint32_t* hist) {
-    __shared__ uint32_t h[4][256];
-    for (int i = threadIdx.x; i < 4 * 256; i += 256) (&h[0][0])[i] = 0;
-    __syncthreads();
-    const uint64_t prefix = sel[0];
-    const int shift = 56 - 8 * pass;
-    uint32_t* mine = h[threadIdx.x >> 6];
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+// row source of the select: the eligible negatives; an item is four state bytes, one load
+struct NegRows {
+    const uint32_t* state4;
+    template <typename F>
+    __device__ void operator()(int64_t i, F count) const {
         const uint32_t w = state4[i];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (((w >> (8 * k)) & 255u) != (uint32_t)ST_NEG) continue;
-            const uint64_t key = row_key(seed, (uint64_t)(i * 4 + k));
-            if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&mine[(key >> shift) & 255u], 1u);
-        }
+        for (int k = 0; k < 4; ++k)
+            if (((w >> (8 * k)) & 255u) == (uint32_t)ST_NEG) count(i * 4 + k);
     }
-    __syncthreads();
-    const uint32_t s = h[0][threadIdx.x] + h[1][threadIdx.x] + h[2][threadIdx.x] + h[3][threadIdx.x];
-    if (s) atomicAdd(hist + threadIdx.x, s);
-}
-
-__global__ __launch_bounds__(64) void k_sel_pick(const uint32_t* hist, uint64_t* sel, int pass, uint64_t m) {
-    __shared__ uint32_t sm[256];
-    for (int i = threadIdx.x; i < 256; i += 64) sm[i] = hist[i];
-    wave_lds_sync();
-    if (threadIdx.x == 0) {
-        const uint64_t prefix = pass == 0 ? 0ull : sel[0];
-        uint64_t k = pass == 0 ? m : sel[1];
-        int d = 0;
-        for (; d < 255; ++d) {                         // the last digit takes what is left: no index past the table
-            if (sm[d] >= k) break;
-            k -= sm[d];
-        }
-        sel[0] = (prefix << 8) | (uint64_t)d;
-        sel[1] = k;
-    }
-}
+};
 
 __device__ __forceinline__ bool row_kept(uint32_t st, uint64_t seed, int64_t r, int mode, uint64_t threshold) {
     if (st == (uint32_t)ST_VAL || st == (uint32_t)ST_POS) return true;
@@ -490,8 +453,8 @@ EmitLayout emit_layout(int64_t Q) {
     w.tscan = at; at += align256((Q + 1) * 8);
     w.vscan = at; at += align256((Q + 1) * 8);
     w.partial = at; at += align256((int64_t)scan_partial_bytes(Q));
-    w.hist = at; at += align256(8 * 256 * 4);
-    w.sel = at; at += 256;
+    w.hist = at; at += SELECT_HIST_BYTES;
+    w.sel = at; at += SELECT_SEL_BYTES;
     w.bytes = at;
     return w;
 }
@@ -651,17 +614,8 @@ extern "C" int otto_folds_emit(const uint8_t* d_state, const int64_t* d_query_of
     uint32_t* err = nullptr;
     OTTO_TRY(err_begin(&err, s));
     const int mode = m == 0 ? MODE_NONE : m == n_eligible ? MODE_ALL : MODE_THRESHOLD;
-    if (mode == MODE_THRESHOLD) {
-        OTTO_HIP(hipMemsetAsync(hist, 0, 8 * 256 * 4, s));
-        const int64_t n4 = (n + 3) / 4;                                // d_state is padded with ST_OUT (otto_folds_state_bytes)
-        const unsigned grid = (unsigned)((n4 + 255) / 256 < SEL_BLOCKS ? (n4 + 255) / 256 : SEL_BLOCKS);
-        for (int pass = 0; pass < 8; ++pass) {
-            k_sel_hist<<<grid, 256, 0, s>>>((const uint32_t*)d_state, n4, seed, sel, pass, hist + pass * 256);
-            OTTO_HIP(hipGetLastError());
-            k_sel_pick<<<1, 64, 0, s>>>(hist + pass * 256, sel, pass, (uint64_t)m);
-            OTTO_HIP(hipGetLastError());
-        }
-    }
+    if (mode == MODE_THRESHOLD)     // d_state is padded with ST_OUT to whole dwords (otto_folds_state_bytes)
+        OTTO_TRY(device_select(NegRows{(const uint32_t*)d_state}, (n + 3) / 4, m, seed, hist, sel, s));
     const unsigned qgrid = (unsigned)(Q == 0 ? 1 : (Q + 3) / 4 < GRID_WAVES_BLOCKS ? (Q + 3) / 4 : GRID_WAVES_BLOCKS);
     k_query_counts<<<qgrid, 256, 0, s>>>(d_state, d_query_off, Q, n, seed, mode, sel, qcnt, err);
     OTTO_HIP(hipGetLastError());

@@ -20,10 +20,8 @@
 //   k_part_count, k_part_scan, k_part_scatter   stable partition of a leaf's row list: left rows per 2048-row block, one
 //                  workgroup's exclusive scan of those counts, then the scatter.
 //   k_add_tree     one lane per row walks the tree over the bins; bounded, range-checked.
-//   k_bag_hist, k_bag_pick   the row bag: radix select of the m-th smallest key among all n rows, 8 digits of 8 bits from
-//                  the top. A pass recomputes every key from its row index (no key array, nothing read from memory) and
-//                  counts the digit of the keys that carry the prefix found so far: wave-private LDS histograms, merged
-//                  once per workgroup, one integer global atomic per touched bin; one wave picks the digit.
+//   device_select  (select.h) the row bag: radix select of the m-th smallest key among all n rows; AllRows reads nothing
+//                  from memory.
 //   k_bag_count, device_scan (scan.h), k_bag_emit   every wave owns a contiguous run of rows: kept rows (key <= threshold)
 //                  per wave, an exclusive scan of the workgroups' sums, then the row ids by ballot rank behind the wave's
 //                  base: ascending ids, contiguous writes, every write checked against the caller's buffer.
@@ -33,6 +31,7 @@
 #include "common.h"
 #include "wave.h"
 #include "scan.h"
+#include "select.h"
 #include "../../include/otto_covis.h"
 #include "../../include/otto_forest.h"
 #include "../../include/otto_gbdt.h"
@@ -53,7 +52,7 @@ constexpr int PART_ROWS = 2048;     // rows per partition workgroup
 constexpr int SW = OTTO_GBDT_SPLIT_WORDS;
 // error words of a call
 constexpr int ERR_QUERY = 0, ERR_LABEL = 1, ERR_ROW = 2, ERR_WALK = 3, ERR_BAG = 4, ERR_WORDS = 5;
-constexpr int BAG_BLOCKS = 1024;    // fixed grid of the bag kernels (4 waves per workgroup)
+constexpr int BAG_BLOCKS = 1024;    // grid cap of k_bag_count and k_bag_emit (4 waves per workgroup)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // binning
@@ -648,46 +647,11 @@ __global__ __launch_bounds__(256) void k_add_tree(const uint8_t* bins, int64_t n
 // ---------------------------------------------------------------------------------------------------------------------
 // row bag
 // ---------------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ uint64_t bag_key(uint64_t seed, uint64_t r) {      // mix(seed, r) of SPEC-GBDT
-    uint64_t z = seed + (r + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// sel = { prefix: the digits found so far, k: the rank (1-based) still wanted among the keys that carry the prefix }
-__global__ __launch_bounds__(256) void k_bag_hist(int64_t n, uint64_t seed, const uint64_t* sel, int pass, uint32_t* hist) {
-    __shared__ uint32_t h[4][256];
-    for (int i = threadIdx.x; i < 4 * 256; i += 256) (&h[0][0])[i] = 0;
-    __syncthreads();
-    const uint64_t prefix = pass == 0 ? 0ull : sel[0];
-    const int shift = 56 - 8 * pass;
-    uint32_t* mine = h[threadIdx.x >> 6];
-    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
-        const uint64_t key = bag_key(seed, (uint64_t)r);
-        if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&mine[(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    const uint32_t t = h[0][threadIdx.x] + h[1][threadIdx.x] + h[2][threadIdx.x] + h[3][threadIdx.x];
-    if (t) atomicAdd(hist + threadIdx.x, t);
-}
-
-__global__ __launch_bounds__(64) void k_bag_pick(const uint32_t* hist, uint64_t* sel, int pass, uint64_t m) {
-    __shared__ uint32_t sm[256];
-    for (int i = threadIdx.x; i < 256; i += 64) sm[i] = hist[i];
-    wave_lds_sync();
-    if (threadIdx.x == 0) {
-        const uint64_t prefix = pass == 0 ? 0ull : sel[0];
-        uint64_t k = pass == 0 ? m : sel[1];
-        int d = 0;
-        for (; d < 255; ++d) {                         // the last digit takes what is left: no index past the table
-            if (sm[d] >= k) break;
-            k -= sm[d];
-        }
-        sel[0] = (prefix << 8) | (uint64_t)d;
-        sel[1] = k;
-    }
-}
+// row source of the select: every row, one per item
+struct AllRows {
+    template <typename F>
+    __device__ void operator()(int64_t i, F count) const { count(i); }
+};
 
 // wave w of the grid owns rows [w * per, (w + 1) * per), per a multiple of 64; wave_cnt[w] = its rows with key <= sel[0]
 __global__ __launch_bounds__(256) void k_bag_count(int64_t n, int64_t per, uint64_t seed, const uint64_t* sel, uint32_t* wave_cnt) {
@@ -698,7 +662,7 @@ __global__ __launch_bounds__(256) void k_bag_count(int64_t n, int64_t per, uint6
     uint32_t cnt = 0;
     for (int64_t r0 = lo; r0 < hi; r0 += 64) {
         const int64_t r = r0 + lane;
-        cnt += (uint32_t)__popcll(__ballot(r < hi && bag_key(seed, (uint64_t)r) <= threshold));
+        cnt += (uint32_t)__popcll(__ballot(r < hi && row_key(seed, (uint64_t)r) <= threshold));
     }
     if (lane == 0) wave_cnt[w] = cnt;
 }
@@ -724,7 +688,7 @@ __global__ __launch_bounds__(256) void k_bag_emit(int64_t n, int64_t per, uint64
     bool over = false;
     for (int64_t r0 = lo; r0 < hi; r0 += 64) {
         const int64_t r = r0 + lane;
-        const bool keep = r < hi && bag_key(seed, (uint64_t)r) <= threshold;
+        const bool keep = r < hi && row_key(seed, (uint64_t)r) <= threshold;
         const uint64_t mask = __ballot(keep);
         const int64_t pos = at + __popcll(mask & below);
         if (keep) {
@@ -742,8 +706,8 @@ struct BagLayout {
 BagLayout bag_layout() {
     BagLayout w;
     int64_t at = 0;
-    w.hist = at; at += align256((int64_t)8 * 256 * 4);
-    w.sel = at; at += 256;
+    w.hist = at; at += SELECT_HIST_BYTES;
+    w.sel = at; at += SELECT_SEL_BYTES;
     w.wave_cnt = at; at += align256((int64_t)BAG_BLOCKS * 4 * 4);
     w.scan = at; at += align256((int64_t)(BAG_BLOCKS + 1) * 8);
     w.partial = at; at += align256((int64_t)scan_partial_bytes(BAG_BLOCKS));
@@ -963,14 +927,8 @@ extern "C" int otto_gbdt_bag(int64_t n, int64_t m, uint64_t seed, int32_t* d_row
     uint64_t* partial = (uint64_t*)(base + w.partial);
     uint32_t* err = nullptr;
     OTTO_TRY(err_begin(&err, s));
-    OTTO_HIP(hipMemsetAsync(hist, 0, 8 * 256 * 4, s));
+    OTTO_TRY(device_select(AllRows{}, n, m, seed, hist, sel, s));
     const unsigned blocks = (unsigned)((n + 255) / 256 < BAG_BLOCKS ? (n + 255) / 256 : BAG_BLOCKS);
-    for (int pass = 0; pass < 8; ++pass) {
-        k_bag_hist<<<blocks, 256, 0, s>>>(n, seed, sel, pass, hist + pass * 256);
-        OTTO_HIP(hipGetLastError());
-        k_bag_pick<<<1, 64, 0, s>>>(hist + pass * 256, sel, pass, (uint64_t)m);
-        OTTO_HIP(hipGetLastError());
-    }
     const int64_t waves = (int64_t)blocks * 4;
     const int64_t per = ((n + waves - 1) / waves + 63) / 64 * 64;
     k_bag_count<<<blocks, 256, 0, s>>>(n, per, seed, sel, wave_cnt);
