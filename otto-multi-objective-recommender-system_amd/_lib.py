@@ -139,6 +139,12 @@ SIGNATURES = {
     'otto_jsonl_count': (_i32, [_vp, _i64, _p_i64, _vp, _i64, _vp]),
     'otto_jsonl_parse': (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _p_i64, _vp, _i64, _vp]),
     'otto_jsonl_newlines': (_i32, [_vp, _i64, _i64, _p_i64, _vp]),
+    # include/otto_parquet.h
+    'otto_parquet_workspace': (_i64, [_vp, _i64]),
+    'otto_parquet_decode': (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
+    'otto_parquet_snappy_workspace': (_i64, [_i64]),
+    'otto_parquet_snappy': (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
+    'otto_parquet_reason': (C.c_char_p, [_i32]),
     # include/otto_pairs.h
     'otto_pairs_raw_count': (_i32, [_vp, _i64, _i32, _p_i64, _vp]),
     'otto_pairs_workspace': (_i64, [_i64]),

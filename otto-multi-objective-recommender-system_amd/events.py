@@ -206,3 +206,37 @@ def jsonl_to_events_device(paths, device='cuda:0', n_aids=None, ts_unit='auto', 
         if n_aids is None:
             n_aids = (int((d_aid.to(torch.int64) & 0xFFFFFFFF).max()) if n else 0) + 1
         return _sort_to_events(dev, d_sess, d_ts, d_aid, d_type, n, div, n_aids)
+
+
+def parquet_to_events_device(paths, device='cuda:0', n_aids=None, ts_unit='auto', batch_bytes=256 << 20):
+    """The split files -> :class:`DeviceEvents`: ``DATA/splits/{train,val}.parquet`` or the part files of the chunk writers
+    (one path or a list, read in order) are decoded on the device (``parquet.read_columns``, ``include/otto_parquet.h``),
+    then the division rule of :func:`jsonl_to_events_device` applies -- for a ``ts`` column annotated ``TIMESTAMP(unit)`` the
+    divisor is that unit's ticks per second instead, and a negative timestamp is refused -- and the same
+    ``otto_events_sort`` call. The result is bit-identical, ``order`` included, to ``frame_to_events_device`` of the
+    ``pyarrow.parquet.read_table(p, columns=['session', 'aid', 'ts', 'type'])`` tables of the same files."""
+    import os
+    import torch
+    from . import _lib, parquet
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.OttoError('parquet_to_events_device needs a ROCm device (no CPU fallback)')
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+    with torch.cuda.device(dev):
+        d_sess, d_aid, d_ts, d_type = parquet.read_columns(
+            paths, ('session', 'aid', 'ts', 'type'), dev, batch_bytes=batch_bytes,
+            dtypes={'session': torch.int32, 'aid': torch.int32, 'ts': torch.int64, 'type': torch.uint8})
+        n = int(d_ts.numel())
+        logical = parquet.check_column(parquet.read_metadata(paths[0]), 'ts').logical if paths else None
+        div = 1
+        if logical and logical[0] == 'TIMESTAMP':
+            div = parquet.TICKS_PER_SECOND[logical[1]]
+            if n and int(d_ts.min()) < 0:
+                raise _lib.OttoError(f'{os.fspath(paths[0])}: column \'ts\': a negative timestamp is not supported')
+        elif n and (ts_unit == 'ms' or (ts_unit == 'auto' and int(d_ts.max()) > 10 ** 11)):
+            div = 1000
+        if n_aids is None:
+            n_aids = (int((d_aid.to(torch.int64) & 0xFFFFFFFF).max()) if n else 0) + 1
+        return _sort_to_events(dev, d_sess, d_ts, d_aid, d_type, n, div, n_aids)
