@@ -248,6 +248,14 @@ SIGNATURES = {
                                  _vp]),
     'otto_sgns_hs_tree_sizes': (_i32, [_vp, _i64, _i64, _p_i64]),
     'otto_sgns_hs_tree': (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    # include/otto_submit.h
+    'otto_submit_workspace': (_i64, [_i64, _i32]),
+    'otto_submit_measure': (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int32), _vp, _i64, _i32, _i64, _i32, _p_i64,
+                                   _vp, _i64, _vp]),
+    'otto_submit_format': (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int32), _vp, _i64, _i32, _i64, _i32, _vp, _i64,
+                                  _i64, _vp, _i64, _vp]),
+    'otto_freq_count': (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    'otto_freq_topk': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

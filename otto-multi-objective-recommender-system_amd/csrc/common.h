@@ -90,7 +90,7 @@ constexpr int WAVE = 64;
 // of one family on one device must not overlap.
 enum { SCRATCH_CAND = 0, SCRATCH_RECENCY, SCRATCH_RECENCY_PRED, SCRATCH_EVENTS, SCRATCH_PAIRS_A, SCRATCH_PAIRS_B, SCRATCH_FOREST,
        SCRATCH_FOREST_TOPK, SCRATCH_BLEND, SCRATCH_EVAL, SCRATCH_GBDT, SCRATCH_GBDT_MAX, SCRATCH_FOLDS, SCRATCH_SGNS, SCRATCH_SGNS_STEP,
-       SCRATCH_SLOTS };
+       SCRATCH_FREQ, SCRATCH_SLOTS };
 inline int device_scratch(int slot, size_t bytes, void** out, hipStream_t s) {
     static DevBuf bufs[16][SCRATCH_SLOTS];
     int dev = 0;
