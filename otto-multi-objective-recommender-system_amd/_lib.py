@@ -95,6 +95,14 @@ class SgnsTable(C.Structure):
     ]
 
 
+class XgbTree(C.Structure):
+    # mirrors otto_xgb_tree (include/otto_xgb.h): 16 host arrays, then what the call writes
+    _fields_ = [(name, C.c_void_p) for name in (
+        'split_feature', 'split_bin', 'threshold', 'decision_type', 'left_child', 'right_child', 'split_gain', 'cover',
+        'sum_grad', 'count', 'left_id', 'right_id', 'leaf_value', 'leaf_cover', 'leaf_sum_grad', 'leaf_count')] + [
+        ('n_leaves', C.c_int32), ('n_syncs', C.c_int32), ('hist_rows', C.c_int64)]
+
+
 _vp, _i64, _i32, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_uint32
 _p_i64 = C.POINTER(C.c_int64)
 
@@ -225,6 +233,15 @@ SIGNATURES = {
     'otto_gbdt_grow_tree_sampled': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, C.c_double, C.c_double, C.c_double,
                                            C.c_double, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _i64, _vp]),
+    # include/otto_xgb.h
+    'otto_xgb_pairwise': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, C.c_uint64, _vp, _vp, _vp]),
+    'otto_xgb_workspace_bytes': (_i64, [_i64, _i32, _i32]),
+    'otto_xgb_grow_tree': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, C.c_double, C.c_double, C.c_double, C.c_double, _vp,
+                                  _i64, _vp, _i32, C.POINTER(XgbTree), _vp, _i64, _vp]),
+    'otto_xgb_level_hist': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp]),
+    'otto_xgb_level_split': (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, C.c_double, C.c_double, C.c_double, _vp, _i32, _vp, _vp,
+                                    _i64, _vp]),
+    'otto_xgb_level_partition': (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     # include/otto_folds.h
     'otto_folds_kfold_workspace': (_i64, [_i64]),
     'otto_folds_group_kfold': (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, C.POINTER(C.c_float), _vp, _i64, _vp]),

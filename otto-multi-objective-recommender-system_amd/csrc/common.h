@@ -108,6 +108,9 @@ __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 
+// mix(s, i) of SPEC-GBDT and of the fold trainer
+__host__ __device__ __forceinline__ uint64_t row_key(uint64_t seed, uint64_t r) { return mix64(seed + r * 0x9E3779B97F4A7C15ull); }
+
 __device__ __forceinline__ unsigned lane_id() { return threadIdx.x & 63u; }
 
 // LDS traffic between the lanes of ONE wave: the LDS queue of a wave is in order, so only the compiler needs a fence

@@ -7,9 +7,6 @@
 
 namespace otto {
 
-// mix(s, i) of SPEC-GBDT and of the fold trainer
-__host__ __device__ __forceinline__ uint64_t row_key(uint64_t seed, uint64_t r) { return mix64(seed + r * 0x9E3779B97F4A7C15ull); }
-
 constexpr int SELECT_BLOCKS = 1024;                     // grid cap of the histogram kernel (4 waves per workgroup)
 // workspace of a select: hist, then sel; a layout embeds both behind a 256-byte boundary
 constexpr int64_t SELECT_HIST_BYTES = 8 * 256 * 4;      // one 256-bin histogram per pass

@@ -8,3 +8,4 @@ from .features import (AID_COLUMNS, SESSION_COLUMNS, aid_feature_table, feature_
 from .folds import cross_validate, feature_importance, fold_indices, gather_bins, group_kfold  # noqa: E402,F401
 from .gbdt import (BinMapper, Sampling, TrainResult, ap_at_k, bin_matrix, fit_bins, lambdarank_gradients,  # noqa: E402,F401
                    sampling_from_params, train, write_lightgbm_model)
+from . import xgb  # noqa: E402,F401

@@ -154,7 +154,8 @@ class CVResult:
     """``forests``: one ``ranker.forest.Forest`` per fold; ``trees``: their ``BinTree`` lists; ``best_iterations``,
     ``histories``: per fold, as ``gbdt.TrainResult``; ``mappers``: the fold's ``BinMapper``; ``oof_prediction`` float32
     [n] on the device; ``fold_of_query`` int32 [Q], ``fold_rows`` int64 [n_splits]; ``importance_gain`` float64 and
-    ``importance_split`` int64 [F, n_splits]. With ``aid`` and ``truth``: ``top_aid`` int32 [Q, 20] and ``top_n``, the
+    ``importance_split`` int64 [F, n_splits], ``importance_cover`` float64 [F, n_splits] (``booster='xgboost'`` only, else
+    None). With ``aid`` and ``truth``: ``top_aid`` int32 [Q, 20] and ``top_n``, the
     out-of-fold top-20 of every session; ``fold_hits``, ``fold_denom``, ``fold_recall``: per fold; ``hits``, ``denom``,
     ``recall``: over all folds (otherwise None)."""
 
@@ -163,8 +164,14 @@ class CVResult:
 
 
 def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ratio=0.3, seed=42, num_boost_round=100,
-                   early_stopping_rounds=None, feature_names=None, aid=None, truth=None, sampling=None):
-    """The fold loop of ``lgb_trainer.py:81-198`` on the device: a :class:`CVResult`.
+                   early_stopping_rounds=None, feature_names=None, aid=None, truth=None, sampling=None, booster='lightgbm'):
+    """The fold loop of ``lgb_trainer.py:81-198`` (and of ``xgb_trainer.py:81-200``) on the device: a :class:`CVResult`.
+
+    ``booster='xgboost'`` trains the XGBoost family instead (``ranker.xgb``): ``params`` under XGBoost's key names
+    (``xgb.resolve_params``; ``sampling`` must stay None, the sampling keys are part of ``params``), ``xgb.train``, the
+    out-of-fold prediction by ``xgb.predict`` (``base_score`` included), and the importances of ``xgb.feature_importance``:
+    ``importance_gain`` (mean gain per split), ``importance_split`` (= weight) and ``importance_cover`` (None for
+    ``'lightgbm'``). Everything else in the loop is the same.
 
     ``X`` float32 [n, F] (``ranker.features.feature_matrix``), ``label`` uint8 or int32 [n], ``query_off`` int64 [Q+1]
     (the ``row_off`` of ``ranker_table``), on the device; ``params`` and ``sampling`` as ``gbdt.train`` takes them
@@ -188,7 +195,16 @@ def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ra
     n, F = int(X.shape[0]), int(X.shape[1])
     if label.numel() != n:
         raise ValueError(f'label has {label.numel()} rows, X has {n}')
-    p = gbdt.resolve_params(params)
+    if booster not in ('lightgbm', 'xgboost'):
+        raise ValueError(f"booster = {booster!r}: expected 'lightgbm' or 'xgboost'")
+    xgboost = booster == 'xgboost'
+    if xgboost:
+        from . import xgb
+        if sampling is not None:
+            raise ValueError("sampling: with booster='xgboost' subsample / colsample_bytree / seed are keys of params")
+        p = xgb.resolve_params(params)[0]
+    else:
+        p = gbdt.resolve_params(params)
     n_splits = int(n_splits)
     fold_of_query, fold_rows = group_kfold(query_off, n_splits, n=n)
     label32 = label if label.dtype == torch.int32 else label.to(torch.int32)
@@ -196,6 +212,7 @@ def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ra
     forests, trees, best, histories, mappers = [], [], [], [], []
     imp_gain = np.zeros((F, n_splits), dtype=np.float64)
     imp_split = np.zeros((F, n_splits), dtype=np.int64)
+    imp_cover = np.zeros((F, n_splits), dtype=np.float64) if xgboost else None
     for fold in range(n_splits):
         fi = fold_indices(label, query_off, fold_of_query, fold, negative_sampling_ratio, seed)
         Mt = fi.train_idx.numel()
@@ -205,21 +222,28 @@ def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ra
         train_bins, val_bins = gather_bins(bins, fi.train_idx), gather_bins(bins, fi.val_idx)
         del bins
         train_label, val_label = label32[fi.train_idx.long()], label32[fi.val_idx.long()]
-        res = gbdt.train(train_bins, train_label, fi.train_query_off, mapper, params,
-                         valid=(val_bins, val_label, fi.val_query_off), num_boost_round=num_boost_round,
-                         early_stopping_rounds=early_stopping_rounds, feature_names=feature_names, sampling=sampling)
-        score = torch.zeros(fi.val_idx.numel(), dtype=torch.float64, device=dev)
-        for tree in res.trees:
-            gbdt.add_tree(val_bins, tree, score)
+        common = dict(valid=(val_bins, val_label, fi.val_query_off), num_boost_round=num_boost_round,
+                      early_stopping_rounds=early_stopping_rounds, feature_names=feature_names)
+        if xgboost:
+            res = xgb.train(train_bins, train_label, fi.train_query_off, mapper, params, **common)
+            score = xgb.predict(res, X[fi.val_idx.long()])
+        else:
+            res = gbdt.train(train_bins, train_label, fi.train_query_off, mapper, params, sampling=sampling, **common)
+            score = torch.zeros(fi.val_idx.numel(), dtype=torch.float64, device=dev)
+            for tree in res.trees:
+                gbdt.add_tree(val_bins, tree, score)
         oof[fi.val_idx.long()] = score.to(torch.float32)
         forests.append(res.forest)
         trees.append(res.trees)
         best.append(res.best_iteration)
         histories.append(res.history)
         mappers.append(mapper)
-        imp_gain[:, fold], imp_split[:, fold] = feature_importance(res.trees, F)
+        if xgboost:
+            imp_gain[:, fold], imp_split[:, fold], imp_cover[:, fold] = xgb.feature_importance(res.trees, F)
+        else:
+            imp_gain[:, fold], imp_split[:, fold] = feature_importance(res.trees, F)
     out = CVResult(forests=forests, trees=trees, best_iterations=best, histories=histories, mappers=mappers, oof_prediction=oof,
-                   fold_of_query=fold_of_query, fold_rows=fold_rows, importance_gain=imp_gain, importance_split=imp_split,
+                   fold_of_query=fold_of_query, fold_rows=fold_rows, importance_gain=imp_gain, importance_split=imp_split, importance_cover=imp_cover,
                    top_aid=None, top_n=None, fold_hits=None, fold_denom=None, fold_recall=None, hits=None, denom=None, recall=None)
     if (aid is None) != (truth is None):
         raise ValueError('recall@20 needs both aid and truth')
