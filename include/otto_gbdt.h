@@ -85,7 +85,9 @@
  * features are zero.
  * Seeds. bagging_seed defaults to 3, feature_fraction_seed to 2 (LightGBM's defaults). `seed` is ignored: LightGBM
  * would derive the two seeds from it, and that derivation is not reproduced.
- * Refused: feature_fraction_bynode < 1, pos_bagging_fraction / neg_bagging_fraction != 1, bagging_fraction or
+ * Objectives and metrics beyond these (the `binary` objective, NDCG, AUC, logloss): SPEC-OBJ, include/otto_objective.h.
+ * Refused: an objective other than lambdarank / binary, a metric other than map / ndcg / auc / binary_logloss, is_unbalance
+ * together with scale_pos_weight != 1, feature_fraction_bynode < 1, pos_bagging_fraction / neg_bagging_fraction != 1, bagging_fraction or
  * feature_fraction outside (0, 1], bagging_freq < 0.
  */
 #ifndef OTTO_GBDT_H

@@ -68,10 +68,12 @@
  * positive counts 1.0 (with `map-`: 0.0); the mean over all queries, float64 on the host over otto_gbdt_ap_at_k. Early
  * stopping as in SPEC-GBDT's trainer: strict improvement, cut at the best iteration.
  *
- * Refused by the host (ValueError naming the key): objective other than rank:pairwise, booster other than gbtree,
- * tree_method outside hist / gpu_hist / auto, grow_policy lossguide, max_leaves != 0, alpha != 0, max_delta_step != 0,
- * colsample_bylevel / colsample_bynode != 1, scale_pos_weight != 1, num_pairsample != 1, num_parallel_tree != 1,
- * eval_metric other than map / map-, sampling_method other than uniform, max_depth outside [1, 10].
+ * Refused by the host (ValueError naming the key): objective other than rank:pairwise, rank:ndcg and binary:logistic (the
+ * latter two: SPEC-OBJ, otto_objective.h), booster other than gbtree, tree_method outside hist / gpu_hist / auto,
+ * grow_policy lossguide, max_leaves != 0, alpha != 0, max_delta_step != 0, colsample_bylevel / colsample_bynode != 1,
+ * scale_pos_weight != 1 with a rank objective, num_pairsample != 1, num_parallel_tree != 1, eval_metric other than map /
+ * map- / map@k / ndcg / ndcg- / ndcg@k and, with binary:logistic only, auc / logloss; base_score outside (0, 1) with
+ * binary:logistic; sampling_method other than uniform, max_depth outside [1, 10].
  */
 #ifndef OTTO_XGB_H
 #define OTTO_XGB_H
@@ -90,6 +92,13 @@ extern "C" {
 int otto_xgb_pairwise(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n,
                       const double* d_sigmoid, double sigmoid_lo, double sigmoid_factor, uint64_t seed_it, double* d_grad,
                       double* d_hess, void* stream);
+
+/* The same objective with LambdaMART's pair weights (SPEC-OBJ, include/otto_objective.h): weighting = 0 is
+ * otto_xgb_pairwise bit for bit (d_discount is not read and may be NULL); weighting = 1 is rank:ndcg, every pair's g and h2
+ * multiplied by the |delta NDCG| of swapping its rows; d_discount float64 [OTTO_GBDT_MAX_QUERY] (otto_gbdt.h). */
+int otto_xgb_lambdamart(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n,
+                        const double* d_sigmoid, double sigmoid_lo, double sigmoid_factor, uint64_t seed_it, int32_t weighting,
+                        const double* d_discount, double* d_grad, double* d_hess, void* stream);
 
 /* One tree of otto_xgb_grow_tree. The arrays are HOST buffers of the caller: node arrays of 2^max_depth - 1 entries, leaf
  * arrays of 2^max_depth. The last three fields are written by the call. */

@@ -235,6 +235,7 @@ SIGNATURES = {
                                            _vp, _i64, _vp]),
     # include/otto_xgb.h
     'otto_xgb_pairwise': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, C.c_uint64, _vp, _vp, _vp]),
+    'otto_xgb_lambdamart': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, C.c_uint64, _i32, _vp, _vp, _vp, _vp]),
     'otto_xgb_workspace_bytes': (_i64, [_i64, _i32, _i32]),
     'otto_xgb_grow_tree': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, C.c_double, C.c_double, C.c_double, C.c_double, _vp,
                                   _i64, _vp, _i32, C.POINTER(XgbTree), _vp, _i64, _vp]),
@@ -242,6 +243,16 @@ SIGNATURES = {
     'otto_xgb_level_split': (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, C.c_double, C.c_double, C.c_double, _vp, _i32, _vp, _vp,
                                     _i64, _vp]),
     'otto_xgb_level_partition': (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    # include/otto_objective.h
+    'otto_obj_constants': (None, [C.POINTER(C.c_int32)]),
+    'otto_obj_binary': (_i32, [_vp, _vp, _i64, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp,
+                               _vp]),
+    'otto_obj_label_counts': (_i32, [_vp, _i64, _vp, _vp]),
+    'otto_obj_ndcg_at_k': (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    'otto_obj_auc_workspace_bytes': (_i64, [_i64]),
+    'otto_obj_auc': (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    'otto_obj_logloss': (_i32, [_vp, _vp, _i64, C.c_double, _vp, _vp, _vp]),
+    'otto_obj_logloss_grid': (_i32, [_vp, _vp, _i64, C.c_double, _i32, _vp, _vp, _vp]),
     # include/otto_folds.h
     'otto_folds_kfold_workspace': (_i64, [_i64]),
     'otto_folds_group_kfold': (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, C.POINTER(C.c_float), _vp, _i64, _vp]),

@@ -8,7 +8,10 @@
 //                    record position, a row's place inside its bucket is the number of earlier ranks with its label; one
 //                    thread per record position draws the partner and leaves the pair (ranks of high and low, g, 2h) in
 //                    LDS; one thread per row then walks the pair list in ascending index and adds the pairs it is part
-//                    of: no float atomics, the order of every sum is pinned.
+//                    of: no float atomics, the order of every sum is pinned. Both are templates on NDCG: true is
+//                    rank:ndcg (SPEC-OBJ, include/otto_objective.h): thread 0 also adds the query's ideal DCG from the
+//                    label counts, and the pair thread scales g and 2h by the pair's |delta NDCG|; false is rank:pairwise,
+//                    with that code compiled out.
 //   k_level_hist     grid = (row chunks of all nodes of the level, groups of 8 features). A workgroup finds its node by
 //                    binary search over the nodes' first chunk, then is k_hist's body (hist_block) on that node's rows
 //                    and histogram slot.
@@ -63,6 +66,7 @@ struct PairArgs {
     const double* sigmoid;
     double sig_lo, sig_factor;
     uint64_t seed;
+    const double* discount;   // LambdaMART weighting only
     double* grad;
     double* hess;
     uint32_t* err;
@@ -84,10 +88,12 @@ struct PairLds {
     uint32_t start[OTTO_GBDT_MAX_LABEL + 1];    // first record position of a label's bucket
     uint16_t rec[CAP];        // record position -> rank
     uint16_t hi[CAP], lo[CAP];    // pair index -> rank of its high / low row
+    double inv_idcg;          // LambdaMART weighting only
 };
 
-// one query, rows [lo, lo + cnt), by the whole workgroup; cnt >= 1. Ends without a barrier.
-template <int CAP>
+// one query, rows [lo, lo + cnt), by the whole workgroup; cnt >= 1. Ends without a barrier. NDCG: SPEC-OBJ's rank:ndcg, every
+// pair weighted by the |delta NDCG| of swapping its two rows; false: rank:pairwise, the code the flag adds compiled out.
+template <bool NDCG, int CAP>
 __device__ __forceinline__ void pair_query(PairLds<CAP>& s, const PairArgs& a, int64_t lo, int cnt) {
 #pragma clang fp contract(off)
     const int tid = threadIdx.x, nt = blockDim.x;
@@ -96,6 +102,15 @@ __device__ __forceinline__ void pair_query(PairLds<CAP>& s, const PairArgs& a, i
     if (tid == 0) {
         uint32_t at = 0;
         for (int lab = OTTO_GBDT_MAX_LABEL; lab >= 0; --lab) { s.start[lab] = at; at += s.lcnt[lab]; }
+        if constexpr (NDCG) {
+            double idcg = 0.0;
+            int r = 0;
+            for (int lab = OTTO_GBDT_MAX_LABEL; lab >= 0; --lab) {
+                const double gain = (double)((1ull << lab) - 1ull);
+                for (uint32_t c = s.lcnt[lab]; c > 0; --c, ++r) idcg = idcg + gain * a.discount[r];
+            }
+            s.inv_idcg = idcg == 0.0 ? 0.0 : 1.0 / idcg;
+        }
     }
     __syncthreads();
     for (int r = tid; r < cnt; r += nt) {
@@ -126,8 +141,15 @@ __device__ __forceinline__ void pair_query(PairLds<CAP>& s, const PairArgs& a, i
         h = h > 1e-16 ? h : 1e-16;
         s.hi[pid] = (uint16_t)hi_r;
         s.lo[pid] = (uint16_t)lo_r;
-        s.disc[pid] = g;
-        s.key[pid] = (uint64_t)__double_as_longlong(2.0 * h);
+        if constexpr (NDCG) {
+            const double dg = (double)((1ull << s.label[hi_r]) - 1ull) - (double)((1ull << s.label[lo_r]) - 1ull);
+            const double delta = fabs(dg * (a.discount[hi_r] - a.discount[lo_r])) * s.inv_idcg;
+            s.disc[pid] = g * delta;
+            s.key[pid] = (uint64_t)__double_as_longlong(2.0 * h * delta);
+        } else {
+            s.disc[pid] = g;
+            s.key[pid] = (uint64_t)__double_as_longlong(2.0 * h);
+        }
     }
     __syncthreads();
     for (int r = tid; r < cnt; r += nt) {
@@ -150,23 +172,25 @@ __device__ __forceinline__ void pair_query(PairLds<CAP>& s, const PairArgs& a, i
 
 // one workgroup of one wave per query: the queries of at most SHORT_QUERY rows (4.7 KB of LDS, so that a CU holds its 32
 // waves); it also counts the queries the spec refuses
+template <bool NDCG>
 __global__ __launch_bounds__(64) void k_xgb_pairwise_short(PairArgs a) {
     __shared__ PairLds<SHORT_QUERY> s;
     int64_t lo;
     int cnt;
     if (!query_range(a.query_off, blockIdx.x, a.n, &lo, &cnt, a.err)) return;   // grad / hess were zeroed
     if (cnt == 0 || cnt > SHORT_QUERY) return;
-    pair_query(s, a, lo, cnt);
+    pair_query<NDCG>(s, a, lo, cnt);
 }
 
 // the longer queries: workgroup b walks queries [b * per, (b + 1) * per) and works on those above SHORT_QUERY rows
+template <bool NDCG>
 __global__ __launch_bounds__(256) void k_xgb_pairwise_long(PairArgs a, int64_t Q, int64_t per) {
     __shared__ PairLds<MAXQ> s;
     const int64_t q1 = ((int64_t)blockIdx.x + 1) * per < Q ? ((int64_t)blockIdx.x + 1) * per : Q;
     for (int64_t q = (int64_t)blockIdx.x * per; q < q1; ++q) {
         const int64_t lo = a.query_off[q], hi = a.query_off[q + 1];
         if (!(lo >= 0 && lo <= hi && hi <= a.n && hi - lo <= MAXQ) || hi - lo <= SHORT_QUERY) continue;
-        pair_query(s, a, lo, (int)(hi - lo));
+        pair_query<NDCG>(s, a, lo, (int)(hi - lo));
         __syncthreads();                                // the next query reuses the LDS
     }
 }
@@ -375,11 +399,25 @@ int check_xgb_params(double min_child_weight, double lambda, double gamma) {
 
 using namespace otto;
 
-extern "C" int otto_xgb_pairwise(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n,
-                                 const double* d_sigmoid, double sigmoid_lo, double sigmoid_factor, uint64_t seed_it, double* d_grad,
-                                 double* d_hess, void* stream) {
+template <bool NDCG>
+static int launch_pairs(const PairArgs& a, int64_t Q, hipStream_t s) {
+    // OTTO's queries hold 50 to 100 candidates: one wave each; the second launch finds nothing to do there
+    k_xgb_pairwise_short<NDCG><<<(unsigned)Q, 64, 0, s>>>(a);
+    OTTO_HIP(hipGetLastError());
+    if (a.n > SHORT_QUERY) {
+        const int64_t blocks = Q < LONG_BLOCKS ? Q : LONG_BLOCKS;
+        k_xgb_pairwise_long<NDCG><<<(unsigned)blocks, 256, 0, s>>>(a, Q, (Q + blocks - 1) / blocks);
+        OTTO_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int otto_xgb_lambdamart(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n,
+                                   const double* d_sigmoid, double sigmoid_lo, double sigmoid_factor, uint64_t seed_it, int32_t weighting,
+                                   const double* d_discount, double* d_grad, double* d_hess, void* stream) {
     OTTO_TRY(check_query_args(d_score, d_label, d_query_off, Q, n));
     OTTO_REQUIRE(sigmoid_factor > 0.0 && sigmoid_lo == sigmoid_lo, "sigmoid_lo = %g, sigmoid_factor = %g", sigmoid_lo, sigmoid_factor);
+    OTTO_REQUIRE(weighting == 0 || weighting == 1, "weighting = %d: 0 (rank:pairwise) or 1 (rank:ndcg)", weighting);
     OTTO_REQUIRE((d_grad && d_hess) || n == 0, "null d_grad or d_hess");
     hipStream_t s = (hipStream_t)stream;
     if (n) {
@@ -388,18 +426,20 @@ extern "C" int otto_xgb_pairwise(const double* d_score, const int32_t* d_label, 
     }
     if (Q == 0) return 0;
     OTTO_REQUIRE(d_sigmoid, "null d_sigmoid");
+    OTTO_REQUIRE(weighting == 0 || d_discount, "null d_discount");
     uint32_t* err = nullptr;
     OTTO_TRY(err_begin(&err, s));
-    PairArgs a{d_score, d_label, d_query_off, n, d_sigmoid, sigmoid_lo, sigmoid_factor, seed_it, d_grad, d_hess, err};
-    // OTTO's queries hold 50 to 100 candidates: one wave each; the second launch finds nothing to do there
-    k_xgb_pairwise_short<<<(unsigned)Q, 64, 0, s>>>(a);
-    OTTO_HIP(hipGetLastError());
-    if (n > SHORT_QUERY) {
-        const int64_t blocks = Q < LONG_BLOCKS ? Q : LONG_BLOCKS;
-        k_xgb_pairwise_long<<<(unsigned)blocks, 256, 0, s>>>(a, Q, (Q + blocks - 1) / blocks);
-        OTTO_HIP(hipGetLastError());
-    }
+    PairArgs a{d_score, d_label, d_query_off, n, d_sigmoid, sigmoid_lo, sigmoid_factor, seed_it, d_discount, d_grad, d_hess, err};
+    if (weighting) OTTO_TRY(launch_pairs<true>(a, Q, s));
+    else OTTO_TRY(launch_pairs<false>(a, Q, s));
     return err_end(err, s);
+}
+
+extern "C" int otto_xgb_pairwise(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n,
+                                 const double* d_sigmoid, double sigmoid_lo, double sigmoid_factor, uint64_t seed_it, double* d_grad,
+                                 double* d_hess, void* stream) {
+    return otto_xgb_lambdamart(d_score, d_label, d_query_off, Q, n, d_sigmoid, sigmoid_lo, sigmoid_factor, seed_it, 0, nullptr, d_grad,
+                               d_hess, stream);
 }
 
 extern "C" int64_t otto_xgb_workspace_bytes(int64_t n, int32_t F, int32_t max_depth) {

@@ -9,3 +9,4 @@ from .folds import cross_validate, feature_importance, fold_indices, gather_bins
 from .gbdt import (BinMapper, Sampling, TrainResult, ap_at_k, bin_matrix, fit_bins, lambdarank_gradients,  # noqa: E402,F401
                    sampling_from_params, train, write_lightgbm_model)
 from . import xgb  # noqa: E402,F401
+from . import objectives  # noqa: E402,F401

@@ -173,6 +173,11 @@ def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ra
     ``importance_gain`` (mean gain per split), ``importance_split`` (= weight) and ``importance_cover`` (None for
     ``'lightgbm'``). Everything else in the loop is the same.
 
+    ``params`` may name SPEC-OBJ's objectives and metrics (``objective: binary`` / ``binary:logistic`` / ``rank:ndcg``,
+    ``metric`` / ``eval_metric``: ``ndcg``, ``auc``, ``binary_logloss`` / ``logloss``): both trainers
+    take them as they are. The out-of-fold prediction of a binary model is its raw score (the blend rescales every column
+    anyway); ``objectives.transform`` turns it into a probability.
+
     ``X`` float32 [n, F] (``ranker.features.feature_matrix``), ``label`` uint8 or int32 [n], ``query_off`` int64 [Q+1]
     (the ``row_off`` of ``ranker_table``), on the device; ``params`` and ``sampling`` as ``gbdt.train`` takes them
     (``gbdt.sampling_from_params`` makes both from a section of the reference's config). :func:`group_kfold`
@@ -202,9 +207,9 @@ def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ra
         from . import xgb
         if sampling is not None:
             raise ValueError("sampling: with booster='xgboost' subsample / colsample_bytree / seed are keys of params")
-        p = xgb.resolve_params(params)[0]
+        p = xgb.resolve_params(params, extended=True)[0]
     else:
-        p = gbdt.resolve_params(params)
+        p = gbdt.resolve_params(params, extended=True)
     n_splits = int(n_splits)
     fold_of_query, fold_rows = group_kfold(query_off, n_splits, n=n)
     label32 = label if label.dtype == torch.int32 else label.to(torch.int32)
@@ -226,7 +231,7 @@ def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ra
                       early_stopping_rounds=early_stopping_rounds, feature_names=feature_names)
         if xgboost:
             res = xgb.train(train_bins, train_label, fi.train_query_off, mapper, params, **common)
-            score = xgb.predict(res, X[fi.val_idx.long()])
+            score = xgb.predict(res, X[fi.val_idx.long()], output_margin=True)
         else:
             res = gbdt.train(train_bins, train_label, fi.train_query_off, mapper, params, sampling=sampling, **common)
             score = torch.zeros(fi.val_idx.numel(), dtype=torch.float64, device=dev)

@@ -5,7 +5,8 @@ What this replaces in the reference: ``lgb.train`` on the (session, candidate) m
 (``src/ranker/lgb_trainer.py:134-165``). The caller keeps GroupKFold and the negative down-sampling
 (``lgb_trainer.py:81-128``), hands over the float32 matrix of ``ranker.features.feature_matrix`` with the rows of a
 session contiguous, and gets a :class:`~otto_amd.ranker.forest.Forest` that ``ranker.forest`` scores. LightGBM's own
-arithmetic is not reproduced: SPEC-GBDT states what is computed.
+arithmetic is not reproduced: SPEC-GBDT states what is computed. The ``binary`` objective and the NDCG, AUC and logloss
+validation metrics (SPEC-OBJ) come from ``ranker.objectives``; :func:`train` takes them by name.
 """
 import ctypes as C
 import dataclasses
@@ -26,8 +27,18 @@ SPLIT_WORDS = 12            # OTTO_GBDT_SPLIT_WORDS
 DEFAULTS = {
     'num_leaves': 128, 'min_data_in_leaf': 2000, 'min_sum_hessian_in_leaf': 1e-3, 'lambda_l2': 0.01, 'min_gain_to_split': 1e-5,
     'learning_rate': 0.1, 'lambdarank_truncation_level': 30, 'lambdarank_norm': True, 'sigmoid': 1.0, 'max_bin': 255,
-    'eval_at': 20,
+    'eval_at': 20, 'objective': 'lambdarank', 'metric': 'map', 'is_unbalance': False, 'scale_pos_weight': 1.0,
+    'boost_from_average': True,
 }
+# LightGBM's names of the objectives and metrics SPEC-GBDT and SPEC-OBJ implement -> the name used here
+_OBJECTIVES = {'lambdarank': 'lambdarank', 'binary': 'binary'}
+_METRICS = {'map': 'map', 'mean_average_precision': 'map', 'ndcg': 'ndcg', 'lambdarank': 'ndcg', 'rank_xendcg': 'ndcg',
+            'xendcg': 'ndcg', 'xe_ndcg': 'ndcg', 'xe_ndcg_mart': 'ndcg', 'xendcg_mart': 'ndcg', 'auc': 'auc',
+            'binary_logloss': 'logloss', 'binary': 'logloss'}
+_DEFAULT_METRIC = {'lambdarank': 'ndcg', 'binary': 'logloss'}       # LightGBM's, behind metric = '' / 'default' only
+_OBJECTIVE_KEYS = ('objective', 'objective_type', 'app', 'application', 'loss')
+_METRIC_KEYS = ('metric', 'metrics', 'metric_types')
+_UNBALANCE_KEYS = ('is_unbalance', 'unbalance', 'unbalanced_sets')
 _ALIASES = {
     'min_child_samples': 'min_data_in_leaf', 'min_child_weight': 'min_sum_hessian_in_leaf', 'reg_lambda': 'lambda_l2',
     'reg_alpha': 'lambda_l1', 'min_split_gain': 'min_gain_to_split', 'eta': 'learning_rate', 'subsample': 'bagging_fraction',
@@ -484,8 +495,40 @@ def sampling_from_params(params):
     return rest, Sampling(**kw)
 
 
-def resolve_params(params):
-    """LightGBM's key names and aliases -> the resolved dict. ``config['model'][event_type]`` of the reference's YAML can be
+def _flag(key, val):
+    if isinstance(val, str) and val.lower() in ('true', 'false', '+', '-'):
+        return val.lower() in ('true', '+')
+    if val in (True, False, 0, 1):
+        return bool(val)
+    raise ValueError(f'{key} = {val!r}: expected a boolean')
+
+
+def _metric_name(key, val, objective):
+    """The first entry of a metric value (a name, a comma-separated string or a list) as one of map / ndcg / auc /
+    logloss; '' and 'default' are LightGBM's default for the objective."""
+    if isinstance(val, str):
+        val = val.split(',')
+    val = [str(v).strip() for v in (val if isinstance(val, (list, tuple)) else [val])]
+    first = val[0] if val else ''
+    if first in ('', 'default'):
+        return _DEFAULT_METRIC[objective]
+    if first not in _METRICS:
+        raise ValueError(f'{key} = {first!r} is not supported (only {" / ".join(_METRICS)})')
+    return _METRICS[first]
+
+
+def resolve_params(params, extended=False):
+    """``extended`` (what :func:`train` and ``folds.cross_validate`` pass): also accept SPEC-OBJ's objectives and metrics
+    (DESIGN.md section 3l). ``objective``: ``lambdarank`` or ``binary``. ``metric`` (aliases ``metrics``, ``metric_types``;
+    of a list or a comma-separated string the first entry decides): ``map`` / ``mean_average_precision``, ``ndcg`` /
+    ``lambdarank`` (and LightGBM's xendcg aliases of it), ``auc``, ``binary_logloss`` / ``binary``; without the key the
+    metric stays AP@``eval_at`` whatever the objective, and only an explicit ``''`` or ``'default'`` selects LightGBM's
+    default for the objective (``ndcg`` for ``lambdarank``, ``binary_logloss`` for ``binary``). ``sigmoid``, ``is_unbalance``
+    (aliases ``unbalance``, ``unbalanced_sets``), ``scale_pos_weight`` and ``boost_from_average`` are read for ``binary``;
+    ``is_unbalance`` together with ``scale_pos_weight != 1`` is refused, as in LightGBM. Without ``extended`` the call keeps
+    its first contract: ``lambdarank`` only, and these keys change nothing.
+
+    LightGBM's key names and aliases -> the resolved dict. ``config['model'][event_type]`` of the reference's YAML can be
     passed once the keys SPEC-GBDT refuses are taken out (:func:`sampling_from_params` takes the sampling keys out and
     hands them to :func:`train` as a :class:`Sampling`). Raises ``ValueError`` for what changes the arithmetic and is not
     implemented: ``lambda_l1 != 0``, ``bagging_fraction < 1``, ``feature_fraction < 1``, ``feature_fraction_bynode < 1``,
@@ -495,9 +538,23 @@ def resolve_params(params):
     (seeds, ``verbose``, ``n_jobs``, ``metric``, ...) changes no arithmetic here and is ignored. ``eval_at``: the first entry
     of a list is the k of the validation metric."""
     p = dict(DEFAULTS)
-    for key, val in dict(params or {}).items():
+    params = dict(params or {})
+    metric = None
+    for key, val in params.items():
         key = _ALIASES.get(key, key)
-        if key == 'lambda_l1':
+        if key in _METRIC_KEYS:
+            if key == 'metric' or 'metric' not in params:                 # the main name wins over its aliases
+                metric = (key, val)
+        elif key in _UNBALANCE_KEYS:
+            if extended and (key == 'is_unbalance' or 'is_unbalance' not in params):
+                p['is_unbalance'] = _flag(key, val)
+        elif key == 'boost_from_average':
+            if extended:
+                p[key] = _flag(key, val)
+        elif key == 'scale_pos_weight':
+            if extended:
+                p[key] = val
+        elif key == 'lambda_l1':
             if float(val) != 0.0:
                 raise ValueError('lambda_l1 != 0 is not supported (SPEC-GBDT has no L1 term)')
         elif key == 'bagging_fraction':
@@ -512,9 +569,11 @@ def resolve_params(params):
         elif key == 'max_depth':
             if int(val) > 0:
                 raise ValueError('max_depth > 0 is not supported (growth is leaf-wise up to num_leaves)')
-        elif key in ('objective', 'objective_type', 'app', 'application', 'loss'):
-            if str(val) != 'lambdarank':
-                raise ValueError(f'objective {val!r} is not supported (only lambdarank)')
+        elif key in _OBJECTIVE_KEYS:
+            if str(val) not in (_OBJECTIVES if extended else ('lambdarank',)):
+                raise ValueError(f'objective {val!r} is not supported (only {" / ".join(_OBJECTIVES) if extended else "lambdarank"})')
+            if key == 'objective' or 'objective' not in params:
+                p['objective'] = _OBJECTIVES[str(val)]
         elif key in ('boosting', 'boosting_type', 'boost'):
             if str(val) != 'gbdt':
                 raise ValueError(f'boosting {val!r} is not supported (only gbdt)')
@@ -531,8 +590,14 @@ def resolve_params(params):
     p['num_leaves'], p['min_data_in_leaf'], p['eval_at'] = int(p['num_leaves']), int(p['min_data_in_leaf']), int(p['eval_at'])
     p['lambdarank_truncation_level'], p['max_bin'] = int(p['lambdarank_truncation_level']), int(p['max_bin'])
     p['lambdarank_norm'] = bool(p['lambdarank_norm'])
-    for key in ('min_sum_hessian_in_leaf', 'lambda_l2', 'min_gain_to_split', 'learning_rate', 'sigmoid'):
+    for key in ('min_sum_hessian_in_leaf', 'lambda_l2', 'min_gain_to_split', 'learning_rate', 'sigmoid', 'scale_pos_weight'):
         p[key] = float(p[key])
+    if extended and metric is not None:
+        p['metric'] = _metric_name(metric[0], metric[1], p['objective'])
+    if not p['scale_pos_weight'] > 0:
+        raise ValueError(f'scale_pos_weight = {p["scale_pos_weight"]} must be positive')
+    if p['is_unbalance'] and p['scale_pos_weight'] != 1.0:
+        raise ValueError('is_unbalance and scale_pos_weight != 1 cannot be used together (LightGBM refuses the pair too)')
     if p['num_leaves'] > MAX_LEAVES:
         raise ValueError(f'num_leaves = {p["num_leaves"]} above OTTO_FOREST_MAX_LEAVES = {MAX_LEAVES}')
     if p['num_leaves'] < 2:
@@ -572,9 +637,16 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
     iterations have passed without a strict improvement and the forest is cut at the best iteration. ``keep_leaves``
     also returns the leaf of every (row, tree). ``sampling``: a :class:`Sampling`; the bag is redrawn every
     ``bagging_freq`` iterations and the feature list for every tree, each tree is grown on its bag and list, and its
-    values are added to the score of every row. Raises ``OttoError`` if not a single tree could be grown."""
+    values are added to the score of every row. Raises ``OttoError`` if not a single tree could be grown.
+
+    ``params`` may also name SPEC-OBJ's ``binary`` objective and the metrics ``ndcg``, ``auc``, ``binary_logloss``
+    (:func:`resolve_params` with ``extended``). ``binary``: positives are the rows with ``label > 0``; with
+    ``boost_from_average`` every score starts at ``objectives.init_score`` and that value is added once into the leaf
+    values of the first tree, so ``forest`` and ``trees`` scored from 0.0 return ``train_score``'s bits.
+    ``binary_logloss`` stops early on a strict decrease, every other metric on a strict increase."""
     import torch
-    p = resolve_params(params)
+    from . import objectives
+    p = resolve_params(params, extended=True)
     if sampling is not None and not isinstance(sampling, Sampling):
         raise ValueError('sampling: expected a gbdt.Sampling (see sampling_from_params)')
     F, n = check_bins(bins)
@@ -592,6 +664,17 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
     elif early_stopping_rounds:
         raise ValueError('early_stopping_rounds needs a validation set')
     work = torch.empty(workspace_bytes(n, F, p['num_leaves']), dtype=torch.uint8, device=dev)
+    binary = p['objective'] == 'binary'
+    init = 0.0
+    if binary:
+        n_pos, _ = objectives.label_counts(label)
+        w_pos, w_neg = objectives.class_weights(n_pos, n, p['is_unbalance'], p['scale_pos_weight'])
+        if p['boost_from_average'] and n:
+            init = objectives.init_score(n_pos, n, p['sigmoid'])
+            score.fill_(init)
+            if valid is not None:
+                vscore.fill_(init)
+    higher = objectives.HIGHER_IS_BETTER[p['metric']]
     trees, leaves, history = [], [], []
     best_metric, best_iter = None, 0
     bag_on = sampling is not None and sampling.bag_active
@@ -599,8 +682,11 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
     m = bag_size(sampling.bagging_fraction, n) if bag_on else n       # refuses an empty bag before any launch
     bag = features = None
     for it in range(int(num_boost_round)):
-        grad, hess = lambdarank_gradients(score, label, query_off, p['sigmoid'], p['lambdarank_truncation_level'],
-                                          p['lambdarank_norm'])
+        if binary:
+            grad, hess = objectives.binary_gradients(score, label, p['sigmoid'], w_pos, w_neg, 0.0)
+        else:
+            grad, hess = lambdarank_gradients(score, label, query_off, p['sigmoid'], p['lambdarank_truncation_level'],
+                                              p['lambdarank_norm'])
         gh, exp = quantize_gradients(grad, hess)
         if bag_on and it % sampling.bagging_freq == 0:
             bag = bag_rows(n, m, mix(sampling.bagging_seed, 2 * (it // sampling.bagging_freq)), dev)
@@ -615,15 +701,23 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
             leaves.append(leaf)
         if valid is not None:
             add_tree(vbins, tree, vscore)
-            metric = mean_ap(ap_at_k(vscore, vlabel, voff, p['eval_at']))
+            if p['metric'] == 'map':
+                metric = mean_ap(ap_at_k(vscore, vlabel, voff, p['eval_at']))
+            else:
+                metric = objectives.evaluate(p['metric'], vscore, vlabel, voff, k=p['eval_at'], minus=False, sigma=p['sigmoid'])
             history.append(metric)
-            if best_metric is None or metric > best_metric:
+            if best_metric is None or (metric > best_metric if higher else metric < best_metric):
                 best_metric, best_iter = metric, it + 1
             if early_stopping_rounds and it + 1 - best_iter >= int(early_stopping_rounds):
                 break
     if not trees:
         raise _lib.OttoError('no tree could be grown: no split of the root is admissible (min_data_in_leaf, '
                              'min_sum_hessian_in_leaf, min_gain_to_split) or every label of a query is the same')
+    if init != 0.0:
+        # LightGBM's AddBias: 0.0 + (value + init) has the bits of init + value, so the trees score from 0.0 from here on
+        first = BinTree(**trees[0].__dict__)
+        first.leaf_value = first.leaf_value + np.float64(init)
+        trees[0] = first
     if valid is None or not early_stopping_rounds:
         best_iter = len(trees)
     elif best_iter < len(trees):
@@ -632,14 +726,19 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
             add_tree(bins, tree, score)
     trees = trees[:best_iter]
     train_leaf = torch.stack(leaves[:best_iter], dim=1).contiguous() if keep_leaves else None
-    return TrainResult(forest_from_trees(trees, F, feature_names), best_iter, history, score, trees, train_leaf)
+    forest = forest_from_trees(trees, F, feature_names)
+    if binary:
+        forest.objective = f'binary sigmoid:{p["sigmoid"]:g}'
+    return TrainResult(forest, best_iter, history, score, trees, train_leaf)
 
 
 def write_lightgbm_model(forest, feature_names=None):
     """A text dump of ``forest`` in the layout of LightGBM's v3 model files, holding what
     :func:`~otto_amd.ranker.forest.parse_lightgbm_model` reads, and read back by it to identical arrays (every float is
     written with ``repr``, which round-trips a float64). It carries no ``feature_infos``, ``split_gain``, ``leaf_count`` or
-    ``internal_*`` lines; whether LightGBM's own loader accepts it has not been tried."""
+    ``internal_*`` lines; whether LightGBM's own loader accepts it has not been tried. The ``objective`` line is the
+    forest's: ``lambdarank``, or ``binary sigmoid:<sigma>`` for a model of :func:`train` with ``objective: binary`` (whose
+    first tree carries the initial score, as LightGBM's does)."""
     names = list(feature_names) if feature_names is not None else list(forest.feature_names)
     if len(names) != forest.n_features:
         raise ValueError(f'{len(names)} feature_names for {forest.n_features} features')

@@ -7,6 +7,8 @@ What this replaces in the reference: ``xgb.train`` on the (session, candidate) m
 (``src/ranker/inference.py:64-85``). The reference keeps no XGBoost config: the defaults here are XGBoost 1.7's documented
 ones. XGBoost's own arithmetic is not reproduced and the library is not available to this project: SPEC-XGB states what
 is computed, ``tests/xgb_restatement.py`` pins it, and parity with a run of xgboost is neither claimed nor tested.
+``rank:ndcg``, ``binary:logistic`` and the ``ndcg`` / ``auc`` / ``logloss`` metrics are SPEC-OBJ's (DESIGN.md section 3l,
+``ranker.objectives``).
 """
 import ctypes as C
 import json
@@ -23,7 +25,9 @@ _ROOT_PARENT = 2147483647   # XGBoost's "no parent"
 
 # XGBoost 1.7's documented defaults (max_bin: 256 there, 255 here, see resolve_params)
 DEFAULTS = {'max_depth': 6, 'min_child_weight': 1.0, 'lambda': 1.0, 'gamma': 0.0, 'eta': 0.3, 'max_bin': 255, 'base_score': 0.5,
-            'subsample': 1.0, 'colsample_bytree': 1.0, 'seed': 0, 'eval_metric': 'map'}
+            'subsample': 1.0, 'colsample_bytree': 1.0, 'seed': 0, 'eval_metric': 'map', 'objective': 'rank:pairwise',
+            'scale_pos_weight': 1.0}
+OBJECTIVES = ('rank:pairwise', 'rank:ndcg', 'binary:logistic')        # what resolve_params(extended=True) accepts
 _ALIASES = {'learning_rate': 'eta', 'min_split_loss': 'gamma', 'reg_lambda': 'lambda', 'reg_alpha': 'alpha', 'random_state': 'seed'}
 # key -> the only value(s) accepted
 _ONLY = {'objective': ('rank:pairwise',), 'booster': ('gbtree',), 'tree_method': ('hist', 'gpu_hist', 'auto'),
@@ -37,8 +41,30 @@ def derived_seeds(seed):
     return mix(seed, 1), mix(seed, 2), mix(seed, 3)
 
 
-def resolve_params(params):
-    """XGBoost's key names and aliases -> ``(p, sampling)``: the resolved dict (``max_depth``, ``min_child_weight``,
+def parse_metric(name):
+    """``(metric, k, minus)`` of an ``eval_metric`` string: ``map`` / ``ndcg`` with an optional ``@k`` (default: the whole
+    query) and an optional trailing ``-`` (a query without a positive counts 0.0, not 1.0), ``auc``, ``logloss``; None for
+    anything else."""
+    name = str(name)
+    if name in ('auc', 'logloss'):
+        return name, MAX_QUERY, False
+    minus = name.endswith('-')
+    head, _, k = (name[:-1] if minus else name).partition('@')
+    if head not in ('map', 'ndcg') or (k and not k.isdigit()) or ('@' in name and not k):
+        return None
+    k = int(k) if k else MAX_QUERY
+    return (head, k, minus) if 1 <= k <= MAX_QUERY else None
+
+
+def resolve_params(params, extended=False):
+    """``extended`` (what :func:`train`, :func:`write_xgboost_json` and ``folds.cross_validate`` pass): also accept SPEC-OBJ's
+    objectives and metrics (DESIGN.md section 3l): ``objective`` in ``rank:pairwise`` / ``rank:ndcg`` / ``binary:logistic``;
+    ``eval_metric`` in ``map``, ``map-``, ``map@k``, ``ndcg``, ``ndcg-``, ``ndcg@k`` and, with ``binary:logistic`` only,
+    ``auc`` and ``logloss`` (``p['metric']`` = :func:`parse_metric` of it); ``scale_pos_weight`` with ``binary:logistic``
+    (it stays refused for the rank objectives), whose ``base_score`` must lie inside (0, 1). Without ``extended`` the call
+    keeps its first contract: ``rank:pairwise`` with ``map`` / ``map-``.
+
+    XGBoost's key names and aliases -> ``(p, sampling)``: the resolved dict (``max_depth``, ``min_child_weight``,
     ``lambda``, ``gamma``, ``eta``, ``max_bin``, ``base_score``, ``subsample``, ``colsample_bytree``, ``seed``,
     ``eval_metric``, ``objective_seed``) and the ``gbdt.Sampling`` that ``subsample`` / ``colsample_bytree`` / ``seed`` map
     to. Aliases: ``learning_rate``, ``min_split_loss``, ``reg_lambda``, ``reg_alpha``, ``random_state``; where a key stands
@@ -52,7 +78,13 @@ def resolve_params(params):
         name = _ALIASES.get(key, key)
         if name != key and name in params:
             continue
-        if name in _ONLY:
+        if extended and name == 'objective':
+            if str(val) not in OBJECTIVES:
+                raise ValueError(f'{key} = {val!r} is not supported (only {" / ".join(OBJECTIVES)})')
+            p[name] = str(val)
+        elif extended and name == 'scale_pos_weight':
+            p[name] = val
+        elif name in _ONLY:
             if str(val) not in _ONLY[name]:
                 raise ValueError(f'{key} = {val!r} is not supported (only {" / ".join(_ONLY[name])})')
         elif name in _ONLY_NUMBER:
@@ -63,14 +95,26 @@ def resolve_params(params):
                 if len(val) != 1:
                     raise ValueError(f'eval_metric = {val!r}: expected one metric, map or map-')
                 val = val[0]
-            if val not in ('map', 'map-'):
-                raise ValueError(f'eval_metric = {val!r} is not supported (only map / map-)')
+            if val not in ('map', 'map-') and not (extended and parse_metric(val)):
+                raise ValueError(f'eval_metric = {val!r} is not supported (only map / map-' +
+                                 (' / map@k / ndcg / ndcg- / ndcg@k / auc / logloss)' if extended else ')'))
             p[name] = val
         elif name in DEFAULTS:
             p[name] = val
     p['max_depth'], p['max_bin'], p['seed'] = int(p['max_depth']), int(p['max_bin']), int(p['seed'])
-    for key in ('min_child_weight', 'lambda', 'gamma', 'eta', 'base_score', 'subsample', 'colsample_bytree'):
+    for key in ('min_child_weight', 'lambda', 'gamma', 'eta', 'base_score', 'subsample', 'colsample_bytree', 'scale_pos_weight'):
         p[key] = float(p[key])
+    p['metric'] = parse_metric(p['eval_metric'])
+    if p['objective'] == 'binary:logistic':
+        if not p['scale_pos_weight'] > 0:
+            raise ValueError(f'scale_pos_weight = {p["scale_pos_weight"]} must be positive')
+        if not 0.0 < p['base_score'] < 1.0:
+            raise ValueError(f'base_score = {p["base_score"]} outside (0, 1): binary:logistic starts from its logit')
+    else:
+        if p['scale_pos_weight'] != 1.0:
+            raise ValueError(f'scale_pos_weight = {p["scale_pos_weight"]} is not supported with {p["objective"]} (only 1)')
+        if p['metric'][0] in ('auc', 'logloss'):
+            raise ValueError(f'eval_metric = {p["eval_metric"]!r} needs objective binary:logistic')
     if not 1 <= p['max_depth'] <= MAX_DEPTH:
         raise ValueError(f'max_depth = {p["max_depth"]} outside [1, {MAX_DEPTH}] (0, "no limit", is not supported)')
     if p['max_bin'] == 256:
@@ -106,6 +150,21 @@ def pairwise_gradients(score, label, query_off, seed, it, out=None):
     _lib.need(hess, 'hess', torch.float64, 1, device=dev, numel=score.numel())
     _lib.call('otto_xgb_pairwise', dev, score, label, query_off, query_off.numel() - 1, score.numel(), table, lo, factor,
               mix(seed, it), grad, hess)
+    return grad, hess
+
+
+def lambdamart_gradients(score, label, query_off, seed, it, weighting=1, out=None):
+    """:func:`pairwise_gradients` through ``otto_xgb_lambdamart``: ``weighting = 0`` gives its bits, ``weighting = 1`` is
+    SPEC-OBJ's ``rank:ndcg`` (every pair weighted by the |delta NDCG| of swapping its rows)."""
+    import torch
+    gbdt._check_queries(score, label, query_off)
+    dev = score.device
+    table, lo, factor, disc = gbdt._tables(1.0, dev)
+    grad, hess = out if out is not None else (torch.empty_like(score), torch.empty_like(score))
+    _lib.need(grad, 'grad', torch.float64, 1, device=dev, numel=score.numel())
+    _lib.need(hess, 'hess', torch.float64, 1, device=dev, numel=score.numel())
+    _lib.call('otto_xgb_lambdamart', dev, score, label, query_off, query_off.numel() - 1, score.numel(), table, lo, factor,
+              mix(seed, it), int(weighting), disc, grad, hess)
     return grad, hess
 
 
@@ -240,12 +299,22 @@ def feature_importance(trees, n_features):
     return gain, weight, cover
 
 
-class TrainResult(gbdt.TrainResult):
-    """``gbdt.TrainResult`` plus ``base_score``: ``train_score`` = ``base_score`` + the forest's raw score."""
+def _base_margin(base_score, objective):
+    """What a raw score starts from: ``base_score`` itself for the rank objectives (SPEC-XGB), its logit for
+    ``binary:logistic`` (SPEC-OBJ; exactly 0.0 at 0.5)."""
+    from . import objectives
+    return objectives.base_margin(base_score) if objective == 'binary:logistic' else float(base_score)
 
-    def __init__(self, base_score, *args):
+
+class TrainResult(gbdt.TrainResult):
+    """``gbdt.TrainResult`` plus ``base_score`` and ``base_margin``: ``train_score`` = ``base_margin`` + the forest's raw
+    score; ``base_margin`` is ``base_score`` itself, or its logit for ``binary:logistic``."""
+
+    def __init__(self, base_score, *args, objective='rank:pairwise'):
         super().__init__(*args)
         self.base_score = float(base_score)
+        self.objective = objective
+        self.base_margin = _base_margin(base_score, objective)
 
 
 class XgbModel:
@@ -254,6 +323,7 @@ class XgbModel:
 
     def __init__(self, forest, base_score, feature_names, objective):
         self.forest, self.base_score, self.feature_names, self.objective = forest, float(base_score), feature_names, objective
+        self.base_margin = _base_margin(base_score, objective)
 
 
 def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_round=10, early_stopping_rounds=None,
@@ -265,12 +335,16 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
     recorded after every tree; early stopping on a strict improvement, cut at the best iteration. Boosting stops at a tree
     whose root has no admissible split. Raises ``OttoError`` if not a single tree could be grown."""
     import torch
-    p, sampling = resolve_params(params)
+    from . import objectives
+    p, sampling = resolve_params(params, extended=True)
     F, n = gbdt.check_bins(bins)
     dev = bins.device
     if mapper.n_features != F:
         raise ValueError(f'the mapper has {mapper.n_features} features, bins has {F}')
-    base = p['base_score']
+    objective = p['objective']
+    base = _base_margin(p['base_score'], objective)
+    metric, metric_k, minus = p['metric']
+    higher = objectives.HIGHER_IS_BETTER[metric]
     margin = torch.zeros(n, dtype=torch.float64, device=dev)
     gbdt._check_queries(margin, label, query_off)
     if valid is not None:
@@ -286,7 +360,12 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
     trees, history = [], []
     best_metric, best_iter = None, 0
     for it in range(int(num_boost_round)):
-        grad, hess = pairwise_gradients(margin + base, label, query_off, p['objective_seed'], it)
+        if objective == 'binary:logistic':
+            grad, hess = objectives.binary_gradients(margin + base, label, 1.0, p['scale_pos_weight'], 1.0, 1e-16)
+        elif objective == 'rank:ndcg':
+            grad, hess = lambdamart_gradients(margin + base, label, query_off, p['objective_seed'], it, 1)
+        else:
+            grad, hess = pairwise_gradients(margin + base, label, query_off, p['objective_seed'], it)
         gh, exp = gbdt.quantize_gradients(grad, hess)
         bag = gbdt.bag_rows(n, m, mix(sampling.bagging_seed, 2 * it), dev) if sampling.bag_active else None
         features = gbdt.sample_features(F, sampling.feature_fraction, sampling.feature_fraction_seed, it) \
@@ -298,10 +377,13 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
         gbdt.add_tree(bins, tree, margin)
         if valid is not None:
             gbdt.add_tree(vbins, tree, vmargin)
-            metric = mean_average_precision(gbdt.ap_at_k(vmargin + base, vlabel, voff, MAX_QUERY), p['eval_metric'] == 'map-')
-            history.append(metric)
-            if best_metric is None or metric > best_metric:
-                best_metric, best_iter = metric, it + 1
+            if metric == 'map':
+                value = mean_average_precision(gbdt.ap_at_k(vmargin + base, vlabel, voff, metric_k), minus)
+            else:
+                value = objectives.evaluate(metric, vmargin + base, vlabel, voff, k=metric_k, minus=minus)
+            history.append(value)
+            if best_metric is None or (value > best_metric if higher else value < best_metric):
+                best_metric, best_iter = value, it + 1
             if early_stopping_rounds and it + 1 - best_iter >= int(early_stopping_rounds):
                 break
     if not trees:
@@ -315,14 +397,19 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
             gbdt.add_tree(bins, tree, margin)
     trees = trees[:best_iter]
     forest = gbdt.forest_from_trees(trees, F, feature_names)
-    forest.objective = 'rank:pairwise'
-    return TrainResult(base, forest, best_iter, history, margin + base, trees, None)
+    forest.objective = objective
+    return TrainResult(p['base_score'], forest, best_iter, history, margin + base, trees, None, objective=objective)
 
 
-def predict(model, X):
-    """``base_score + forest_predict(model.forest, X)`` float64 [n] on the device; ``model``: a :class:`TrainResult` or
-    an :class:`XgbModel`."""
-    return forest_predict(model.forest, X) + model.base_score
+def predict(model, X, output_margin=False):
+    """``base_margin + forest_predict(model.forest, X)`` float64 [n] on the device; ``model``: a :class:`TrainResult` or
+    an :class:`XgbModel`. A ``binary:logistic`` model returns the probability ``sigmoid(margin)`` unless
+    ``output_margin``; for the rank objectives the margin is the prediction and ``base_margin`` is ``base_score``."""
+    margin = forest_predict(model.forest, X) + model.base_margin
+    if model.objective == 'binary:logistic' and not output_margin:
+        from . import objectives
+        return objectives.transform(margin)
+    return margin
 
 
 # ---- XGBoost's JSON model layout
@@ -383,7 +470,12 @@ def write_xgboost_json(result, feature_names=None, params=None):
     ``params``: the training parameters (``lambda`` and ``eta`` enter ``base_weights`` of the internal nodes; default: the
     defaults). The layout is restated from XGBoost's documentation; the file has never been loaded by xgboost itself (the
     library is not available to this project). :func:`parse_xgboost_json` reads it back to identical arrays."""
-    p, _ = resolve_params(params)
+    p, _ = resolve_params(params, extended=True)
+    objective = getattr(result, 'objective', None) or p['objective']
+    if objective == 'binary:logistic':
+        objective_json = {'name': objective, 'reg_loss_param': {'scale_pos_weight': repr(float(p['scale_pos_weight']))}}
+    else:
+        objective_json = {'lambda_rank_param': {'fix_list_weight': '0', 'num_pairsample': '1'}, 'name': objective}
     forest = result.forest
     F = forest.n_features
     names = list(feature_names) if feature_names is not None else list(forest.feature_names)
@@ -397,7 +489,7 @@ def write_xgboost_json(result, feature_names=None, params=None):
                                        'tree_info': [0] * len(trees), 'trees': trees}, 'name': 'gbtree'},
         'learner_model_param': {'base_score': repr(float(result.base_score)), 'boost_from_average': '1',
                                 'num_class': '0', 'num_feature': str(F), 'num_target': '1'},
-        'objective': {'lambda_rank_param': {'fix_list_weight': '0', 'num_pairsample': '1'}, 'name': 'rank:pairwise'}},
+        'objective': objective_json},
         'version': [1, 7, 2]}
     return json.dumps(model)
 
