@@ -284,6 +284,11 @@ SIGNATURES = {
                                   _i64, _vp, _i64, _vp]),
     'otto_freq_count': (_i32, [_vp, _vp, _i64, _i64, _vp, _vp]),
     'otto_freq_topk': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    # include/otto_deflate.h
+    'otto_deflate_bound': (_i64, [_i64, _i32]),
+    'otto_deflate_workspace': (_i64, [_i64, _i32]),
+    'otto_deflate_plan': (_i32, [_vp, _i64, _i32, _p_i64, _vp, _i64, _vp]),
+    'otto_deflate_emit': (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 """The submission file from the device (SPEC-SUBMIT): per-session top lists -> the bytes of the
 ``session_type,labels`` CSV, formatted by HIP kernels (``include/otto_submit.h``), then copied out in chunks and written
-plain or as multi-member gzip.
+plain or as multi-member gzip: compressed by zlib on the host or, with ``compressor='device'``, by the DEFLATE kernels of
+``otto_amd.deflate`` (SPEC-DEFLATE) before the copy.
 
 Reference code replaced: the per-row ``' '.join(str(aid) ...)`` loops and ``DataFrame.to_csv`` of
 ``src/ranker/inference.py:403-408,566-572`` (``blend_submission.csv.gz``) and ``src/covisitation/inference.py:387-391,
@@ -9,7 +10,8 @@ and takes host parts too, so it runs without a GPU.
 
 ``python -m otto_amd.submission blend --out blend_submission.csv.gz --clicks 0.3:a.npz 0.7:b.npz --carts ... --orders ...``
 (every ``.npz`` holds ``session``, ``aid``, ``score``) and ``python -m otto_amd.submission covisitation --out
-covisitation_submission.csv.gz predictions.npz`` (``session_id`` [S], ``pred`` [3, S, k], ``n`` [3, S]).
+covisitation_submission.csv.gz predictions.npz`` (``session_id`` [S], ``pred`` [3, S, k], ``n`` [3, S]). ``--device-gzip``
+compresses on the device.
 """
 import gzip
 import time
@@ -20,6 +22,7 @@ HEADER = b'session_type,labels\n'
 TYPES = ('clicks', 'carts', 'orders')          # type code -> suffix
 MAX_K = 64                                     # OTTO_SUBMIT_MAX_K
 MAX_WORKERS = 16
+COMPRESSORS = ('zlib', 'device')
 
 
 def format_rows(session_id, tables, types, interleave=False, header=False):
@@ -117,14 +120,52 @@ def _device_chunks(part, chunk_bytes, state, stats):
     part.record_stream(side)
 
 
-def write_csv(path, parts, level=6, chunk_bytes=32 << 20, threads=8):
+class _Ready:
+    """A chunk that is compressed already, in the place of a future of the zlib pool."""
+
+    def __init__(self, data):
+        self.data = data
+
+    def result(self):
+        return self.data, 0.0
+
+
+def _device_members(part, chunk_bytes, state, stats):
+    """Chunks of a device uint8 tensor, each compressed on the device (one call of ``deflate.gzip_members`` per chunk, so
+    its scratch is bounded by ``chunk_bytes``) and brought across through the pinned buffer pair: (bytes, chunk length)."""
+    import torch
+    from . import deflate
+    n = int(part.numel())
+    size = min(chunk_bytes, n)
+    if state.get('z_size', 0) < size or state.get('z_dev') != part.device:      # one workspace and one output for all chunks
+        state.update(z_size=size, z_dev=part.device,
+                     z_work=torch.empty(deflate.workspace_bytes(size), dtype=torch.uint8, device=part.device),
+                     z_out=torch.empty(deflate.compressed_bound(size), dtype=torch.uint8, device=part.device))
+    for lo in range(0, n, chunk_bytes):
+        m = min(chunk_bytes, n - lo)
+        t0 = time.perf_counter()
+        z = deflate.gzip_members(part[lo:lo + m], work=state['z_work'], out=state['z_out'])
+        torch.cuda.current_stream(part.device).synchronize()
+        stats['device_s'] += time.perf_counter() - t0
+        first = True
+        for data in _device_chunks(z, chunk_bytes, state, stats):
+            yield data, m if first else 0
+            first = False
+
+
+def write_csv(path, parts, level=6, chunk_bytes=32 << 20, threads=8, compressor='zlib'):
     """Write the concatenation of ``parts`` to ``path``. A part is a device uint8 tensor (:func:`format_rows`), host
     ``bytes`` or a NumPy uint8 array. Parts are cut into chunks of ``chunk_bytes``; device chunks come across through one
     pinned buffer pair on a side stream. A path that ends in ``.gz`` compresses every chunk as a gzip member of its own
     (``mtime=0``, so two runs give identical files; ``gzip`` and ``pandas.read_csv`` read the members as one stream) in a
     pool of ``min(threads, 16)`` workers and writes them in order; any other path is written plain. Returns a dict of
     ``bytes`` (uncompressed), ``file_bytes`` and the seconds spent waiting for copies (``copy_s``), inside zlib summed
-    over the workers (``zlib_s``) and in file writes (``file_s``)."""
+    over the workers (``zlib_s``) and in file writes (``file_s``).
+
+    ``compressor='device'`` compresses the chunks of device parts with the DEFLATE kernels (``otto_amd.deflate``: gzip
+    members of 64 KiB, ``level`` does not apply) and copies the compressed bytes across; host parts still go through the
+    zlib pool, and a file of mixed members is a valid gzip file. The seconds inside those calls are ``device_s``, an
+    entry that exists only under ``'device'``. A plain path ignores the compressor. Any other name is a ``ValueError``."""
     import collections
     import concurrent.futures
     import os
@@ -132,24 +173,34 @@ def write_csv(path, parts, level=6, chunk_bytes=32 << 20, threads=8):
         raise ValueError('chunk_bytes must be at least 1')
     if threads < 1:
         raise ValueError('threads must be at least 1')
+    if compressor not in COMPRESSORS:
+        raise ValueError(f'compressor must be one of {COMPRESSORS} (got {compressor!r})')
     workers = min(int(threads), MAX_WORKERS)
     zipped = str(os.fspath(path)).endswith('.gz')
     stats = dict(bytes=0, file_bytes=0, copy_s=0.0, zlib_s=0.0, file_s=0.0)
+    on_device = zipped and compressor == 'device'
+    if compressor == 'device':
+        stats['device_s'] = 0.0
     state = {}
 
     def chunks():
+        """(bytes, uncompressed length, compressed already)"""
+        raw = lambda it: ((data, len(data), False) for data in it)
         for part in parts:
             if isinstance(part, (bytes, bytearray, memoryview, np.ndarray)):
-                yield from _host_chunks(part, chunk_bytes)
+                yield from raw(_host_chunks(part, chunk_bytes))
             else:
                 import torch
                 from . import _lib
                 if not isinstance(part, torch.Tensor) or part.dtype != torch.uint8 or part.dim() != 1:
                     raise ValueError('parts: expected 1-d uint8 device tensors, bytes or NumPy uint8 arrays')
                 if part.device.type != 'cuda':
-                    yield from _host_chunks(part.numpy(), chunk_bytes)
+                    yield from raw(_host_chunks(part.numpy(), chunk_bytes))
+                elif on_device:
+                    for data, m in _device_members(part.contiguous(), chunk_bytes, state, stats):
+                        yield data, m, True
                 else:
-                    yield from _device_chunks(part.contiguous(), chunk_bytes, state, stats)
+                    yield from raw(_device_chunks(part.contiguous(), chunk_bytes, state, stats))
 
     def job(data):
         t0 = time.perf_counter()
@@ -164,7 +215,7 @@ def write_csv(path, parts, level=6, chunk_bytes=32 << 20, threads=8):
 
     with open(path, 'wb') as f:
         if not zipped:
-            for data in chunks():
+            for data, _, _ in chunks():
                 stats['bytes'] += len(data)
                 put(f, data)
             return stats
@@ -177,9 +228,9 @@ def write_csv(path, parts, level=6, chunk_bytes=32 << 20, threads=8):
                 put(f, z)
 
         with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
-            for data in chunks():
-                stats['bytes'] += len(data)
-                pending.append(pool.submit(job, data))
+            for data, m, ready in chunks():
+                stats['bytes'] += m
+                pending.append(_Ready(data) if ready else pool.submit(job, data))
                 drain(2 * workers)                           # bounds the chunks held in memory
             drain(0)
         if stats['bytes'] == 0:
@@ -230,9 +281,11 @@ def _main(argv=None):
         p.add_argument('--device', default='cuda:0')
         p.add_argument('--level', type=int, default=6)
         p.add_argument('--threads', type=int, default=8)
+        p.add_argument('--device-gzip', action='store_true', help='compress on the device (otto_amd.deflate) instead of zlib')
     args = parser.parse_args(argv)
     dev = torch.device(args.device)
     put = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    write_args = dict(level=args.level, threads=args.threads, compressor='device' if args.device_gzip else 'zlib')
     if args.mode == 'blend':
         families, weights = [], []
         for name in TYPES:
@@ -244,11 +297,11 @@ def _main(argv=None):
                 w.append(float(weight))
             families.append(models)
             weights.append(w)
-        stats = blend_submission(args.out, families, weights, k=args.k, level=args.level, threads=args.threads)
+        stats = blend_submission(args.out, families, weights, k=args.k, **write_args)
     else:
         z = np.load(args.predictions)
         stats = covisitation_submission(args.out, put(z['session_id'], np.int32), put(z['pred'], np.int32), put(z['n'], np.int32),
-                                        level=args.level, threads=args.threads)
+                                        **write_args)
     print(f"{args.out}: {stats['bytes']} bytes of text, {stats['file_bytes']} bytes written")
 
 
