@@ -11,6 +11,7 @@
  * supplies the workspace, sized by the *_workspace function; no allocation per call (the error words and the counts
  * live in a 256-byte per-device scratch the library keeps); all device work on the caller's stream; a call
  * synchronises the stream at most once (otto_blend_scale: never).
+ * The functions without a stream parameter (the two *_workspace sizes) run on the host and enqueue nothing.
  *
  * SPEC-BLEND.
  *

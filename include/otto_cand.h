@@ -19,6 +19,7 @@
  * The matrices are the dense [n_aids][k] top-k arrays otto_covis_finalize leaves in HBM (no parquet -> dict round trip).
  *
  * Conventions as in otto_covis.h (return codes, otto_last_error(), caller-owned device buffers, caller's stream).
+ * otto_cand_ranker_workspace, the one function without a stream parameter, runs on the host and enqueues nothing.
  */
 #ifndef OTTO_CAND_H
 #define OTTO_CAND_H

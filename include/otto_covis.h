@@ -18,6 +18,12 @@
  * in; all pointers named d_* are DEVICE pointers (hipMalloc / torch CUDA tensors);
  * all work is enqueued on the caller's hipStream_t (passed as void*); one context
  * per device, not thread-safe; no exceptions or Python objects cross the ABI.
+ * Entry points WITHOUT a stream parameter: otto_last_error, otto_covis_create, otto_covis_reset, otto_covis_set_option,
+ * otto_covis_timings and otto_covis_kernel_names do no device work and enqueue nothing (create makes the timing events,
+ * timings reads them). otto_covis_stats and otto_covis_copy_records read what earlier feeds and imports wrote: they first
+ * wait for ALL work on the device (whatever streams the caller used), may then use stream 0, and return only after their
+ * own device work is complete. otto_covis_destroy frees the context's device memory: the caller must have drained every
+ * stream that works on the context.
  */
 #ifndef OTTO_COVIS_H
 #define OTTO_COVIS_H
@@ -111,6 +117,9 @@ int otto_covis_feed(otto_covis_ctx* ctx, const uint32_t* d_aid, const int32_t* d
 int otto_covis_finalize(otto_covis_ctx* ctx, int group, int k, uint32_t* d_out_y, uint64_t* d_out_w,
                         int32_t* d_out_n, void* stream);
 
+/* The context's counters (host values). No stream parameter: the first call after a feed or an import waits for all work on
+ * the device, counts SHARED_RUNS and ROW_RECORDS over the pair-expand output on stream 0 and returns with that work
+ * complete; every other value is host state. */
 int otto_covis_stats(otto_covis_ctx* ctx, int64_t* out /* [OTTO_COVIS_STAT_COUNT] */);
 
 /* Tuning knobs and A/B switches; results are exact for every value (each is exercised by tests/test_covis_gpu.py).
@@ -170,7 +179,8 @@ int otto_covis_export_fill_range(otto_covis_ctx* ctx, int n_owners, const uint32
 
 /* Test hook: copy the raw K1 output to HOST buffers (any pointer may be NULL).
  * h_rec/h_tw: [PAIR_SLOTS] uint32, h_run_x: [TAIL_EVENTS] uint32, h_run_desc: [TAIL_EVENTS] uint64
- * (desc = slot_offset << 8 | len). rec = aid_y | type_y << 26 | filter_bits << 28. */
+ * (desc = slot_offset << 8 | len). rec = aid_y | type_y << 26 | filter_bits << 28.
+ * No stream parameter: waits for all work on the device, then copies with blocking copies. */
 int otto_covis_copy_records(otto_covis_ctx* ctx, uint32_t* h_rec, uint32_t* h_tw, uint32_t* h_run_x,
                             uint64_t* h_run_desc);
 

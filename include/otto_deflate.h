@@ -73,6 +73,7 @@
  *
  * Conventions as in otto_submit.h: 0 / negative code + otto_last_error(); caller owns every buffer; d_* are device
  * pointers, h_* host pointers; launches go to the caller's hipStream_t.
+ * The functions without a stream parameter (otto_deflate_bound, otto_deflate_workspace) run on the host and enqueue nothing.
  */
 #ifndef OTTO_DEFLATE_H
 #define OTTO_DEFLATE_H

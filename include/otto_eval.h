@@ -10,6 +10,7 @@
  * supplies the workspace, sized by the *_workspace function (256-byte aligned); no allocation per call (error words,
  * list lengths and totals live in a 256-byte per-device scratch the library keeps); all device work on the caller's
  * stream; a call synchronises the stream at most once, stated per function. Everything is integer work.
+ * The functions without a stream parameter (the two *_workspace sizes) run on the host and enqueue nothing.
  *
  * SPEC-EVAL.
  *

@@ -11,6 +11,7 @@
  *
  * Conventions as in otto_covis.h: 0 / negative code + otto_last_error(); caller owns every buffer; d_* are device
  * pointers; launches go to the caller's hipStream_t.
+ * otto_events_sort_workspace, the one function without a stream parameter, runs on the host and enqueues nothing.
  */
 #ifndef OTTO_EVENTS_H
 #define OTTO_EVENTS_H

@@ -12,6 +12,7 @@
  * only the device can see (an aid >= n_aids, a candidate outside [0, n_aids), a day outside the day table, a type > 2, a
  * session longer than OTTO_FEAT_MAX_SESSION, an integer column value above 2^24) sets the error word: the call returns an
  * error and nothing is read or written out of bounds.
+ * The functions without a stream parameter (the three *_workspace sizes) run on the host and enqueue nothing.
  *
  * SPEC-FEAT. Events are the (session, ts)-sorted SoA of otto_events.h with CSR session offsets; the given order is
  * authoritative. Clock: t = ts + 7200 (ts in seconds, ts >= 0), day = t floordiv 86400, hour = (t mod 86400) / 3600. The

@@ -11,6 +11,7 @@
  * the caller's stream; no buffer is allocated per call (the *_workspace functions size d_work; error words and counters
  * live in a per-device scratch the library keeps). A call that can detect an error on the device synchronises the stream
  * once to read its error words. The feature holds no floating-point arithmetic: every output is pinned bit for bit.
+ * The functions without a stream parameter (the *_workspace and *_bytes sizes) run on the host and enqueue nothing.
  *
  * SPEC-FOLDS.
  * Inputs. query_off int64 [Q+1] on the device, the row_off of ranker_table: the rows of a session are contiguous and

@@ -9,6 +9,7 @@
  * Conventions of otto_knn.h: 0 or a negative OTTO_E* code plus otto_last_error; caller-owned buffers; all device work on
  * the caller's stream; no buffer is allocated per call (the error words live in a 256-byte per-device scratch the library
  * keeps, as the candidate entry points do). A device call synchronises the stream once to read its error words.
+ * The functions without a stream parameter (otto_forest_packed_bytes, otto_forest_pack) work on host arrays alone and enqueue nothing.
  *
  * SPEC-FOREST. A forest is T trees over F features. Tree t has L_t >= 1 leaves and L_t - 1 internal nodes; an internal
  * node has split_feature, threshold (float64 in the model file), decision_type, left_child, right_child. A child c >= 0

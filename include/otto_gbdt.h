@@ -10,6 +10,7 @@
  * work on the caller's stream; no buffer is allocated per call (otto_gbdt_workspace_bytes sizes d_work; the error words
  * live in a per-device scratch the library keeps). A call that can detect an error on the device synchronises the
  * stream once to read its error words.
+ * The functions without a stream parameter (the two *_workspace_bytes sizes) run on the host and enqueue nothing.
  *
  * SPEC-GBDT.
  * Inputs. X float32 [n, >= F] row-major, 1 <= F <= OTTO_FOREST_MAX_FEATURES; label int32 [n] in 0..31 (gain =

@@ -16,6 +16,7 @@
  * counts up to 65,535, recency weights in (0, 4]) however small the spread is against the mean.
  *
  * Conventions as in otto_covis.h.
+ * otto_inter_workspace, the one function without a stream parameter, runs on the host and enqueues nothing.
  */
 #ifndef OTTO_INTER_H
 #define OTTO_INTER_H

@@ -36,6 +36,7 @@
  *
  * Conventions as in otto_events.h: 0 / negative code + otto_last_error(); caller owns every buffer; d_* are device
  * pointers, h_* host pointers; launches go to the caller's hipStream_t. d_bytes must be 16-byte aligned.
+ * otto_jsonl_workspace, the one function without a stream parameter, runs on the host and enqueues nothing.
  */
 #ifndef OTTO_JSONL_H
 #define OTTO_JSONL_H

@@ -8,6 +8,7 @@
  *
  * Conventions of otto_covis.h: 0 or a negative OTTO_E* code plus otto_last_error; caller-owned device buffers;
  * all work on the caller's stream; nothing is allocated inside.
+ * otto_knn_workspace, the one function without a stream parameter, runs on the host and enqueues nothing.
  *
  * Per query aid a = d_rows[r] (d_rows == NULL: a = r, n_rows == N): all b != a with valid[b] != 0, ordered by
  * (key asc, b asc), the first k:

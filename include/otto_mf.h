@@ -17,6 +17,9 @@
  * (PyTorch holds the embedding tables and optimizer state and passes data_ptr()); d_* are device
  * pointers; launches go to the caller's hipStream_t; not thread-safe per context.
  * Embedding tables are row-major float32 [n, d]; d in {4, 8, 16, 32, 64, 128, 256}.
+ * Entry points WITHOUT a stream parameter: otto_mf_create clears the context's per-row words on stream 0 and returns only
+ * after these clears are complete, so the first call on any stream finds them done; otto_mf_destroy frees device memory:
+ * the caller must have drained every stream that works on the context; otto_mf_score_workspace runs on the host.
  */
 #ifndef OTTO_MF_H
 #define OTTO_MF_H
@@ -36,7 +39,8 @@ extern "C" {
 typedef struct otto_mf_ctx otto_mf_ctx;
 
 /* n1/n2 rows of table 1/2 (shared_table != 0: one table used for both index columns, n2 ignored --
- * CollaborativeFiltering), factors d, largest batch any step/eval call will pass. */
+ * CollaborativeFiltering), factors d, largest batch any step/eval call will pass. No stream parameter: the per-row words
+ * are cleared on stream 0 and the call returns after the clears are complete. */
 int otto_mf_create(otto_mf_ctx** ctx, int64_t n1, int64_t n2, int32_t d, int64_t max_batch, int32_t shared_table);
 void otto_mf_destroy(otto_mf_ctx* ctx);
 

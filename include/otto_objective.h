@@ -10,6 +10,7 @@
  * Conventions of otto_gbdt.h: 0 or a negative OTTO_E* code plus otto_last_error; caller-owned buffers; all device work on
  * the caller's stream; no buffer is allocated per call (the error words live in the per-device scratch of the GBDT family:
  * calls of the families on one device must not overlap); one synchronisation where an error word is read.
+ * The functions without a stream parameter (otto_obj_constants, otto_obj_auc_workspace_bytes) run on the host and enqueue nothing.
  *
  * SPEC-OBJ. Normative. All float64 arithmetic runs without contraction, products left to right. T, lo, factor: SPEC-GBDT's
  * sigmoid table at sigma = 1 (entry i = 1/(1+exp(lo + i/factor)), lo = -25, BINS = OTTO_GBDT_SIGMOID_BINS); discount[r] =

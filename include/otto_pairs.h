@@ -19,6 +19,7 @@
  * equal pairs. Output rows are sorted by (x1, x2).
  *
  * Conventions as in otto_covis.h. Events are the sorted SoA + CSR of otto_events_sort.
+ * otto_pairs_workspace, the one function without a stream parameter, runs on the host and enqueues nothing.
  */
 #ifndef OTTO_PAIRS_H
 #define OTTO_PAIRS_H

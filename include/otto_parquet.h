@@ -41,6 +41,7 @@
  *
  * Conventions as in otto_events.h: 0 / negative code + otto_last_error(); caller owns every buffer; d_* are device
  * pointers, h_* host pointers; launches go to the caller's hipStream_t. d_bytes must be 16-byte aligned.
+ * The functions without a stream parameter (the two *_workspace sizes, otto_parquet_reason) run on the host and enqueue nothing.
  */
 #ifndef OTTO_PARQUET_H
 #define OTTO_PARQUET_H

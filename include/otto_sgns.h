@@ -13,6 +13,8 @@
  * the caller's stream; fixed grids with grid-stride loops; no buffer is allocated per call (the *_workspace functions size
  * d_work; error words live in a per-device scratch the library keeps). A call that can detect an error on the device
  * synchronises the stream once to read its error words.
+ * The functions without a stream parameter (the *_workspace sizes, otto_sgns_hs_tree_sizes, otto_sgns_hs_tree) work on host
+ * arrays alone and enqueue nothing.
  *
  * SPEC-SGNS.
  * Inputs. aid int32 [E] sorted by (session, ts); sess_off int64 [S+1] with sess_off[0] = 0, ascending, sess_off[S] = E;

@@ -31,6 +31,7 @@
  *
  * Conventions as in otto_jsonl.h: 0 / negative code + otto_last_error(); caller owns every buffer; d_* are device
  * pointers, h_* host pointers (h_d_* a host array of device pointers); launches go to the caller's hipStream_t.
+ * otto_submit_workspace, the one function without a stream parameter, runs on the host and enqueues nothing.
  */
 #ifndef OTTO_SUBMIT_H
 #define OTTO_SUBMIT_H

@@ -13,6 +13,7 @@
  * Conventions of otto_gbdt.h: 0 or a negative OTTO_E* code plus otto_last_error; caller-owned buffers; all device work on
  * the caller's stream; no buffer is allocated per call (otto_xgb_workspace_bytes sizes d_work; the error words live in
  * the per-device scratch the GBDT family keeps, so calls of the two families on one device must not overlap).
+ * otto_xgb_workspace_bytes, the one function without a stream parameter, runs on the host and enqueues nothing.
  *
  * SPEC-XGB. Normative; everything not restated here is SPEC-GBDT's (otto_gbdt.h).
  *

@@ -4262,13 +4262,17 @@ extern "C" int otto_covis_stats(otto_covis_ctx* c, int64_t* out) {
     if (!c->desc_totals_valid) {
         c->desc_totals[0] = c->desc_totals[1] = 0;
         if (c->run_used) {
+            // no stream parameter: wait for every stream's work on this device (the feeds that wrote run_desc), then clear,
+            // count and read back on stream 0, in order; the wait on stream 0 at the end makes the call complete on return
+            const hipStream_t s0 = nullptr;
             OTTO_HIP(hipDeviceSynchronize());
-            OTTO_TRY(c->exp_totals.ensure(2 * MAX_OWNERS * 8, 0, nullptr));
-            OTTO_HIP(hipMemset(c->exp_totals.p, 0, 16));
+            OTTO_TRY(c->exp_totals.ensure(2 * MAX_OWNERS * 8, 0, s0));
+            OTTO_HIP(hipMemsetAsync(c->exp_totals.p, 0, 16, s0));
             const int64_t nb = ((int64_t)c->run_used + 255) / 256;
-            k_desc_totals<<<(unsigned)(nb < 4096 ? nb : 4096), 256>>>(c->run_desc.as<uint64_t>(), (int64_t)c->run_used, c->exp_totals.as<unsigned long long>());
+            k_desc_totals<<<(unsigned)(nb < 4096 ? nb : 4096), 256, 0, s0>>>(c->run_desc.as<uint64_t>(), (int64_t)c->run_used, c->exp_totals.as<unsigned long long>());
             OTTO_HIP(hipGetLastError());
-            OTTO_HIP(hipMemcpy(c->desc_totals, c->exp_totals.p, 16, hipMemcpyDeviceToHost));
+            OTTO_HIP(hipMemcpyAsync(c->desc_totals, c->exp_totals.p, 16, hipMemcpyDeviceToHost, s0));
+            OTTO_HIP(hipStreamSynchronize(s0));
             c->exp_planned = 0;                       // the export cursors shared that buffer
         }
         c->desc_totals_valid = true;

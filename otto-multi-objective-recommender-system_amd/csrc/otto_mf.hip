@@ -807,6 +807,9 @@ extern "C" int otto_mf_create(otto_mf_ctx** out, int64_t n1, int64_t n2, int32_t
               hipMemset(c->err.p, 0, 64) == hipSuccess && hipMemset(c->sums.p, 0, 64) == hipSuccess;
     if (ok && !c->shared)
         ok = hipMemset(c->owner2.p, 0x7F, (size_t)n2 * 4) == hipSuccess && hipMemset(c->cnt2.p, 0, (size_t)n2 * 4) == hipSuccess;
+    // no stream parameter: the clears above went to stream 0 and hipMemset of device memory may return before they ran. The
+    // caller's streams need not order themselves against stream 0 (non-blocking streams do not), so wait here, once per ctx
+    ok = ok && hipStreamSynchronize(0) == hipSuccess;
     if (!ok) {
         set_error("hipMemset of the per-row words failed");
         return fail(-5);

@@ -31,6 +31,8 @@ def feed_host_events(builder, ev, device, chunk_sessions=2_000_000, pinned=True)
     devb = [tuple(torch.empty_like(t, device=dev) for t in h) for h in host]
     copy_stream = torch.cuda.Stream(device=dev)
     compute = torch.cuda.current_stream(dev)
+    # the device sets come from the caller's stream's allocator: a block it freed may still be read by work queued there
+    copy_stream.wait_stream(compute)
     sent = [torch.cuda.Event(), torch.cuda.Event()]          # H2D of the set finished
     used = [torch.cuda.Event(), torch.cuda.Event()]          # feed() no longer reads the set
     aid_i32 = ev.aid.view(np.int32) if ev.aid.dtype == np.uint32 else ev.aid.astype(np.int32)

@@ -104,6 +104,8 @@ def read_columns(paths, device, chunk_bytes=256 << 20):
     if on_gpu:
         copy_stream = torch.cuda.Stream(device=dev)
         compute = torch.cuda.current_stream(dev)
+        # the device sets come from the caller's stream's allocator: a block it freed may still be read by work queued there
+        copy_stream.wait_stream(compute)
         sent = [torch.cuda.Event(), torch.cuda.Event()]      # H2D of the set finished
         used = [torch.cuda.Event(), torch.cuda.Event()]      # the parse no longer reads the set
     cols = [[], [], [], []]

@@ -393,6 +393,8 @@ def read_columns(paths, columns, device, dtypes=None, batch_bytes=256 << 20, out
             devb = [torch.empty(max(stage, 16), dtype=torch.uint8, device=dev) for _ in range(2)]
             copy_stream = torch.cuda.Stream(device=dev)
             compute = torch.cuda.current_stream(dev)
+            # the device sets come from the caller's stream's allocator: a block it freed may still be read by work queued there
+            copy_stream.wait_stream(compute)
             sent = [torch.cuda.Event(), torch.cuda.Event()]      # H2D of the set finished
             used = [torch.cuda.Event(), torch.cuda.Event()]      # the decode no longer reads the set
         files = {}

@@ -1,0 +1,1712 @@
+"""One small case per public wrapper family for the calling-contract tests (tests/test_contract_cpu.py and
+tests/test_contract_gpu.py): a kernel family must give the same bytes off the default stream, behind late inputs and on
+scratch that an earlier call of the same family left dirty.
+
+A case is built from the existing ``*_inputs.py`` builders and checked by the family's existing restatement or oracle:
+
+    make(seed, scale=1)    host inputs, a dict of NumPy arrays. The SHAPES and dtypes depend on ``scale`` alone: session and
+                           list lengths are one fixed multiset that the seed permutes, values are drawn from the seed. So
+                           ``make(DECOY_SEED)`` is a valid input of the same family with identical shapes (a kernel that reads
+                           it by mistake gives a wrong answer, never an index out of range), ``make(DECOY_SEED, 2)`` is the
+                           same builder at twice the size.
+    run(dev, d)            ``d``: the inputs as device tensors (``upload``; the keys in ``host_keys`` stay NumPy because the
+                           wrapper takes host data). Returns a tuple of tensors / arrays / scalars obtained through the
+                           Python wrapper the family's GPU tests use.
+    restate(inputs)        what the family's restatement or oracle gives for these inputs, in the order of ``run``.
+    check(inputs, outputs) the family's comparison of ``outputs`` (NumPy, see ``host``) against ``restate(inputs)``.
+    entry_points           the C names the case is meant to reach (the GPU test asserts that it reaches them).
+    refusals               name -> (edit(inputs) -> inputs, call(dev, d), match): bad input that is detected ON THE DEVICE; the
+                           wrapper must raise OttoError matching ``match`` -- also behind a delay on a side stream. ``edit`` is
+                           None where the bad input is a file that ``call`` writes itself.
+    context                the family keeps a context: ``new_context(dev, inputs)`` makes one, ``run(dev, d, ctx)`` works on it (None:
+                           on a fresh one), ``reset(ctx)`` is what a caller does between two jobs on one context.
+    shape_outputs          positions of outputs that the shapes alone decide (equal for real and decoy), each with its reason.
+
+Sizes: the smallest at which the family runs more than one workgroup and more than one of its tiles; the constants are the
+ones the families' input files name (SCAN_TILE 4096, RS_TILE 4096, 64 KiB deflate blocks, 128-row knn tiles, ...).
+"""
+import numpy as np
+
+REAL_SEED, DECOY_SEED = 11, 23
+
+
+class Case:
+    def __init__(self, name, entry_points, make, run, restate, same=None, refusals=None, host_keys=(), context=False,
+                 shape_outputs=(), check=None, new_context=None, reset=None):
+        self.name, self.entry_points = name, tuple(entry_points)
+        self.custom_check = check is not None
+        if check is not None:
+            self.check = check                     # a family whose comparison is not output by output (frames, bands)
+        self.new_context, self.reset = new_context, reset
+        self.make, self.run, self.restate = make, run, restate
+        self.same = same or exact
+        self.refusals = refusals or {}
+        self.host_keys = tuple(host_keys)
+        self.context = context
+        self.shape_outputs = tuple(shape_outputs)      # outputs that the shapes alone decide: equal for real and decoy
+
+    def check(self, inputs, outputs):
+        want = self.restate(inputs)
+        assert len(want) == len(outputs), (self.name, len(want), len(outputs))
+        for i, (g, w) in enumerate(zip(outputs, want)):
+            self.same(host(g), host(w), f'{self.name}: output {i}')
+
+    def __repr__(self):
+        return f'Case({self.name})'
+
+
+def host(x):
+    """An output as a NumPy array: tensors are read back, scalars and bytes are wrapped."""
+    if hasattr(x, 'detach'):
+        return x.detach().cpu().numpy()
+    if isinstance(x, (bytes, bytearray)):
+        return np.frombuffer(bytes(x), dtype=np.uint8)
+    return np.asarray(x)
+
+
+def on_host(v):
+    """An input as NumPy, whether ``run`` got it as a device tensor or ``restate`` as the array itself."""
+    return v.cpu().numpy() if hasattr(v, 'cpu') else v
+
+
+def exact(got, want, tag):
+    """Integer and bit-exact families: same shape, same dtype width, same bytes."""
+    assert got.shape == want.shape, (tag, got.shape, want.shape)
+    if got.dtype.kind == 'f' or want.dtype.kind == 'f':
+        assert got.dtype == want.dtype, (tag, got.dtype, want.dtype)
+        assert np.array_equal(got.view(f'u{got.dtype.itemsize}'), want.view(f'u{want.dtype.itemsize}')), tag
+    else:
+        assert np.array_equal(got, want), tag
+
+
+def same_bytes(a, b):
+    """Byte identity of two outputs (what 'the same answer' means between two runs of one case)."""
+    a, b = host(a), host(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def upload(dev, inputs, host_keys=()):
+    import torch
+    return {k: (v if k in host_keys or not isinstance(v, np.ndarray) else torch.from_numpy(np.ascontiguousarray(v)).to(dev))
+            for k, v in inputs.items()}
+
+
+def permuted(lengths, rng):
+    """The fixed multiset of lengths in the seed's order: equal totals, other offsets."""
+    return np.asarray(lengths)[rng.permutation(len(lengths))]
+
+
+def offsets(lengths):
+    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+
+
+def _long_session(off, i):
+    j = int(np.searchsorted(i['off'], 513))                    # sessions 0 .. j - 1 become empty, session j takes their events
+    off[1:j + 1] = 0
+    assert i['off'][j + 1] > 512 and np.all(np.diff(off) >= 0)
+
+
+def _edit(key, fn):
+    """A refusal edit: a copy of the inputs with ``fn`` applied to a copy of ``inputs[key]``."""
+    def edit(inputs):
+        out = dict(inputs)
+        out[key] = inputs[key].copy()
+        fn(out[key], inputs)
+        return out
+    return edit
+
+
+# ---- blend: robust_stats / scale / join -----------------------------------------------------------------------------------
+def _blend_make(seed, scale=1):
+    import blend_inputs as bi
+    rng = np.random.default_rng(seed)
+    n = (2 * 4096 + 77) * scale                                # the select's tile is SCAN_TILE rows
+    x = rng.standard_normal(n) * 4.0 - 1.0                     # bi.scale_input('normal', n) with the seed's generator
+    x[rng.permutation(n)[:n // 7 + seed % 5]] = np.nan             # (the count of valid rows is an output)
+    models = bi._models(seed, 3, 3000 * scale, 0.5, 1500 * scale)       # 4,500 rows: two tiles of the sort; the seed picks the keys
+    d = {'x': x}
+    for m, (s, a, v) in enumerate(models):
+        d.update({f's{m}': s, f'a{m}': a, f'v{m}': v})
+    return d
+
+
+_BLEND_W, _BLEND_LEFT = (0.2, 0.3, 0.5), (0, 1, 0)
+
+
+def _blend_run(dev, d):
+    from otto_amd.ranker import blend
+    nv, stats = blend.robust_stats(d['x'])
+    out, center, scale = blend.robust_scale(d['x'])
+    models = [(d[f's{m}'], d[f'a{m}'], d[f'v{m}']) for m in range(3)]
+    sid, off, aid, pred = blend.blend_predictions(models, _BLEND_W, _BLEND_LEFT, scale=False)
+    return nv, stats, out, sid, off, aid, pred
+
+
+def _blend_restate(i):
+    import blend_restatement as br
+    nv, stats = br.robust_stats(i['x'])
+    out, _, _ = br.robust_scale(i['x'])
+    models = [(i[f's{m}'], i[f'a{m}'], i[f'v{m}']) for m in range(3)]
+    sid, off, aid, pred = br.blend(models, _BLEND_W, _BLEND_LEFT)
+    return nv, stats, out, sid, off, aid, pred
+
+
+def _blend_same(got, want, tag):
+    import blend_restatement as br
+    if want.dtype.kind == 'f':
+        assert br.same_bits(got, want), tag                    # zeros are sign-blind where the spec says so
+    else:
+        assert got.shape == want.shape and np.array_equal(got, want), tag
+
+
+def _blend_join(dev, d):
+    from otto_amd.ranker import blend
+    return blend.blend_predictions([(d[f's{m}'], d[f'a{m}'], d[f'v{m}']) for m in range(3)], _BLEND_W, _BLEND_LEFT, scale=False)
+
+
+def _blend_stats(dev, d):
+    from otto_amd.ranker import blend
+    return blend.robust_stats(d['x'])
+
+
+def _blend_dup(i):
+    out = dict(i, s1=i['s1'].copy(), a1=i['a1'].copy())
+    out['s1'][-1], out['a1'][-1] = out['s1'][0], out['a1'][0]
+    return out
+
+
+BLEND = Case('blend', ('otto_blend_robust_stats', 'otto_blend_scale', 'otto_blend_join'), _blend_make, _blend_run, _blend_restate,
+             same=_blend_same, refusals={
+                 'inf': (_edit('x', lambda x, i: x.__setitem__(len(x) // 2, np.inf)), _blend_stats, r'code -22.*infinite'),
+                 'every entry NaN': (_edit('x', lambda x, i: x.fill(np.nan)), _blend_stats, r'code -22.*NaN'),
+                 'repeated key': (_blend_dup, _blend_join, r'code -22.*repeat'),
+                 'negative id': (_edit('a2', lambda a, i: a.__setitem__(1200, -3)), _blend_join, r'code -22.*negative')})
+
+
+# ---- eval: last_click / cutoffs / split_count / split / hits ----------------------------------------------------------------
+_EVAL_SEED = 2 ** 63 + 5
+
+
+def _eval_lengths(scale):
+    rng = np.random.default_rng(5)
+    S = 300 * scale                                            # 8-lane groups, waves and workgroups; more than one block
+    r = rng.random(S)
+    return np.where(r < 0.7, rng.integers(0, 9, S), np.where(r < 0.93, rng.integers(9, 65, S), rng.integers(65, 400, S)))
+
+
+def _eval_make(seed, scale=1):
+    import eval_inputs as ei
+    rng = np.random.default_rng(seed)
+    lens = permuted(_eval_lengths(scale), rng)
+    aid, ts, typ, off, cutoff = ei.pack([ei.random_session(rng, int(n), n_aids=40) for n in lens])
+    S, k = len(lens), 20
+    lab_len = permuted(np.where(np.arange(S) % 9 == 1, 21 + np.arange(S) % 38, np.arange(S) % 4), rng)     # some past the cap of 20
+    l_off = offsets(lab_len)
+    l_aid = rng.integers(0, 3 * k + 5, int(l_off[-1])).astype(np.int32)
+    pred = rng.integers(0, 3 * k + 5, (S, k)).astype(np.int32)
+    n = permuted(np.arange(S) % (k + 1), rng).astype(np.int32)
+    for s in range(S):
+        pred[s, n[s]:] = -1
+    mask = (rng.random(S) < 0.4).astype(np.uint8)
+    ids = ei.subset_ids(S, seed)[0]                            # session ids, ascending with gaps: the labels' and the predictions'
+    return dict(aid=aid, ts=ts, typ=typ, off=off, cutoff=cutoff, l_off=l_off, l_aid=l_aid, pred=pred, n=n, mask=mask, ids=ids,
+                pids=ids.copy())
+
+
+def _eval_events(d):
+    from otto_amd.events import DeviceEvents
+    return DeviceEvents(d['aid'], d['ts'], d['typ'], d['off'], None, None, 40)
+
+
+def _eval_run(dev, d):
+    from otto_amd.ranker import evaluate as ev
+    events = _eval_events(d)
+    last = ev.last_click(events)
+    cut, n_without = ev.cutoffs(events, _EVAL_SEED)
+    kept, labels = ev.split(events, d['cutoff'])
+    h, dn, tot = _eval_hits(dev, d)
+    out = [last, cut, kept.sess_off, kept.aid, kept.ts, kept.type]
+    for name in ev.TYPES:
+        out += list(labels[name])
+    return tuple(out) + (h, dn, np.array([tot[k] for k in ('hits', 'denom', 'mask_hits', 'mask_denom')]))
+
+
+def _eval_restate(i):
+    import eval_restatement as er
+    last = er.last_click(i['typ'], i['off'])
+    cut, _ = er.cutoffs(i['typ'], i['off'], _EVAL_SEED)
+    kept, labels = er.split(i['aid'], i['ts'], i['typ'], i['off'], i['cutoff'])
+    out = [last, cut, kept['sess_off'], kept['aid'], kept['ts'], kept['typ']]
+    for name in ('clicks', 'carts', 'orders'):
+        out += list(labels[name])
+    lab = er.lists_csr(i['l_off'], i['l_aid'])
+    h, dn = er.hits(lab, er.rows_padded(i['pred'], i['n']), i['ids'], i['pids'], cap=20)
+    tot = er.totals(h, dn, i['mask'])
+    return tuple(out) + (h, dn, np.array([tot[k] for k in ('hits', 'denom', 'mask_hits', 'mask_denom')]))
+
+
+def _eval_hits(dev, d):
+    from otto_amd.ranker import evaluate as ev
+    return ev.hits((d['l_off'], d['l_aid']), (d['pred'], d['n']), d['ids'], d['pids'], cap=20, mask=d['mask'])
+
+
+def _foreign_session(pids, i):
+    g = int(np.flatnonzero(np.diff(i['ids']) > 1)[0])
+    pids[g] = i['ids'][g] + 1                                  # an id in a gap of the label sessions; still ascending
+
+
+def _swapped_sessions(pids, i):
+    pids[[5, 6]] = pids[[6, 5]]
+
+
+def _eval_split(dev, d):
+    from otto_amd.ranker import evaluate as ev
+    return ev.split(_eval_events(d), d['cutoff'])
+
+
+def _eval_last(dev, d):
+    from otto_amd.ranker import evaluate as ev
+    return ev.last_click(_eval_events(d))
+
+
+def _eval_cut(dev, d):
+    from otto_amd.ranker import evaluate as ev
+    return ev.cutoffs(_eval_events(d), 1)
+
+
+def _bad_typ(typ, i):
+    typ[len(typ) - 1] = 3
+
+
+def _bad_cutoff(cutoff, i):
+    s = int(np.flatnonzero(np.diff(i['off']) > 70)[0])
+    cutoff[s] = np.diff(i['off'])[s]
+
+
+EVAL = Case('eval', ('otto_eval_last_click', 'otto_eval_cutoffs', 'otto_eval_split_count', 'otto_eval_split', 'otto_eval_hits'),
+            _eval_make, _eval_run, _eval_restate, refusals={
+                'typ 3: split': (_edit('typ', _bad_typ), _eval_split, r'code -22.*typ'),
+                'typ 3: last_click': (_edit('typ', _bad_typ), _eval_last, r'code -22.*typ'),
+                'typ 3: cutoffs': (_edit('typ', _bad_typ), _eval_cut, r'code -22.*typ'),
+                'cutoff past the session': (_edit('cutoff', _bad_cutoff), _eval_split, r'code -22.*cutoff'),
+                'hits: a foreign prediction session': (_edit('pids', _foreign_session), _eval_hits,
+                                                       r'code -22.*not among the label sessions'),
+                'hits: prediction sessions not ascending': (_edit('pids', _swapped_sessions), _eval_hits, r'code -22.*ascending')})
+
+
+# ---- events: sort (with its CSR) and type_from_strings ------------------------------------------------------------------------
+_TYPE_NAMES = np.array(['clicks', 'carts', 'orders'], dtype=object)
+
+
+def _events_make(seed, scale=1):
+    import edge_inputs as ei
+    n = (2 * 16384 + 77) * scale                               # 16384 rows: one workgroup's span of the sort
+    sess, ts, div = ei.sort_case('generic', n, seed)
+    assert div == 1000
+    rng = np.random.default_rng(seed)
+    return dict(sess=sess, ts=ts, aid=rng.integers(0, 1_855_603, n).astype(np.int32), typ=rng.integers(0, 3, n).astype(np.uint8))
+
+
+def _events_run(dev, d):
+    import pandas as pd
+    from otto_amd import events
+    n = int(d['ts'].numel())
+    ev = events._sort_to_events(dev, d['sess'], d['ts'], d['aid'], d['typ'], n, 1000, 1_855_603)
+    out = [ev.aid, ev.ts, ev.type, ev.sess_off, ev.session_ids, ev.order]
+    # the frame entrance with its string types: host columns, uploaded by the wrapper on the current stream
+    h = {k: v.cpu().numpy() for k, v in d.items()}
+    fr = pd.DataFrame({'session': h['sess'], 'aid': h['aid'], 'ts': h['ts'], 'type': _TYPE_NAMES[h['typ']]})
+    ev = events.frame_to_events_device(fr, dev, ts_unit='ms')
+    return tuple(out + [ev.aid, ev.ts, ev.type, ev.sess_off, ev.session_ids, ev.order])
+
+
+def _events_restate(i):
+    import edge_inputs as ei
+    order, sec, ids, off = ei.sort_reference(i['sess'], i['ts'], 1000)
+    one = [i['aid'][order], sec.astype(np.int32), i['typ'][order], off, ids, order.astype(np.int32)]
+    return tuple(one + one)
+
+
+def _events_sort_only(dev, d):
+    from otto_amd import events
+    return events._sort_to_events(dev, d['sess'], d['ts'], d['aid'], d['typ'], int(d['ts'].numel()), 1000, 1_855_603)
+
+
+EVENTS = Case('events', ('otto_events_sort', 'otto_events_type_from_strings'), _events_make, _events_run, _events_restate,
+              refusals={'negative timestamp': (_edit('ts', lambda ts, i: ts.__setitem__(1234, -1)), _events_sort_only,
+                                               'timestamps are negative or beyond')})
+
+
+# ---- pairs: raw_count / time / diff (diff sorts its shuffle through otto_events_sort) --------------------------------------------
+def _pairs_lengths(scale):
+    return np.minimum(np.random.default_rng(3).geometric(0.12, 1500 * scale), 40)      # 60,000 raw slots: 4 sort workgroups
+
+
+def _pairs_make(seed, scale=1):
+    import edge_inputs as ei
+    rng = np.random.default_rng(seed)
+    lens = permuted(_pairs_lengths(scale), rng)
+    sessions = [(rng.integers(0, 400, n), ei.T0 + np.sort(rng.integers(0, 4000, n))) for n in lens]     # ei.random_sessions' rows
+    aid, ts, off, _ = ei.stream_to_frame(sessions)
+    return dict(aid=aid, ts=ts, off=off, keys=rng.integers(0, 2 ** 31, len(aid)).astype(np.int64))
+
+
+def _pairs_run(dev, d):
+    import torch
+    from otto_amd.events import DeviceEvents
+    from otto_amd.matrix_factorization.data import build_aid_pairs_device
+    S = int(d['off'].numel()) - 1
+    ev = DeviceEvents(d['aid'], d['ts'], torch.zeros_like(d['aid'], dtype=torch.uint8), d['off'], torch.arange(S, device=dev), None, 400)
+    out = []
+    for agg in ('mean', 'max'):
+        out += list(build_aid_pairs_device(ev, 'time', hour_difference=0.5, target_aggregation=agg, sample_frac=1.0))
+    out += list(build_aid_pairs_device(ev, 'diff', shuffle_keys=d['keys']))
+    return tuple(out)
+
+
+def _pairs_restate(i):
+    import pandas as pd
+    import pairs_oracle as po
+    fr = pd.DataFrame({'session': np.repeat(np.arange(len(i['off']) - 1), np.diff(i['off'])), 'aid': i['aid'].astype(np.int64),
+                       'ts': i['ts'].astype(np.int64), 'type': np.zeros(len(i['aid']), dtype=np.uint8)})
+    out = []
+    frames = [po.pairs_time(fr, hour_difference=0.5, target_aggregation=agg) for agg in ('mean', 'max')]
+    frames.append(po.pairs_diff(fr, shuffle_keys=i['keys']))
+    for f in frames:
+        out += [f[c].to_numpy().astype(np.int64) for c in ('x1', 'x2', 'target')]
+    return tuple(out)
+
+
+def _pairs_sorted_restate(i):
+    import edge_inputs as ei
+    cols = _pairs_restate(i)
+    out = []
+    for j in range(0, len(cols), 3):
+        rows = ei.pair_rows(cols[j:j + 3])
+        out += [rows[:, 0].copy(), rows[:, 1].copy(), rows[:, 2].copy()]
+    return tuple(out)
+
+
+PAIRS = Case('pairs', ('otto_pairs_raw_count', 'otto_pairs_time', 'otto_pairs_diff', 'otto_events_sort'), _pairs_make, _pairs_run,
+             _pairs_sorted_restate, host_keys=('keys',))
+
+
+# ---- most frequent aids: count / topk -------------------------------------------------------------------------------------------
+_FREQ_AIDS, _FREQ_K = 1300, 20                                 # 256 aids per workgroup of the top-k, 64 per list
+
+
+def _freq_make(seed, scale=1):
+    import submit_inputs as si
+    aid, typ, _, _, _ = si._freq_random(seed, _FREQ_AIDS, 6000 * scale, _FREQ_K)
+    return dict(aid=aid.astype(np.int32), typ=typ)
+
+
+def _freq_run(dev, d):
+    from otto_amd import frequency
+    counts, lists = frequency.most_frequent(d['aid'], d['typ'], _FREQ_AIDS, k=_FREQ_K)
+    return (counts,) + tuple(x for name in frequency.ROWS for x in lists[name])
+
+
+def _freq_restate(i):
+    import submit_restatement as sr
+    counts = sr.frequency_counts(i['aid'].astype(np.uint32), i['typ'], _FREQ_AIDS)
+    lists = sr.frequency_lists(counts, _FREQ_K)
+    return (counts,) + tuple(x for name in sr.ROWS for x in lists[name])
+
+
+def _freq_same(got, want, tag):
+    assert got.shape == want.shape and np.array_equal(got.astype(np.int64), np.asarray(want).astype(np.int64)), tag
+
+
+def _freq_count(dev, d):
+    from otto_amd import frequency
+    return frequency.count_events(d['aid'], d['typ'], _FREQ_AIDS)
+
+
+FREQ = Case('freq', ('otto_freq_count', 'otto_freq_topk'), _freq_make, _freq_run, _freq_restate, same=_freq_same, refusals={
+    'aid outside the table': (_edit('aid', lambda a, i: a.__setitem__(4000, _FREQ_AIDS)), _freq_count, r'code -22'),
+    'type above 2': (_edit('typ', lambda t, i: t.__setitem__(len(t) - 1, 3)), _freq_count, r'code -22')})
+
+
+# ---- submission text: measure / format ------------------------------------------------------------------------------------------
+_SUBMIT_K, _SUBMIT_LD = 4, 5
+
+
+def _submit_make(seed, scale=1):
+    import submit_inputs as si
+    S = (si.SCAN_TILE + si.L + 5) * scale                      # more than one tile of the scan, a ragged last workgroup
+    c = si._shape_case(seed, S, 3, _SUBMIT_K, _SUBMIT_LD, (0, 1, _SUBMIT_K - 1, _SUBMIT_K, -1, _SUBMIT_K))
+    assert c['types'] == [2, 1, 0] and c['ld'] == _SUBMIT_LD
+    d = {'session_id': c['session_id']}
+    for t, (top, n) in enumerate(c['tables']):
+        n = permuted(n, np.random.default_rng(seed + t))       # which sessions have no line is the seed's too
+        top = np.where(np.arange(_SUBMIT_LD)[None, :] < np.maximum(n, 0)[:, None], np.abs(top), -1).astype(np.int32)
+        d.update({f'top{t}': top, f'n{t}': n})
+    return d
+
+
+def _submit_tables(d):
+    return [(d[f'top{t}'][:, :_SUBMIT_K], d[f'n{t}']) for t in range(3)]
+
+
+def _submit_run(dev, d):
+    from otto_amd import submission
+    return (submission.format_rows(d['session_id'], _submit_tables(d), [2, 1, 0], interleave=False),
+            submission.format_rows(d['session_id'], _submit_tables(d), [2, 1, 0], interleave=True, header=True))
+
+
+def _submit_restate(i):
+    import submit_restatement as sr
+    return (sr.submission_bytes(i['session_id'], _submit_tables(i), [2, 1, 0], False),
+            sr.submission_bytes(i['session_id'], _submit_tables(i), [2, 1, 0], True, header=True))
+
+
+def _submit_first(dev, d):
+    from otto_amd import submission
+    return submission.format_rows(d['session_id'], _submit_tables(d), [2, 1, 0])
+
+
+SUBMIT = Case('submit', ('otto_submit_measure', 'otto_submit_format'), _submit_make, _submit_run, _submit_restate, refusals={
+    'n above k': (_edit('n1', lambda n, i: n.__setitem__(4100, _SUBMIT_K + 1)), _submit_first, 'otto_submit_measure: line'),
+    'negative session': (_edit('session_id', lambda s, i: s.__setitem__(60, -1)), _submit_first, 'otto_submit_measure: line')})
+
+
+# ---- deflate: plan / emit -------------------------------------------------------------------------------------------------------
+def _deflate_make(seed, scale=1):
+    import deflate_inputs as di
+    n = (di.dr.BLOCK_MAX + 4500) * scale                       # a full 64 KiB block and a short one
+    text = di.text_a(lines=300 * scale, seed=seed)
+    assert len(text) >= n
+    return dict(text=np.frombuffer(text[:n], dtype=np.uint8).copy())
+
+
+def _deflate_run(dev, d):
+    from otto_amd import deflate
+    return (deflate.gzip_members(d['text']),)
+
+
+def _deflate_restate(i):
+    import deflate_restatement as dr
+    return (dr.gzip_members(i['text'].tobytes()),)
+
+
+DEFLATE = Case('deflate', ('otto_deflate_plan', 'otto_deflate_emit'), _deflate_make, _deflate_run, _deflate_restate)
+
+
+# ---- knn table ------------------------------------------------------------------------------------------------------------------
+_KNN_D, _KNN_K = 32, 45
+
+
+def _knn_make(seed, scale=1):
+    # the inputs of test_exact_ties_prefer_smaller_id: small integers, every product and sum exact in fp32, so the ids and
+    # the distances are the restatement's bit for bit. 1100 items: two item ranges of 1024; 300 query rows: three 128-row tiles
+    rng = np.random.default_rng(seed)
+    N, d = 1100 * scale, _KNN_D
+    E = rng.integers(-2, 3, (N, d)).astype(np.float32)
+    E[:, 3:] *= (rng.random((N, d - 3)) < 4.0 / d)
+    valid = (rng.random(N) > 0.1).astype(np.uint8)
+    rows = rng.permutation(N)[:300 * scale].astype(np.int32)
+    return dict(E=E, valid=valid, rows=rows)
+
+
+def _knn_run(dev, d):
+    from otto_amd.matrix_factorization.neighbours import neighbour_table
+    out = []
+    for metric in ('euclidean', 'dot'):
+        out += list(neighbour_table(d['E'], k=_KNN_K, metric=metric, valid=d['valid'], rows=d['rows']))
+    return tuple(out)
+
+
+def _knn_restate(i):
+    import knn_restatement as kr
+    out = []
+    for metric in ('euclidean', 'dot'):
+        ids, val, n, _, _ = kr.knn(i['E'], _KNN_K, metric, valid=i['valid'], rows=i['rows'])
+        out += [ids, val.astype(np.float32), n]
+    return tuple(out)
+
+
+def _knn_one(dev, d):
+    from otto_amd.matrix_factorization.neighbours import neighbour_table
+    return neighbour_table(d['E'], k=_KNN_K, metric='euclidean', valid=d['valid'], rows=d['rows'])
+
+
+KNN = Case('knn', ('otto_knn_table',), _knn_make, _knn_run, _knn_restate, refusals={
+    'row id outside the table': (_edit('rows', lambda r, i: r.__setitem__(200, len(i['E']))), _knn_one, 'outside')})
+
+
+# ---- forest: predict / leaves / session_topk ------------------------------------------------------------------------------------
+_FOREST_ARRAYS = ('node_off', 'leaf_off', 'split_feature', 'threshold', 'decision_type', 'left_child', 'right_child', 'leaf_value')
+_FOREST_T, _FOREST_L, _FOREST_F = 9, 128, 54                   # 8 trees of 128 leaves fill one LDS group: two groups
+
+
+def _forest_make(seed, scale=1):
+    import forest_restatement as fr
+    rng = np.random.default_rng(seed)
+    n = 1000 * scale                                           # 256 rows per workgroup
+    X = fr.random_rows(rng, n, _FOREST_F)
+    forest = fr.random_forest(rng, _FOREST_T, _FOREST_L, _FOREST_F, X=X)
+    d = {name: getattr(forest, name) for name in _FOREST_ARRAYS}
+    lens = permuted(np.r_[np.arange(60 * scale) % 30, [0, 0, 70, 1000 * scale - 70 - 870 * scale]], rng)
+    assert lens.sum() == n and lens.min() >= 0
+    d.update(X=X, aid=rng.integers(0, 1 << 21, n).astype(np.int32), row_off=offsets(lens))
+    return d
+
+
+def _forest_of(d):
+    from otto_amd.ranker.forest import Forest
+    return Forest(*[on_host(d[name]) for name in _FOREST_ARRAYS], _FOREST_F)
+
+
+def _forest_run(dev, d):
+    from otto_amd.ranker import forest as fo
+    f = _forest_of(d)
+    return (fo.forest_predict(f, d['X']), fo.forest_leaves(f, d['X'])) + tuple(fo.rank_candidates([f], d['X'], d['aid'], d['row_off'], k=20))
+
+
+def _forest_restate(i):
+    import forest_restatement as fr
+    f = _forest_of(i)
+    leaf = fr.leaves(f, i['X'])
+    top = fr.session_topk(fr.ensemble([f], i['X']), i['aid'], i['row_off'], 20)
+    assert top[3] == 0
+    return (fr.raw_scores(f, i['X'], leaf), leaf) + tuple(top[:3])
+
+
+def _forest_topk(dev, d):
+    from otto_amd.ranker import forest as fo
+    return fo.rank_candidates([_forest_of(d)], d['X'], d['aid'], d['row_off'], k=20)
+
+
+def _bad_row_off(off, i):
+    off[5] = off[-1] + 1
+
+
+FOREST = Case('forest', ('otto_forest_predict', 'otto_forest_leaves', 'otto_forest_session_topk'), _forest_make, _forest_run,
+              _forest_restate, host_keys=_FOREST_ARRAYS,
+              refusals={'row_off past the rows': (_edit('row_off', _bad_row_off), _forest_topk, r'code -22')})
+
+
+# ---- objectives: binary / label_counts / ndcg / auc / logloss ---------------------------------------------------------------------
+_OBJ_SHORT = (2, 50, 64, 65, 1, 30, 129)                       # objectives_inputs.LAMBDAMART_SIZES; one query of 1024 rows is added
+
+
+def _obj_make(seed, scale=1):
+    rng = np.random.default_rng(seed)
+    lens = permuted(np.r_[np.tile(_OBJ_SHORT, 25 * scale), [1024]], rng)      # 9,549 rows: two tiles of the AUC sort and a part of a third
+    off = offsets(lens)
+    n = int(off[-1])
+    score = np.round(rng.standard_normal(n) * 2, 1)            # ties inside the queries (objectives_inputs.ndcg_problem)
+    score[rng.permutation(n)[:8]] = [25.0, -25.0, 0.0, -0.0, 24.5, -24.5, 12.0, -12.0]
+    label = ((rng.random(n) < 0.3) * rng.integers(1, 4, n)).astype(np.int32)
+    return dict(score=score, label=label, off=off)
+
+
+def _obj_run(dev, d):
+    from otto_amd.ranker import objectives as ob
+    g, h = ob.binary_gradients(d['score'], d['label'], 1.0, 2.0, 0.75, 0.0)
+    return (g, h, np.array(ob.label_counts(d['label'])), ob.ndcg_at_k(d['score'], d['label'], d['off'], 20),
+            np.array(ob.auc_counts(d['score'], d['label'])), np.float64(ob.logloss_sum(d['score'], d['label'], 1.0)),
+            np.float64(ob.logloss_sum(d['score'], d['label'], 1.0, grid=7)))
+
+
+def _obj_restate(i):
+    import objectives_restatement as orr
+    g, h, bad = orr.binary(i['score'], i['label'], 1.0, 2.0, 0.75, 0.0)
+    ndcg, invalid = orr.ndcg_at_k(i['score'], i['label'], i['off'], 20)
+    assert not bad and not invalid
+    ll = np.float64(orr.logloss_sum(i['score'], i['label'], 1.0))
+    return (g, h, np.array(orr.label_counts(i['label'])), ndcg, np.array(orr.auc_counts(i['score'], i['label'])), ll, ll)
+
+
+def _obj_same(got, want, tag):
+    import objectives_inputs as oi
+    if want.ndim == 0:                                         # the logloss sums: exp and log1p of the device are not pinned
+        assert abs(float(got) - float(want)) <= oi.LOGLOSS_RTOL * abs(float(want)), (tag, got, want)
+    else:
+        exact(got, want, tag)
+
+
+def _obj_binary(dev, d):
+    from otto_amd.ranker import objectives as ob
+    return ob.binary_gradients(d['score'], d['label'], 1.0, 2.0, 0.75, 0.0)
+
+
+def _obj_ndcg(dev, d):
+    from otto_amd.ranker import objectives as ob
+    return ob.ndcg_at_k(d['score'], d['label'], d['off'], 20)
+
+
+def _long_query(off, i):
+    q = int(np.flatnonzero(np.diff(i['off']) == 1024)[-1])
+    assert q > 0 and off[q] - off[q - 1] >= 1
+    off[q] -= 1                                                # 1025 rows: one above MAX_QUERY
+
+
+OBJECTIVES = Case('objectives', ('otto_obj_binary', 'otto_obj_label_counts', 'otto_obj_ndcg_at_k', 'otto_obj_auc', 'otto_obj_logloss',
+                                 'otto_obj_logloss_grid'), _obj_make, _obj_run, _obj_restate, same=_obj_same, refusals={
+    'label 32': (_edit('label', lambda l, i: l.__setitem__(5170, 32)), _obj_binary, 'label'),
+    'query above 1024 rows': (_edit('off', _long_query), _obj_ndcg, 'quer')})
+
+
+# ---- folds: group_kfold / classify / emit / gather_u8 -------------------------------------------------------------------------------
+def _folds_make(seed, scale=1):
+    rng = np.random.default_rng(seed)
+    sizes = permuted(np.r_[np.arange(4200 * scale) % 9, [1024]], rng)      # 4,201 queries: two blocks of the walk
+    off = offsets(sizes)
+    n = int(off[-1])
+    label = np.zeros(n, dtype=np.uint8)
+    for q in np.flatnonzero(sizes):                            # the compositions of test_folds_gpu._index_case
+        a, b, u = off[q], off[q + 1], rng.random()
+        if u < 0.2:
+            continue
+        label[a:b] = 1 + (rng.random(b - a) < 0.3) if u < 0.35 else (rng.random(b - a) < 0.3) * rng.integers(1, 3, b - a)
+    return dict(label=label, off=off, bins=rng.integers(0, 256, (3, n)).astype(np.uint8))
+
+
+def _folds_run(dev, d):
+    from otto_amd.ranker import folds
+    fold, rows = folds.group_kfold(d['off'], 5, n=int(d['label'].numel()))
+    idx = folds.fold_indices(d['label'], d['off'], fold, 1, 0.3, 42)
+    return (fold, rows) + tuple(getattr(idx, name) for name in _FOLD_ARRAYS) + (folds.gather_bins(d['bins'], idx.train_idx),)
+
+
+_FOLD_ARRAYS = ('train_idx', 'train_query_off', 'train_query', 'val_idx', 'val_query_off', 'val_query')
+
+
+def _folds_restate(i):
+    import folds_restatement as fr
+    fold, rows = fr.group_kfold(i['off'], 5)
+    idx = fr.fold_indices(i['label'], i['off'], fold, 1, 0.3, 42)
+    return (fold, rows) + tuple(idx[name] for name in _FOLD_ARRAYS) + (i['bins'][:, idx['train_idx']],)
+
+
+def _folds_kfold(dev, d):
+    from otto_amd.ranker import folds
+    return folds.group_kfold(d['off'], 5, n=int(d['label'].numel()))
+
+
+def _folds_gather(dev, d):
+    import torch
+    from otto_amd.ranker import folds
+    return folds.gather_bins(d['bins'], d['off'][:2000].to(torch.int32))
+
+
+def _folds_indices(dev, d):
+    import torch
+    from otto_amd.ranker import folds
+    fold_of_query = (torch.arange(d['off'].numel() - 1, device=dev) % 5).to(torch.int32)
+    # int32 labels, the uint8 value 255 read as -1: the one label dtype that can hold the value the library refuses. Fold 7
+    # validates no query, so every query's labels are looked at
+    return folds.fold_indices(d['label'].view(torch.int8).to(torch.int32), d['off'], fold_of_query, 7, 0.3, 42)
+
+
+def _descending(off, i):
+    off[41] = off[40] - 1 if off[40] > 0 else -1
+
+
+FOLDS = Case('folds', ('otto_folds_group_kfold', 'otto_folds_classify', 'otto_folds_emit', 'otto_folds_gather_u8'), _folds_make,
+             _folds_run, _folds_restate, shape_outputs=(1,),     # rows per fold: the walk balances n rows over 5 folds whatever the order
+             refusals={
+                 'descending query_off': (_edit('off', _descending), _folds_kfold, 'query_off'),
+                 'classify: descending query_off': (_edit('off', _descending), _folds_indices, 'query_off'),
+                 'classify: a label below 0': (_edit('label', lambda l, i: l.__setitem__(7, 255)), _folds_indices, 'label'),
+                 'gather index outside the rows': (_edit('off', lambda off, i: off.__setitem__(7, len(i['label']))), _folds_gather,
+                                                   'index')})
+
+
+# ---- interaction features, both forms -----------------------------------------------------------------------------------------------
+_INTER_AIDS, _INTER_C = 700, 65                                # 65 candidates: one past the wave width
+
+
+def _inter_make(seed, scale=1):
+    import edge_inputs as ei
+    rng = np.random.default_rng(seed)
+    S = 400 * scale
+    lengths = permuted(np.random.default_rng(9).integers(1, 50, S), rng)
+    aid, typ, off = ei.inter_sessions(lengths, _INTER_AIDS, seed)
+    cand = np.full((S, _INTER_C), -1, dtype=np.int32)
+    score = np.zeros((S, _INTER_C), dtype=np.float32)
+    sizes = permuted(np.where(np.arange(S) % 3 == 0, _INTER_C, np.arange(S) * 7 % (_INTER_C + 1)), rng)
+    rows = []
+    for s in range(S):                                         # the rows of test_inter_gpu._dense_case, aid 0 in every row that has one
+        n = int(sizes[s])
+        pick = ei.unique_candidates(rng, aid[off[s]:off[s + 1]], _INTER_AIDS, n)
+        if n and 0 not in pick:
+            pick[0] = 0
+        cand[s, :n] = pick
+        score[s, :n] = ei.inter_scores('mixed', n, rng)
+        rows.append(pick)
+    rcand = np.concatenate(rows).astype(np.int32)
+    return dict(aid=aid, typ=typ, off=off, cand=cand, score=score, row_off=offsets(sizes), rcand=rcand,
+                rscore=ei.inter_scores('fractional', len(rcand), rng))
+
+
+def _inter_table(d, session):
+    return {'candidates': d['rcand'], 'candidate_scores': d['rscore'], 'row_off': d['row_off'], 'session': session}
+
+
+def _inter_run(dev, d):
+    from otto_amd.ranker import interaction_feature_engineering as ife
+    return tuple(ife.interaction_features(d['aid'], d['typ'], d['off'], d['cand'], d['score'], _INTER_AIDS)) + \
+        tuple(ife.interaction_features_rows(d['aid'], d['typ'], d['off'], _inter_table(d, None), _INTER_AIDS))
+
+
+def _inter_want(i):
+    import pandas as pd
+    import edge_inputs as ei
+    import inter_oracle as io
+    events = ei.events_frame(i['aid'], i['typ'], i['off'])
+    keep = i['cand'] >= 0
+    s_idx, _ = np.nonzero(keep)
+    dense = io.interaction_features(pd.DataFrame({'session': s_idx.astype(np.int64), 'candidates': i['cand'][keep].astype(np.int64),
+                                                  'candidate_scores': i['score'][keep].astype(np.float64)}), events)
+    r_idx = np.repeat(np.arange(len(i['off']) - 1), np.diff(i['row_off']))
+    rows = io.interaction_features(pd.DataFrame({'session': r_idx.astype(np.int64), 'candidates': i['rcand'].astype(np.int64),
+                                                 'candidate_scores': i['rscore'].astype(np.float64)}), events)
+    return dense, rows, r_idx
+
+
+def _inter_restate(i):
+    from otto_amd.ranker import interaction_feature_engineering as ife
+    dense, rows, _ = _inter_want(i)
+    key = ['session', 'candidates', 'candidate_scores']
+    cols = ife.ROW_COLUMNS + ife.SESSION_COLUMNS + ife.AID_COLUMNS
+    return tuple(f.sort_values(key)[list(part)].to_numpy().astype(np.float64) for f in (dense, rows)
+                 for part in (ife.ROW_COLUMNS, ife.SESSION_COLUMNS, ife.AID_COLUMNS))
+
+
+def _inter_check(i, outputs):
+    import torch
+    import test_inter_gpu as family
+    from otto_amd.ranker import interaction_feature_engineering as ife
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(host(a)))
+    row, sf, af, row2, sf2, af2 = (t(o) for o in outputs)
+    dense, rows, r_idx = _inter_want(i)
+    family._compare(ife.to_frame(np.arange(len(i['off']) - 1), t(i['cand']), t(i['score']), row, sf, af), dense, ife)
+    tab = {k: t(v) for k, v in _inter_table(i, r_idx.astype(np.int64)).items()}
+    family._compare(ife.table_to_frame(tab, row2, sf2, af2), rows, ife)
+
+
+def _inter_dense(dev, d):
+    from otto_amd.ranker import interaction_feature_engineering as ife
+    return ife.interaction_features(d['aid'], d['typ'], d['off'], d['cand'], d['score'], _INTER_AIDS)
+
+
+def _inter_rows(dev, d):
+    from otto_amd.ranker import interaction_feature_engineering as ife
+    return ife.interaction_features_rows(d['aid'], d['typ'], d['off'], _inter_table(d, None), _INTER_AIDS)
+
+
+_INTER_REFUSED = 'sessions longer than 512 events or candidates outside'
+
+
+INTER = Case('inter', ('otto_inter_features', 'otto_inter_features_rows'), _inter_make, _inter_run, _inter_restate, check=_inter_check,
+             refusals={'candidate outside the catalogue': (_edit('cand', lambda c, i: c.__setitem__((3, 0), _INTER_AIDS)), _inter_dense,
+                                                           _INTER_REFUSED),
+                       'rows: candidate outside the catalogue': (_edit('rcand', lambda c, i: c.__setitem__(0, _INTER_AIDS)), _inter_rows,
+                                                                 _INTER_REFUSED),
+                       'session of more than 512 events': (_edit('off', _long_session), _inter_dense, _INTER_REFUSED),
+                       'rows: session of more than 512 events': (_edit('off', _long_session), _inter_rows,
+                                                                 _INTER_REFUSED)})
+
+
+# ---- feature tables and the feature matrix ----------------------------------------------------------------------------------------------
+_FEAT_COUNTS = [1, 63, 64, 65, 1025, 4097] + [0, 0] + [1, 2, 3, 4, 5] * 60 + [0] * 10      # feat_inputs.edge_events' segments
+_FEAT_NAMES = ('candidate_scores', 'session_candidate_cumcount_last', 'aid_count', 'session_candidate_score_mean', 'aid_candidate_score_std')
+
+
+def _feat_make(seed, scale=1):
+    import feat_inputs as fi
+    import test_feat_gpu as family
+    rng = np.random.default_rng(seed)
+    counts = permuted(np.tile(_FEAT_COUNTS, scale), rng)       # which aid is hot is the seed's
+    n_aids, total = len(counts), int(counts.sum())
+    shape = np.random.default_rng(4)
+    lengths = [512]
+    while sum(lengths) < total:
+        lengths.append(min(int(shape.integers(1, 21)), total - sum(lengths)))
+    lengths = permuted(lengths, rng)
+    off = offsets(lengths)
+    pool = rng.permutation(np.repeat(np.arange(n_aids), counts)).astype(np.int32)
+    ts = np.empty(total, dtype=np.int64)
+    for s, n in enumerate(lengths):                            # fi.events' stamps: a session inside two days of 64
+        day = int(rng.integers(0, 63 if n > 1 else 64))
+        ts[off[s]:off[s + 1]] = fi.SUNDAY + day * 86400 + np.sort(rng.choice((2 if n > 1 else 1) * 86400, n, replace=False))
+    typ = rng.choice(3, total, p=[0.8, 0.15, 0.05]).astype(np.uint8)
+    sizes = permuted(np.r_[np.arange(80 * scale) % 130, [0, 0, 0]], rng)      # 5,000 rows of the matrix: 256 per workgroup
+    m = family._matrix_inputs(rng, sizes, n_aids=997)
+    m['inter_row'] = m['inter_row'].view(np.int16)
+    return dict(aid=pool, ts=ts.astype(np.int32), typ=typ, off=off, **m)
+
+
+def _feat_run(dev, d):
+    from otto_amd.ranker import features as ft
+    at, _ = ft.aid_feature_table(d['aid'], d['ts'], d['typ'], d['off'], len(_FEAT_COUNTS) * (int(d['aid'].numel()) // sum(_FEAT_COUNTS)))
+    st = ft.session_feature_table(d['aid'], d['ts'], d['typ'], d['off'], at)
+    table = {'row_off': d['row_off'], 'candidates': d['cand'], 'candidate_scores': d['score']}
+    X = ft.feature_matrix(table, d['inter_row'], d['inter_sess'], d['inter_aid'], d['aid_tab'], d['sess_tab'], list(_FEAT_NAMES))
+    return at, st, X
+
+
+def _feat_restate(i):
+    import feat_restatement as fr
+    from otto_amd.ranker import interaction_feature_engineering as ife
+    n_aids = len(_FEAT_COUNTS) * (len(i['aid']) // sum(_FEAT_COUNTS))
+    at = fr.aid_table(i['aid'], i['ts'], i['typ'], i['off'], n_aids)
+    st = fr.session_table(i['aid'], i['ts'], i['typ'], i['off'], at)
+    prog = fr.resolve(list(_FEAT_NAMES), ife.ROW_COLUMNS, ife.SESSION_COLUMNS, ife.AID_COLUMNS)
+    X = fr.matrix(i['row_off'], i['cand'], i['score'], i['inter_row'].view(np.uint16), i['inter_sess'], i['inter_aid'], i['aid_tab'],
+                  i['sess_tab'], prog)
+    return at, st, X
+
+
+def _feat_same(got, want, tag):
+    import feat_inputs as fi
+    assert fi.same(got, want), tag
+
+
+def _feat_aid_table(dev, d):
+    from otto_amd.ranker import features as ft
+    return ft.aid_feature_table(d['aid'], d['ts'], d['typ'], d['off'], len(_FEAT_COUNTS))
+
+
+def _feat_matrix(dev, d):
+    from otto_amd.ranker import features as ft
+    table = {'row_off': d['row_off'], 'candidates': d['cand'], 'candidate_scores': d['score']}
+    return ft.feature_matrix(table, d['inter_row'], d['inter_sess'], d['inter_aid'], d['aid_tab'], d['sess_tab'], list(_FEAT_NAMES))
+
+
+def _feat_session_table(dev, d):
+    import torch
+    from otto_amd.ranker import features as ft
+    table = torch.zeros((len(_FEAT_COUNTS), len(ft.AID_COLUMNS)), dtype=torch.float32, device=dev)
+    return ft.session_feature_table(d['aid'], d['ts'], d['typ'], d['off'], table)
+
+
+FEAT = Case('feat', ('otto_feat_aid_table', 'otto_feat_session_table', 'otto_feat_matrix'), _feat_make, _feat_run, _feat_restate,
+            same=_feat_same, refusals={
+                'aid outside the table': (_edit('aid', lambda a, i: a.__setitem__(700, len(_FEAT_COUNTS))), _feat_aid_table, 'bad inputs'),
+                'session table: aid outside the aid table': (_edit('aid', lambda a, i: a.__setitem__(700, len(_FEAT_COUNTS))),
+                                                             _feat_session_table, 'bad inputs'),
+                'candidate outside the table': (_edit('cand', lambda c, i: c.__setitem__(40, 997)), _feat_matrix, 'bad inputs')})
+
+
+# ---- candidates: lookup, lookup_self, predictions, ranker rows / table, recency candidates / predictions ------------------------------------
+_CAND_AIDS, _CAND_K = 500, 15
+_CAND_KINDS = ('time_weighted', 'click_weighted', 'cart_weighted', 'click_cart', 'cart_order', 'neighbours')
+_CAND_FREQUENT = [int(a) for a in np.random.default_rng(8).permutation(_CAND_AIDS)[:20]]
+
+
+def _cand_make(seed, scale=1):
+    rng = np.random.default_rng(seed)
+    # sessions on either side of the 32-event class boundary (cand_inputs.LEN_SHORT / LEN_LONG), some empty, two long ones
+    lens = permuted(np.tile([32, 0, 33, 1, 40, 32, 33, 5, 64, 65, 2, 31, 130, 3, 0, 12, 7, 7, 9, 20], 15 * scale), rng)
+    off = offsets(lens)
+    E = int(off[-1])
+    d = dict(aid=rng.integers(0, _CAND_AIDS, E).astype(np.int32), typ=rng.integers(0, 3, E).astype(np.uint8), off=off)
+    for kind in _CAND_KINDS:                                   # stand-in lists, as in test_cand_gpu: distinct aids per row
+        d[f'y_{kind}'] = np.stack([rng.permutation(_CAND_AIDS)[:_CAND_K] for _ in range(_CAND_AIDS)]).astype(np.int32)
+        n = rng.integers(0, _CAND_K + 1, _CAND_AIDS).astype(np.int32)
+        n[::7] = _CAND_K
+        d[f'n_{kind}'] = n
+    lab = permuted(np.arange(len(lens)) % 4, rng)
+    d['l_off'] = offsets(lab)
+    d['l_aid'] = np.concatenate([np.sort(rng.permutation(_CAND_AIDS)[:n]) for n in lab] + [np.zeros(0, np.int64)]).astype(np.int32)
+    return d
+
+
+def _cand_mats(d):
+    return {kind: (d[f'y_{kind}'], None, d[f'n_{kind}']) for kind in _CAND_KINDS}
+
+
+_TABLE_KEYS = ('row_off', 'session', 'candidates', 'candidate_scores', 'candidate_labels')
+
+
+def _cand_run(dev, d):
+    from otto_amd.covisitation import candidates as cd
+    aid, typ, off, mats = d['aid'], d['typ'], d['off'], _cand_mats(d)
+    cand, cnt, n = cd.candidate_lookup(aid, typ, off, mats, cd.INFERENCE_CLICK_RECIPE, n_common=20)
+    pred, npred = cd.predictions(aid, off, cand, n, _CAND_FREQUENT, n_pred=20)
+    cand100, cnt100, n100 = cd.candidate_lookup(aid, typ, off, mats, cd.INFERENCE_CART_RECIPE, n_common=100)
+    tab = cd.ranker_table(aid, off, cand100, cnt100, n100, labels=(d['l_off'], d['l_aid']))
+    return (cand, cnt, n, pred, npred, cand100, cnt100, n100) + tuple(tab[k] for k in _TABLE_KEYS) + \
+        tuple(cd.recency_candidates(aid, typ, off)) + tuple(cd.recency_predictions(aid, typ, off, mats, min_unique=20))
+
+
+def _cand_oracle(i):
+    """Per session, from the stdlib loops of oracle/cand_oracle.py and oracle/recency_oracle.py."""
+    import cand_oracle as cdo
+    import recency_oracle as ro
+    top = {kind: cdo.matrix_to_dict(i[f'y_{kind}'], i[f'n_{kind}']) for kind in _CAND_KINDS}
+    nbd = top['neighbours']
+    aid, typ, off = i['aid'], i['typ'], i['off']
+    lab = [i['l_aid'][i['l_off'][s]:i['l_off'][s + 1]].tolist() for s in range(len(off) - 1)]
+    w20 = cdo.all_candidates(aid, typ, off, top, cdo.INFERENCE_CLICK_RECIPE, 20)
+    w100 = cdo.all_candidates(aid, typ, off, top, cdo.INFERENCE_CART_RECIPE, 100)
+    out = []
+    for s in range(len(off) - 1):
+        own, ty = aid[off[s]:off[s + 1]], typ[off[s]:off[s + 1]]
+        rec = None
+        if len(set(own.tolist())) >= 20:
+            rec = ro.session_recency_predictions(own, ty, top, nbd)
+        out.append(dict(c20=w20[s], pred=cdo.session_predictions(own, w20[s][0], _CAND_FREQUENT, 20)[:20], c100=w100[s],
+                        rows=cdo.session_ranker_rows(own, w100[s][0], w100[s][1], lab[s]), recency=ro.session_recency(own, ty), rpred=rec))
+    return out
+
+
+def _cand_restate(i):
+    want = _cand_oracle(i)
+    flat = lambda rows, dt: np.asarray([v for r in rows for v in r], dtype=dt)
+    return (flat([w['c20'][0] for w in want], np.int64), flat([w['c20'][1] for w in want], np.int64),
+            flat([w['pred'] for w in want], np.int64), flat([w['c100'][0] for w in want], np.int64),
+            flat([w['rows'][0] for w in want], np.int64), flat([w['rows'][1] for w in want], np.float64),
+            flat([w['rows'][2] for w in want], np.int64), flat([w['recency'][0][0] for w in want], np.int64),
+            flat([w['recency'][1][1] for w in want], np.float64),
+            flat([w['rpred'][t][0] for w in want if w['rpred'] for t in range(3)], np.int64))
+
+
+def _cand_check(i, outputs):
+    (cand, cnt, n, pred, npred, cand100, cnt100, n100, row_off, t_s, t_c, t_w, t_l, rc, rw, rn, rp, rpw, rpn) = (host(o) for o in outputs)
+    want, off = _cand_oracle(i), i['off']
+    checked = 0
+    for s, w in enumerate(want):                               # the comparisons of tests/test_cand_gpu.py, session by session
+        for (wa, wc), c, k, m in ((w['c20'], cand, cnt, n), (w['c100'], cand100, cnt100, n100)):
+            assert m[s] == len(wa) and c[s, :m[s]].tolist() == wa and k[s, :m[s]].tolist() == wc and (c[s, m[s]:] == -1).all(), s
+        assert npred[s] == len(w['pred']) and pred[s, :npred[s]].tolist() == w['pred'] and (pred[s, npred[s]:] == -1).all(), s
+        a, b = row_off[s], row_off[s + 1]
+        rows, sc, lb = w['rows']
+        assert b - a == len(rows) and t_c[a:b].tolist() == rows and t_w[a:b].tolist() == [float(v) for v in sc], s
+        assert t_l[a:b].tolist() == lb and (t_s[a:b] == s).all(), s
+        lo = int(off[s])
+        for c, (wa, ww) in enumerate(w['recency']):
+            assert rn[s] == len(wa) and rc[c, lo:lo + rn[s]].tolist() == wa, (s, c)
+            np.testing.assert_allclose(rw[c, lo:lo + rn[s]], np.array(ww), rtol=1e-12, atol=0)
+        if w['rpred'] is None:
+            assert (rpn[:, s] == -1).all() and (rp[:, s] == -1).all(), s
+            continue
+        checked += 1
+        for t, (wa, ww) in enumerate(w['rpred']):
+            assert rpn[t, s] == len(wa), (s, t)
+            got, gw = rp[t, s, :rpn[t, s]].tolist(), rpw[t, s, :rpn[t, s]]
+            np.testing.assert_allclose(gw, np.array(ww), rtol=1e-12, atol=0)
+            for j, (g, e) in enumerate(zip(got, wa)):          # may trade places only where the weights collide at exp2's rounding
+                if g != e:
+                    q = wa.index(g) if g in wa else j
+                    assert abs(ww[q] - ww[j]) <= 1e-9 * abs(ww[j]), (s, t, j, g, e)
+            assert (rp[t, s, rpn[t, s]:] == -1).all()
+    assert row_off[-1] == len(t_c) and checked >= 20
+
+
+def _cand_lookup(self_counts):
+    def call(dev, d):
+        from otto_amd.covisitation import candidates as cd
+        return cd.candidate_lookup(d['aid'], d['typ'], d['off'], _cand_mats(d), cd.INFERENCE_CART_RECIPE, n_common=100, self_counts=self_counts)
+    return call
+
+
+def _cand_recency(dev, d):
+    from otto_amd.covisitation import candidates as cd
+    return cd.recency_candidates(d['aid'], d['typ'], d['off'])
+
+
+CAND = Case('cand', ('otto_cand_lookup', 'otto_cand_lookup_self', 'otto_cand_predictions', 'otto_cand_ranker_rows', 'otto_cand_ranker_table',
+                     'otto_recency_candidates', 'otto_recency_predictions'), _cand_make, _cand_run, _cand_restate, check=_cand_check,
+            refusals={'session of more than 512 events: lookup': (_edit('off', _long_session), _cand_lookup(False), 'longer than 512 events'),
+                      'session of more than 512 events: recency_candidates': (_edit('off', _long_session), _cand_recency,
+                                                                              'longer than 512 events'),
+                      'session of more than 512 events: lookup_self': (_edit('off', _long_session), _cand_lookup(True),
+                                                                       'longer than 512 events')})
+
+
+# ---- MF: forward, eval, eval_sums (+ read_sums, check), SparseAdam step, BPR step, score_topk, topk_merge -------------------------------------
+_MF_N1, _MF_N2, _MF_D = 3000, 200, 32
+
+
+def _mf_make(seed, scale=1):
+    import edge_inputs as ei
+    rng = np.random.default_rng(seed)
+    B = 3000 * scale                                           # 32 samples per workgroup at d = 32
+    d = dict(E1=(rng.standard_normal((_MF_N1, _MF_D)) * 0.3).astype(np.float32), E2=(rng.standard_normal((_MF_N2, _MF_D)) * 0.3).astype(np.float32),
+             i1=rng.integers(0, _MF_N1, B), i2=np.minimum(rng.zipf(1.3, B) - 1, _MF_N2 - 1), tg=rng.integers(0, 3, B))
+    d['U'], d['V'] = ei.exact_inputs(200 * scale, 2100 * scale, _MF_D, seed)       # 1024 items per range: three ranges and the merge
+    d['ps'], d['pi'] = ei.merge_lists(3, 70 * scale, 20, seed)
+    return d
+
+
+def _mf_context(dev, inputs):
+    from otto_amd.matrix_factorization.engine import MFEngine
+    return MFEngine(_MF_N1, _MF_N2, _MF_D, len(inputs['i1']) * 2, device=dev)
+
+
+def _mf_reset(eng):
+    eng.read_sums(reset=True)
+    eng.check()
+
+
+def _mf_run(dev, d, eng=None):
+    import torch
+    from otto_amd.matrix_factorization.engine import MFEngine, score_topk, topk_merge
+    B = int(d['i1'].numel())
+    eng = eng or MFEngine(_MF_N1, _MF_N2, _MF_D, 2 * B, device=dev)
+    idx = (d['i1'], d['i2'])
+    out = [eng.forward(d['E1'], d['E2'], *idx)]
+    loss, pred = torch.zeros(2, device=dev), torch.empty((2, B), device=dev)
+    eng.eval(d['E1'], d['E2'], *idx, d['tg'], 0, loss[0:1], pred[0])
+    eng.eval_sums(d['E1'], d['E2'], *idx, d['tg'], 0, loss[1:2], pred[1])
+    sums = np.array(eng.read_sums(reset=True))
+    eng.check()
+    return tuple(out + [loss, pred, sums] + list(score_topk(d['U'], d['V'], k=20, pad_col=0)) + list(topk_merge(d['ps'], d['pi'], 20)))
+
+
+def _mf_restate(i):
+    import edge_inputs as ei
+    import mf_oracle as mo
+    E1, E2, i1, i2, tg = i['E1'], i['E2'], i['i1'], i['i2'], i['tg']
+    fwd = (E1[i1].astype(np.float64) * E2[i2].astype(np.float64)).sum(1)
+    ev = mo.eval_batch(E1, E2, i1, i2, tg, 'MSELoss')[0]
+    ids, sc = mo.score_topk(i['U'], i['V'], k=20, pad_col=0)
+    return (fwd, np.array([ev, ev]), np.stack([fwd, fwd]), np.array(mo.eval_sums(E1, E2, i1, i2, tg, 'MSELoss')), ids, sc) + \
+        tuple(ei.merge_reference(i['ps'], i['pi'], 20))
+
+
+def _mf_check(i, outputs):
+    from test_mf_edges_gpu import PRED_ATOL, RTOL as _MF_RTOL  # the family's bands
+    got, want = [host(o) for o in outputs], _mf_restate(i)
+    close = np.testing.assert_allclose
+    close(got[0], want[0], rtol=_MF_RTOL, atol=PRED_ATOL)                       # forward
+    close(got[1], want[1], rtol=_MF_RTOL)                                  # the losses of eval and eval_sums
+    close(got[2], want[2], rtol=_MF_RTOL, atol=PRED_ATOL)                       # their predictions
+    close(got[3][:2], want[3][:2], rtol=_MF_RTOL)
+    assert got[3][2] == want[3][2] and got[3][3] == want[3][3]             # hits and count
+    assert np.array_equal(got[4], want[4])                                 # exact scores: ids by (score desc, id asc)
+    assert np.array_equal(got[5], want[5].astype(np.float32))
+    assert np.array_equal(got[6], want[6]) and np.array_equal(got[7], want[7])
+
+
+def _mf_tables(d):
+    import torch
+    return [d['E1'].clone(), torch.zeros_like(d['E1']), torch.zeros_like(d['E1']), d['E2'].clone(), torch.zeros_like(d['E2']),
+            torch.zeros_like(d['E2'])]
+
+
+def _mf_train_run(dev, d, eng=None):
+    import torch
+    from otto_amd.matrix_factorization.engine import BPR_BATCH, MFEngine
+    B = int(d['i1'].numel())
+    eng = eng or MFEngine(_MF_N1, _MF_N2, _MF_D, 2 * B, device=dev)
+    idx, loss, t = (d['i1'], d['i2']), torch.zeros(2, device=dev), _mf_tables(d)
+    eng.step_sparse_adam(*t, *idx, d['tg'], 0, 0.05, (0.9, 0.999), 1e-8, 1, loss[0:1])
+    eng.check()
+    Ub, Vb, neg = d['E1'].clone(), d['E2'].clone(), torch.zeros(B, dtype=torch.int64, device=dev)
+    eng.bpr_step(Ub, Vb, *idx, seed=42, epoch=0, row0=12345, lr=0.05, l2=0.01, mode=BPR_BATCH, loss_sum=loss[1:2], neg_out=neg)
+    eng.check()
+    return tuple([loss] + t + [Ub, Vb, neg])
+
+
+def _mf_train_restate(i):
+    import mf_oracle as mo
+    E1, E2, i1, i2, tg = i['E1'], i['E2'], i['i1'], i['i2'], i['tg']
+    t = [E1.copy(), np.zeros_like(E1), np.zeros_like(E1), E2.copy(), np.zeros_like(E2), np.zeros_like(E2)]
+    adam = mo.sparse_adam_step(*t, i1, i2, tg, 'MSELoss', 0.05, step=1)[0]
+    Ub, Vb = E1.copy(), E2.copy()
+    neg = mo.bpr_negatives(42, 0, 12345, i2, _MF_N2)
+    bpr = mo.bpr_step_batch(Ub, Vb, i1, i2, neg, 0.05, 0.01)
+    return (np.array([adam, bpr]),) + tuple(t) + (Ub, Vb, neg)
+
+
+def _mf_train_check(i, outputs):
+    from test_mf_edges_gpu import ELEM_ATOL, ELEM_RTOL, RTOL as _MF_RTOL
+    from test_sgns_gpu import ATOL as BPR_ATOL                  # 'the project's fp32 band (test_mf_gpu.py, BPR batch step)'
+    got, want = [host(o) for o in outputs], _mf_train_restate(i)
+    close = np.testing.assert_allclose
+    close(got[0], want[0], rtol=_MF_RTOL)
+    for g, w in zip(got[1:7], want[1:7]):                                  # the SparseAdam step: tests/test_mf_gpu.py's bands
+        close(g, w, rtol=ELEM_RTOL, atol=ELEM_ATOL)
+        assert np.linalg.norm(g - w) <= _MF_RTOL * np.linalg.norm(w)
+    close(got[7], want[7], rtol=_MF_RTOL, atol=BPR_ATOL)                       # BPR batch step
+    close(got[8], want[8], rtol=_MF_RTOL, atol=BPR_ATOL)
+    assert np.array_equal(got[9], want[9])                                 # the negatives: integer work
+
+
+def _mf_bad_step(dev, d):
+    import torch
+    from otto_amd.matrix_factorization.engine import MFEngine
+    eng = MFEngine(_MF_N1, _MF_N2, _MF_D, int(d['i1'].numel()), device=dev)
+    eng.step_sparse_adam(*_mf_tables(d), d['i1'], d['i2'], d['tg'], 0, 0.05, (0.9, 0.999), 1e-8, 1, torch.zeros(1, device=dev))
+    eng.check()
+
+
+def _mf_bad_forward(dev, d):
+    from otto_amd.matrix_factorization.engine import MFEngine
+    eng = MFEngine(_MF_N1, _MF_N2, _MF_D, int(d['i1'].numel()), device=dev)
+    eng.forward(d['E1'], d['E2'], d['i1'], d['i2'])
+    eng.check()
+
+
+_MF_BAD_ID = _edit('i1', lambda a, i: a.__setitem__(77, _MF_N1))
+MF = Case('mf', ('otto_mf_forward', 'otto_mf_eval', 'otto_mf_eval_sums', 'otto_mf_read_sums', 'otto_mf_check', 'otto_mf_score_topk',
+                 'otto_mf_topk_merge'), _mf_make, _mf_run, _mf_restate, check=_mf_check, context=True, new_context=_mf_context,
+          reset=_mf_reset, refusals={'row id outside the table': (_MF_BAD_ID, _mf_bad_forward, 'outside the embedding tables')})
+MF_TRAIN = Case('mf-train', ('otto_mf_step_sparse_adam', 'otto_mf_bpr_step', 'otto_mf_check'), _mf_make, _mf_train_run, _mf_train_restate,
+                check=_mf_train_check, context=True, new_context=_mf_context, reset=_mf_reset,
+                refusals={'row id outside the table': (_MF_BAD_ID, _mf_bad_step, 'outside the embedding tables')})
+
+
+# ---- covisitation: feed, finalize, export / import, stats -------------------------------------------------------------------------------------
+_COVIS_AIDS = 1200
+_COVIS_TS = (1_659_304_800, 1_662_500_000)                     # synth.TS_LO and a bound past every stamp: the context's t0 / t1
+_COVIS_STATS = ('sessions', 'tail_events', 'pair_slots', 'pairs', 'runs', 'shared_runs', 'row_records')
+
+
+def _covis_make(seed, scale=1):
+    import math
+    from otto_amd import synth
+    rng = np.random.default_rng(seed)
+    S = 1500 * scale
+    # synth.generate_sessions' laws, with the session lengths drawn once for every seed
+    L = permuted(np.clip(np.rint(np.random.default_rng(1).lognormal(math.log(6.0), 1.435, S)), 2, 300).astype(np.int64), rng)
+    off = offsets(L)
+    E = int(off[-1])
+    sess = np.repeat(np.arange(S), L)
+    pos = np.arange(E) - off[:-1][sess]
+    cdf = np.cumsum(rng.lognormal(math.log(20.0), 1.88, _COVIS_AIDS))
+    base = np.minimum(np.searchsorted(cdf / cdf[-1], rng.random(E)), _COVIS_AIDS - 1)
+    rep = (rng.random(E) < 0.25) & (pos > 0)
+    src = off[:-1][sess] + np.floor(rng.random(E) * pos).astype(np.int64)
+    aid = np.where(rep, base[np.minimum(src, E - 1)], base).astype(np.int32)
+    typ = np.searchsorted(np.cumsum(synth.TYPE_P), rng.random(E)).clip(0, 2).astype(np.uint8)
+    gaps = rng.exponential(60.0, E) + (rng.random(E) < 0.05) * rng.uniform(3600.0, 259200.0, E)
+    gaps[off[:-1]] = 0.0
+    c = np.cumsum(np.floor(gaps).astype(np.int64))
+    ts = np.minimum(rng.integers(synth.TS_LO, synth.TS_HI + 1, S)[sess] + (c - c[off[:-1]][sess]), _COVIS_TS[1]).astype(np.int32)
+    return dict(aid=aid, ts=ts, typ=typ, off=off)
+
+
+def _covis_context(dev, inputs=None):
+    from otto_amd.covisitation.engine import CovisBuilder
+    from otto_amd.covisitation.spec import ALL_KINDS
+    return CovisBuilder(_COVIS_AIDS, kinds=ALL_KINDS, ts_min=_COVIS_TS[0], ts_max=_COVIS_TS[1], device=dev)
+
+
+def _covis_run(dev, d, b=None):
+    import torch
+    from otto_amd.covisitation.spec import ALL_KINDS
+    b = b or _covis_context(dev)
+    b.feed(d['aid'], d['ts'], d['typ'], d['off'])
+    direct = b.finalize(k=20)
+    stats = b.stats()
+    # the same runs through both export forms into fresh owners: one piece, and two owners' pieces of one buffer
+    one = _covis_context(dev)
+    hdr, rec, tw = b.export_runs(0, _COVIS_AIDS)
+    r, t = one.import_reserve(rec.numel())
+    r.copy_(rec)
+    t.copy_(tw)
+    one.import_runs(hdr, r, t)
+    two = _covis_context(dev)
+    hdr, rec, tw, runs, recs = b.export_all([0, _COVIS_AIDS // 3, _COVIS_AIDS])
+    r0 = c0 = 0
+    for o in range(2):
+        two.import_runs(hdr[r0:r0 + runs[o]].contiguous(), rec[c0:c0 + recs[o]].contiguous(), tw[c0:c0 + recs[o]].contiguous())
+        r0, c0 = r0 + runs[o], c0 + recs[o]
+    ranged = _covis_context(dev)                               # the range form: the run slots in three cuts, two owners
+    bounds, slots = [0, _COVIS_AIDS // 3, _COVIS_AIDS], b.run_slots()
+    for lo, hi in ((0, slots // 4), (slots // 4, slots // 2), (slots // 2, slots)):
+        runs, recs = b.export_plan_range(bounds, lo, hi)
+        hdr = torch.empty((sum(runs), 2), dtype=torch.int32, device=dev)
+        rec, tw = torch.empty(sum(recs), dtype=torch.int32, device=dev), torch.empty(sum(recs), dtype=torch.int32, device=dev)
+        b.export_fill_range(bounds, lo, hi, runs, recs, hdr, rec, tw)
+        r0 = c0 = 0
+        for o in range(2):
+            if runs[o]:
+                ranged.import_runs(hdr[r0:r0 + runs[o]].contiguous(), rec[c0:c0 + recs[o]].contiguous(), tw[c0:c0 + recs[o]].contiguous())
+            r0, c0 = r0 + runs[o], c0 + recs[o]
+    out = [np.array([stats[k] for k in _COVIS_STATS])]
+    for res in (direct, one.finalize(k=20), two.finalize(k=20), ranged.finalize(k=20)):
+        for kind in ALL_KINDS:
+            y, w, n = res[kind]
+            listed = torch.arange(y.shape[1], device=dev)[None, :] < n[:, None]      # the entries past n are not written
+            out += [torch.where(listed, y, -1), torch.where(listed, w, 0), n]
+    return tuple(out)
+
+
+def _covis_want(i):
+    import covis_oracle as co
+    sp = co.CovisSpec(kinds=co.ALL_KINDS, ts_min=_COVIS_TS[0], ts_max=_COVIS_TS[1])
+    st = {}
+    return co.covis_topk_numpy(i['aid'].astype(np.uint32), i['ts'], i['typ'], i['off'], sp, k=20, stats=st), st
+
+
+def _covis_restate(i):
+    import covis_oracle as co
+    want, st = _covis_want(i)
+    return (np.array([st['P']]),) + tuple(np.asarray(x) for kind in co.ALL_KINDS for x in want[kind])
+
+
+def _covis_check(i, outputs):
+    import torch
+    import covis_oracle as co
+    import test_covis_gpu as family
+    from otto_amd.covisitation.engine import topk_to_rows
+    want, st = _covis_want(i)
+    stats = dict(zip(_COVIS_STATS, host(outputs[0]).tolist()))
+    assert stats['pairs'] == st['P'] and stats['sessions'] == len(i['off']) - 1
+    t = lambda o: torch.from_numpy(np.ascontiguousarray(host(o)))
+    n = 3 * len(co.ALL_KINDS)
+    for build in range(4):                                     # the direct build and the three imported ones
+        part = outputs[1 + build * n:1 + (build + 1) * n]
+        got = {kind: topk_to_rows(*(t(o) for o in part[3 * j:3 * j + 3])) for j, kind in enumerate(co.ALL_KINDS)}
+        family._assert_rows_equal(got, want, co.ALL_KINDS)
+
+
+COVIS = Case('covis', ('otto_covis_feed', 'otto_covis_finalize', 'otto_covis_export_count', 'otto_covis_export_runs', 'otto_covis_import_reserve',
+                       'otto_covis_import_runs', 'otto_covis_export_plan', 'otto_covis_export_fill', 'otto_covis_export_plan_range',
+                       'otto_covis_export_fill_range'), _covis_make, _covis_run,
+             _covis_restate, check=_covis_check, context=True, new_context=_covis_context, reset=lambda b: b.reset())
+
+
+# ---- gbdt: bin, lambdarank, quantize, hist, best_split, partition, grow_tree, add_tree, ap_at_k, bag, the sampled forms ----------------------------
+_GBDT_F = 8
+_GBDT_EDGES = [np.linspace(-2.0, 2.0, 30 + 7 * f).astype(np.float32) for f in range(_GBDT_F)]     # the same bins for every seed
+_GBDT_FEATURES = np.array([0, 1, 2, 4, 5, 7], dtype=np.int32)
+_GBDT_SPLIT = (20, 1e-3, 0.01, 1e-5)
+_TREE_KEYS = ('split_feature', 'split_bin', 'default_left', 'left_child', 'right_child', 'threshold', 'decision_type', 'split_gain',
+              'leaf_value', 'leaf_count')
+_SPLIT_KEYS = ('feature', 'bin', 'default_left', 'cnt_left', 'g_left', 'h_left', 'cnt', 'g', 'h')
+
+
+def _gbdt_params():
+    import gbdt_restatement as gr
+    return dict(gr.DEFAULTS, num_leaves=8, min_data_in_leaf=20, lambdarank_norm=False)
+
+
+def _gbdt_make(seed, scale=1):
+    rng = np.random.default_rng(seed)
+    lens = permuted(np.r_[np.random.default_rng(2).integers(5, 46, 220 * scale), [1024]], rng)     # 6,500 rows: 2048 per block
+    off = offsets(lens)
+    n = int(off[-1])
+    X = rng.standard_normal((n, _GBDT_F)).astype(np.float32)                # gbdt_restatement.random_problem's rows and labels
+    signal = X[:, 0] - 0.7 * X[:, 1] + 0.5 * np.abs(X[:, 2]) + rng.standard_normal(n) * 0.8
+    label = (signal > np.quantile(signal, 0.85)).astype(np.int32)
+    X[rng.random((n, _GBDT_F)) < 0.10] = np.nan
+    return dict(X=X, label=label, off=off, score=np.round(rng.standard_normal(n), 2),
+                rows=np.sort(rng.permutation(n)[:n * 2 // 3]).astype(np.int32))
+
+
+def _split_arrays(split):
+    if split is None:
+        return np.zeros(len(_SPLIT_KEYS), dtype=np.int64), np.float64(0.0)
+    return np.array([split[k] for k in _SPLIT_KEYS], dtype=np.int64), np.float64(split['gain'])
+
+
+def _gbdt_run(dev, d):
+    import test_gbdt_gpu as family
+    from otto_amd import _lib
+    from otto_amd.ranker import gbdt
+    mapper, p = family._mapper(_GBDT_EDGES), _gbdt_params()
+    bins = gbdt.bin_matrix(d['X'], mapper)
+    n = int(bins.shape[1])
+    g, h = gbdt.lambdarank_gradients(d['score'], d['label'], d['off'], norm=False)
+    gh, exp = gbdt.quantize_gradients(g, h)
+    hist = gbdt.leaf_histogram(bins, gh, d['rows'])
+    hist_f = gbdt.leaf_histogram(bins, gh, d['rows'], features=_GBDT_FEATURES)
+    split = _split_arrays(gbdt.best_split(hist, mapper, exp, *_GBDT_SPLIT))
+    split_f = _split_arrays(gbdt.best_split(hist_f, mapper, exp, *_GBDT_SPLIT, features=_GBDT_FEATURES))
+    part, n_left = gbdt.partition_rows(bins, d['rows'], 1, 12, 1)
+    work = _lib.workspace(gbdt.workspace_bytes(n, _GBDT_F, p['num_leaves']), dev)
+    tree = gbdt.grow_tree(bins, gh, exp, mapper, p, work=work)
+    bag = gbdt.bag_rows(n, n // 2, gbdt.mix(42, 0), dev)
+    sampled = gbdt.grow_tree(bins, gh, exp, mapper, p, work=work, bag=bag, features=_GBDT_FEATURES)
+    score = d['score'].clone()
+    leaf = gbdt.add_tree(bins, tree, score, want_leaf=True)
+    ap = gbdt.ap_at_k(d['score'], d['label'], d['off'], k=20)
+    return (bins, g, h, gh, exp, hist, hist_f) + split + split_f + (part, np.int64(n_left)) + \
+        tuple(getattr(tree, k) for k in _TREE_KEYS) + tuple(getattr(sampled, k) for k in _TREE_KEYS) + (score, leaf, ap)
+
+
+def _gbdt_restate(i):
+    import gbdt_restatement as gr
+    import gbdt_sampling_restatement as gs
+    from otto_amd.ranker import gbdt
+    p, n_edges = _gbdt_params(), [len(e) for e in _GBDT_EDGES]
+    bins = gr.bin_rows(i['X'], _GBDT_EDGES)
+    n = bins.shape[1]
+    g, h, invalid = gr.lambdarank(i['score'], i['label'], i['off'], norm=False)
+    assert invalid == 0
+    q, exps = gr.quantize(g, h)
+    hist, hist_f = gr.histogram(bins, q, i['rows']), gs.histogram(bins, q, i['rows'], _GBDT_FEATURES)
+    split = _split_arrays(gr.best_split(hist, n_edges, exps, *_GBDT_SPLIT))
+    split_f = _split_arrays(gs.best_split(hist_f, n_edges, exps, *_GBDT_SPLIT, features=_GBDT_FEATURES))
+    left, right = gr.partition(bins, i['rows'], 1, 12, 1)
+    tree = gr.grow_tree(bins, q, exps, _GBDT_EDGES, p)
+    sampled = gs.grow_tree(bins, q, exps, _GBDT_EDGES, p, bag_rows=gs.bag(n, n // 2, gbdt.mix(42, 0)), features=_GBDT_FEATURES)
+    leaf = gr.route(bins, tree)
+    return (bins, g, h, q, np.array(exps, dtype=np.int32), hist, hist_f) + split + split_f + \
+        (np.concatenate([left, right]).astype(np.int32), np.int64(left.size)) + tuple(tree[k] for k in _TREE_KEYS) + \
+        tuple(sampled[k] for k in _TREE_KEYS) + (i['score'] + tree['leaf_value'][leaf], leaf, gr.ap_at_k(i['score'], i['label'], i['off'], 20)[0])
+
+
+def _gbdt_hist(dev, d):
+    import test_gbdt_gpu as family
+    from otto_amd.ranker import gbdt
+    bins = gbdt.bin_matrix(d['X'], family._mapper(_GBDT_EDGES))
+    g, h = gbdt.lambdarank_gradients(d['score'], d['label'], d['off'], norm=False)
+    return gbdt.leaf_histogram(bins, gbdt.quantize_gradients(g, h)[0], d['rows'])
+
+
+def _gbdt_grow_on_bag(dev, d):
+    import test_gbdt_gpu as family
+    from otto_amd.ranker import gbdt
+    mapper = family._mapper(_GBDT_EDGES)
+    bins = gbdt.bin_matrix(d['X'], mapper)
+    g, h = gbdt.lambdarank_gradients(d['score'], d['label'], d['off'], norm=False)
+    gh, exp = gbdt.quantize_gradients(g, h)
+    return gbdt.grow_tree(bins, gh, exp, mapper, _gbdt_params(), bag=d['rows'])
+
+
+def _gbdt_objective(dev, d):
+    from otto_amd.ranker import gbdt
+    return gbdt.lambdarank_gradients(d['score'], d['label'], d['off'], norm=False)
+
+
+def _gbdt_ap(dev, d):
+    from otto_amd.ranker import gbdt
+    return gbdt.ap_at_k(d['score'], d['label'], d['off'], k=20)
+
+
+GBDT = Case('gbdt', ('otto_gbdt_bin', 'otto_gbdt_lambdarank', 'otto_gbdt_quantize', 'otto_gbdt_hist', 'otto_gbdt_hist_features',
+                     'otto_gbdt_best_split', 'otto_gbdt_best_split_features', 'otto_gbdt_partition', 'otto_gbdt_grow_tree',
+                     'otto_gbdt_grow_tree_sampled', 'otto_gbdt_bag', 'otto_gbdt_add_tree', 'otto_gbdt_ap_at_k'), _gbdt_make, _gbdt_run,
+            _gbdt_restate, refusals={
+                'row id outside the rows': (_edit('rows', lambda r, i: r.__setitem__(len(r) - 1, len(i['label']))), _gbdt_hist, 'row id'),
+                'grow_tree: bag row outside the rows': (_edit('rows', lambda r, i: r.__setitem__(len(r) - 1, len(i['label']))),
+                                                        _gbdt_grow_on_bag, 'row id'),
+                'query above 1024 rows: objective': (_edit('off', _long_query), _gbdt_objective, 'quer'),
+                'query above 1024 rows: metric': (_edit('off', _long_query), _gbdt_ap, 'quer')})
+
+
+# ---- xgb: pairwise, lambdamart, grow_tree, the level launches -------------------------------------------------------------------------------------
+_XGB_EDGES = [np.arange(45, dtype=np.float32) for _ in range(_GBDT_F)]
+_XGB_EXPS = (28, 29)
+_XGB_SEGMENTS = (1, 2047, 2048, 2049)                          # xgb_inputs.HIST_SEGMENTS: 2048 is the chunk floor and a partition block
+_XGB_KEYS = ('split_feature', 'split_bin', 'default_left', 'threshold', 'decision_type', 'left_child', 'right_child', 'split_gain', 'cover',
+             'sum_grad', 'count', 'left_id', 'right_id', 'leaf_value', 'leaf_cover', 'leaf_sum_grad', 'leaf_count')
+
+
+def _xgb_params():
+    import xgb_inputs as xi
+    return dict(xi.BASE, max_depth=4, gamma=14.0)             # about half of these inputs' gains lie below: which nodes split is the data's
+
+
+def _xgb_make(seed, scale=1):
+    import gbdt_restatement as gr
+    rng = np.random.default_rng(seed)
+    lens = permuted(np.r_[np.tile(_OBJ_SHORT, 16 * scale), [1024]], rng)      # 6,480 rows; queries on both sides of the one-wave kernel's 128
+    off = offsets(lens)
+    n = int(off[-1])
+    bins = rng.integers(0, 40, (_GBDT_F, n)).astype(np.uint8)  # xgb_inputs.level_problem's bins and gradients
+    bins[rng.random((_GBDT_F, n)) < 0.05] = gr.NAN_BIN
+    q = rng.integers(-2 ** 29, 2 ** 29, (n, 2)).astype(np.int32)
+    q[:, 1] = np.abs(q[:, 1])
+    return dict(score=np.round(rng.standard_normal(n) * 2, 1), label=rng.integers(0, 4, n).astype(np.int32), off=off, bins=bins, q=q,
+                exp=np.array(_XGB_EXPS, dtype=np.int32), rows=rng.permutation(n).astype(np.int32),
+                bag=np.sort(rng.permutation(n)[:n * 7 // 10]).astype(np.int32))
+
+
+def _xgb_nodes(splits=None):
+    import xgb_inputs as xi
+    segs = xi.segments(_XGB_SEGMENTS)
+    splits = splits or [(0, 0, 0)] * len(segs)
+    return segs, np.array([[b, c, slot, -1, 0, f, sb, dl] for slot, ((b, c), (f, sb, dl)) in enumerate(zip(segs, splits))], dtype=np.int32)
+
+
+_XGB_PART = [(f, 20, f & 1) for f in range(len(_XGB_SEGMENTS))]
+
+
+def _split_record(found, want):
+    """[found, feature, bin, default_left, the bits of the gain, cnt_left, g_left, h_left, cnt, g, h]; zeros where nothing was found"""
+    if not found:
+        return [0] * 11
+    return [1, want['feature'], want['bin'], want['default_left'], int(np.float64(want['gain']).view(np.int64)), want['cnt_left'],
+            want['g_left'], want['h_left'], want['cnt'], want['g'], want['h']]
+
+
+def _xgb_run(dev, d):
+    import test_gbdt_gpu as family
+    import xgb_inputs as xi
+    from otto_amd import _lib
+    from otto_amd.ranker import xgb
+    mapper, p = family._mapper(_XGB_EDGES), _xgb_params()
+    n = int(d['bins'].shape[1])
+    out = list(xgb.pairwise_gradients(d['score'], d['label'], d['off'], xi.OBJECTIVE_SEED, 0))
+    out += list(xgb.lambdamart_gradients(d['score'], d['label'], d['off'], xi.OBJECTIVE_SEED, 1, weighting=1))
+    work = _lib.workspace(xgb.workspace_bytes(n, _GBDT_F, p['max_depth']), dev)
+    tree = xgb.grow_tree(d['bins'], d['q'], d['exp'], mapper, p, work=work, bag=d['bag'], features=_GBDT_FEATURES)
+    out += [getattr(tree, k) for k in _XGB_KEYS]
+    segs, nodes = _xgb_nodes()
+    hist = xgb.level_histograms(d['bins'], d['q'], d['rows'], nodes, len(segs))
+    rec = xgb.level_splits(hist, mapper, d['exp'], nodes, 1.0, 1.0, 0.0)[:, :11].copy()
+    rec[rec[:, 0] == 0, 1:] = 0                                # the record of a node without a split holds nothing to compare
+    part, n_left = xgb.level_partition(d['bins'], d['rows'], _xgb_nodes(_XGB_PART)[1])
+    return tuple(out + [hist, rec, part, n_left])
+
+
+def _xgb_restate(i):
+    import gbdt_restatement as gr
+    import gbdt_sampling_restatement as sr
+    import objectives_restatement as orr
+    import xgb_inputs as xi
+    import xgb_restatement as xr
+    g, h, invalid, bad = xr.pairwise(i['score'], i['label'], i['off'], xi.OBJECTIVE_SEED, 0)
+    g2, h2, invalid2, bad2 = orr.lambdamart(i['score'], i['label'], i['off'], xi.OBJECTIVE_SEED, 1, 1)
+    assert not (invalid or bad or invalid2 or bad2)
+    tree = xr.grow_tree(i['bins'], i['q'], _XGB_EXPS, _XGB_EDGES, _xgb_params(), i['bag'], _GBDT_FEATURES)
+    segs, _ = _xgb_nodes()
+    n_edges = [len(e) for e in _XGB_EDGES]
+    hists = [sr.histogram(i['bins'], i['q'], i['rows'][b:b + c]) for b, c in segs]
+    rec = []
+    for hist in hists:
+        want = sr.best_split(hist, n_edges, _XGB_EXPS, 0, 1.0, 1.0, 0.0)
+        rec.append(_split_record(want is not None, want))
+    part, n_left = i['rows'].copy(), []
+    for (b, c), (f, sb, dl) in zip(segs, _XGB_PART):
+        left, right = gr.partition(i['bins'], i['rows'][b:b + c], f, sb, dl)
+        part[b:b + c] = np.concatenate([left, right])
+        n_left.append(left.size)
+    return (g, h, g2, h2) + tuple(tree[k] for k in _XGB_KEYS) + (np.stack(hists), np.array(rec, dtype=np.int64), part, np.array(n_left))
+
+
+def _xgb_pairwise(dev, d):
+    import xgb_inputs as xi
+    from otto_amd.ranker import xgb
+    return xgb.pairwise_gradients(d['score'], d['label'], d['off'], xi.OBJECTIVE_SEED, 0)
+
+
+def _xgb_lambdamart(dev, d):
+    import xgb_inputs as xi
+    from otto_amd.ranker import xgb
+    return xgb.lambdamart_gradients(d['score'], d['label'], d['off'], xi.OBJECTIVE_SEED, 0, weighting=1)
+
+
+def _xgb_grow(dev, d):
+    import test_gbdt_gpu as family
+    from otto_amd.ranker import xgb
+    return xgb.grow_tree(d['bins'], d['q'], d['exp'], family._mapper(_XGB_EDGES), _xgb_params(), bag=d['bag'])
+
+
+XGB = Case('xgb', ('otto_xgb_pairwise', 'otto_xgb_lambdamart', 'otto_xgb_grow_tree', 'otto_xgb_level_hist', 'otto_xgb_level_split',
+                   'otto_xgb_level_partition'), _xgb_make, _xgb_run, _xgb_restate,
+           refusals={
+    'label 32': (_edit('label', lambda l, i: l.__setitem__(45, 32)), _xgb_pairwise, 'label'),
+    'query above 1024 rows': (_edit('off', _long_query), _xgb_lambdamart, 'quer'),
+    'bag row outside the rows': (_edit('bag', lambda b, i: b.__setitem__(len(b) - 1, len(i['label']))), _xgb_grow, 'row id')})
+
+
+# ---- sgns: neg_table, draw, plan, step, step_hs (and the host-side hs_tree) ---------------------------------------------------------------------------
+_SGNS_AIDS, _SGNS_D, _SGNS_WS, _SGNS_NEG, _SGNS_SEED, _SGNS_LR = 400, 32, 3, 5, 6, 0.05
+_PLAN_KEYS = ('tok_aid', 'tok_src', 'tok_off', 'radius', 'tok_left', 'pair_off')
+
+
+def _sgns_make(seed, scale=1):
+    from otto_amd.gensim_fasttext import skipgram as sg
+    rng = np.random.default_rng(seed)
+    lens = permuted(np.tile([9, 1, 2, 9, 5, 9, 3, 9, 9, 9, 4, 9, 9, 6, 9, 9], 12 * scale), rng)      # test_sgns_gpu.step_data's sessions
+    off = offsets(lens)
+    E = int(off[-1])
+    # every aid occurs, so the Huffman tree has the same number of inner nodes for every seed; the rest repeat heavily
+    aid = rng.permutation(np.r_[np.arange(_SGNS_AIDS), np.minimum(rng.zipf(1.2, E - _SGNS_AIDS) - 1, _SGNS_AIDS - 1)]).astype(np.int32)
+    _, keep_q, weight = sg.vocab_tables(aid, _SGNS_AIDS, 1, 0.05, 0.5)
+    table = lambda rows: rng.uniform(-0.5, 0.5, (rows, _SGNS_D)).astype(np.float32)
+    return dict(aid=aid, off=off, count=np.bincount(aid, minlength=_SGNS_AIDS), keep_q=keep_q, weight=weight, keys=rng.integers(0, 1 << 64, 5000 * scale, dtype=np.uint64).view(np.int64),
+                In=table(_SGNS_AIDS), Out=table(_SGNS_AIDS), Syn1=table(_SGNS_AIDS - 1))
+
+
+def _sgns_run(dev, d):
+    import torch
+    from otto_amd.gensim_fasttext import skipgram as sg
+    out = []
+    for hs in (None, sg.huffman_tables(d['count'])):       # the counts are a host key: no read of the late inputs before the kernels
+        eng = sg.SkipGramEngine(_SGNS_AIDS, _SGNS_D, _SGNS_WS, _SGNS_NEG, d['keep_q'], d['weight'], seed=_SGNS_SEED, device=dev, hs=hs)
+        plan = eng.plan(d['aid'], d['off'], 0)
+        In, Out = d['In'].clone(), d['Out'].clone()
+        ctx = torch.empty(max(plan.P, 1), dtype=torch.int32, device=dev)
+        neg = torch.empty((max(plan.P, 1), _SGNS_NEG), dtype=torch.int32, device=dev)
+        Syn1 = None if hs is None else d['Syn1'].clone()
+        loss = eng.step(plan, 0, plan.T, In, Out, _SGNS_LR, sg.BATCH, ctx_out=ctx, neg_out=neg, Syn1=Syn1)
+        if hs is None:
+            out += [eng.cum, eng.draw(d['keys'])] + [getattr(plan, k) for k in _PLAN_KEYS] + [ctx[:plan.P], neg[:plan.P]]
+        out += [loss.clone(), In, Out] + ([] if hs is None else [Syn1])
+    return tuple(out)
+
+
+def _sgns_restate(i):
+    import sgns_hs_restatement as hr
+    import sgns_restatement as sr
+    cum = sr.cum_table(i['weight'])
+    p = sr.plan(i['aid'], i['off'], i['keep_q'], _SGNS_SEED, 0, _SGNS_WS)
+    T = len(p['tok_aid'])
+    ctx, neg = sr.negatives(p, cum, _SGNS_SEED, 0, _SGNS_NEG, 0, T, _SGNS_AIDS)
+    drawn = np.array([sr.draw(cum, int(k)) for k in i['keys'].view(np.uint64)], dtype=np.int32)
+    In, Out = i['In'].copy(), i['Out'].copy()
+    loss = sr.step_batch(p, cum, In, Out, _SGNS_SEED, 0, _SGNS_NEG, _SGNS_LR, 0, T)
+    In2, Out2, Syn1 = i['In'].copy(), i['Out'].copy(), i['Syn1'].copy()
+    hs = hr.huffman(i['count'])
+    assert hs['n_inner'] == _SGNS_AIDS - 1
+    loss2 = hr.step_batch_hs(p, cum, In2, Out2, Syn1, hs, _SGNS_SEED, 0, _SGNS_NEG, _SGNS_LR, 0, T)
+    return (cum.view(np.int64), drawn) + tuple(p[k] for k in _PLAN_KEYS) + (ctx, neg, np.array([loss]), In, Out, np.array([loss2]), In2, Out2,
+                                                                             Syn1)
+
+
+def _sgns_same(got, want, tag):
+    if want.dtype.kind == 'f':                                 # the losses and the tables: the family's fp32 band
+        from test_sgns_gpu import ATOL, RTOL
+        np.testing.assert_allclose(got, want, rtol=RTOL, atol=ATOL, err_msg=tag)
+    else:
+        exact(got, want, tag)
+
+
+def _sgns_plan(dev, d):
+    from otto_amd.gensim_fasttext import skipgram as sg
+    eng = sg.SkipGramEngine(_SGNS_AIDS, _SGNS_D, _SGNS_WS, _SGNS_NEG, d['keep_q'], d['weight'], seed=_SGNS_SEED, device=dev)
+    return eng.plan(d['aid'], d['off'], 0)
+
+
+SGNS = Case('sgns', ('otto_sgns_neg_table', 'otto_sgns_draw', 'otto_sgns_plan', 'otto_sgns_step', 'otto_sgns_step_hs'), _sgns_make, _sgns_run,
+            _sgns_restate, same=_sgns_same, host_keys=('count', 'keep_q', 'weight'), refusals={
+                'aid outside the vocabulary': (_edit('aid', lambda a, i: a.__setitem__(len(a) // 2, _SGNS_AIDS)), _sgns_plan, r'code -22'),
+                'descending sess_off': (_edit('off', lambda o, i: o.__setitem__(3, o[4] + 1)), _sgns_plan, r'code -22')})
+
+
+# ---- jsonl: count / parse / newlines ----------------------------------------------------------------------------------------------------------------
+_JSONL_NAMES = ('session', 'aid', 'ts', 'type', 'sess_off', 'sess_id')
+
+
+def _jsonl_make(seed, scale=1):
+    import jsonl_inputs as ji
+    n = (3 * 4096 + 100) * scale                               # TILE_BYTES = 4096: four tiles, the last one short
+    buf = ji.exact_size(n, seed)
+    assert len(buf) == n
+    return dict(buf=np.frombuffer(buf, dtype=np.uint8).copy())
+
+
+def _jsonl_run(dev, d):
+    from otto_amd import jsonl
+    return tuple(jsonl.parse_bytes(d['buf']))
+
+
+def _jsonl_restate(i):
+    import jsonl_restatement as jr
+    want = jr.parse(i['buf'].tobytes())
+    return tuple(want[k].view(np.int32) if want[k].dtype == np.uint32 else want[k] for k in _JSONL_NAMES)     # the bit patterns of uint32
+
+
+def _bad_byte(buf, i):
+    at = len(buf) // 2
+    while not 48 <= buf[at] <= 57:
+        at += 1
+    buf[at] = ord('x')                                         # a letter where a digit stood: the line violates SPEC-JSONL
+
+
+JSONL = Case('jsonl', ('otto_jsonl_count', 'otto_jsonl_parse', 'otto_jsonl_newlines'), _jsonl_make, _jsonl_run, _jsonl_restate,
+             refusals={'a letter in a number': (_edit('buf', _bad_byte), _jsonl_run, r'line \d+:')})
+
+
+# ---- parquet: decode (through read_columns) and the snappy seam ---------------------------------------------------------------------------------------
+_SNAPPY_PIECES = (0, 1, 5, 63, 64, 65, 1000, 5000, 20000, 70000)   # test_parquet_gpu's mixed sizes; 70000: past the 64 KiB block edge
+
+
+def _parquet_make(seed, scale=1):
+    import parquet_inputs as pi
+    rng = np.random.default_rng(seed)
+    d = pi.frame(20000 * scale, seed)                          # about 40 pages of 4 KiB per column: several workgroups
+    m = sum(_SNAPPY_PIECES) * scale
+    kinds = [rng.integers(0, 256, m, dtype=np.uint8), rng.integers(0, 3, m, dtype=np.uint8), (np.arange(m) % (1 + seed % 11)).astype(np.uint8)]
+    d['raw'] = np.where(np.arange(m) % 3000 < 1000, kinds[0], np.where(np.arange(m) % 3000 < 2000, kinds[1], kinds[2])).astype(np.uint8)
+    return d
+
+
+def _parquet_write(directory, d):
+    import pathlib
+    import parquet_inputs as pi
+    cols = {k: np.asarray(on_host(d[k])) for k in pi.COLUMNS}
+    return pi._write(pathlib.Path(directory) / 'contract.parquet', cols, data_page_size=4096, row_group_size=len(cols['aid']) // 2 + 1)
+
+
+def _snappy_streams(raw):
+    import pyarrow as pa
+    codec = pa.Codec('snappy')
+    scale = len(raw) // sum(_SNAPPY_PIECES)
+    cuts = np.cumsum([0] + [n for n in _SNAPPY_PIECES for _ in range(scale)])
+    return [(codec.compress(raw[a:b].tobytes(), asbytes=True), int(b - a)) for a, b in zip(cuts[:-1], cuts[1:])]
+
+
+def _parquet_run(dev, d):
+    import tempfile
+    import torch
+    import parquet_inputs as pi
+    from otto_amd import parquet
+    with tempfile.TemporaryDirectory() as tmp:
+        cols = parquet.read_columns(_parquet_write(tmp, d), pi.COLUMNS, dev, batch_bytes=1 << 18)      # two batches: both staging sets
+    streams = _snappy_streams(on_host(d['raw']))
+    buf = torch.from_numpy(np.frombuffer(b''.join(b for b, _ in streams), dtype=np.uint8).copy()).to(dev)
+    lens = [len(b) for b, _ in streams]
+    out, status = parquet.snappy_decompress(buf, np.cumsum([0] + lens)[:-1], lens, [n for _, n in streams])
+    return tuple(cols) + (out, status)
+
+
+def _parquet_restate(i):
+    import tempfile
+    import parquet_inputs as pi
+    with tempfile.TemporaryDirectory() as tmp:
+        want = pi.expected(_parquet_write(tmp, i))             # pyarrow's own decode of the file
+    return tuple(want[c] for c in pi.COLUMNS) + (i['raw'], np.zeros(len(_SNAPPY_PIECES) * (len(i['raw']) // sum(_SNAPPY_PIECES)), np.int32))
+
+
+def _parquet_bad(which):
+    def call(dev, d):
+        import pathlib
+        import tempfile
+        import parquet_inputs as pi
+        from otto_amd import parquet
+        with tempfile.TemporaryDirectory() as tmp:
+            path, _ = getattr(pi, which)(pathlib.Path(tmp))
+            return parquet.read_columns(path, ['aid'], dev)
+    return call
+
+
+PARQUET = Case('parquet', ('otto_parquet_decode', 'otto_parquet_snappy'), _parquet_make, _parquet_run, _parquet_restate,
+               host_keys=('session', 'aid', 'ts', 'type', 'raw'), shape_outputs=(5,),      # the status words of valid streams are zero
+               refusals={'a null (a file of its own)': (None, _parquet_bad('null_v1_file'), 'a null'),
+                         'dictionary index outside the dictionary (a file of its own)': (None, _parquet_bad('bad_index_file'),
+                                                                                           "dictionary index not below")})
+
+
+CASES = [BLEND, EVAL, EVENTS, PAIRS, FREQ, SUBMIT, DEFLATE, KNN, FOREST, OBJECTIVES, FOLDS, INTER, FEAT, CAND, MF, MF_TRAIN, COVIS, GBDT, XGB,
+         SGNS, JSONL, PARQUET]
+BY_NAME = {c.name: c for c in CASES}
+
+# ---- entry points that take a stream and have no case: name (or prefix ending in *) -> the one-line reason -----------------
+EXEMPT = {
+    'otto_mf_dp_local': 'needs several ranks: the data-parallel step (tests/test_mf_dp_gpu.py runs it with its exchange)',
+    'otto_mf_dp_apply': 'needs several ranks: the data-parallel step (tests/test_mf_dp_gpu.py runs it with its exchange)',
+    'otto_debug_calibrate': 'diagnostic only: moves a known byte count for counter calibration, no result',
+}
+
+
+def streamed_entry_points():
+    """The names of ``_lib.SIGNATURES`` whose entry takes a stream: the functions that ``include/*.h`` declare with
+    ``void* stream`` as their last parameter (the place where ``_lib.call`` appends it)."""
+    import glob
+    import os
+    import re
+    from otto_amd import _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = set()
+    for path in glob.glob(os.path.join(root, 'include', '*.h')):
+        with open(path) as f:
+            text = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+        for m in re.finditer(r'\b(otto_\w+)\s*\(([^;{}]*?)\)\s*;', text):
+            if re.search(r'void\s*\*\s*stream\s*$', m.group(2).strip()):
+                names.add(m.group(1))
+    assert names <= set(_lib.SIGNATURES), sorted(names - set(_lib.SIGNATURES))
+    return names
