@@ -124,24 +124,17 @@ int otto_gbdt_lambdarank(const double* d_score, const int32_t* d_label, const in
 int otto_gbdt_quantize(const double* d_grad, const double* d_hess, int64_t n, int32_t* d_gh, int32_t* d_exp, void* stream);
 
 /* d_rows int32 [n_rows]: the leaf's rows (an entry outside [0, n) is skipped and the call returns OTTO_EINVAL);
- * d_hist int64 [3, F, 256], overwritten. */
+ * d_hist int64 [3, F, 256], overwritten.
+ * The feature list, here and wherever d_features / n_used appear: d_features int32 [n_used] on the device, strictly
+ * ascending inside [0, F), 1 <= n_used <= F (copied to the host and checked there: one synchronisation; OTTO_EINVAL
+ * otherwise); d_features == NULL (n_used ignored): every feature. The histogram fills the listed features' planes and
+ * leaves the others zero; the split search walks the listed features only and takes the parent sums from the first of
+ * them. */
 int otto_gbdt_hist(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_rows, int64_t n_rows,
-                   int64_t* d_hist, void* stream);
-
+                   const int32_t* d_features, int32_t n_used, int64_t* d_hist, void* stream);
 int otto_gbdt_best_split(const int64_t* d_hist, int32_t F, const int32_t* d_n_edges, const int32_t* d_exp,
                          int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2, double min_gain_to_split,
-                         int64_t* d_split, void* stream);
-
-/* The two calls above over a feature list: d_features int32 [n_used] on the device, strictly ascending inside [0, F),
- * 1 <= n_used <= F (copied to the host and checked there: one synchronisation; OTTO_EINVAL otherwise). The histogram
- * fills the listed features' planes and leaves the others zero; the split search walks the listed features only and takes
- * the parent sums from the first of them. d_features == NULL (n_used ignored) is otto_gbdt_hist / otto_gbdt_best_split. */
-int otto_gbdt_hist_features(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_rows, int64_t n_rows,
-                            const int32_t* d_features, int32_t n_used, int64_t* d_hist, void* stream);
-int otto_gbdt_best_split_features(const int64_t* d_hist, int32_t F, const int32_t* d_n_edges, const int32_t* d_exp,
-                                  int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2,
-                                  double min_gain_to_split, const int32_t* d_features, int32_t n_used, int64_t* d_split,
-                                  void* stream);
+                         const int32_t* d_features, int32_t n_used, int64_t* d_split, void* stream);
 
 /* The row bag: d_rows_out int32 receives, ascending, the m rows of [0, n) with the smallest mix(seed, r); seed is the
  * already mixed mix(bagging_seed, 2*d). 1 <= m <= n < 2^31. out_rows: the row ids d_rows_out has room for; out_rows < m
@@ -169,31 +162,23 @@ int otto_gbdt_add_tree(const uint8_t* d_bins, int64_t n, int32_t F, int32_t n_le
 int otto_gbdt_ap_at_k(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n,
                       int32_t k, double* d_ap, void* stream);
 
-/* One whole tree over all n rows. h_* are HOST buffers: h_edges float32 [F, OTTO_GBDT_MAX_EDGES]; node arrays of
- * num_leaves - 1 entries, leaf arrays of num_leaves; *h_n_leaves the leaves grown (1: no split was admissible, only
- * h_leaf_value[0] and h_leaf_count[0] are written); h_hist_rows int64 [1] or NULL: rows the histogram kernel read. */
+/* One whole tree. h_* are HOST buffers: h_edges float32 [F, OTTO_GBDT_MAX_EDGES]; node arrays of num_leaves - 1
+ * entries, leaf arrays of num_leaves; *h_n_leaves the leaves grown (1: no split was admissible, only h_leaf_value[0] and
+ * h_leaf_count[0] are written); h_hist_rows int64 [1] or NULL: rows the histogram kernel read.
+ * The row bag (SPEC-GBDT, Sampling): d_bag int32 [n_bag] on the device, 1 <= n_bag <= n, is the root's row list;
+ * d_bag == NULL (n_bag ignored): all n rows. Only the range of its entries is checked (one outside [0, n) is skipped and
+ * the call returns OTTO_EINVAL, as for d_rows). That the ids ascend and that none occurs twice is the caller's
+ * responsibility, as it is for d_rows of otto_gbdt_hist: otto_gbdt_bag writes such a list; a row listed twice is counted
+ * twice, and an order other than ascending only costs the histogram its coalesced loads. With a bag, h_leaf_count and
+ * *h_hist_rows count in-bag rows. d_features / n_used: the feature list, as for otto_gbdt_hist. */
 int otto_gbdt_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_exp,
                         const int32_t* d_n_edges, const float* h_edges, int32_t num_leaves, int64_t min_data_in_leaf,
                         double min_sum_hessian_in_leaf, double lambda_l2, double min_gain_to_split, double learning_rate,
+                        const int32_t* d_bag, int64_t n_bag, const int32_t* d_features, int32_t n_used,
                         int32_t* h_n_leaves, int32_t* h_split_feature, int32_t* h_split_bin, double* h_threshold,
                         int8_t* h_decision_type, int32_t* h_left_child, int32_t* h_right_child, double* h_split_gain,
                         double* h_leaf_value, int64_t* h_leaf_count, int64_t* h_hist_rows, void* d_work, int64_t work_bytes,
                         void* stream);
-
-/* The same tree grown on a row bag and a feature list (SPEC-GBDT, Sampling). d_bag int32 [n_bag] on the device,
- * 1 <= n_bag <= n: the root's row list. Only the range of its entries is checked (one outside [0, n) is skipped and the
- * call returns OTTO_EINVAL, as for d_rows). That the ids ascend and that none occurs twice is the caller's
- * responsibility, as it is for d_rows of otto_gbdt_hist: otto_gbdt_bag writes such a list; a row listed twice is counted
- * twice, and an order other than ascending only costs the histogram its coalesced loads. NULL: all n rows. d_features / n_used as for otto_gbdt_hist_features; NULL: every feature. NULL / NULL is
- * otto_gbdt_grow_tree. h_leaf_count and *h_hist_rows count in-bag rows. d_work as for otto_gbdt_grow_tree. */
-int otto_gbdt_grow_tree_sampled(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_exp,
-                                const int32_t* d_n_edges, const float* h_edges, int32_t num_leaves, int64_t min_data_in_leaf,
-                                double min_sum_hessian_in_leaf, double lambda_l2, double min_gain_to_split, double learning_rate,
-                                const int32_t* d_bag, int64_t n_bag, const int32_t* d_features, int32_t n_used,
-                                int32_t* h_n_leaves, int32_t* h_split_feature, int32_t* h_split_bin, double* h_threshold,
-                                int8_t* h_decision_type, int32_t* h_left_child, int32_t* h_right_child, double* h_split_gain,
-                                double* h_leaf_value, int64_t* h_leaf_count, int64_t* h_hist_rows, void* d_work,
-                                int64_t work_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -42,7 +42,7 @@
  *        delta = |(gain_high - gain_low) * (discount[r_high] - discount[r_low])| * inv_idcg
  *        g = (p - 1.0)*delta;   h2 = 2.0*max(p*(1.0 - p), 1e-16)*delta
  *    inv_idcg = 1/IDCG, IDCG = sum over all cnt rows of gain(labels sorted descending)[r]*discount[r] in rank order from 0.0;
- *    0 if IDCG is 0. Accumulation order as in SPEC-XGB. weighting = 0 is otto_xgb_pairwise, bit for bit.
+ *    0 if IDCG is 0. Accumulation order as in SPEC-XGB. weighting = 0 is SPEC-XGB's rank:pairwise, bit for bit.
  *
  * 4. Metrics.
  *    NDCG@k of a query, in SPEC-GBDT's rank order: DCG = sum_{r < min(k, cnt)} gain(label_r)*discount[r] from 0.0 in rank

@@ -89,14 +89,10 @@ extern "C" {
 
 /* d_score float64 [n], d_label int32 [n], d_query_off int64 [Q+1]; d_sigmoid float64 [OTTO_GBDT_SIGMOID_BINS] at sigma = 1
  * with its lo and factor (otto_gbdt.h); seed_it = the already mixed mix(objective_seed, it); d_grad, d_hess float64 [n],
- * overwritten. One synchronisation (the error words). */
-int otto_xgb_pairwise(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n,
-                      const double* d_sigmoid, double sigmoid_lo, double sigmoid_factor, uint64_t seed_it, double* d_grad,
-                      double* d_hess, void* stream);
-
-/* The same objective with LambdaMART's pair weights (SPEC-OBJ, include/otto_objective.h): weighting = 0 is
- * otto_xgb_pairwise bit for bit (d_discount is not read and may be NULL); weighting = 1 is rank:ndcg, every pair's g and h2
- * multiplied by the |delta NDCG| of swapping its rows; d_discount float64 [OTTO_GBDT_MAX_QUERY] (otto_gbdt.h). */
+ * overwritten. One synchronisation (the error words). weighting = 0 is SPEC-XGB's rank:pairwise (d_discount is not read
+ * and may be NULL); weighting = 1 is rank:ndcg, the same pairs with LambdaMART's weights (SPEC-OBJ,
+ * include/otto_objective.h): every pair's g and h2 multiplied by the |delta NDCG| of swapping its rows; d_discount float64
+ * [OTTO_GBDT_MAX_QUERY] (otto_gbdt.h). */
 int otto_xgb_lambdamart(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n,
                         const double* d_sigmoid, double sigmoid_lo, double sigmoid_factor, uint64_t seed_it, int32_t weighting,
                         const double* d_discount, double* d_grad, double* d_hess, void* stream);
@@ -130,8 +126,8 @@ typedef struct otto_xgb_tree {
 int64_t otto_xgb_workspace_bytes(int64_t n, int32_t F, int32_t max_depth);
 
 /* One whole depth-wise tree: one synchronisation per level, none per node. d_bins, d_gh, d_exp, d_n_edges, h_edges as for
- * otto_gbdt_grow_tree; d_bag / n_bag and d_features / n_used as for otto_gbdt_grow_tree_sampled (NULL: all rows / every
- * feature; a feature list costs one more synchronisation). min_child_weight, lambda, gamma, eta: SPEC-XGB. */
+ * otto_gbdt_grow_tree, d_bag / n_bag and d_features / n_used too (NULL: all rows / every feature; a feature list costs
+ * one more synchronisation). min_child_weight, lambda, gamma, eta: SPEC-XGB. */
 int otto_xgb_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_exp,
                        const int32_t* d_n_edges, const float* h_edges, int32_t max_depth, double min_child_weight, double lambda,
                        double gamma, double eta, const int32_t* d_bag, int64_t n_bag, const int32_t* d_features, int32_t n_used,

@@ -219,22 +219,16 @@ SIGNATURES = {
     'otto_gbdt_lambdarank': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, _vp, C.c_double, _i32, _i32, _vp, _vp,
                                     _vp]),
     'otto_gbdt_quantize': (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
-    'otto_gbdt_hist': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),
-    'otto_gbdt_best_split': (_i32, [_vp, _i32, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    'otto_gbdt_hist': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp]),
+    'otto_gbdt_best_split': (_i32, [_vp, _i32, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, _vp, _i32, _vp, _vp]),
     'otto_gbdt_partition': (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     'otto_gbdt_add_tree': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'otto_gbdt_ap_at_k': (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     'otto_gbdt_grow_tree': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, C.c_double, C.c_double, C.c_double, C.c_double,
-                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    'otto_gbdt_hist_features': (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp]),
-    'otto_gbdt_best_split_features': (_i32, [_vp, _i32, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, _vp, _i32, _vp, _vp]),
+                                   _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'otto_gbdt_bag_workspace_bytes': (_i64, [_i64]),
     'otto_gbdt_bag': (_i32, [_i64, _i64, C.c_uint64, _vp, _i64, _vp, _i64, _vp]),
-    'otto_gbdt_grow_tree_sampled': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i64, C.c_double, C.c_double, C.c_double,
-                                           C.c_double, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                           _vp, _i64, _vp]),
     # include/otto_xgb.h
-    'otto_xgb_pairwise': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, C.c_uint64, _vp, _vp, _vp]),
     'otto_xgb_lambdamart': (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, C.c_double, C.c_double, C.c_uint64, _i32, _vp, _vp, _vp, _vp]),
     'otto_xgb_workspace_bytes': (_i64, [_i64, _i32, _i32]),
     'otto_xgb_grow_tree': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, C.c_double, C.c_double, C.c_double, C.c_double, _vp,

@@ -511,8 +511,8 @@ extern "C" int otto_gbdt_quantize(const double* d_grad, const double* d_hess, in
     return 0;
 }
 
-extern "C" int otto_gbdt_hist_features(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_rows,
-                                       int64_t n_rows, const int32_t* d_features, int32_t n_used, int64_t* d_hist, void* stream) {
+extern "C" int otto_gbdt_hist(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_rows,
+                              int64_t n_rows, const int32_t* d_features, int32_t n_used, int64_t* d_hist, void* stream) {
     OTTO_TRY(check_bins_args(d_bins, n, F));
     OTTO_REQUIRE(n_rows >= 0 && n_rows < ((int64_t)1 << 31), "n_rows = %lld outside [0, 2^31)", (long long)n_rows);
     OTTO_REQUIRE(d_hist, "null d_hist");
@@ -525,15 +525,10 @@ extern "C" int otto_gbdt_hist_features(const uint8_t* d_bins, int64_t n, int32_t
     return err_end(err, s);
 }
 
-extern "C" int otto_gbdt_hist(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_rows, int64_t n_rows,
-                              int64_t* d_hist, void* stream) {
-    return otto_gbdt_hist_features(d_bins, n, F, d_gh, d_rows, n_rows, nullptr, 0, d_hist, stream);
-}
-
-extern "C" int otto_gbdt_best_split_features(const int64_t* d_hist, int32_t F, const int32_t* d_n_edges, const int32_t* d_exp,
-                                             int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2,
-                                             double min_gain_to_split, const int32_t* d_features, int32_t n_used, int64_t* d_split,
-                                             void* stream) {
+extern "C" int otto_gbdt_best_split(const int64_t* d_hist, int32_t F, const int32_t* d_n_edges, const int32_t* d_exp,
+                                    int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2,
+                                    double min_gain_to_split, const int32_t* d_features, int32_t n_used, int64_t* d_split,
+                                    void* stream) {
     OTTO_REQUIRE(F >= 1 && F <= OTTO_FOREST_MAX_FEATURES, "F must be in [1, %d] (got %d)", OTTO_FOREST_MAX_FEATURES, F);
     OTTO_REQUIRE(d_hist && d_n_edges && d_exp && d_split, "null argument");
     OTTO_TRY(check_split_params(min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split));
@@ -541,13 +536,6 @@ extern "C" int otto_gbdt_best_split_features(const int64_t* d_hist, int32_t F, c
     SplitJobs jobs{{d_hist, d_hist}, {d_split, d_split}};
     SplitParams p{min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split};
     return launch_best_split(jobs, 1, F, d_n_edges, d_exp, p, d_features, n_used, (hipStream_t)stream);
-}
-
-extern "C" int otto_gbdt_best_split(const int64_t* d_hist, int32_t F, const int32_t* d_n_edges, const int32_t* d_exp,
-                                    int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2,
-                                    double min_gain_to_split, int64_t* d_split, void* stream) {
-    return otto_gbdt_best_split_features(d_hist, F, d_n_edges, d_exp, min_data_in_leaf, min_sum_hessian_in_leaf, lambda_l2,
-                                         min_gain_to_split, nullptr, 0, d_split, stream);
 }
 
 extern "C" int64_t otto_gbdt_bag_workspace_bytes(int64_t n) {
@@ -639,14 +627,14 @@ extern "C" int otto_gbdt_ap_at_k(const double* d_score, const int32_t* d_label, 
     return err_end(err, s);
 }
 
-extern "C" int otto_gbdt_grow_tree_sampled(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_exp,
-                                           const int32_t* d_n_edges, const float* h_edges, int32_t num_leaves,
-                                           int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2,
-                                           double min_gain_to_split, double learning_rate, const int32_t* d_bag, int64_t n_bag,
-                                           const int32_t* d_features, int32_t n_used, int32_t* h_n_leaves, int32_t* h_split_feature,
-                                           int32_t* h_split_bin, double* h_threshold, int8_t* h_decision_type, int32_t* h_left_child,
-                                           int32_t* h_right_child, double* h_split_gain, double* h_leaf_value, int64_t* h_leaf_count,
-                                           int64_t* h_hist_rows, void* d_work, int64_t work_bytes, void* stream) {
+extern "C" int otto_gbdt_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_exp,
+                                   const int32_t* d_n_edges, const float* h_edges, int32_t num_leaves,
+                                   int64_t min_data_in_leaf, double min_sum_hessian_in_leaf, double lambda_l2,
+                                   double min_gain_to_split, double learning_rate, const int32_t* d_bag, int64_t n_bag,
+                                   const int32_t* d_features, int32_t n_used, int32_t* h_n_leaves, int32_t* h_split_feature,
+                                   int32_t* h_split_bin, double* h_threshold, int8_t* h_decision_type, int32_t* h_left_child,
+                                   int32_t* h_right_child, double* h_split_gain, double* h_leaf_value, int64_t* h_leaf_count,
+                                   int64_t* h_hist_rows, void* d_work, int64_t work_bytes, void* stream) {
     OTTO_TRY(check_bins_args(d_bins, n, F));
     OTTO_REQUIRE(!d_bag || (n_bag >= 1 && n_bag <= n), "n_bag = %lld outside [1, n = %lld]", (long long)n_bag, (long long)n);
     OTTO_REQUIRE(n >= 1, "n = 0: nothing to grow a tree on");
@@ -760,17 +748,4 @@ extern "C" int otto_gbdt_grow_tree_sampled(const uint8_t* d_bins, int64_t n, int
     *h_n_leaves = (int32_t)leaves.size();
     if (h_hist_rows) *h_hist_rows = hist_rows;
     return 0;
-}
-
-extern "C" int otto_gbdt_grow_tree(const uint8_t* d_bins, int64_t n, int32_t F, const int32_t* d_gh, const int32_t* d_exp,
-                                   const int32_t* d_n_edges, const float* h_edges, int32_t num_leaves, int64_t min_data_in_leaf,
-                                   double min_sum_hessian_in_leaf, double lambda_l2, double min_gain_to_split, double learning_rate,
-                                   int32_t* h_n_leaves, int32_t* h_split_feature, int32_t* h_split_bin, double* h_threshold,
-                                   int8_t* h_decision_type, int32_t* h_left_child, int32_t* h_right_child, double* h_split_gain,
-                                   double* h_leaf_value, int64_t* h_leaf_count, int64_t* h_hist_rows, void* d_work,
-                                   int64_t work_bytes, void* stream) {
-    return otto_gbdt_grow_tree_sampled(d_bins, n, F, d_gh, d_exp, d_n_edges, h_edges, num_leaves, min_data_in_leaf,
-                                       min_sum_hessian_in_leaf, lambda_l2, min_gain_to_split, learning_rate, nullptr, 0, nullptr, 0,
-                                       h_n_leaves, h_split_feature, h_split_bin, h_threshold, h_decision_type, h_left_child,
-                                       h_right_child, h_split_gain, h_leaf_value, h_leaf_count, h_hist_rows, d_work, work_bytes, stream);
 }

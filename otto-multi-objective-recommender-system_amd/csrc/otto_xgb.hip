@@ -435,13 +435,6 @@ extern "C" int otto_xgb_lambdamart(const double* d_score, const int32_t* d_label
     return err_end(err, s);
 }
 
-extern "C" int otto_xgb_pairwise(const double* d_score, const int32_t* d_label, const int64_t* d_query_off, int64_t Q, int64_t n,
-                                 const double* d_sigmoid, double sigmoid_lo, double sigmoid_factor, uint64_t seed_it, double* d_grad,
-                                 double* d_hess, void* stream) {
-    return otto_xgb_lambdamart(d_score, d_label, d_query_off, Q, n, d_sigmoid, sigmoid_lo, sigmoid_factor, seed_it, 0, nullptr, d_grad,
-                               d_hess, stream);
-}
-
 extern "C" int64_t otto_xgb_workspace_bytes(int64_t n, int32_t F, int32_t max_depth) {
     if (n < 0 || n >= ((int64_t)1 << 31) || F < 1 || F > OTTO_FOREST_MAX_FEATURES || max_depth < 1 || max_depth > OTTO_XGB_MAX_DEPTH)
         return 0;

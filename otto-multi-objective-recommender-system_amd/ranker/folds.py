@@ -9,12 +9,13 @@ per fold and over all folds, and the gain and split feature importances. The fol
 tie order pinned; pandas' Mersenne-Twister permutation is deliberately not reproduced: the kept negatives are the ``m``
 with the smallest ``splitmix64`` keys of their row index (SPEC-FOLDS states both).
 """
+import collections
 import ctypes as C
 
 import numpy as np
 
 from .. import _lib
-from . import gbdt
+from . import gbdt, xgb
 from .forest import MAX_FEATURES
 
 MAX_SPLITS = 16             # OTTO_FOLDS_MAX_SPLITS
@@ -142,12 +143,7 @@ def feature_importance(trees, n_features):
     """(gain float64 [F], split int64 [F]): the sum of ``split_gain`` and the number of splits per feature over a
     ``BinTree`` list, in NumPy on the host. LightGBM's ``feature_importance('gain' | 'split')`` counts the splits with a
     positive gain; every split of SPEC-GBDT has one."""
-    gain = np.zeros(int(n_features), dtype=np.float64)
-    split = np.zeros(int(n_features), dtype=np.int64)
-    for t in trees:
-        np.add.at(gain, t.split_feature, t.split_gain)
-        np.add.at(split, t.split_feature, 1)
-    return gain, split
+    return gbdt.split_sums(trees, n_features, 'split_gain'), gbdt.split_sums(trees, n_features)
 
 
 class CVResult:
@@ -161,6 +157,37 @@ class CVResult:
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
+
+
+def _lightgbm_resolve(params, sampling):
+    return gbdt.resolve_params(params, extended=True)
+
+
+def _lightgbm_oof(res, val_bins, X, val_idx):
+    import torch
+    score = torch.zeros(val_bins.shape[1], dtype=torch.float64, device=val_bins.device)
+    for tree in res.trees:
+        gbdt.add_tree(val_bins, tree, score)
+    return score
+
+
+def _xgboost_resolve(params, sampling):
+    if sampling is not None:
+        raise ValueError("sampling: with booster='xgboost' subsample / colsample_bytree / seed are keys of params")
+    return xgb.resolve_params(params, extended=True)[0]
+
+
+# What cross_validate asks of a booster. resolve(params, sampling) -> the resolved dict; train(*data, params, sampling,
+# **kw) -> a TrainResult; oof_score(result, val_bins, X, val_idx) -> the raw float64 score of the validation rows;
+# importances(trees, F) -> the per-feature columns (gain, split[, cover]).
+_Booster = collections.namedtuple('_Booster', 'resolve train oof_score importances')
+_BOOSTERS = {
+    'lightgbm': _Booster(_lightgbm_resolve, lambda *data, params, sampling, **kw: gbdt.train(*data, params, sampling=sampling, **kw),
+                         _lightgbm_oof, feature_importance),
+    'xgboost': _Booster(_xgboost_resolve, lambda *data, params, sampling, **kw: xgb.train(*data, params, **kw),
+                        lambda res, val_bins, X, val_idx: xgb.predict(res, X[val_idx.long()], output_margin=True),
+                        xgb.feature_importance),
+}
 
 
 def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ratio=0.3, seed=42, num_boost_round=100,
@@ -200,24 +227,16 @@ def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ra
     n, F = int(X.shape[0]), int(X.shape[1])
     if label.numel() != n:
         raise ValueError(f'label has {label.numel()} rows, X has {n}')
-    if booster not in ('lightgbm', 'xgboost'):
+    if booster not in _BOOSTERS:
         raise ValueError(f"booster = {booster!r}: expected 'lightgbm' or 'xgboost'")
-    xgboost = booster == 'xgboost'
-    if xgboost:
-        from . import xgb
-        if sampling is not None:
-            raise ValueError("sampling: with booster='xgboost' subsample / colsample_bytree / seed are keys of params")
-        p = xgb.resolve_params(params, extended=True)[0]
-    else:
-        p = gbdt.resolve_params(params, extended=True)
+    family = _BOOSTERS[booster]
+    p = family.resolve(params, sampling)
     n_splits = int(n_splits)
     fold_of_query, fold_rows = group_kfold(query_off, n_splits, n=n)
     label32 = label if label.dtype == torch.int32 else label.to(torch.int32)
     oof = torch.zeros(n, dtype=torch.float32, device=dev)
     forests, trees, best, histories, mappers = [], [], [], [], []
-    imp_gain = np.zeros((F, n_splits), dtype=np.float64)
-    imp_split = np.zeros((F, n_splits), dtype=np.int64)
-    imp_cover = np.zeros((F, n_splits), dtype=np.float64) if xgboost else None
+    importances = []
     for fold in range(n_splits):
         fi = fold_indices(label, query_off, fold_of_query, fold, negative_sampling_ratio, seed)
         Mt = fi.train_idx.numel()
@@ -227,26 +246,17 @@ def cross_validate(X, label, query_off, params, n_splits=5, negative_sampling_ra
         train_bins, val_bins = gather_bins(bins, fi.train_idx), gather_bins(bins, fi.val_idx)
         del bins
         train_label, val_label = label32[fi.train_idx.long()], label32[fi.val_idx.long()]
-        common = dict(valid=(val_bins, val_label, fi.val_query_off), num_boost_round=num_boost_round,
-                      early_stopping_rounds=early_stopping_rounds, feature_names=feature_names)
-        if xgboost:
-            res = xgb.train(train_bins, train_label, fi.train_query_off, mapper, params, **common)
-            score = xgb.predict(res, X[fi.val_idx.long()], output_margin=True)
-        else:
-            res = gbdt.train(train_bins, train_label, fi.train_query_off, mapper, params, sampling=sampling, **common)
-            score = torch.zeros(fi.val_idx.numel(), dtype=torch.float64, device=dev)
-            for tree in res.trees:
-                gbdt.add_tree(val_bins, tree, score)
-        oof[fi.val_idx.long()] = score.to(torch.float32)
+        res = family.train(train_bins, train_label, fi.train_query_off, mapper, params=params, sampling=sampling,
+                           valid=(val_bins, val_label, fi.val_query_off), num_boost_round=num_boost_round,
+                           early_stopping_rounds=early_stopping_rounds, feature_names=feature_names)
+        oof[fi.val_idx.long()] = family.oof_score(res, val_bins, X, fi.val_idx).to(torch.float32)
         forests.append(res.forest)
         trees.append(res.trees)
         best.append(res.best_iteration)
         histories.append(res.history)
         mappers.append(mapper)
-        if xgboost:
-            imp_gain[:, fold], imp_split[:, fold], imp_cover[:, fold] = xgb.feature_importance(res.trees, F)
-        else:
-            imp_gain[:, fold], imp_split[:, fold] = feature_importance(res.trees, F)
+        importances.append(family.importances(res.trees, F))
+    imp_gain, imp_split, imp_cover = ([np.stack(columns, axis=1) for columns in zip(*importances)] + [None])[:3]
     out = CVResult(forests=forests, trees=trees, best_iterations=best, histories=histories, mappers=mappers, oof_prediction=oof,
                    fold_of_query=fold_of_query, fold_rows=fold_rows, importance_gain=imp_gain, importance_split=imp_split, importance_cover=imp_cover,
                    top_aid=None, top_n=None, fold_hits=None, fold_denom=None, fold_recall=None, hits=None, denom=None, recall=None)

@@ -1,5 +1,6 @@
 """LambdaRank gradient-boosted tree training on the device (SPEC-GBDT): the bin mapper, thin Python
-over ``include/otto_gbdt.h``, the boosting loop and a LightGBM v3 model writer.
+over ``include/otto_gbdt.h``, :func:`train` (the family's side of the boosting loop of ``ranker.boost``) and a LightGBM v3
+model writer.
 
 What this replaces in the reference: ``lgb.train`` on the (session, candidate) matrix, one model per event type and fold
 (``src/ranker/lgb_trainer.py:134-165``). The caller keeps GroupKFold and the negative down-sampling
@@ -169,19 +170,24 @@ def _check_queries(score, label, query_off):
         raise ValueError('query_off: expected int64 [Q+1]')
 
 
+def gradient_outputs(score, out):
+    """The (grad, hess) a gradient wrapper writes: ``out`` where the caller passed it, checked to be two float64 [n]
+    tensors beside ``score``; otherwise two new ones."""
+    import torch
+    grad, hess = out if out is not None else (torch.empty_like(score), torch.empty_like(score))
+    _lib.need(grad, 'grad', torch.float64, 1, device=score.device, numel=score.numel())
+    _lib.need(hess, 'hess', torch.float64, 1, device=score.device, numel=score.numel())
+    return grad, hess
+
+
 def lambdarank_gradients(score, label, query_off, sigma=1.0, truncation_level=30, norm=True, out=None):
     """(grad, hess) float64 [n] of the LambdarankNDCG objective; ``score`` float64 [n], ``label`` int32 [n] in 0..31,
     ``query_off`` int64 [Q+1], on the device. Raises ``OttoError`` for a query longer than ``MAX_QUERY`` or a malformed
     ``query_off``: the rows of such a query are zero in ``out`` = (grad, hess), if the caller passed these tensors."""
-    import torch
     _check_queries(score, label, query_off)
     dev = score.device
     table, lo, factor, disc = _tables(sigma, dev)
-    grad, hess = out if out is not None else (torch.empty_like(score), torch.empty_like(score))
-    _lib.need(grad, 'grad', torch.float64, 1, device=dev)
-    _lib.need(hess, 'hess', torch.float64, 1, device=dev)
-    if grad.numel() != score.numel() or hess.numel() != score.numel():
-        raise ValueError('out: expected two float64 tensors [n]')
+    grad, hess = gradient_outputs(score, out)
     _lib.call('otto_gbdt_lambdarank', dev, score, label, query_off, query_off.numel() - 1, score.numel(), table, lo, factor, disc,
               float(sigma), int(truncation_level), int(bool(norm)), grad, hess)
     return grad, hess
@@ -219,6 +225,11 @@ def _feature_list(features, F, dev):
     return torch.from_numpy(f).to(dev)
 
 
+def _numel(t):
+    """The length that goes with an optional device list (a bag, a feature list): 0 beside None."""
+    return 0 if t is None else t.numel()
+
+
 def leaf_histogram(bins, gh, rows, features=None):
     """int64 [3, F, 256] = (sum qg, sum qh, rows) of the leaf whose row ids are ``rows`` int32. ``features``: an ascending
     list of feature ids (a tree's feature sample); the planes of the other features are zero."""
@@ -226,11 +237,8 @@ def leaf_histogram(bins, gh, rows, features=None):
     F, n = check_bins(bins)
     _lib.need(rows, 'rows', torch.int32, 1, device=bins.device)
     hist = torch.empty((3, F, 256), dtype=torch.int64, device=bins.device)
-    if features is None:
-        _lib.call('otto_gbdt_hist', bins.device, bins, n, F, gh, rows, rows.numel(), hist)
-    else:
-        feats = _feature_list(features, F, bins.device)
-        _lib.call('otto_gbdt_hist_features', bins.device, bins, n, F, gh, rows, rows.numel(), feats, feats.numel(), hist)
+    feats = _feature_list(features, F, bins.device)
+    _lib.call('otto_gbdt_hist', bins.device, bins, n, F, gh, rows, rows.numel(), feats, _numel(feats), hist)
     return hist
 
 
@@ -242,13 +250,9 @@ def best_split(hist, mapper, exp, min_data_in_leaf, min_sum_hessian_in_leaf, lam
     dev = hist.device
     _, n_edges = mapper.to(dev)
     out = torch.empty(SPLIT_WORDS, dtype=torch.int64, device=dev)
-    if features is None:
-        _lib.call('otto_gbdt_best_split', dev, hist, int(hist.shape[1]), n_edges, exp, int(min_data_in_leaf),
-                  float(min_sum_hessian_in_leaf), float(lambda_l2), float(min_gain_to_split), out)
-    else:
-        feats = _feature_list(features, int(hist.shape[1]), dev)
-        _lib.call('otto_gbdt_best_split_features', dev, hist, int(hist.shape[1]), n_edges, exp, int(min_data_in_leaf),
-                  float(min_sum_hessian_in_leaf), float(lambda_l2), float(min_gain_to_split), feats, feats.numel(), out)
+    feats = _feature_list(features, int(hist.shape[1]), dev)
+    _lib.call('otto_gbdt_best_split', dev, hist, int(hist.shape[1]), n_edges, exp, int(min_data_in_leaf),
+              float(min_sum_hessian_in_leaf), float(lambda_l2), float(min_gain_to_split), feats, _numel(feats), out)
     w = out.cpu().numpy()
     if not w[0]:
         return None
@@ -320,14 +324,10 @@ def grow_tree(bins, gh, exp, mapper, p, work=None, bag=None, features=None):
     lv, cnt = np.zeros(L, dtype=np.float64), np.zeros(L, dtype=np.int64)
     n_leaves, hist_rows = C.c_int32(0), C.c_int64(0)
     # the NumPy arrays are host buffers: the edges the thresholds come from, and the tree the call writes
-    head = (bins, n, F, gh, exp, n_edges, mapper.edges, L, int(p['min_data_in_leaf']), float(p['min_sum_hessian_in_leaf']),
-            float(p['lambda_l2']), float(p['min_gain_to_split']), float(p['learning_rate']))
-    tail = (C.byref(n_leaves), sf, sb, thr, dt, lc, rc, gain, lv, cnt, C.byref(hist_rows), work, work.numel())
-    if bag is None and feats is None:
-        _lib.call('otto_gbdt_grow_tree', dev, *head, *tail)
-    else:
-        _lib.call('otto_gbdt_grow_tree_sampled', dev, *head, bag, 0 if bag is None else bag.numel(), feats,
-                  0 if feats is None else feats.numel(), *tail)
+    _lib.call('otto_gbdt_grow_tree', dev, bins, n, F, gh, exp, n_edges, mapper.edges, L, int(p['min_data_in_leaf']),
+              float(p['min_sum_hessian_in_leaf']), float(p['lambda_l2']), float(p['min_gain_to_split']), float(p['learning_rate']),
+              bag, _numel(bag), feats, _numel(feats), C.byref(n_leaves), sf, sb, thr, dt, lc, rc, gain, lv, cnt,
+              C.byref(hist_rows), work, work.numel())
     k = n_leaves.value
     return BinTree(split_feature=sf[:k - 1], split_bin=sb[:k - 1], default_left=((dt[:k - 1] & 2) >> 1).astype(np.int32),
                    left_child=lc[:k - 1], right_child=rc[:k - 1], threshold=thr[:k - 1], decision_type=dt[:k - 1],
@@ -618,6 +618,16 @@ def forest_from_trees(trees, n_features, feature_names=None):
                   feature_names=feature_names, objective='lambdarank')
 
 
+def split_sums(trees, n_features, name=None):
+    """Per feature, over the splits on it in a :class:`BinTree` list: the float64 sum of the per-node array ``name``
+    (``'split_gain'``, ``'cover'``, ...) added in tree order, or with ``name`` None the int64 number of splits. The one
+    accumulation behind ``folds.feature_importance`` and ``xgb.feature_importance``."""
+    out = np.zeros(int(n_features), dtype=np.int64 if name is None else np.float64)
+    for t in trees:
+        np.add.at(out, t.split_feature, 1 if name is None else getattr(t, name))
+    return out
+
+
 class TrainResult:
     """``forest``: the first ``best_iteration`` trees as a ``ranker.forest.Forest``; ``best_iteration``; ``history``: the
     validation metric after every iteration (empty without a validation set); ``train_score`` float64 [n] on the device:
@@ -643,93 +653,50 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
     (:func:`resolve_params` with ``extended``). ``binary``: positives are the rows with ``label > 0``; with
     ``boost_from_average`` every score starts at ``objectives.init_score`` and that value is added once into the leaf
     values of the first tree, so ``forest`` and ``trees`` scored from 0.0 return ``train_score``'s bits.
-    ``binary_logloss`` stops early on a strict decrease, every other metric on a strict increase."""
+    ``binary_logloss`` stops early on a strict decrease, every other metric on a strict increase.
+
+    The loop itself is ``boost.boost``, shared with ``xgb.train``: this function resolves the parameters, hands over its
+    gradients, :func:`grow_tree` and ``objectives.evaluate``, and wraps the result."""
     import torch
-    from . import objectives
+    from . import boost, objectives
     p = resolve_params(params, extended=True)
-    if sampling is not None and not isinstance(sampling, Sampling):
-        raise ValueError('sampling: expected a gbdt.Sampling (see sampling_from_params)')
-    F, n = check_bins(bins)
-    dev = bins.device
-    if mapper.n_features != F:
-        raise ValueError(f'the mapper has {mapper.n_features} features, bins has {F}')
-    score = torch.zeros(n, dtype=torch.float64, device=dev)
-    _check_queries(score, label, query_off)
-    if valid is not None:
-        vbins, vlabel, voff = valid
-        if check_bins(vbins)[0] != F:
-            raise ValueError('the validation bins have another feature count')
-        vscore = torch.zeros(vbins.shape[1], dtype=torch.float64, device=dev)
-        _check_queries(vscore, vlabel, voff)
-    elif early_stopping_rounds:
-        raise ValueError('early_stopping_rounds needs a validation set')
-    work = torch.empty(workspace_bytes(n, F, p['num_leaves']), dtype=torch.uint8, device=dev)
     binary = p['objective'] == 'binary'
-    init = 0.0
-    if binary:
-        n_pos, _ = objectives.label_counts(label)
+    w_pos = w_neg = 1.0
+
+    def start():
+        nonlocal w_pos, w_neg
+        if not binary:
+            return 0.0
+        n_pos, n = objectives.label_counts(label)
         w_pos, w_neg = objectives.class_weights(n_pos, n, p['is_unbalance'], p['scale_pos_weight'])
-        if p['boost_from_average'] and n:
-            init = objectives.init_score(n_pos, n, p['sigmoid'])
-            score.fill_(init)
-            if valid is not None:
-                vscore.fill_(init)
-    higher = objectives.HIGHER_IS_BETTER[p['metric']]
-    trees, leaves, history = [], [], []
-    best_metric, best_iter = None, 0
-    bag_on = sampling is not None and sampling.bag_active
-    features_on = sampling is not None and sampling.features_active
-    m = bag_size(sampling.bagging_fraction, n) if bag_on else n       # refuses an empty bag before any launch
-    bag = features = None
-    for it in range(int(num_boost_round)):
+        return objectives.init_score(n_pos, n, p['sigmoid']) if p['boost_from_average'] and n else 0.0
+
+    def gradients(score, it):
         if binary:
-            grad, hess = objectives.binary_gradients(score, label, p['sigmoid'], w_pos, w_neg, 0.0)
-        else:
-            grad, hess = lambdarank_gradients(score, label, query_off, p['sigmoid'], p['lambdarank_truncation_level'],
-                                              p['lambdarank_norm'])
-        gh, exp = quantize_gradients(grad, hess)
-        if bag_on and it % sampling.bagging_freq == 0:
-            bag = bag_rows(n, m, mix(sampling.bagging_seed, 2 * (it // sampling.bagging_freq)), dev)
-        if features_on:
-            features = sample_features(F, sampling.feature_fraction, sampling.feature_fraction_seed, it)
-        tree = grow_tree(bins, gh, exp, mapper, p, work, bag=bag, features=features)
-        if tree.n_leaves < 2:
-            break
-        trees.append(tree)
-        leaf = add_tree(bins, tree, score, want_leaf=keep_leaves)
-        if keep_leaves:
-            leaves.append(leaf)
-        if valid is not None:
-            add_tree(vbins, tree, vscore)
-            if p['metric'] == 'map':
-                metric = mean_ap(ap_at_k(vscore, vlabel, voff, p['eval_at']))
-            else:
-                metric = objectives.evaluate(p['metric'], vscore, vlabel, voff, k=p['eval_at'], minus=False, sigma=p['sigmoid'])
-            history.append(metric)
-            if best_metric is None or (metric > best_metric if higher else metric < best_metric):
-                best_metric, best_iter = metric, it + 1
-            if early_stopping_rounds and it + 1 - best_iter >= int(early_stopping_rounds):
-                break
-    if not trees:
-        raise _lib.OttoError('no tree could be grown: no split of the root is admissible (min_data_in_leaf, '
-                             'min_sum_hessian_in_leaf, min_gain_to_split) or every label of a query is the same')
-    if init != 0.0:
+            return objectives.binary_gradients(score, label, p['sigmoid'], w_pos, w_neg, 0.0)
+        return lambdarank_gradients(score, label, query_off, p['sigmoid'], p['lambdarank_truncation_level'], p['lambdarank_norm'])
+
+    b = boost.boost(
+        bins, label, query_off, mapper, gradients=gradients, start=start,
+        grow=lambda gh, exp, bag, features, work: grow_tree(bins, gh, exp, mapper, p, work, bag=bag, features=features),
+        work_bytes=lambda n, F: workspace_bytes(n, F, p['num_leaves']),
+        metric=lambda vscore: objectives.evaluate(p['metric'], vscore, valid[1], valid[2], k=p['eval_at'], minus=None,
+                                                  sigma=p['sigmoid']),
+        higher_is_better=objectives.HIGHER_IS_BETTER[p['metric']], sampling=sampling, valid=valid,
+        num_boost_round=num_boost_round, early_stopping_rounds=early_stopping_rounds, keep_leaves=keep_leaves,
+        no_tree='no tree could be grown: no split of the root is admissible (min_data_in_leaf, min_sum_hessian_in_leaf, '
+                'min_gain_to_split) or every label of a query is the same')
+    trees = b.trees
+    if b.start != 0.0:
         # LightGBM's AddBias: 0.0 + (value + init) has the bits of init + value, so the trees score from 0.0 from here on
         first = BinTree(**trees[0].__dict__)
-        first.leaf_value = first.leaf_value + np.float64(init)
+        first.leaf_value = first.leaf_value + np.float64(b.start)
         trees[0] = first
-    if valid is None or not early_stopping_rounds:
-        best_iter = len(trees)
-    elif best_iter < len(trees):
-        score.zero_()                      # the same float64 additions in the same order: the bits of iteration best_iter
-        for tree in trees[:best_iter]:
-            add_tree(bins, tree, score)
-    trees = trees[:best_iter]
-    train_leaf = torch.stack(leaves[:best_iter], dim=1).contiguous() if keep_leaves else None
-    forest = forest_from_trees(trees, F, feature_names)
+    train_leaf = torch.stack(b.leaves, dim=1).contiguous() if keep_leaves else None
+    forest = forest_from_trees(trees, int(bins.shape[0]), feature_names)
     if binary:
         forest.objective = f'binary sigmoid:{p["sigmoid"]:g}'
-    return TrainResult(forest, best_iter, history, score, trees, train_leaf)
+    return TrainResult(forest, b.best_iteration, b.history, b.score, trees, train_leaf)
 
 
 def write_lightgbm_model(forest, feature_names=None):

@@ -38,13 +38,11 @@ def binary_gradients(score, label, sigma=1.0, w_pos=1.0, w_neg=1.0, hess_floor=0
     """(grad, hess) float64 [n] of SPEC-OBJ's pointwise logistic objective; ``score`` float64 [n], ``label`` int32 [n] in
     0..31 (positive: > 0), on the device. Raises ``OttoError`` for a label outside 0..31: such a row's outputs are zero in
     ``out`` = (grad, hess), if the caller passed these tensors."""
-    import torch
+    from . import gbdt
     _rows(score, label)
     dev = score.device
     table, lo, factor, _ = _tables(dev)
-    grad, hess = out if out is not None else (torch.empty_like(score), torch.empty_like(score))
-    _lib.need(grad, 'grad', torch.float64, 1, device=dev, numel=score.numel())
-    _lib.need(hess, 'hess', torch.float64, 1, device=dev, numel=score.numel())
+    grad, hess = gbdt.gradient_outputs(score, out)
     _lib.call('otto_obj_binary', dev, score, label, score.numel(), table, lo, factor, float(sigma), float(w_pos), float(w_neg),
               float(hess_floor), grad, hess)
     return grad, hess
@@ -101,12 +99,17 @@ def ndcg_at_k(score, label, query_off, k=MAX_QUERY):
     return out
 
 
-def mean_ndcg(ndcg, minus=False):
-    """The mean over all queries; a query without a positive (-1) counts 1.0 (LightGBM's and XGBoost's ``ndcg``), with
-    ``minus`` (``ndcg-``) 0.0; ``np.sum / Q`` in float64 on the host (nan without a query)."""
-    v = ndcg.detach().cpu().numpy() if hasattr(ndcg, 'detach') else np.asarray(ndcg, dtype=np.float64)
+def query_mean(values, minus=False):
+    """The mean of a per-query figure (float64 [Q], device tensor or array) over all queries: a query without a positive
+    (-1) counts 1.0, with ``minus`` 0.0; ``np.sum / Q`` in float64 on the host (nan without a query)."""
+    v = values.detach().cpu().numpy() if hasattr(values, 'detach') else np.asarray(values, dtype=np.float64)
     v = np.where(v < 0, 0.0 if minus else 1.0, v)
     return float(np.sum(v) / v.size) if v.size else float('nan')
+
+
+def mean_ndcg(ndcg, minus=False):
+    """:func:`query_mean` of per-query NDCG: LightGBM's and XGBoost's ``ndcg``, with ``minus`` ``ndcg-``."""
+    return query_mean(ndcg, minus)
 
 
 def auc_counts(score, label, work=None):
@@ -172,11 +175,7 @@ def evaluate(metric, score, label, query_off, k=MAX_QUERY, minus=None, sigma=1.0
     from . import gbdt
     if metric == 'map':
         ap = gbdt.ap_at_k(score, label, query_off, k)
-        if minus is None:
-            return gbdt.mean_ap(ap)
-        v = ap.detach().cpu().numpy()
-        v = np.where(v < 0, 0.0 if minus else 1.0, v)
-        return float(np.sum(v) / v.size) if v.size else float('nan')
+        return gbdt.mean_ap(ap) if minus is None else query_mean(ap, minus)
     if metric == 'ndcg':
         return mean_ndcg(ndcg_at_k(score, label, query_off, k), bool(minus))
     if metric == 'auc':

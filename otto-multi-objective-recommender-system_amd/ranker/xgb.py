@@ -1,6 +1,7 @@
 """The XGBoost ranker family on the device (SPEC-XGB): the ``rank:pairwise`` objective, depth-wise
-trees, the boosting loop and an XGBoost JSON model writer / parser; thin Python over ``include/otto_xgb.h`` and the pieces
-of ``ranker.gbdt`` it shares (bins, quantisation, row bag, feature sample, ``add_tree``, AP).
+trees, :func:`train` (the family's side of the boosting loop of ``ranker.boost``) and an XGBoost JSON model writer / parser;
+thin Python over ``include/otto_xgb.h`` and the pieces of ``ranker.gbdt`` it shares (bins, quantisation, row bag, feature
+sample, ``add_tree``, AP).
 
 What this replaces in the reference: ``xgb.train`` on the (session, candidate) matrix, one model per event type and fold
 (``src/ranker/xgb_trainer.py:134-165``), whose out-of-fold scores are the ``gunes_xgboost_*`` columns of the final blend
@@ -141,28 +142,17 @@ def pairwise_gradients(score, label, query_off, seed, it, out=None):
     ``query_off`` int64 [Q+1], on the device; ``seed``: the objective seed (``derived_seeds(xgb_seed)[0]``), ``it``: the
     0-based iteration. Raises ``OttoError`` for a query longer than ``MAX_QUERY``, a malformed ``query_off`` or a label
     outside 0..31: the rows of a refused query are zero in ``out`` = (grad, hess), if the caller passed these tensors."""
-    import torch
-    gbdt._check_queries(score, label, query_off)
-    dev = score.device
-    table, lo, factor, _ = gbdt._tables(1.0, dev)
-    grad, hess = out if out is not None else (torch.empty_like(score), torch.empty_like(score))
-    _lib.need(grad, 'grad', torch.float64, 1, device=dev, numel=score.numel())
-    _lib.need(hess, 'hess', torch.float64, 1, device=dev, numel=score.numel())
-    _lib.call('otto_xgb_pairwise', dev, score, label, query_off, query_off.numel() - 1, score.numel(), table, lo, factor,
-              mix(seed, it), grad, hess)
-    return grad, hess
+    return lambdamart_gradients(score, label, query_off, seed, it, weighting=0, out=out)
 
 
 def lambdamart_gradients(score, label, query_off, seed, it, weighting=1, out=None):
-    """:func:`pairwise_gradients` through ``otto_xgb_lambdamart``: ``weighting = 0`` gives its bits, ``weighting = 1`` is
-    SPEC-OBJ's ``rank:ndcg`` (every pair weighted by the |delta NDCG| of swapping its rows)."""
-    import torch
+    """The pairwise objective of ``otto_xgb_lambdamart``, arguments as :func:`pairwise_gradients` takes them:
+    ``weighting = 0`` is ``rank:pairwise``, ``weighting = 1`` is SPEC-OBJ's ``rank:ndcg`` (every pair weighted by the
+    |delta NDCG| of swapping its rows)."""
     gbdt._check_queries(score, label, query_off)
     dev = score.device
     table, lo, factor, disc = gbdt._tables(1.0, dev)
-    grad, hess = out if out is not None else (torch.empty_like(score), torch.empty_like(score))
-    _lib.need(grad, 'grad', torch.float64, 1, device=dev, numel=score.numel())
-    _lib.need(hess, 'hess', torch.float64, 1, device=dev, numel=score.numel())
+    grad, hess = gbdt.gradient_outputs(score, out)
     _lib.call('otto_xgb_lambdamart', dev, score, label, query_off, query_off.numel() - 1, score.numel(), table, lo, factor,
               mix(seed, it), int(weighting), disc, grad, hess)
     return grad, hess
@@ -208,8 +198,8 @@ def grow_tree(bins, gh, exp, mapper, p, work=None, bag=None, features=None):
     out = _lib.XgbTree(**{k: v.ctypes.data_as(C.c_void_p) for k, v in a.items()})
     # mapper.edges is a host buffer: the thresholds come from it
     _lib.call('otto_xgb_grow_tree', dev, bins, n, F, gh, exp, n_edges, mapper.edges, depth, float(p['min_child_weight']),
-              float(p['lambda']), float(p['gamma']), float(p['eta']), bag, 0 if bag is None else bag.numel(), feats,
-              0 if feats is None else feats.numel(), C.byref(out), work, work.numel())
+              float(p['lambda']), float(p['gamma']), float(p['eta']), bag, gbdt._numel(bag), feats, gbdt._numel(feats),
+              C.byref(out), work, work.numel())
     k = out.n_leaves
     tree = {name: (v[:k] if name.startswith('leaf_') else v[:k - 1]) for name, v in a.items()}
     tree['default_left'] = ((tree['decision_type'] & 2) >> 1).astype(np.int32)
@@ -237,8 +227,8 @@ def level_histograms(bins, gh, rows, nodes, n_slots, features=None, hist=None):
         hist = torch.zeros((int(n_slots), 3, F, 256), dtype=torch.int64, device=dev)
     _lib.need(hist, 'hist', torch.int64, 4, device=dev, numel=int(n_slots) * 3 * F * 256)
     work = _lib.workspace(workspace_bytes(rows.numel(), 1, 1), dev)
-    _lib.call('otto_xgb_level_hist', dev, bins, n, F, gh, rows, rows.numel(), nodes, nodes.shape[0], feats,
-              0 if feats is None else feats.numel(), hist, int(n_slots), work, work.numel())
+    _lib.call('otto_xgb_level_hist', dev, bins, n, F, gh, rows, rows.numel(), nodes, nodes.shape[0], feats, gbdt._numel(feats),
+              hist, int(n_slots), work, work.numel())
     return hist
 
 
@@ -255,7 +245,7 @@ def level_splits(hist, mapper, exp, nodes, min_child_weight=1.0, lam=1.0, gamma=
     out = torch.empty((nodes.shape[0], gbdt.SPLIT_WORDS), dtype=torch.int64, device=dev)
     work = _lib.workspace(workspace_bytes(0, 1, 1), dev)
     _lib.call('otto_xgb_level_split', dev, hist, int(hist.shape[0]), F, n_edges, exp, nodes, nodes.shape[0], float(min_child_weight),
-              float(lam), float(gamma), feats, 0 if feats is None else feats.numel(), out, work, work.numel())
+              float(lam), float(gamma), feats, gbdt._numel(feats), out, work, work.numel())
     return out.cpu().numpy()
 
 
@@ -278,21 +268,16 @@ def level_partition(bins, rows, nodes):
 def mean_average_precision(ap, minus=False):
     """SPEC-XGB's ``map`` from per-query AP (``gbdt.ap_at_k`` at k = MAX_QUERY): a query without a positive (-1) counts
     1.0, with ``minus`` (``map-``) 0.0; ``np.sum(ap) / Q`` in float64 on the host (nan without a query)."""
-    ap = ap.detach().cpu().numpy() if hasattr(ap, 'detach') else np.asarray(ap, dtype=np.float64)
-    ap = np.where(ap < 0, 0.0 if minus else 1.0, ap)
-    return float(np.sum(ap) / ap.size) if ap.size else float('nan')
+    from . import objectives
+    return objectives.query_mean(ap, minus)
 
 
 def feature_importance(trees, n_features):
     """(gain float64 [F], weight int64 [F], cover float64 [F]) over an :class:`XgbTree` list as ``Booster.get_score``
     defines them: the mean ``split_gain`` per split of the feature, the number of splits, the mean ``cover`` per split. A
     feature that was never used gets 0 (XGBoost leaves it out; ``xgb_trainer.py:175-180`` adds into zeros)."""
-    F = int(n_features)
-    gain, cover, weight = np.zeros(F, np.float64), np.zeros(F, np.float64), np.zeros(F, np.int64)
-    for t in trees:
-        np.add.at(gain, t.split_feature, t.split_gain)
-        np.add.at(cover, t.split_feature, t.cover)
-        np.add.at(weight, t.split_feature, 1)
+    gain, cover = gbdt.split_sums(trees, n_features, 'split_gain'), gbdt.split_sums(trees, n_features, 'cover')
+    weight = gbdt.split_sums(trees, n_features)
     used = weight > 0
     gain[used] /= weight[used]
     cover[used] /= weight[used]
@@ -333,72 +318,33 @@ def train(bins, label, query_off, mapper, params=None, valid=None, num_boost_rou
     are ``xgb.train``'s. The score of iteration ``it`` is ``base_score + margin``, ``margin`` the leaf values of the trees
     so far added in tree order from 0.0: the float64 operations of :func:`predict`. ``valid``: its ``map`` / ``map-`` is
     recorded after every tree; early stopping on a strict improvement, cut at the best iteration. Boosting stops at a tree
-    whose root has no admissible split. Raises ``OttoError`` if not a single tree could be grown."""
-    import torch
-    from . import objectives
+    whose root has no admissible split. Raises ``OttoError`` if not a single tree could be grown.
+
+    The loop itself is ``boost.boost``, shared with ``gbdt.train``: this function resolves the parameters, hands over its
+    gradients, :func:`grow_tree` and ``objectives.evaluate``, and wraps the result."""
+    from . import boost, objectives
     p, sampling = resolve_params(params, extended=True)
-    F, n = gbdt.check_bins(bins)
-    dev = bins.device
-    if mapper.n_features != F:
-        raise ValueError(f'the mapper has {mapper.n_features} features, bins has {F}')
     objective = p['objective']
     base = _base_margin(p['base_score'], objective)
     metric, metric_k, minus = p['metric']
-    higher = objectives.HIGHER_IS_BETTER[metric]
-    margin = torch.zeros(n, dtype=torch.float64, device=dev)
-    gbdt._check_queries(margin, label, query_off)
-    if valid is not None:
-        vbins, vlabel, voff = valid
-        if gbdt.check_bins(vbins)[0] != F:
-            raise ValueError('the validation bins have another feature count')
-        vmargin = torch.zeros(vbins.shape[1], dtype=torch.float64, device=dev)
-        gbdt._check_queries(vmargin, vlabel, voff)
-    elif early_stopping_rounds:
-        raise ValueError('early_stopping_rounds needs a validation set')
-    work = torch.empty(workspace_bytes(n, F, p['max_depth']), dtype=torch.uint8, device=dev)
-    m = gbdt.bag_size(sampling.bagging_fraction, n) if sampling.bag_active else n
-    trees, history = [], []
-    best_metric, best_iter = None, 0
-    for it in range(int(num_boost_round)):
+
+    def gradients(margin, it):
         if objective == 'binary:logistic':
-            grad, hess = objectives.binary_gradients(margin + base, label, 1.0, p['scale_pos_weight'], 1.0, 1e-16)
-        elif objective == 'rank:ndcg':
-            grad, hess = lambdamart_gradients(margin + base, label, query_off, p['objective_seed'], it, 1)
-        else:
-            grad, hess = pairwise_gradients(margin + base, label, query_off, p['objective_seed'], it)
-        gh, exp = gbdt.quantize_gradients(grad, hess)
-        bag = gbdt.bag_rows(n, m, mix(sampling.bagging_seed, 2 * it), dev) if sampling.bag_active else None
-        features = gbdt.sample_features(F, sampling.feature_fraction, sampling.feature_fraction_seed, it) \
-            if sampling.features_active else None
-        tree = grow_tree(bins, gh, exp, mapper, p, work, bag=bag, features=features)
-        if tree.n_leaves < 2:
-            break
-        trees.append(tree)
-        gbdt.add_tree(bins, tree, margin)
-        if valid is not None:
-            gbdt.add_tree(vbins, tree, vmargin)
-            if metric == 'map':
-                value = mean_average_precision(gbdt.ap_at_k(vmargin + base, vlabel, voff, metric_k), minus)
-            else:
-                value = objectives.evaluate(metric, vmargin + base, vlabel, voff, k=metric_k, minus=minus)
-            history.append(value)
-            if best_metric is None or (value > best_metric if higher else value < best_metric):
-                best_metric, best_iter = value, it + 1
-            if early_stopping_rounds and it + 1 - best_iter >= int(early_stopping_rounds):
-                break
-    if not trees:
-        raise _lib.OttoError('no tree could be grown: no split of the root is admissible (min_child_weight, gamma) or every '
-                             'label of a query is the same')
-    if valid is None or not early_stopping_rounds:
-        best_iter = len(trees)
-    elif best_iter < len(trees):
-        margin.zero_()
-        for tree in trees[:best_iter]:
-            gbdt.add_tree(bins, tree, margin)
-    trees = trees[:best_iter]
-    forest = gbdt.forest_from_trees(trees, F, feature_names)
+            return objectives.binary_gradients(margin + base, label, 1.0, p['scale_pos_weight'], 1.0, 1e-16)
+        return lambdamart_gradients(margin + base, label, query_off, p['objective_seed'], it, int(objective == 'rank:ndcg'))
+
+    b = boost.boost(
+        bins, label, query_off, mapper, gradients=gradients, start=lambda: 0.0,
+        grow=lambda gh, exp, bag, features, work: grow_tree(bins, gh, exp, mapper, p, work, bag=bag, features=features),
+        work_bytes=lambda n, F: workspace_bytes(n, F, p['max_depth']),
+        metric=lambda vmargin: objectives.evaluate(metric, vmargin + base, valid[1], valid[2], k=metric_k, minus=minus),
+        higher_is_better=objectives.HIGHER_IS_BETTER[metric], sampling=sampling, valid=valid,
+        num_boost_round=num_boost_round, early_stopping_rounds=early_stopping_rounds,
+        no_tree='no tree could be grown: no split of the root is admissible (min_child_weight, gamma) or every label of a '
+                'query is the same')
+    forest = gbdt.forest_from_trees(b.trees, int(bins.shape[0]), feature_names)
     forest.objective = objective
-    return TrainResult(p['base_score'], forest, best_iter, history, margin + base, trees, None, objective=objective)
+    return TrainResult(p['base_score'], forest, b.best_iteration, b.history, b.score + base, b.trees, None, objective=objective)
 
 
 def predict(model, X, output_margin=False):

@@ -1374,9 +1374,9 @@ def _gbdt_ap(dev, d):
     return gbdt.ap_at_k(d['score'], d['label'], d['off'], k=20)
 
 
-GBDT = Case('gbdt', ('otto_gbdt_bin', 'otto_gbdt_lambdarank', 'otto_gbdt_quantize', 'otto_gbdt_hist', 'otto_gbdt_hist_features',
-                     'otto_gbdt_best_split', 'otto_gbdt_best_split_features', 'otto_gbdt_partition', 'otto_gbdt_grow_tree',
-                     'otto_gbdt_grow_tree_sampled', 'otto_gbdt_bag', 'otto_gbdt_add_tree', 'otto_gbdt_ap_at_k'), _gbdt_make, _gbdt_run,
+GBDT = Case('gbdt', ('otto_gbdt_bin', 'otto_gbdt_lambdarank', 'otto_gbdt_quantize', 'otto_gbdt_hist', 'otto_gbdt_best_split',
+                     'otto_gbdt_partition', 'otto_gbdt_grow_tree', 'otto_gbdt_bag', 'otto_gbdt_add_tree', 'otto_gbdt_ap_at_k'),
+            _gbdt_make, _gbdt_run,
             _gbdt_restate, refusals={
                 'row id outside the rows': (_edit('rows', lambda r, i: r.__setitem__(len(r) - 1, len(i['label']))), _gbdt_hist, 'row id'),
                 'grow_tree: bag row outside the rows': (_edit('rows', lambda r, i: r.__setitem__(len(r) - 1, len(i['label']))),
@@ -1494,7 +1494,7 @@ def _xgb_grow(dev, d):
     return xgb.grow_tree(d['bins'], d['q'], d['exp'], family._mapper(_XGB_EDGES), _xgb_params(), bag=d['bag'])
 
 
-XGB = Case('xgb', ('otto_xgb_pairwise', 'otto_xgb_lambdamart', 'otto_xgb_grow_tree', 'otto_xgb_level_hist', 'otto_xgb_level_split',
+XGB = Case('xgb', ('otto_xgb_lambdamart', 'otto_xgb_grow_tree', 'otto_xgb_level_hist', 'otto_xgb_level_split',
                    'otto_xgb_level_partition'), _xgb_make, _xgb_run, _xgb_restate,
            refusals={
     'label 32': (_edit('label', lambda l, i: l.__setitem__(45, 32)), _xgb_pairwise, 'label'),

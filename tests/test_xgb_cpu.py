@@ -305,5 +305,8 @@ def test_input_shapes():
     assert w['best_iteration'] < w['n_grown'] and len(w['history']) == w['n_grown']
     w = xi.train_want('sampled')
     assert all(b.size == int(0.8 * xi.train_problem()['label'].size) for b in w['bags']) and all(f.size == 9 for f in w['features'])
+    w = xi.train_want('sampled_stop')                                       # sampling and the early-stopping cut together
+    assert w['best_iteration'] < w['n_grown'] < 10
+    assert all(b.size == int(0.7 * xi.train_problem()['label'].size) for b in w['bags']) and all(f.size == 6 for f in w['features'])
     d = xi.train_problem()
     assert not d['vlabel'][d['voff'][3]:d['voff'][4]].any()

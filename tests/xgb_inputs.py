@@ -183,6 +183,8 @@ TRAIN_CASES = {
     'sampled': dict(params={'subsample': 0.8, 'colsample_bytree': 0.75, 'max_depth': 4, 'seed': 3}, rounds=5, early=None),
     'plain': dict(params={'max_depth': 4, 'eval_metric': 'map-'}, rounds=5, early=None),
     'early_stopping': dict(params={'max_depth': 3, 'eta': 1.0, 'min_child_weight': 0.1}, rounds=8, early=2),
+    'sampled_stop': dict(params={'max_depth': 3, 'eta': 1.0, 'min_child_weight': 0.1, 'subsample': 0.7, 'colsample_bytree': 0.5,
+                                 'seed': 5}, rounds=10, early=2),
 }
 
 

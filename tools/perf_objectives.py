@@ -4,11 +4,11 @@ profiles/objectives/perf_objectives.json.
 2^24 rows in queries of 50. Timed, alternated inside every repeat so that all see the same power state: ``otto_obj_binary``
 against ``otto_gbdt_quantize`` (the streaming kernel whose HBM rate it should sit near; both rates over their algorithmic
 bytes per row: 12 in and 16 out; 16 for the maxima, then 16 in and 8 out), ``otto_obj_ndcg_at_k`` against ``otto_gbdt_ap_at_k``, ``otto_xgb_lambdamart`` with the NDCG
-weights against ``otto_xgb_pairwise`` and ``otto_gbdt_lambdarank``, ``otto_obj_auc`` against the 64-bit radix sort of as many
+weights against the same call without them (``weighting = 0``, ``rank:pairwise``) and ``otto_gbdt_lambdarank``, ``otto_obj_auc`` against the 64-bit radix sort of as many
 keys (``otto_events_sort`` stands in: a pair sort plus one scan), ``otto_obj_logloss`` and ``otto_obj_label_counts``. Device
 events, 1 warm-up and 5 repeats, median (min - max).
 
-``--only-pairwise`` times ``otto_xgb_pairwise`` alone after the set-up and prints one JSON line; ``--root DIR`` imports the
+``--only-pairwise`` times ``xgb.pairwise_gradients`` alone after the set-up and prints one JSON line; ``--root DIR`` imports the
 package from another checkout of this repository (built there). Alternating the two in one job is how the pairwise kernel
 is compared with the commit before the NDCG template parameter, since kernel times move by several per cent with the chip's
 power state.

@@ -78,7 +78,7 @@ out = dict(
     objective_ms=spread(objective),
     depthwise=dict(max_depth=a.max_depth, tree_ms=spread(depthwise), leaves=int(tx.n_leaves), hist_rows=int(tx.hist_rows),
                    stream_synchronisations=int(tx.n_syncs)),
-    # otto_gbdt_grow_tree_sampled: one synchronisation for the root, one per split that searches its children (every split but
+    # otto_gbdt_grow_tree: one synchronisation for the root, one per split that searches its children (every split but
     # the one that fills num_leaves), one for the error words
     leafwise=dict(num_leaves=L, min_data_in_leaf=0, tree_ms=spread(leafwise), leaves=int(tl.n_leaves), hist_rows=int(tl.hist_rows),
                   stream_synchronisations=1 + max(tl.n_leaves - 1 - (1 if tl.n_leaves == L else 0), 0) + 1),
