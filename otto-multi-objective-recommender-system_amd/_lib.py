@@ -103,6 +103,23 @@ class XgbTree(C.Structure):
         ('n_leaves', C.c_int32), ('n_syncs', C.c_int32), ('hist_rows', C.c_int64)]
 
 
+class PqwColumn(C.Structure):
+    # mirrors otto_pqw_column (include/otto_pqwrite.h)
+    _fields_ = [('d_data', C.c_void_p), ('n_rows', C.c_int64), ('elem_bytes', C.c_int32), ('kind', C.c_int32),
+                ('encoding', C.c_int32), ('reserved', C.c_int32)]
+
+
+class PqwPage(C.Structure):
+    # mirrors otto_pqw_page (include/otto_pqwrite.h); parquet_write.PAGE_DTYPE is its NumPy image
+    _fields_ = [('first_row', C.c_int64), ('n_values', C.c_int32), ('column', C.c_int32)]
+
+
+class PqwJob(C.Structure):
+    # mirrors otto_pqw_job (include/otto_pqwrite.h)
+    _fields_ = [('columns', C.POINTER(PqwColumn)), ('n_columns', C.c_int64), ('pages', C.POINTER(PqwPage)), ('n_pages', C.c_int64),
+                ('d_work', C.c_void_p), ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
+
+
 _vp, _i64, _i32, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_uint32
 _p_i64 = C.POINTER(C.c_int64)
 
@@ -283,6 +300,10 @@ SIGNATURES = {
     'otto_deflate_workspace': (_i64, [_i64, _i32]),
     'otto_deflate_plan': (_i32, [_vp, _i64, _i32, _p_i64, _vp, _i64, _vp]),
     'otto_deflate_emit': (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
+    # include/otto_pqwrite.h
+    'otto_pqw_workspace': (_i64, [C.POINTER(PqwJob)]),
+    'otto_pqw_plan': (_i32, [C.POINTER(PqwJob), _vp]),
+    'otto_pqw_emit': (_i32, [C.POINTER(PqwJob), _vp, _vp, _i64]),
 }
 
 _lib = None

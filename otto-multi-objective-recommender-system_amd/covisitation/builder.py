@@ -6,6 +6,10 @@ Usage (same convention as every reference script, ``src/covisitation/inference.p
     python builder.py validation --device-parquet
                                       decode the split files on the device (``events.parquet_to_events_device``) instead
                                       of reading them with pyarrow; the part files written are the same
+    python builder.py <mode> --device-write
+                                      encode the part files on the device (``parquet_write.encode_tables``: aid_x and aid_y
+                                      as DELTA_BINARY_PACKED pages, wgt PLAIN, no compressor) instead of copying the rows
+                                      to the host for pyarrow; same names, part counts, rows and dtypes
 
 Reads the event frames the reference reads (validation: ``DATA/splits/{train,val}.parquet``;
 submission: ``DATA/{train,test}.pkl`` -- ``src/ranker/aid_feature_engineering.py:21-36``), builds the
@@ -60,10 +64,22 @@ def load_events(mode):
     raise ValueError('Invalid mode')
 
 
+def part_bounds(n_parts, n_aids):
+    """The first aid of parts 1 .. n_parts - 1 (equal aid spans)."""
+    return np.linspace(0, n_aids, n_parts + 1).round().astype(np.int64)[1:-1]
+
+
 def split_parts(aid_x, n_parts, n_aids):
     """Row ranges of ``n_parts`` disjoint aid_x ranges (equal aid spans)."""
-    bounds = np.searchsorted(aid_x, np.linspace(0, n_aids, n_parts + 1).round().astype(np.int64)[1:-1])
+    bounds = np.searchsorted(aid_x, part_bounds(n_parts, n_aids))
     return np.r_[0, bounds, len(aid_x)]
+
+
+def split_parts_device(aid_x, n_parts, n_aids):
+    """:func:`split_parts` of a device column: the search runs there, the n_parts + 1 cut points come back."""
+    import torch
+    bounds = torch.searchsorted(aid_x, torch.from_numpy(part_bounds(n_parts, n_aids)).to(aid_x.device, aid_x.dtype))
+    return np.r_[0, bounds.cpu().numpy(), len(aid_x)]
 
 
 def part_jobs(directory, prefix, kind, rows, n_parts, n_aids):
@@ -97,11 +113,23 @@ def write_parts(directory, prefix, kind, rows, n_parts, n_aids):
     write_jobs(part_jobs(directory, prefix, kind, rows, n_parts, n_aids))
 
 
+def write_device_parts(directory, prefix, kind, rows, n_parts, n_aids):
+    """The parts of :func:`part_jobs` from device rows ``(aid_x, aid_y, wgt)`` (``engine.topk_to_device_rows``): one encode
+    on the device for all parts of the row set, one ``write`` per file."""
+    from .. import parquet_write
+    aid_x, aid_y, wgt = rows
+    parquet_write.write_tables([directory / f'{prefix}_{kind}_{i}.pqt' for i in range(n_parts)],
+                               {'aid_x': aid_x, 'aid_y': aid_y, 'wgt': wgt}, split_parts_device(aid_x, n_parts, n_aids),
+                               {'aid_x': 'delta', 'aid_y': 'delta'})
+
+
 def build_matrices(ev, kinds=REFERENCE_KINDS, ks=(15, 20), device='cuda:0', window=30, max_gap=86400,
-                   chunk_sessions=2_000_000):
-    """Events -> {k: {kind: (aid_x, aid_y, W)}} rows in (aid_x, rank) order, via the HIP engine."""
+                   chunk_sessions=2_000_000, device_rows=False):
+    """Events -> {k: {kind: (aid_x, aid_y, W)}} rows in (aid_x, rank) order, via the HIP engine. ``device_rows``: the rows
+    stay on the device as ``(aid_x, aid_y, wgt)`` (``engine.topk_to_device_rows``), for :func:`write_device_parts`."""
     import torch
-    from .engine import CovisBuilder, topk_to_rows
+    from .engine import CovisBuilder, topk_to_rows, topk_to_device_rows
+    to_rows = topk_to_device_rows if device_rows else topk_to_rows
     dev = torch.device(device)
     b = CovisBuilder(ev.n_aids, kinds=kinds, window=window, max_gap=max_gap,
                      ts_min=int(ev.ts.min()) if ev.n_events else 0, ts_max=int(ev.ts.max()) if ev.n_events else 0, device=dev)
@@ -124,18 +152,21 @@ def build_matrices(ev, kinds=REFERENCE_KINDS, ks=(15, 20), device='cuda:0', wind
         res[k] = {}
         for kind in kinds:
             y, w, n = out[kind]
-            res[k][kind] = topk_to_rows(y[:, :k].contiguous(), w[:, :k].contiguous(), torch.clamp(n, max=k))
+            res[k][kind] = to_rows(y[:, :k].contiguous(), w[:, :k].contiguous(), torch.clamp(n, max=k))
     logging.info(f'covisitation stats: {b.stats()}  kernel ms: {b.timings()}')
     return res
 
 
-def all_part_jobs(directory, mode, res, n_aids):
-    jobs = []
+def part_sets(mode, res):
+    """(prefix, kind, rows, number of parts) of the 14 row sets of one mode, in the order they are written."""
     for kind in REFERENCE_KINDS:
         co = kind == 'cart_order'
-        jobs += part_jobs(directory, 'top_15', kind, res[15][kind], TOP15_CART_ORDER_PARTS[mode] if co else TOP15_PARTS[mode], n_aids)
-        jobs += part_jobs(directory, 'top', kind, res[20][kind], TOP_CART_ORDER_PARTS if co else TOP_PARTS, n_aids)
-    return jobs
+        yield 'top_15', kind, res[15][kind], TOP15_CART_ORDER_PARTS[mode] if co else TOP15_PARTS[mode]
+        yield 'top', kind, res[20][kind], TOP_CART_ORDER_PARTS if co else TOP_PARTS
+
+
+def all_part_jobs(directory, mode, res, n_aids):
+    return [job for prefix, kind, rows, n_parts in part_sets(mode, res) for job in part_jobs(directory, prefix, kind, rows, n_parts, n_aids)]
 
 
 def main(argv=None):
@@ -143,6 +174,8 @@ def main(argv=None):
     parser.add_argument('mode', type=str)
     parser.add_argument('--device-parquet', action='store_true',
                         help='validation: decode DATA/splits/{train,val}.parquet on the device, not with pyarrow')
+    parser.add_argument('--device-write', action='store_true',
+                        help='encode the part files on the device (delta pages for aid_x and aid_y), not with pyarrow')
     args = parser.parse_args(argv)
     if args.mode not in ('validation', 'submission'):
         raise ValueError('Invalid mode')
@@ -155,8 +188,12 @@ def main(argv=None):
     else:
         ev = frame_to_events_device(load_events(args.mode))      # H2D once, then type map / sort / CSR in HIP kernels
     logging.info(f'Building covisitation matrices in {args.mode} mode: {ev.n_sessions} sessions, {ev.n_events} events')
-    res = build_matrices(ev)
-    write_jobs(all_part_jobs(directory, args.mode, res, ev.n_aids))
+    res = build_matrices(ev, device_rows=args.device_write)
+    if args.device_write:
+        for prefix, kind, rows, n_parts in part_sets(args.mode, res):
+            write_device_parts(directory, prefix, kind, rows, n_parts, ev.n_aids)
+    else:
+        write_jobs(all_part_jobs(directory, args.mode, res, ev.n_aids))
     logging.info(f'Saved covisitation parquet parts to {directory}')
 
 

@@ -206,3 +206,15 @@ def topk_to_rows(y, w, n):
         a = t.cpu().numpy()
         return a.view(dt) if a.dtype.itemsize == np.dtype(dt).itemsize else a.astype(dt)
     return host(aid_x, np.uint32), host(y[valid], np.uint32), host(w[valid], np.uint64)
+
+
+def topk_to_device_rows(y, w, n):
+    """The selection of :func:`topk_to_rows` with the three columns left on the device, as the part files store them:
+    ``aid_x int32, aid_y int32, wgt float32``. ``wgt`` is bit-equal to the host chain ``(W.astype(float64) / Q16)
+    .astype(float32)``: a division by a power of two, and both conversions round to nearest."""
+    import torch
+    from .spec import Q16
+    k = y.shape[1]
+    valid = torch.arange(k, device=y.device)[None, :] < n[:, None]
+    aid_x = torch.arange(y.shape[0], device=y.device, dtype=torch.int32)[:, None].expand(-1, k)[valid]
+    return aid_x, y[valid].to(torch.int32), (w[valid].double() / Q16).float()
