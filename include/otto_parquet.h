@@ -15,13 +15,32 @@
  * levels are RLE with a 4-byte length prefix); DATA_PAGE_V2 (the levels are outside the compressed body, their lengths come
  * from the header, is_compressed is honoured); INDEX_PAGE is skipped. Value encodings: PLAIN; RLE_DICTIONARY /
  * PLAIN_DICTIONARY (one bit-width byte, then RLE / bit-packed hybrid runs, widths 0 to 32, width 0 means every index is 0).
- * A column chunk may mix dictionary-coded and PLAIN data pages. Page CRCs are not checked.
+ * DELTA_BINARY_PACKED on data pages of INT32 / INT64 columns ("Delta pages" below). A column chunk may mix delta,
+ * dictionary-coded and PLAIN data pages. Page CRCs are not checked.
+ *
+ * Float columns. The host side reads FLOAT and DOUBLE columns when asked to (floats=True): encodings PLAIN and dictionary,
+ * the column record's element size equals the physical size, no zero extension, so every value is a bit copy. A delta-coded
+ * page of such a column is refused on the host by name.
+ *
+ * Delta pages. Behind the levels the body holds ULEB128 B (values per block), ULEB128 M (miniblocks per block), ULEB128 n
+ * (values) and the zigzag ULEB128 first value. Accepted: B a multiple of 128 with 128 <= B <= 65536, M >= 1, B % M == 0,
+ * B / M a multiple of 32 (pyarrow writes 128, 4 for INT32 and 256, 4 for INT64; the project's writer 128, 4 for both). n must
+ * equal the page's non-null value count; n == 0 is a page of its header alone, n == 1 ends behind the first value. The
+ * n - 1 deltas come in blocks of B: a zigzag ULEB128 min_delta, M width bytes, then the miniblocks, each B / M fields of its
+ * width packed LSB-first. A width above 8 x the physical size is refused. The last miniblock that holds a delta is stored
+ * whole; miniblocks behind it have no bytes and their width bytes are ignored whatever they hold. A varint of more than 10
+ * bytes, or one whose tenth byte carries bits above 2^64, is refused. Arithmetic: v[i] = v[i-1] + min_delta + field, modulo
+ * 2^(8 x physical size); then the widening and the cast of "Output dtype" apply. Extent: the stream must end exactly at the
+ * body's end; running past it and a single trailing byte are each refused with a reason of their own. No byte outside the
+ * body is read -- a field is fetched through the bytes that hold its bits and no others -- and nothing outside the page's rows
+ * of its column is written.
  *
  * Refused, each with an error that names the file, the column, the row group and, where it applies, the page ordinal and a
  * reason: an encrypted footer ("PARE"); any other physical type, codec or encoding (named in the message); a repeated or
  * nested requested column; a null (V2: num_nulls != 0, refused on the host; V1: the device counts the definition levels
  * equal to 1 and the count must equal num_values); a dictionary index >= the dictionary's size; a page whose decoded size
- * differs from its header; any Snappy violation; a row group whose requested columns disagree on num_rows.
+ * differs from its header; any Snappy violation; any violation of "Delta pages"; a row group whose requested columns disagree
+ * on num_rows.
  *
  * Snappy. The preamble varint must equal the size the page header declares. Every element is checked BEFORE any of its
  * bytes is touched: the tag and its length / offset bytes and a literal's bytes against the compressed extent; the bytes
@@ -56,7 +75,8 @@ enum {
     OTTO_PQ_COMP_SIZE,             /* compressed_page_size */
     OTTO_PQ_UNCOMP_SIZE,           /* uncompressed_page_size */
     OTTO_PQ_PAGE_TYPE,             /* 0 DATA_PAGE, 2 DICTIONARY_PAGE, 3 DATA_PAGE_V2 */
-    OTTO_PQ_ENCODING,              /* 0 PLAIN, 8 RLE_DICTIONARY (the legacy 2 is taken as 8 on a data page, as 0 on a dictionary page) */
+    OTTO_PQ_ENCODING,              /* 0 PLAIN, 5 DELTA_BINARY_PACKED (data pages), 8 RLE_DICTIONARY (the legacy 2 is taken as 8 on a
+                                      data page, as 0 on a dictionary page) */
     OTTO_PQ_DEF_LEN,               /* V2: definition_levels_byte_length; V1: -1 = levels with a 4-byte prefix open the body, 0 = none */
     OTTO_PQ_REP_LEN,               /* V2: repetition_levels_byte_length; V1: 0 */
     OTTO_PQ_NUM_VALUES,
@@ -85,13 +105,17 @@ extern "C" {
 #endif
 
 /* bytes of scratch otto_parquet_decode needs for the page table: the decompressed bodies, the run checkpoints, the
- * device copies of the records. -22 (as a negative size) on a malformed table. */
+ * device copies of the records, and ceil((num_values - 1) / 128) block records per delta page (the host cannot see B: a
+ * body may be compressed). -22 (as a negative size) on a malformed table. */
 int64_t otto_parquet_workspace(const int64_t* h_pages, int64_t n_pages);
 
 /* Decode the pages of h_pages out of d_bytes[0 .. n_bytes), n_bytes in [0, 2^31), into the columns of h_cols
  * (n_cols records of OTTO_PQ_COL_FIELDS int64). Three kernels: k_pq_snappy, one wave per compressed page, into the
  * workspace; k_pq_runs, one lane per data page, validates the levels and the index runs and leaves one checkpoint per
- * OTTO_PQ_TILE values; k_pq_decode, one wave per tile, extracts, gathers and stores with the cast. Every record is checked
+ * OTTO_PQ_TILE values; k_pq_decode, one wave per tile, extracts, gathers and stores with the cast. Delta pages run four
+ * kernels of their own: k_pq_delta_walk, one lane per page, validates the header and every block header and leaves one
+ * record per block; k_pq_delta_sum, one wave per block, reduces the block's deltas; k_pq_delta_scan, one wave per page,
+ * scans the block sums; k_pq_delta_out, one wave per block, scans inside the block and stores. Every record is checked
  * on the host before anything is launched: no page reads outside d_bytes or writes outside its column's rows.
  * h_err[0] = the table index of the smallest violating page, -1 without one; h_err[1] = its reason (otto_last_error()
  * carries the text); the call then returns -22 and the outputs' contents are unspecified. phases: OTTO_PQ_PHASE_* or'ed,

@@ -120,6 +120,13 @@ class PqwJob(C.Structure):
                 ('d_work', C.c_void_p), ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
 
 
+class RowsJob(C.Structure):
+    # mirrors otto_rows_job (include/otto_rows.h)
+    _fields_ = [('d_aid_x', C.c_void_p), ('d_aid_y', C.c_void_p), ('d_wgt', C.c_void_p), ('n_rows', C.c_int64), ('d_y', C.c_void_p),
+                ('d_w', C.c_void_p), ('d_n', C.c_void_p), ('n_aids', C.c_int64), ('k', C.c_int32), ('reserved', C.c_int32),
+                ('d_work', C.c_void_p), ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
+
+
 _vp, _i64, _i32, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_uint32
 _p_i64 = C.POINTER(C.c_int64)
 
@@ -304,6 +311,9 @@ SIGNATURES = {
     'otto_pqw_workspace': (_i64, [C.POINTER(PqwJob)]),
     'otto_pqw_plan': (_i32, [C.POINTER(PqwJob), _vp]),
     'otto_pqw_emit': (_i32, [C.POINTER(PqwJob), _vp, _vp, _i64]),
+    # include/otto_rows.h
+    'otto_rows_workspace': (_i64, [C.POINTER(RowsJob)]),
+    'otto_rows_topk': (_i32, [C.POINTER(RowsJob), _vp]),
 }
 
 _lib = None

@@ -17,9 +17,23 @@
 //                the cast. PLAIN pages are a straight casting copy in the same kernel. The dictionary is read through
 //                the cache: a tile gathers 1024 entries, staging a dictionary of up to 1 MiB in LDS per tile would
 //                read more than it saves.
+//
+// DELTA_BINARY_PACKED pages take no tile of k_pq_decode and are skipped by k_pq_runs; they run four kernels of their own, so
+// that nothing but the block headers of a page is walked serially:
+//   k_pq_delta_walk  one lane per delta page: the levels, the header, every block header and miniblock extent
+//                    (pq_delta_walk); one (width bytes, min_delta) record per block.
+//   k_pq_delta_sum   one wave per block: unpacks the fields 64 at a time and reduces min_delta + field over the block's
+//                    values, modulo 2^64.
+//   k_pq_delta_scan  one wave per delta page: exclusive scan of the block sums, 64 blocks at a time, plus the first value
+//                    -> the value in front of every block; stores the page's first value.
+//   k_pq_delta_out   one wave per block: unpacks again, a wave inclusive scan plus the block's base, stored with the cast.
+// The host cannot see a page's block size (the body may be compressed): the block records of a page are sized for blocks of
+// 128, the smallest accepted, and the last two kernels start one wave per such slot; waves past the page's real block
+// count leave at once.
 #include <vector>
 
 #include "common.h"
+#include "wave.h"
 #include "parquet_decode.h"
 #include "../../include/otto_parquet.h"
 
@@ -37,7 +51,16 @@ struct PqStream {                                           // one Snappy stream
 struct PqPage {
     int64_t body, body_len;                                 // the decoded body: offset in the workspace bodies (in_work) or in d_bytes
     int64_t num_values, out_row, tile0, mark0;              // first tile / first checkpoint of the page
-    int32_t in_work, type, plain, levels, col, dict;
+    int32_t in_work, type, plain, levels, col, dict;        // plain: 1 PLAIN, 0 dictionary indices, 2 DELTA_BINARY_PACKED
+};
+
+struct PqDelta {                                            // one delta page: its slots among the block records
+    int64_t page, blk0;
+};
+
+struct PqBlock {
+    int64_t widths, min_delta;                              // byte of the block's width bytes inside the body
+    uint64_t base;                                          // k_pq_delta_sum: the block's sum; k_pq_delta_scan: the value in front of it
 };
 
 struct PqCol {
@@ -54,13 +77,16 @@ struct PqWs {
     int64_t* vstart;              // [n_pages]  where the values start in the body, -1: the page is not decoded
     int64_t* marks;               // [2 * tiles]
     uint8_t* bodies;              // the decompressed bodies, each 16-byte aligned
+    PqDelta* dpages;              // [n_delta]
+    pq_delta_head* dheads;        // [n_delta]  written by k_pq_delta_walk
+    PqBlock* blocks;              // [block slots]
 };
 
 constexpr int PQ_MAX_COLS = 64;
 
 static inline size_t pq_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-static size_t pq_layout(int64_t n_pages, int64_t tiles, int64_t body_bytes, char* base, PqWs* w) {
+static size_t pq_layout(int64_t n_pages, int64_t tiles, int64_t body_bytes, int64_t n_delta, int64_t slots, char* base, PqWs* w) {
     size_t o = 0;
     auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += pq_align(bytes); return p; };
     PqWs t;
@@ -72,6 +98,9 @@ static size_t pq_layout(int64_t n_pages, int64_t tiles, int64_t body_bytes, char
     t.vstart = (int64_t*)take((size_t)n_pages * 8);
     t.marks = (int64_t*)take((size_t)tiles * 16);
     t.bodies = (uint8_t*)take((size_t)body_bytes);
+    t.dpages = (PqDelta*)take((size_t)n_delta * sizeof(PqDelta));       // nothing without delta pages
+    t.dheads = (pq_delta_head*)take((size_t)n_delta * sizeof(pq_delta_head));
+    t.blocks = (PqBlock*)take((size_t)slots * sizeof(PqBlock));
     if (w) *w = t;
     return o;
 }
@@ -153,6 +182,7 @@ __global__ __launch_bounds__(WAVE) void k_pq_runs(const uint8_t* __restrict__ by
     const int64_t p = (int64_t)blockIdx.x * WAVE + threadIdx.x;
     if (p >= n_pages) return;
     const PqPage pg = pages[p];
+    if (pg.plain == 2) return;                               // k_pq_delta_walk's page
     int64_t start = -1;
     int st = sstat[p];
     if (st == PQ_OK) {
@@ -174,6 +204,145 @@ __global__ __launch_bounds__(WAVE) void k_pq_runs(const uint8_t* __restrict__ by
         if (st != PQ_OK) start = -1;
     }
     vstart[p] = start;
+}
+
+// ---- delta pages ----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(WAVE) void k_pq_delta_walk(const uint8_t* __restrict__ bytes, const uint8_t* __restrict__ bodies,
+                                                        const PqPage* __restrict__ pages, const PqCol* __restrict__ cols,
+                                                        const PqDelta* __restrict__ dpages, int64_t n_delta,
+                                                        const int32_t* __restrict__ sstat, int64_t* __restrict__ vstart,
+                                                        pq_delta_head* __restrict__ heads, PqBlock* __restrict__ blocks,
+                                                        unsigned long long* err) {
+    const int64_t d = (int64_t)blockIdx.x * WAVE + threadIdx.x;
+    if (d >= n_delta) return;
+    const int64_t p = dpages[d].page;
+    const PqPage pg = pages[p];
+    int64_t start = -1;
+    pq_delta_head h = {};
+    if (sstat[p] == PQ_OK) {
+        const uint8_t* b = pq_body(pg, bytes, bodies);
+        int st = pq_v1_values_start(b, pg.body_len, pg.levels != 0, pg.num_values, &start);
+        if (st == PQ_OK) {                                   // a PqBlock opens with the two int64 of pq_delta_walk's record
+            st = pq_delta_walk(b, start, pg.body_len, pg.num_values, cols[pg.col].phys, &h, (int64_t*)(blocks + dpages[d].blk0),
+                               (int)(sizeof(PqBlock) / 8));
+        }
+        if (st != PQ_OK) {
+            atomicMin(err, (unsigned long long)p << 8 | (unsigned long long)st);
+            start = -1;
+        }
+    }
+    vstart[p] = start;
+    heads[d] = h;
+}
+
+// The delta page that owns block slot `slot` (the last one whose first slot is <= slot; a page without slots is never the
+// last such one, since the page behind it starts at the same slot) -> its index among the delta pages
+__device__ __forceinline__ int64_t pq_delta_of_slot(const PqDelta* __restrict__ dpages, int64_t n_delta, int64_t slot) {
+    int64_t lo = 0, hi = n_delta - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (dpages[mid].blk0 <= slot) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// The 64 values i0 + lane of one block, i0 a multiple of 64: min_delta + field where the value exists (i < in_block), else 0.
+// cur: the cursor at value i0, moved to i0 + 64. Wave-uniform but for the lane's own half.
+__device__ __forceinline__ uint64_t pq_delta_chunk(const uint8_t* b, const PqBlock& k, int mv, int64_t i0, int64_t in_block,
+                                                   pq_delta_cursor* cur) {
+    const int lane = (int)lane_id();
+    const pq_delta_cursor lo = *cur;
+    pq_delta_advance(b, k.widths, mv, cur);
+    const pq_delta_cursor hi = *cur;
+    pq_delta_advance(b, k.widths, mv, cur);
+    const pq_delta_cursor c = lane < 32 ? lo : hi;
+    if (i0 + lane >= in_block) return 0;
+    return (uint64_t)k.min_delta + pq_delta_field(b, c.off, c.k + (lane & 31), b[k.widths + c.j]);
+}
+
+// what the three block kernels share: the slot's page and block, or false when the slot is not a block of a clean page
+struct PqDeltaBlock {
+    PqPage pg;
+    pq_delta_head h;
+    const uint8_t* b;
+    int64_t blk, in_block;
+    PqBlock* rec;
+};
+__device__ __forceinline__ bool pq_delta_block(const uint8_t* bytes, const uint8_t* bodies, const PqPage* pages, const PqDelta* dpages,
+                                               int64_t n_delta, const int64_t* vstart, const pq_delta_head* heads, PqBlock* blocks,
+                                               int64_t slot, PqDeltaBlock* o) {
+    const int64_t d = pq_delta_of_slot(dpages, n_delta, slot);
+    const PqDelta dp = dpages[d];
+    if (vstart[dp.page] < 0) return false;
+    o->h = heads[d];
+    o->blk = slot - dp.blk0;
+    if (o->blk >= o->h.n_blocks) return false;
+    o->pg = pages[dp.page];
+    o->b = pq_body(o->pg, bytes, bodies);
+    const int64_t left = o->h.n - 1 - o->blk * o->h.B;
+    o->in_block = left < o->h.B ? left : o->h.B;
+    o->rec = blocks + slot;
+    return true;
+}
+
+__global__ __launch_bounds__(PQ_THREADS) void k_pq_delta_sum(const uint8_t* __restrict__ bytes, const uint8_t* __restrict__ bodies,
+                                                             const PqPage* __restrict__ pages, const PqDelta* __restrict__ dpages,
+                                                             int64_t n_delta, int64_t n_slots, const int64_t* __restrict__ vstart,
+                                                             const pq_delta_head* __restrict__ heads, PqBlock* __restrict__ blocks) {
+    const int64_t slot = (int64_t)blockIdx.x * PQ_WAVES + (threadIdx.x >> 6);
+    if (slot >= n_slots) return;                             // wave-uniform
+    PqDeltaBlock o;
+    if (!pq_delta_block(bytes, bodies, pages, dpages, n_delta, vstart, heads, blocks, slot, &o)) return;
+    const PqBlock k = *o.rec;
+    pq_delta_cursor cur = {k.widths + o.h.M, 0, 0};
+    uint64_t sum = 0;
+    for (int64_t i0 = 0; i0 < o.in_block; i0 += WAVE) sum += pq_delta_chunk(o.b, k, o.h.mv, i0, o.in_block, &cur);
+    sum = wave_reduce<Sum>(sum);
+    if (lane_id() == 0) o.rec->base = sum;
+}
+
+__global__ __launch_bounds__(WAVE) void k_pq_delta_scan(const PqPage* __restrict__ pages, const PqCol* __restrict__ cols,
+                                                        const PqDelta* __restrict__ dpages, const int64_t* __restrict__ vstart,
+                                                        const pq_delta_head* __restrict__ heads, PqBlock* __restrict__ blocks) {
+    const int64_t d = blockIdx.x;
+    const PqDelta dp = dpages[d];
+    if (vstart[dp.page] < 0) return;
+    const pq_delta_head h = heads[d];
+    if (h.n == 0) return;
+    const int lane = (int)lane_id();
+    const PqPage pg = pages[dp.page];
+    const PqCol col = cols[pg.col];
+    if (lane == 0) pq_store(col.out, pg.out_row, col.elem, pq_widen((uint64_t)h.first, col.phys, col.zext != 0));
+    uint64_t carry = (uint64_t)h.first;
+    for (int64_t b0 = 0; b0 < h.n_blocks; b0 += WAVE) {
+        const int64_t b = b0 + lane;
+        const uint64_t v = b < h.n_blocks ? blocks[dp.blk0 + b].base : 0;
+        const uint64_t incl = wave_incl_scan<uint64_t>(v);
+        if (b < h.n_blocks) blocks[dp.blk0 + b].base = carry + incl - v;
+        carry += __shfl(incl, 63, 64);
+    }
+}
+
+__global__ __launch_bounds__(PQ_THREADS) void k_pq_delta_out(const uint8_t* __restrict__ bytes, const uint8_t* __restrict__ bodies,
+                                                             const PqPage* __restrict__ pages, const PqCol* __restrict__ cols,
+                                                             const PqDelta* __restrict__ dpages, int64_t n_delta, int64_t n_slots,
+                                                             const int64_t* __restrict__ vstart, const pq_delta_head* __restrict__ heads,
+                                                             PqBlock* __restrict__ blocks) {
+    const int64_t slot = (int64_t)blockIdx.x * PQ_WAVES + (threadIdx.x >> 6);
+    if (slot >= n_slots) return;                             // wave-uniform
+    PqDeltaBlock o;
+    if (!pq_delta_block(bytes, bodies, pages, dpages, n_delta, vstart, heads, blocks, slot, &o)) return;
+    const PqBlock k = *o.rec;
+    const PqCol col = cols[o.pg.col];
+    const int lane = (int)lane_id();
+    const int64_t row0 = o.pg.out_row + 1 + o.blk * o.h.B;   // value 0 of the page is k_pq_delta_scan's
+    pq_delta_cursor cur = {k.widths + o.h.M, 0, 0};
+    uint64_t carry = k.base;
+    for (int64_t i0 = 0; i0 < o.in_block; i0 += WAVE) {
+        const uint64_t incl = wave_incl_scan<uint64_t>(pq_delta_chunk(o.b, k, o.h.mv, i0, o.in_block, &cur));
+        if (i0 + lane < o.in_block) pq_store(col.out, row0 + i0 + lane, col.elem, pq_widen(carry + incl, col.phys, col.zext != 0));
+        carry += __shfl(incl, 63, 64);
+    }
 }
 
 __device__ __forceinline__ uint64_t pq_value(const uint8_t* p, int64_t i, int phys) {
@@ -241,7 +410,8 @@ __global__ __launch_bounds__(PQ_THREADS) void k_pq_decode(const uint8_t* __restr
 struct PqPlan {
     std::vector<PqPage> pages;
     std::vector<PqStream> streams;
-    int64_t tiles = 0, body_bytes = 0;
+    std::vector<PqDelta> deltas;
+    int64_t tiles = 0, body_bytes = 0, slots = 0;           // slots: block records, one per 128 deltas of every delta page
 };
 
 static int pq_plan(const int64_t* h_pages, int64_t n_pages, int64_t n_bytes, const int64_t* h_cols, int32_t n_cols, PqPlan* plan) {
@@ -256,7 +426,8 @@ static int pq_plan(const int64_t* h_pages, int64_t n_pages, int64_t n_bytes, con
         const int64_t col = r[OTTO_PQ_COL_SLOT], dict = r[OTTO_PQ_DICT_SLOT];
         int64_t lev = 0;
         OTTO_REQUIRE(type == 0 || type == 2 || type == 3, "otto_parquet: page %lld: page type %lld", (long long)p, (long long)type);
-        OTTO_REQUIRE(enc == 0 || enc == 2 || enc == 8, "otto_parquet: page %lld: encoding %lld", (long long)p, (long long)enc);
+        OTTO_REQUIRE(enc == 0 || enc == 2 || enc == 8 || (enc == 5 && type != 2), "otto_parquet: page %lld: encoding %lld", (long long)p,
+                     (long long)enc);
         OTTO_REQUIRE(src >= 0 && comp >= 0 && uncomp >= 0 && comp < (1ll << 31) && uncomp < (1ll << 31) && nv >= 0 && nv < (1ll << 31),
                      "otto_parquet: page %lld: negative or oversized extent", (long long)p);
         OTTO_REQUIRE(n_bytes < 0 || src + comp <= n_bytes, "otto_parquet: page %lld: body outside the %lld bytes", (long long)p,
@@ -275,7 +446,7 @@ static int pq_plan(const int64_t* h_pages, int64_t n_pages, int64_t n_bytes, con
         g.num_values = nv;
         g.out_row = r[OTTO_PQ_OUT_ROW];
         g.type = (int32_t)type;
-        g.plain = type == 2 || enc == 0;
+        g.plain = type == 2 || enc == 0 ? 1 : enc == 5 ? 2 : 0;
         g.levels = type == 0 && r[OTTO_PQ_DEF_LEN] == -1;
         g.col = (int32_t)col;
         g.dict = -1;
@@ -303,7 +474,7 @@ static int pq_plan(const int64_t* h_pages, int64_t n_pages, int64_t n_bytes, con
                              (long long)nv, (long long)g.body_len);
             }
         } else {
-            if (!g.plain) {
+            if (g.plain == 0) {
                 OTTO_REQUIRE(dict >= 0 && dict < p && plan->pages[(size_t)dict].type == 2 && plan->pages[(size_t)dict].col == g.col,
                              "otto_parquet: page %lld: dictionary slot %lld", (long long)p, (long long)dict);
                 g.dict = (int32_t)dict;
@@ -313,7 +484,12 @@ static int pq_plan(const int64_t* h_pages, int64_t n_pages, int64_t n_bytes, con
                              "otto_parquet: page %lld: rows %lld + %lld outside the column's %lld", (long long)p, (long long)g.out_row,
                              (long long)nv, (long long)h_cols[col * OTTO_PQ_COL_FIELDS + OTTO_PQ_COL_ROWS]);
             }
-            plan->tiles += (nv + PQ_TILE - 1) / PQ_TILE;
+            if (g.plain == 2) {                               // no tile of k_pq_decode: the delta kernels' page
+                plan->deltas.push_back(PqDelta{p, plan->slots});
+                plan->slots += (nv > 1 ? nv - 1 + 127 : 0) / 128;
+            } else {
+                plan->tiles += (nv + PQ_TILE - 1) / PQ_TILE;
+            }
         }
     }
     return 0;
@@ -328,7 +504,7 @@ extern "C" const char* otto_parquet_reason(int32_t code) { return pq_reason(code
 extern "C" int64_t otto_parquet_workspace(const int64_t* h_pages, int64_t n_pages) {
     PqPlan plan;
     if (pq_plan(h_pages, n_pages, -1, nullptr, -1, &plan) != 0) return -22;
-    return (int64_t)pq_layout(n_pages, plan.tiles, plan.body_bytes, nullptr, nullptr);
+    return (int64_t)pq_layout(n_pages, plan.tiles, plan.body_bytes, (int64_t)plan.deltas.size(), plan.slots, nullptr, nullptr);
 }
 
 extern "C" int otto_parquet_decode(const uint8_t* d_bytes, int64_t n_bytes, const int64_t* h_pages, int64_t n_pages, const int64_t* h_cols,
@@ -355,13 +531,15 @@ extern "C" int otto_parquet_decode(const uint8_t* d_bytes, int64_t n_bytes, cons
     OTTO_REQUIRE(d_bytes && d_work, "otto_parquet_decode: null argument");
     OTTO_REQUIRE(((uintptr_t)d_bytes & 15) == 0 && ((uintptr_t)d_work & 255) == 0, "otto_parquet_decode: d_bytes must be 16-byte, d_work 256-byte aligned");
     PqWs w;
-    const int64_t need = (int64_t)pq_layout(n_pages, plan.tiles, plan.body_bytes, (char*)d_work, &w);
+    const int64_t n_delta = (int64_t)plan.deltas.size();
+    const int64_t need = (int64_t)pq_layout(n_pages, plan.tiles, plan.body_bytes, n_delta, plan.slots, (char*)d_work, &w);
     OTTO_REQUIRE(work_bytes >= need, "otto_parquet_decode: workspace too small (%lld < %lld)", (long long)work_bytes, (long long)need);
     hipStream_t s = (hipStream_t)stream;
     OTTO_HIP(hipMemsetAsync(w.err, 0xFF, 8, s));
     OTTO_HIP(hipMemcpyAsync(w.pages, plan.pages.data(), (size_t)n_pages * sizeof(PqPage), hipMemcpyHostToDevice, s));
     OTTO_HIP(hipMemcpyAsync(w.streams, plan.streams.data(), (size_t)n_pages * sizeof(PqStream), hipMemcpyHostToDevice, s));
     OTTO_HIP(hipMemcpyAsync(w.cols, hc, sizeof(hc), hipMemcpyHostToDevice, s));
+    if (n_delta > 0) OTTO_HIP(hipMemcpyAsync(w.dpages, plan.deltas.data(), (size_t)n_delta * sizeof(PqDelta), hipMemcpyHostToDevice, s));
     if (phases & OTTO_PQ_PHASE_SNAPPY) {
         k_pq_snappy<<<(unsigned)((n_pages + PQ_WAVES - 1) / PQ_WAVES), PQ_THREADS, 0, s>>>(d_bytes, w.streams, n_pages, w.bodies, w.sstat, w.err);
         OTTO_HIP(hipGetLastError());
@@ -374,6 +552,23 @@ extern "C" int otto_parquet_decode(const uint8_t* d_bytes, int64_t n_bytes, cons
             k_pq_decode<<<(unsigned)((plan.tiles + PQ_WAVES - 1) / PQ_WAVES), PQ_THREADS, 0, s>>>(d_bytes, w.bodies, w.pages, w.cols, n_pages,
                                                                                                 plan.tiles, w.vstart, w.marks, w.err);
             OTTO_HIP(hipGetLastError());
+        }
+        if (n_delta > 0) {
+            k_pq_delta_walk<<<(unsigned)((n_delta + WAVE - 1) / WAVE), WAVE, 0, s>>>(d_bytes, w.bodies, w.pages, w.cols, w.dpages, n_delta, w.sstat,
+                                                                                   w.vstart, w.dheads, w.blocks, w.err);
+            OTTO_HIP(hipGetLastError());
+            const unsigned grid = (unsigned)((plan.slots + PQ_WAVES - 1) / PQ_WAVES);
+            if (grid > 0) {
+                k_pq_delta_sum<<<grid, PQ_THREADS, 0, s>>>(d_bytes, w.bodies, w.pages, w.dpages, n_delta, plan.slots, w.vstart, w.dheads, w.blocks);
+                OTTO_HIP(hipGetLastError());
+            }
+            k_pq_delta_scan<<<(unsigned)n_delta, WAVE, 0, s>>>(w.pages, w.cols, w.dpages, w.vstart, w.dheads, w.blocks);
+            OTTO_HIP(hipGetLastError());
+            if (grid > 0) {
+                k_pq_delta_out<<<grid, PQ_THREADS, 0, s>>>(d_bytes, w.bodies, w.pages, w.cols, w.dpages, n_delta, plan.slots, w.vstart, w.dheads,
+                                                           w.blocks);
+                OTTO_HIP(hipGetLastError());
+            }
         }
     }
     unsigned long long herr = 0;

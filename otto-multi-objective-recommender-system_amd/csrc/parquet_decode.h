@@ -14,7 +14,8 @@
 #endif
 
 enum { PQ_OK = 0, PQ_E_SNAPPY_TRUNC, PQ_E_SNAPPY_OFFSET, PQ_E_SNAPPY_OVERRUN, PQ_E_SNAPPY_PREAMBLE, PQ_E_SNAPPY_SHORT,
-       PQ_E_LEVELS, PQ_E_NULL, PQ_E_WIDTH, PQ_E_RUNS, PQ_E_INDEX, PQ_E_SIZE, PQ_N_REASONS };
+       PQ_E_LEVELS, PQ_E_NULL, PQ_E_WIDTH, PQ_E_RUNS, PQ_E_INDEX, PQ_E_SIZE, PQ_E_DELTA_VARINT, PQ_E_DELTA_SHAPE, PQ_E_DELTA_COUNT,
+       PQ_E_DELTA_WIDTH, PQ_E_DELTA_TRUNC, PQ_E_DELTA_TRAILING, PQ_N_REASONS };
 
 static inline const char* pq_reason(int r) {
     static const char* const names[PQ_N_REASONS] = {
@@ -22,7 +23,10 @@ static inline const char* pq_reason(int r) {
         "snappy: output runs past the declared uncompressed size", "snappy: preamble disagrees with the declared uncompressed size",
         "snappy: stream ends before the declared uncompressed size", "definition levels run past the page",
         "a null (definition level 0)", "dictionary index width above 32 bits", "index runs cut short, empty or short of num_values",
-        "dictionary index not below the dictionary's size", "decoded size differs from the page header"};
+        "dictionary index not below the dictionary's size", "decoded size differs from the page header",
+        "delta: a varint of more than 10 bytes or 64 bits", "delta: block shape (values per block, miniblocks per block) is not accepted",
+        "delta: the header's value count differs from the page's", "delta: miniblock width above the physical type's bits",
+        "delta: the stream runs past the page body", "delta: bytes behind the last miniblock"};
     return r >= 0 && r < PQ_N_REASONS ? names[r] : "?";
 }
 
@@ -231,4 +235,105 @@ OTTO_PQ_HD void pq_store(void* out, int64_t row, int elem, int64_t v) {
     else if (elem == 2) ((uint16_t*)out)[row] = (uint16_t)v;
     else if (elem == 4) ((uint32_t*)out)[row] = (uint32_t)v;
     else ((uint64_t*)out)[row] = (uint64_t)v;
+}
+
+// ---- DELTA_BINARY_PACKED (SPEC-PARQUET, "Delta pages") ----------------------------------------------------------------------
+
+// ULEB128 of at most 64 bits at p[*pos .. end): PQ_E_DELTA_TRUNC when it is cut short, PQ_E_DELTA_VARINT when it is longer
+// than 10 bytes or its tenth byte carries bits above 2^64
+OTTO_PQ_HD int pq_varint64(const uint8_t* p, int64_t* pos, int64_t end, uint64_t* out) {
+    uint64_t v = 0;
+    int64_t i = *pos;
+    for (int shift = 0; shift < 70; shift += 7) {
+        if (i >= end) return PQ_E_DELTA_TRUNC;
+        const uint64_t b = p[i++];
+        if (shift == 63 && (b & 0xFEu)) return PQ_E_DELTA_VARINT;
+        v |= (b & 0x7Fu) << shift;
+        if (!(b & 0x80u)) {
+            *pos = i;
+            *out = v;
+            return PQ_OK;
+        }
+    }
+    return PQ_E_DELTA_VARINT;
+}
+OTTO_PQ_HD int64_t pq_unzigzag(uint64_t u) { return (int64_t)((u >> 1) ^ (0 - (u & 1))); }
+
+// The header of a delta page: values per block, miniblocks per block, values per miniblock, the value count, the first value
+struct pq_delta_head {
+    int32_t B, M, mv, pad;
+    int64_t n, first, n_blocks;
+};
+
+// Walks a delta stream at p[pos .. end) once: the header, then every block header (min_delta, the M width bytes) and the
+// extent of every miniblock the page's values need, each checked against `end` before it is used. Block b's record opens at
+// blk[stride * b]: the byte of its width bytes, then its min_delta; at most ceil((num_values - 1) / 128) records are
+// written, which covers every accepted block shape. phys: 4 or 8, the bytes of the physical type.
+OTTO_PQ_HD int pq_delta_walk(const uint8_t* p, int64_t pos, int64_t end, int64_t num_values, int phys, pq_delta_head* h, int64_t* blk,
+                             int stride) {
+    uint64_t B = 0, M = 0, n = 0, first = 0;
+    int st = pq_varint64(p, &pos, end, &B);
+    if (st == PQ_OK) st = pq_varint64(p, &pos, end, &M);
+    if (st == PQ_OK) st = pq_varint64(p, &pos, end, &n);
+    if (st == PQ_OK) st = pq_varint64(p, &pos, end, &first);
+    if (st != PQ_OK) return st;
+    if (B < 128 || B > 65536 || B % 128 || M < 1 || B % M || (B / M) % 32) return PQ_E_DELTA_SHAPE;
+    if (n != (uint64_t)num_values) return PQ_E_DELTA_COUNT;
+    const int64_t mv = (int64_t)(B / M), nd = num_values > 0 ? num_values - 1 : 0;
+    h->B = (int32_t)B;
+    h->M = (int32_t)M;
+    h->mv = (int32_t)mv;
+    h->pad = 0;
+    h->n = num_values;
+    h->first = pq_unzigzag(first);
+    h->n_blocks = (nd + (int64_t)B - 1) / (int64_t)B;
+    for (int64_t b = 0; b < h->n_blocks; ++b) {
+        uint64_t md = 0;
+        st = pq_varint64(p, &pos, end, &md);
+        if (st != PQ_OK) return st;
+        if (pos + (int64_t)M > end) return PQ_E_DELTA_TRUNC;
+        blk[stride * b] = pos;
+        blk[stride * b + 1] = pq_unzigzag(md);
+        const int64_t left = nd - b * (int64_t)B, in_block = left < (int64_t)B ? left : (int64_t)B;
+        const int64_t need = (in_block + mv - 1) / mv;      // miniblocks behind these have no bytes, their width bytes are not looked at
+        const int64_t widths = pos;
+        pos += (int64_t)M;
+        for (int64_t j = 0; j < need; ++j) {
+            const int64_t w = p[widths + j];
+            if (w > 8 * phys) return PQ_E_DELTA_WIDTH;
+            if (pos + mv / 8 * w > end) return PQ_E_DELTA_TRUNC;
+            pos += mv / 8 * w;
+        }
+    }
+    return pos == end ? PQ_OK : PQ_E_DELTA_TRAILING;
+}
+
+// field `k` of a miniblock whose bytes start at p[data], width in 0..64. Reads the bytes that hold the field's bits and no
+// other: they lie inside the miniblock, which pq_delta_walk has checked against the body's end.
+OTTO_PQ_HD uint64_t pq_delta_field(const uint8_t* p, int64_t data, int64_t k, int width) {
+    if (width == 0) return 0;
+    const int64_t bit = k * width;
+    const int64_t b0 = data + (bit >> 3);
+    const int sh = (int)(bit & 7);
+    const int nb = (sh + width + 7) >> 3;                    // 1 .. 9 bytes
+    uint64_t v = 0;
+    for (int i = 0; i < nb && i < 8; ++i) v |= (uint64_t)p[b0 + i] << (8 * i);
+    v >>= sh;
+    if (nb == 9) v |= (uint64_t)p[b0 + 8] << (64 - sh);      // sh >= 1 here
+    return width == 64 ? v : v & ((1ull << width) - 1);
+}
+
+// Where the 32 values that start at value `u32 * 32` of a block lie: a cursor that moves through the block's miniblocks
+// 32 values at a time (a miniblock holds a multiple of 32). j: the miniblock, off: its first byte, k: values of it behind.
+struct pq_delta_cursor {
+    int64_t off;
+    int32_t j, k;
+};
+OTTO_PQ_HD void pq_delta_advance(const uint8_t* p, int64_t widths, int mv, pq_delta_cursor* c) {
+    c->k += 32;
+    if (c->k == mv) {
+        c->off += (int64_t)(mv / 8) * p[widths + c->j];
+        c->j += 1;
+        c->k = 0;
+    }
 }

@@ -1,6 +1,7 @@
 """Device-side Parquet decode: the split files ``DATA/splits/*.parquet`` and the
 part files of the reference's chunk writers -> device columns, unpacked by HIP kernels (``include/otto_parquet.h``,
-SPEC-PARQUET): a Snappy decompressor, an RLE / bit-packed hybrid decoder and a dictionary gather.
+SPEC-PARQUET): a Snappy decompressor, an RLE / bit-packed hybrid decoder, a dictionary gather and a DELTA_BINARY_PACKED
+decoder. With ``floats=True`` FLOAT / DOUBLE columns (the ``wgt`` column of the covisitation part files) come back as bit copies.
 
 Reference code replaced: the pyarrow / pandas host decode in front of every consumer of the split files
 (``src/ranker/aid_feature_engineering.py:21-36``). The host side here is pure Python + NumPy and imports no pyarrow: a
@@ -190,16 +191,29 @@ def _name(table, k):
     return table[k] if isinstance(table, tuple) and 0 <= k < len(table) else table.get(k, f'#{k}') if isinstance(table, dict) else f'#{k}'
 
 
-def check_column(meta, name):
-    """The leaf ``name`` of the file, or the ``OttoError`` SPEC-PARQUET names for a column that cannot be read."""
+FLOAT, DOUBLE = 4, 5           # PHYSICAL
+
+
+def check_column(meta, name, floats=False):
+    """The leaf ``name`` of the file, or the ``OttoError`` SPEC-PARQUET names for a column that cannot be read.
+    ``floats``: FLOAT / DOUBLE columns are accepted too."""
     leaf = next((l for l in meta.leaves if l.name == name), None)
     if leaf is None:
         raise _error(f'{meta.path}: column {name!r}: not in the file (top-level columns: {[l.name for l in meta.leaves]})')
     if leaf.nested or leaf.repetition == REPEATED:
         raise _error(f'{meta.path}: column {name!r}: a repeated or nested column is not supported')
-    if leaf.physical not in (1, 2):
+    if leaf.physical not in (1, 2) and not (floats and leaf.physical in (FLOAT, DOUBLE)):
         raise _error(f'{meta.path}: column {name!r}: physical type {_name(PHYSICAL, leaf.physical)} is not supported (INT32, INT64)')
     return leaf
+
+
+def _data_encoding(enc, leaf, where, k):
+    """The OTTO_PQ_ENCODING of a data page: 0 PLAIN, 5 DELTA_BINARY_PACKED (integer columns), 8 dictionary indices."""
+    if enc == 5 and leaf.physical in (FLOAT, DOUBLE):
+        raise _error(f'{where}, page {k}: encoding DELTA_BINARY_PACKED is not supported for a {_name(PHYSICAL, leaf.physical)} column')
+    if enc not in (0, 2, 5, 8):
+        raise _error(f'{where}, page {k}: encoding {_name(ENCODINGS, enc)} is not supported')
+    return 5 if enc == 5 else 8 if enc else 0
 
 
 def walk_pages(buf, chunk, leaf, where):
@@ -225,22 +239,18 @@ def walk_pages(buf, chunk, leaf, where):
             pages.append(Page(pos, body, comp, uncomp, ptype, 0, 0, 0, d.get(1, 0), int(snappy)))
         elif ptype == DATA_PAGE:
             d = h.get(5, {})
-            enc = d.get(2, 0)
-            if enc not in (0, 2, 8):
-                raise _error(f'{where}, page {k}: encoding {_name(ENCODINGS, enc)} is not supported')
+            enc = _data_encoding(d.get(2, 0), leaf, where, k)
             if leaf.repetition == OPTIONAL and d.get(3, 3) != 3:
                 raise _error(f'{where}, page {k}: definition level encoding {_name(ENCODINGS, d.get(3))} is not supported')
-            pages.append(Page(pos, body, comp, uncomp, ptype, 8 if enc else 0, -1 if leaf.repetition == OPTIONAL else 0, 0, d.get(1, 0),
+            pages.append(Page(pos, body, comp, uncomp, ptype, enc, -1 if leaf.repetition == OPTIONAL else 0, 0, d.get(1, 0),
                               int(snappy)))
             seen += d.get(1, 0)
         elif ptype == DATA_PAGE_V2:
             d = h.get(8, {})
-            enc = d.get(4, 0)
-            if enc not in (0, 2, 8):
-                raise _error(f'{where}, page {k}: encoding {_name(ENCODINGS, enc)} is not supported')
+            enc = _data_encoding(d.get(4, 0), leaf, where, k)
             if d.get(2, 0) != 0:
                 raise _error(f'{where}, page {k}: {d.get(2)} null(s): nulls are not supported')
-            pages.append(Page(pos, body, comp, uncomp, ptype, 8 if enc else 0, d.get(5, 0), d.get(6, 0), d.get(1, 0),
+            pages.append(Page(pos, body, comp, uncomp, ptype, enc, d.get(5, 0), d.get(6, 0), d.get(1, 0),
                               int(snappy and d.get(7, True))))
             seen += d.get(1, 0)
         elif ptype != INDEX_PAGE:
@@ -272,11 +282,11 @@ def check_row_group(meta, g, columns):
     return out
 
 
-def page_table(path, columns):
+def page_table(path, columns, floats=False):
     """Host only: ``(metadata, {(row group, column): [Page]})`` of one file -- what :func:`read_columns` walks batch by batch,
     with every refusal the host can make (tests, tools)."""
     meta = read_metadata(path)
-    leaves = [check_column(meta, c) for c in columns]
+    leaves = [check_column(meta, c, floats) for c in columns]
     out = {}
     with open(meta.path, 'rb') as f:
         for g in range(len(meta.row_groups)):
@@ -291,6 +301,8 @@ def default_dtype(leaf):
     16 / 32 / 64 as the signed type of the same width; a TIMESTAMP as its int64 ticks."""
     import torch
     lg = leaf.logical
+    if leaf.physical in (FLOAT, DOUBLE):
+        return torch.float32 if leaf.physical == FLOAT else torch.float64
     if lg and lg[0] == 'INT':
         bits, signed = lg[1], lg[2]
         if bits == 8:
@@ -333,10 +345,12 @@ def _read_full(f, view):
     return got
 
 
-def read_columns(paths, columns, device, dtypes=None, batch_bytes=256 << 20, out=None):
+def read_columns(paths, columns, device, dtypes=None, batch_bytes=256 << 20, out=None, floats=False):
     """The columns ``columns`` of the files ``paths`` (one path or a list) -> a tuple of device tensors, the rows in file and
     row-group order. ``dtypes``: ``{name: torch.dtype}`` for columns that should not get :func:`default_dtype`; the cast
     (two's-complement truncation or sign extension, as ``numpy.astype``) happens in the decode kernel's store.
+    ``floats=True``: FLOAT columns come back as ``torch.float32``, DOUBLE as ``torch.float64``, bit for bit, and no other
+    dtype may be asked of them; without it such a column is refused.
 
     Only the byte ranges of the requested column chunks are read, into two page-locked staging buffers that alternate;
     batch i + 1 is read, its page headers walked and its bytes copied on a side stream while batch i decodes (the event
@@ -357,13 +371,19 @@ def read_columns(paths, columns, device, dtypes=None, batch_bytes=256 << 20, out
     dtypes = dict(dtypes or {})
     sizes = {torch.uint8: 1, torch.int8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
     metas = [read_metadata(p) for p in paths]
-    leaves = [[check_column(m, c) for c in columns] for m in metas]
+    leaves = [[check_column(m, c, floats) for c in columns] for m in metas]
     col_dt = []
     for j, c in enumerate(columns):
         dt = dtypes.get(c) or (default_dtype(leaves[0][j]) if metas else torch.int64)
-        if dt not in sizes:
+        for lv in leaves:                                     # a float column is a bit copy: its own dtype or none
+            if lv[j].physical in (FLOAT, DOUBLE) and dt != default_dtype(lv[j]):
+                raise ValueError(f'dtypes[{c!r}]: {dt} for a {_name(PHYSICAL, lv[j].physical)} column; only {default_dtype(lv[j])} is possible')
+            if lv[j].physical not in (FLOAT, DOUBLE) and dt not in sizes:
+                raise ValueError(f'dtypes[{c!r}]: {dt} is not one of {sorted(map(str, sizes))}')
+        if dt not in sizes and not dt.is_floating_point:
             raise ValueError(f'dtypes[{c!r}]: {dt} is not one of {sorted(map(str, sizes))}')
         col_dt.append(dt)
+    sizes = {**sizes, torch.float32: 4, torch.float64: 8}
     # the batches: runs of whole row groups, over all files
     groups = []                                               # (file, row group, chunks, first row, compressed bytes, both)
     row = 0
@@ -419,7 +439,7 @@ def read_columns(paths, columns, device, dtypes=None, batch_bytes=256 << 20, out
                         if _read_full(f, memoryview(view)[o:o + c.length]) != c.length:
                             raise _lib.OttoError(f'{where}: the column chunk runs past the end of the file')
                         leaf = leaves[fi][j]
-                        key = (j, 4 if leaf.physical == 1 else 8, int(leaf.physical == 1 and leaf.logical == ('INT', 32, False)))
+                        key = (j, 4 if leaf.physical in (1, FLOAT) else 8, int(leaf.physical == 1 and leaf.logical == ('INT', 32, False)))
                         if key not in slots:
                             slots[key] = len(cols)
                             cols.append((result[j].data_ptr(), sizes[col_dt[j]], n_rows, key[1], key[2]))
