@@ -127,6 +127,21 @@ class RowsJob(C.Structure):
                 ('d_work', C.c_void_p), ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
 
 
+class PqlistJob(C.Structure):
+    # mirrors otto_pqlist_job (include/otto_pqlist.h)
+    _fields_ = [('d_bytes', C.c_void_p), ('n_bytes', C.c_int64), ('h_pages', C.c_void_p), ('n_pages', C.c_int64), ('d_off', C.c_void_p),
+                ('d_null', C.c_void_p), ('n_rows', C.c_int64), ('value_base', C.c_int64), ('h_page_out', C.c_void_p),
+                ('d_work', C.c_void_p), ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
+
+
+class LabelsJob(C.Structure):
+    # mirrors otto_labels_job (include/otto_labels.h)
+    _fields_ = [('d_session', C.c_void_p), ('d_type', C.c_void_p), ('d_off', C.c_void_p), ('d_value', C.c_void_p), ('d_null', C.c_void_p),
+                ('n_rows', C.c_int64), ('n_values', C.c_int64), ('d_label_session', C.c_void_p), ('n_sessions', C.c_int64),
+                ('n_aids', C.c_int64), ('d_out_off', C.c_void_p * 3), ('d_out_aid', C.c_void_p * 3), ('d_work', C.c_void_p),
+                ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
+
+
 _vp, _i64, _i32, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_uint32
 _p_i64 = C.POINTER(C.c_int64)
 
@@ -314,6 +329,14 @@ SIGNATURES = {
     # include/otto_rows.h
     'otto_rows_workspace': (_i64, [C.POINTER(RowsJob)]),
     'otto_rows_topk': (_i32, [C.POINTER(RowsJob), _vp]),
+    # include/otto_pqlist.h
+    'otto_pqlist_workspace': (_i64, [C.POINTER(PqlistJob)]),
+    'otto_pqlist_levels': (_i32, [C.POINTER(PqlistJob), _vp]),
+    'otto_pqlist_reason': (C.c_char_p, [_i32]),
+    # include/otto_labels.h
+    'otto_labels_workspace': (_i64, [C.POINTER(LabelsJob)]),
+    'otto_labels_count': (_i32, [C.POINTER(LabelsJob), _vp, _vp]),
+    'otto_labels_fill': (_i32, [C.POINTER(LabelsJob)]),
 }
 
 _lib = None

@@ -2,6 +2,9 @@
 part files of the reference's chunk writers -> device columns, unpacked by HIP kernels (``include/otto_parquet.h``,
 SPEC-PARQUET): a Snappy decompressor, an RLE / bit-packed hybrid decoder, a dictionary gather and a DELTA_BINARY_PACKED
 decoder. With ``floats=True`` FLOAT / DOUBLE columns (the ``wgt`` column of the covisitation part files) come back as bit copies.
+``DATA/splits/val_labels.parquet`` is read by :func:`read_lists` (a three-level LIST column -> offsets, values, null flags;
+``include/otto_pqlist.h``, SPEC-PQLIST) and :func:`read_string_codes` (a dictionary-coded string column -> the caller's codes);
+:func:`read_columns` keeps refusing nested and string columns.
 
 Reference code replaced: the pyarrow / pandas host decode in front of every consumer of the split files
 (``src/ranker/aid_feature_engineering.py:21-36``). The host side here is pure Python + NumPy and imports no pyarrow: a
@@ -133,10 +136,8 @@ def _logical(el):
     return None
 
 
-def read_metadata(path):
-    """The footer of a Parquet file -> :class:`Metadata`: the top-level schema leaves (nested groups marked), the row groups
-    and, per top-level primitive column, the chunk's byte range, codec, ``num_values`` and sizes. Raises ``OttoError`` on a
-    wrong magic, an encrypted or truncated footer."""
+def _footer(path):
+    """(path as str, the bytes of the Thrift footer); ``OttoError`` on a wrong magic, an encrypted or truncated footer"""
     path = os.fspath(path)
     size = os.path.getsize(path)
     with open(path, 'rb') as f:
@@ -154,6 +155,14 @@ def read_metadata(path):
             raise _error(f'{path}: truncated footer ({n} bytes declared, {size} in the file)')
         f.seek(size - 8 - n)
         foot = f.read(n)
+    return path, foot
+
+
+def read_metadata(path):
+    """The footer of a Parquet file -> :class:`Metadata`: the top-level schema leaves (nested groups marked), the row groups
+    and, per top-level primitive column, the chunk's byte range, codec, ``num_values`` and sizes. Raises ``OttoError`` on a
+    wrong magic, an encrypted or truncated footer."""
+    path, foot = _footer(path)
     try:
         md = _Thrift(foot).struct()
         schema = md[2]
@@ -311,8 +320,9 @@ def default_dtype(leaf):
     return torch.int32 if leaf.physical == 1 else torch.int64
 
 
-def _decode(dev, d_bytes, n_bytes, table, cols, infos, phases=3, work=None):
-    """One ``otto_parquet_decode`` call; a violation raises the ``OttoError`` that names file, column, row group and page."""
+def _decode(dev, d_bytes, n_bytes, table, cols, infos, phases=3, work=None, explain=None):
+    """One ``otto_parquet_decode`` call; a violation raises the ``OttoError`` that names file, column, row group and page.
+    ``explain(record, reason)``: the text behind the page instead of the bare reason (``read_lists``)."""
     import ctypes as C
     from . import _lib
     table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, len(FIELDS))
@@ -331,7 +341,7 @@ def _decode(dev, d_bytes, n_bytes, table, cols, infos, phases=3, work=None):
             raise
         where, k = infos[int(err[0])]
         reason = _lib.lib().otto_parquet_reason(int(err[1])).decode()
-        raise _lib.OttoError(f'{where}, page {k}: {reason}') from None
+        raise _lib.OttoError(f'{where}, page {k}: {explain(int(err[0]), reason) if explain else reason}') from None
     return work
 
 
@@ -518,3 +528,561 @@ def snappy_decompress(d_bytes, src_off, src_len, dst_len, out=None, dst_off=None
         _lib.call('otto_parquet_snappy', dev, d_bytes, int(d_bytes.numel()), src_off, src_len, dst_off, dst_len, n, out,
                   int(out.numel()), status, work, int(work.numel()))
     return out, status
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# list columns (include/otto_pqlist.h, SPEC-PQLIST) and dictionary-coded string columns: val_labels.parquet
+# ---------------------------------------------------------------------------------------------------------------------
+PL_FIELDS = ('body_off', 'body_len', 'page_type', 'rep_len', 'def_len', 'num_values', 'flags', 'chunk_rows', 'chunk_pages')   # OTTO_PL_*
+PL_OUTER_OPTIONAL, PL_ELEM_OPTIONAL, PL_CHUNK_FIRST = 1, 2, 4
+BYTE_ARRAY = 6
+MAX_STRING_DICTIONARY = 64 << 10
+
+ListLeaf = namedtuple('ListLeaf', 'name path physical logical outer_optional elem_optional')
+ListMetadata = namedtuple('ListMetadata', 'path num_rows leaf row_groups')       # row_groups: [(num_rows, Chunk or None)]
+
+
+def read_list_metadata(path, column):
+    """The footer of ``path`` for the list column ``column`` -> :class:`ListMetadata`. Accepted is the three-level LIST form
+    of SPEC-PQLIST under any field names; every other nested form raises the ``OttoError`` that names it."""
+    path, foot = _footer(path)
+    try:
+        md = _Thrift(foot).struct()
+        schema = md[2]
+
+        def skip(j):
+            kids = schema[j].get(5, 0) or 0
+            j += 1
+            for _ in range(kids):
+                j = skip(j)
+            return j
+        i, at, names = 1, None, []
+        for _ in range(schema[0].get(5, 0) or 0):
+            names.append(schema[i][4].decode())
+            if names[-1] == column and at is None:
+                at = i
+            i = skip(i)
+        pre = f'{path}: column {column!r}'
+        if at is None:
+            raise _error(f'{pre}: not in the file (top-level columns: {names})')
+        top = schema[at]
+        kids = top.get(5, 0) or 0
+        rep = top.get(3, REQUIRED)
+        is_map = top.get(6) in (1, 2) or 2 in (top.get(10) or {})
+        if not kids:
+            if rep == REPEATED:
+                raise _error(f'{pre}: a repeated primitive at top level (a list without its LIST group) is not supported')
+            raise _error(f'{pre}: not a list column (a flat {_name(PHYSICAL, top.get(1))} column)')
+        if rep == REPEATED:
+            raise _error(f'{pre}: a repeated group at top level is not supported')
+        if is_map:
+            raise _error(f'{pre}: a map is not supported')
+        mid = schema[at + 1]
+        if kids != 1 or mid.get(3, REQUIRED) != REPEATED:
+            raise _error(f'{pre}: a struct (a group of {kids} field(s) that is no LIST) is not supported')
+        mkids = mid.get(5, 0) or 0
+        if not mkids:
+            raise _error(f'{pre}: a two-level legacy list (a repeated primitive inside the group) is not supported')
+        if mkids != 1:
+            raise _error(f'{pre}: a repeated group of {mkids} fields (a map or a two-level list of structs) is not supported')
+        el = schema[at + 2]
+        if el.get(5, 0):
+            inner = schema[at + 3]
+            form = 'a list of lists' if inner.get(3, REQUIRED) == REPEATED or (inner.get(5, 0) and el.get(5, 0) == 1) else 'a list of structs'
+            raise _error(f'{pre}: {form} is not supported')
+        if el.get(3, REQUIRED) == REPEATED:
+            raise _error(f'{pre}: a repeated element inside the list group (a list of lists in legacy form) is not supported')
+        if el.get(1) not in (1, 2):
+            raise _error(f'{pre}: list element type {_name(PHYSICAL, el.get(1))} is not supported (INT32, INT64)')
+        pathn = [top[4].decode(), mid[4].decode(), el[4].decode()]
+        leaf = ListLeaf(column, tuple(pathn), el[1], _logical(el), rep == OPTIONAL, el.get(3, REQUIRED) == OPTIONAL)
+        groups = []
+        for rg in md.get(4, []):
+            chunk = None
+            for cc in rg[1]:
+                cm = cc[3]
+                if [p.decode() for p in cm[3]] == pathn:
+                    dpo, dico = cm[9], cm.get(11)
+                    start = dico if dico is not None and 0 < dico < dpo else dpo
+                    chunk = Chunk(column, cm[1], cm[4], cm[5], start, cm[7], dpo, dico, cm[6], tuple(cm[2]))
+            groups.append((rg[3], chunk))
+        return ListMetadata(path, md[3], leaf, groups)
+    except (ValueError, KeyError, IndexError) as e:
+        raise _error(f'{path}: malformed footer ({e})') from None
+
+
+def _list_chunk(meta, g):
+    n_rows, c = meta.row_groups[g]
+    where = _where(meta, meta.leaf.name, g)
+    if c is None:
+        raise _error(f'{where}: no column chunk')
+    if c.codec not in (0, 1):
+        raise _error(f'{where}: codec {_name(CODECS, c.codec)} is not supported (UNCOMPRESSED, SNAPPY)')
+    if c.physical != meta.leaf.physical:
+        raise _error(f'{where}: the chunk holds {_name(PHYSICAL, c.physical)}, the schema declares {_name(PHYSICAL, meta.leaf.physical)}')
+    return n_rows, c, where
+
+
+def walk_list_pages(buf, chunk, leaf, where):
+    """:func:`walk_pages` for the chunk of a list column: ``num_values`` counts level entries, a V1 page declares both
+    level encodings (RLE; BIT_PACKED is refused by name), a V2 page both level lengths."""
+    pages, pos, seen, k = [], 0, 0, 0
+    n = min(len(buf), chunk.length)
+    snappy = chunk.codec == 1
+    while seen < chunk.num_values and pos < n:
+        t = _Thrift(buf, pos)
+        try:
+            h = t.struct()
+            ptype, uncomp, comp = h[1], h[2], h[3]
+        except (ValueError, KeyError) as e:
+            raise _error(f'{where}, page {k}: malformed page header ({e})') from None
+        body = t.i
+        if comp < 0 or uncomp < 0 or body + comp > n:
+            raise _error(f'{where}, page {k}: the page runs past its column chunk')
+        if ptype == DICTIONARY_PAGE:
+            d = h.get(7, {})
+            if d.get(2, 0) not in (0, 2):
+                raise _error(f'{where}, page {k}: dictionary page encoding {_name(ENCODINGS, d.get(2))} is not supported')
+            pages.append(Page(pos, body, comp, uncomp, ptype, 0, 0, 0, d.get(1, 0), int(snappy)))
+        elif ptype == DATA_PAGE:
+            d = h.get(5, {})
+            enc = _data_encoding(d.get(2, 0), leaf, where, k)
+            for what, e in (('definition', d.get(3, 3)), ('repetition', d.get(4, 3))):
+                if e != 3:
+                    raise _error(f'{where}, page {k}: {what} level encoding {_name(ENCODINGS, e)} is not supported (RLE)')
+            pages.append(Page(pos, body, comp, uncomp, ptype, enc, 0, 0, d.get(1, 0), int(snappy)))
+            seen += d.get(1, 0)
+        elif ptype == DATA_PAGE_V2:
+            d = h.get(8, {})
+            enc = _data_encoding(d.get(4, 0), leaf, where, k)
+            dl, rl = d.get(5, 0), d.get(6, 0)
+            if dl < 0 or rl < 0 or dl + rl > comp or dl + rl > uncomp:
+                raise _error(f'{where}, page {k}: level lengths run past the page body')
+            pages.append(Page(pos, body, comp, uncomp, ptype, enc, dl, rl, d.get(1, 0), int(snappy and d.get(7, True))))
+            seen += d.get(1, 0)
+        elif ptype != INDEX_PAGE:
+            raise _error(f'{where}, page {k}: page type {ptype} is not supported')
+        pos = body + comp
+        k += 1
+    if seen != chunk.num_values:
+        raise _error(f'{where}: the pages hold {seen} level entries, the column chunk declares {chunk.num_values}')
+    return pages
+
+
+def list_page_table(path, column):
+    """Host only: ``(ListMetadata, {row group: [Page]})`` of the list column ``column`` of one file -- what :func:`read_lists`
+    walks batch by batch, with every refusal the host can make (tests, tools)."""
+    meta = read_list_metadata(path, column)
+    out = {}
+    with open(meta.path, 'rb') as f:
+        for g in range(len(meta.row_groups)):
+            _, c, where = _list_chunk(meta, g)
+            f.seek(c.start)
+            out[g] = walk_list_pages(f.read(c.length), c, meta.leaf, where)
+    return meta, out
+
+
+def _list_levels(dev, buf, n_bytes, table, infos, d_off, d_null, n_rows, value_base, work=None):
+    """One ``otto_pqlist_levels`` call -> the per-page report ``int64 [pages, 3]`` (level bytes, values, rows)."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    table = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, len(PL_FIELDS))
+    report = np.zeros((len(table), 3), dtype=np.int64)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    job = _lib.PqlistJob(_lib.ptr(buf, dev), int(n_bytes), vp(table), len(table), _lib.ptr(d_off, dev), _lib.ptr(d_null, dev), int(n_rows),
+                         int(value_base), vp(report), None, 0, _lib.stream(dev))
+    need = int(_lib.lib().otto_pqlist_workspace(C.byref(job)))
+    if need < 0:
+        _lib.check(need, 'otto_pqlist_workspace')
+    if work is None:
+        work = _lib.workspace(need, dev)
+    elif _lib.need(work, 'work', torch.uint8, 1, device=dev).numel() < need:
+        raise ValueError(f'work: {work.numel()} bytes, {need} are needed')
+    job.d_work, job.work_bytes = _lib.ptr(work, dev), int(work.numel())
+    err = np.full(2, -1, dtype=np.int64)
+    try:
+        _lib.call('otto_pqlist_levels', dev, C.byref(job), err, stream=False)
+    except _lib.OttoError:
+        if err[0] < 0:
+            raise
+        where, k = infos[int(err[0])]
+        reason = _lib.lib().otto_pqlist_reason(int(err[1])).decode()
+        raise _lib.OttoError(f'{where}, page {k}: {reason}') from None
+    return report
+
+
+def _list_plan(items, o):
+    """The level job of one batch: ``items`` are ``(where, ListLeaf, rows of the row group, offset of the chunk's bytes, [Page])``
+    per chunk, ``o`` the first free byte behind the chunks. Returns ``(pl, infos, bodies, streams, end)``: the OTTO_PL page
+    records and their ``(where, page number)``, per record ``(body, body_len)``, the Snappy streams of the V1 pages
+    ``(src, n, dst, dst_len, where, page number)`` -- their bodies are laid out from ``o`` on -- and the end of the last body."""
+    from . import _lib
+    at = o
+    streams, pl, infos, bodies = [], [], [], []
+    for where, leaf, rows, base, pages in items:
+        flags = (PL_OUTER_OPTIONAL if leaf.outer_optional else 0) | (PL_ELEM_OPTIONAL if leaf.elem_optional else 0)
+        n_data = sum(p.page_type != DICTIONARY_PAGE for p in pages)
+        first = True
+        for k, p in enumerate(pages):
+            if p.page_type == DICTIONARY_PAGE:
+                continue
+            if p.page_type == DATA_PAGE_V2:
+                body, blen = base + p.src_off, p.rep_len + p.def_len
+            elif p.is_compressed:
+                body, blen = at, p.uncomp_size
+                streams.append((base + p.src_off, p.comp_size, body, blen, where, k))
+                at += blen
+            else:
+                body, blen = base + p.src_off, p.comp_size
+                if p.comp_size != p.uncomp_size:
+                    raise _lib.OttoError(f'{where}, page {k}: decoded size differs from the page header')
+            v2 = p.page_type == DATA_PAGE_V2
+            pl.append((body, blen, p.page_type, p.rep_len if v2 else 0, p.def_len if v2 else 0, p.num_values,
+                       flags | (PL_CHUNK_FIRST if first else 0), rows if first else 0, n_data if first else 0))
+            infos.append((where, k))
+            bodies.append((body, blen))
+            first = False
+        if rows and not n_data:
+            raise _lib.OttoError(f'{where}: no data page in a row group of {rows} rows')
+    return pl, infos, bodies, streams, at
+
+
+def _decode_list_batch(dev, buf, o, items, d_off, d_null, n_rows, value_base, dt, work=None):
+    """The chunks ``items`` of one batch, whose bytes lie in ``buf[:o]`` -> the values of the batch as a fresh tensor; the
+    rows' offsets and null flags go to ``d_off`` / ``d_null``. ``buf`` has room behind ``o`` for the decoded V1 bodies."""
+    import torch
+    from . import _lib
+    sizes = {torch.uint8: 1, torch.int8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
+    pl, pl_infos, bodies, streams, at = _list_plan(items, o)
+    if at > buf.numel() or at >= 1 << 31:
+        raise _lib.OttoError(f'{items[0][0]}: the pages decode to more bytes than the column chunks declare')
+    if streams:
+        a = lambda i: np.ascontiguousarray([s[i] for s in streams], dtype=np.int64)
+        status = np.zeros(len(streams), dtype=np.int32)
+        sw = _lib.workspace(int(_lib.lib().otto_parquet_snappy_workspace(len(streams))), dev)
+        _lib.call('otto_parquet_snappy', dev, buf, at, a(0), a(1), a(2), a(3), len(streams), buf, at, status, sw, int(sw.numel()))
+        bad = np.flatnonzero(status)
+        if len(bad):
+            s = streams[int(bad[0])]
+            raise _lib.OttoError(f'{s[4]}, page {s[5]}: {_lib.lib().otto_parquet_reason(int(status[bad[0]])).decode()}')
+    report = _list_levels(dev, buf, at, pl, pl_infos, d_off, d_null, n_rows, value_base, work)
+    n_values = int(report[:, 1].sum()) if len(report) else 0
+    values = torch.empty(n_values, dtype=dt, device=dev)
+    table, infos, cols, slots, announced = [], [], [], {}, []
+    row, r = 0, 0
+    for it, (where, leaf, rows, base, pages) in enumerate(items):
+        key = (4 if leaf.physical == 1 else 8, int(leaf.physical == 1 and leaf.logical == ('INT', 32, False)))
+        if key not in slots:
+            slots[key] = len(cols)
+            cols.append((values.data_ptr(), sizes[dt], n_values, key[0], key[1]))
+        dict_slot = -1
+        for k, p in enumerate(pages):
+            if p.page_type == DICTIONARY_PAGE:
+                dict_slot = len(table)
+                table.append((base + p.src_off, p.comp_size, p.uncomp_size, p.page_type, 0, 0, 0, p.num_values, p.is_compressed, row, slots[key], -1))
+                infos.append((where, k))
+                announced.append(None)
+                continue
+            body, blen = bodies[r]
+            lev, nv = int(report[r, 0]), int(report[r, 1])
+            r += 1
+            if p.encoding == 8 and dict_slot < 0:
+                raise _lib.OttoError(f'{where}, page {k}: dictionary-coded page without a dictionary page')
+            ds = dict_slot if p.encoding == 8 else -1
+            if p.page_type == DATA_PAGE_V2:
+                if nv == 0 and p.comp_size == lev:
+                    continue
+                table.append((base + p.src_off, p.comp_size, p.uncomp_size, p.page_type, p.encoding, p.def_len, p.rep_len, nv, p.is_compressed,
+                              row, slots[key], ds))
+            else:
+                if nv == 0 and blen == lev:
+                    continue
+                table.append((body + lev, blen - lev, blen - lev, DATA_PAGE, p.encoding, 0, 0, nv, 0, row, slots[key], ds))
+            infos.append((where, k))
+            announced.append(nv)
+            row += nv
+    if table:
+        _decode(dev, buf, at, table, cols, infos,
+                explain=lambda i, reason: reason if announced[i] is None else
+                f'the value stream does not hold the {announced[i]} values its definition levels announce ({reason})')
+    return values
+
+
+def read_lists(paths, column, device, dtype=None, batch_bytes=256 << 20, out=None):
+    """The list column ``column`` (SPEC-PQLIST: a three-level LIST of INT32 / INT64) of the files ``paths`` ->
+    ``(off int64 [R + 1], values [V], null uint8 [R])``, rows in file and row-group order: the values of row r are
+    ``values[off[r]:off[r + 1]]``; ``null[r]`` is 1 for a null list, whose span is empty like an empty list's. ``dtype``:
+    the dtype of ``values`` instead of :func:`default_dtype` of the element, cast as in :func:`read_columns`.
+
+    The batches, the two page-locked staging buffers and the hand-over between the copy stream and the caller's stream
+    are those of :func:`read_columns`. Per batch: V1 bodies are decompressed whole (the levels lie inside), the level
+    kernels leave offsets, null flags and a per-page report (level bytes, values), and the values run through
+    ``otto_parquet_decode`` as level-free pages. A refused file raises ``OttoError`` (file, column, row group, page, reason)
+    and writes nothing the caller can see: ``out`` (three tensors to fill instead of fresh ones) is written only after
+    every batch came back clean."""
+    import torch
+    from . import _lib
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.OttoError('parquet.read_lists needs a ROCm device (no CPU fallback)')
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    _lib.lib()
+    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+    metas = [read_list_metadata(p, column) for p in paths]
+    dt = dtype or (default_dtype(metas[0].leaf) if metas else torch.int64)
+    if dt not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+        raise ValueError(f'dtype: {dt} is not an integer dtype of 1, 2, 4 or 8 bytes')
+    groups, row = [], 0                                       # (file, row group, chunk, where, rows, first row, stored bytes, with bodies)
+    for fi, m in enumerate(metas):
+        for g in range(len(m.row_groups)):
+            n, c, where = _list_chunk(m, g)
+            comp = (c.length + 15) & ~15
+            groups.append((fi, g, c, where, n, row, comp, comp + (c.uncompressed if c.codec == 1 else 0)))
+            row += n
+    n_rows = row
+    batches, cur, cur_bytes = [], [], 0
+    for gr in groups:
+        if cur and cur_bytes + gr[7] > batch_bytes:
+            batches.append(cur)
+            cur, cur_bytes = [], 0
+        cur.append(gr)
+        cur_bytes += gr[7]
+    if cur:
+        batches.append(cur)
+    stage = max([sum(gr[6] for gr in b) for b in batches], default=0)
+    room = max([sum(gr[7] for gr in b) for b in batches], default=0)
+    if room >= 1 << 31:
+        raise _lib.OttoError(f'a row group of {room} stored plus decoded bytes does not fit one call (2^31)')
+    with torch.cuda.device(dev):
+        off = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+        null = torch.zeros(n_rows, dtype=torch.uint8, device=dev)
+        parts, n_values = [], 0
+        if batches:
+            host = [torch.empty(max(stage, 16), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            devb = [torch.empty(max(room, 16), dtype=torch.uint8, device=dev) for _ in range(2)]
+            copy_stream = torch.cuda.Stream(device=dev)
+            compute = torch.cuda.current_stream(dev)
+            copy_stream.wait_stream(compute)                     # as read_columns: the sets come from the caller's stream's allocator
+            sent = [torch.cuda.Event(), torch.cuda.Event()]
+            used = [torch.cuda.Event(), torch.cuda.Event()]
+        files = {}
+
+        def prepared():
+            for i, batch in enumerate(batches):
+                b = i & 1
+                if i >= 2:
+                    used[b].synchronize()
+                view = host[b].numpy()
+                items, o = [], 0
+                for fi, g, c, where, n, row0, _, _ in batch:
+                    m = metas[fi]
+                    if fi not in files:
+                        files[fi] = open(m.path, 'rb', buffering=0)
+                    f = files[fi]
+                    f.seek(c.start)
+                    if _read_full(f, memoryview(view)[o:o + c.length]) != c.length:
+                        raise _lib.OttoError(f'{where}: the column chunk runs past the end of the file')
+                    items.append((where, m.leaf, n, o, walk_list_pages(view[o:o + c.length], c, m.leaf, where)))
+                    o += (c.length + 15) & ~15
+                with torch.cuda.stream(copy_stream):
+                    devb[b][:o].copy_(host[b][:o], non_blocking=True)
+                    sent[b].record(copy_stream)
+                yield b, o, items, batch[0][5], sum(gr[4] for gr in batch)
+
+        try:
+            it = prepared()
+            cur = next(it, None)
+            while cur is not None:
+                nxt = next(it, None)                             # read and send batch i + 1 before batch i decodes
+                b, o, items, row0, rows = cur
+                compute.wait_event(sent[b])
+                v = _decode_list_batch(dev, devb[b], o, items, off[row0:], null[row0:], rows, n_values, dt)
+                used[b].record(compute)
+                parts.append(v)
+                n_values += int(v.numel())
+                cur = nxt
+        finally:
+            for f in files.values():
+                f.close()
+            torch.cuda.synchronize(dev)
+        values = parts[0] if len(parts) == 1 else torch.cat(parts) if parts else torch.empty(0, dtype=dt, device=dev)
+        if out is not None:
+            out, result = tuple(out), (off, values, null)
+            if len(out) != 3 or any(o.shape != r.shape or o.dtype != r.dtype or o.device != r.device for o, r in zip(out, result)):
+                raise ValueError('out: expected (off, values, null) with the shape, dtype and device of the result')
+            for o, r in zip(out, result):
+                o.copy_(r)
+            return out
+    return off, values, null
+
+
+def _snappy_host(data, n):
+    """A raw Snappy stream -> its ``n`` bytes, on the host (the small dictionary page of a string column)."""
+    data = bytes(data)
+    t = _Thrift(data)
+    if t.varint() != n or t.i > 5:
+        raise ValueError('snappy: preamble disagrees with the declared uncompressed size')
+    i, out = t.i, bytearray()
+    cut = ValueError('snappy: stream cut short inside an element')
+    while i < len(data):
+        tag = data[i]
+        i += 1
+        kind = tag & 3
+        if kind == 0:
+            ln = tag >> 2
+            if ln >= 60:
+                nb = ln - 59
+                if i + nb > len(data):
+                    raise cut
+                ln = int.from_bytes(data[i:i + nb], 'little')
+                i += nb
+            ln += 1
+            if i + ln > len(data):
+                raise cut
+            out += data[i:i + ln]
+            i += ln
+        else:
+            nb = 1 if kind == 1 else 2 if kind == 2 else 4
+            if i + nb > len(data):
+                raise cut
+            if kind == 1:
+                ln, offset = 4 + ((tag >> 2) & 7), (tag >> 5) << 8 | data[i]
+                i += 1
+            else:
+                ln, offset = 1 + (tag >> 2), int.from_bytes(data[i:i + nb], 'little')
+                i += nb
+            if offset == 0 or offset > len(out):
+                raise ValueError('snappy: copy offset is 0 or reaches before the output')
+            for _ in range(ln):
+                out.append(out[-offset])
+        if len(out) > n:
+            raise ValueError('snappy: output runs past the declared uncompressed size')
+    if len(out) != n:
+        raise ValueError('snappy: stream ends before the declared uncompressed size')
+    return bytes(out)
+
+
+def string_dictionary(buf, page, where, k):
+    """The strings (bytes) of the PLAIN BYTE_ARRAY dictionary page ``page`` of the chunk bytes ``buf``, decoded on the host."""
+    if page.uncomp_size > MAX_STRING_DICTIONARY:
+        raise _error(f'{where}, page {k}: a string dictionary page of {page.uncomp_size} bytes is not supported ({MAX_STRING_DICTIONARY} at most)')
+    raw = bytes(buf[page.src_off:page.src_off + page.comp_size])
+    try:
+        if page.is_compressed:
+            raw = _snappy_host(raw, page.uncomp_size)
+        elif page.comp_size != page.uncomp_size:
+            raise ValueError('decoded size differs from the page header')
+        out, i = [], 0
+        for _ in range(page.num_values):
+            if i + 4 > len(raw):
+                raise ValueError('the dictionary ends inside a length')
+            n = struct.unpack_from('<I', raw, i)[0]
+            if i + 4 + n > len(raw):
+                raise ValueError('the dictionary ends inside a string')
+            out.append(raw[i + 4:i + 4 + n])
+            i += 4 + n
+    except (ValueError, IndexError) as e:
+        raise _error(f'{where}, page {k}: malformed string dictionary ({e})') from None
+    return out
+
+
+def string_code_table(path, column, mapping):
+    """Host only: the plan of :func:`read_string_codes` for one file, with every refusal the host can make ->
+    ``(num_rows, [(where, chunk, [Page], {page number: int32 codes of that dictionary page})] per row group)``."""
+    meta = read_metadata(path)
+    leaf = next((l for l in meta.leaves if l.name == column), None)
+    if leaf is None:
+        raise _error(f'{meta.path}: column {column!r}: not in the file (top-level columns: {[l.name for l in meta.leaves]})')
+    if leaf.nested or leaf.repetition == REPEATED:
+        raise _error(f'{meta.path}: column {column!r}: a repeated or nested column is not supported')
+    if leaf.physical != BYTE_ARRAY:
+        raise _error(f'{meta.path}: column {column!r}: physical type {_name(PHYSICAL, leaf.physical)} is no string column (BYTE_ARRAY)')
+    codes = {(k.encode() if isinstance(k, str) else bytes(k)): int(v) for k, v in mapping.items()}
+    out = []
+    with open(meta.path, 'rb') as f:
+        for g in range(len(meta.row_groups)):
+            c, = check_row_group(meta, g, [column])
+            where = _where(meta, column, g)
+            f.seek(c.start)
+            buf = f.read(c.length)
+            pages = walk_pages(buf, c, leaf, where)
+            dicts = {}
+            for k, p in enumerate(pages):
+                if p.page_type == DICTIONARY_PAGE:
+                    strings = string_dictionary(buf, p, where, k)
+                    for s in strings:
+                        if s not in codes:
+                            raise _error(f'{where}, page {k}: dictionary string {s.decode("utf-8", "replace")!r} is not in the mapping '
+                                         f'({sorted(x.decode("utf-8", "replace") for x in codes)})')
+                    dicts[k] = np.array([codes[s] for s in strings], dtype=np.int32)
+                elif p.encoding != 8:
+                    raise _error(f'{where}, page {k}: a {"PLAIN" if p.encoding == 0 else "DELTA_BINARY_PACKED"} BYTE_ARRAY data page is not '
+                                 'supported (dictionary-coded strings only)')
+                elif not dicts:
+                    raise _error(f'{where}, page {k}: dictionary-coded page without a dictionary page')
+            out.append((where, c, buf, pages, dicts))
+    return meta.num_rows, out
+
+
+def read_string_codes(paths, column, mapping, device, dtype=None):
+    """The dictionary-coded string column ``column`` of the files ``paths`` -> one device tensor of ``mapping[string]`` per row
+    (``dtype``: ``torch.uint8`` unless given). The host reads every chunk's dictionary page (PLAIN BYTE_ARRAY, at most 64 KiB),
+    maps its strings through ``mapping`` and hands the device an INT32 dictionary in its place; the index pages run through
+    the dictionary gather of ``otto_parquet_decode`` as they lie in the file. Refused by name: a dictionary string that is
+    not in ``mapping``, a PLAIN or DELTA data page, a larger dictionary page. The index pages of all files go across in one
+    piece (a string column of three values is a few bytes per thousand rows)."""
+    import torch
+    from . import _lib
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.OttoError('parquet.read_string_codes needs a ROCm device (no CPU fallback)')
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    _lib.lib()
+    dt = dtype or torch.uint8
+    sizes = {torch.uint8: 1, torch.int8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
+    if dt not in sizes:
+        raise ValueError(f'dtype: {dt} is not one of {sorted(map(str, sizes))}')
+    lo, hi = (0, 1 << 8 * sizes[dt]) if dt == torch.uint8 else (-(1 << 8 * sizes[dt] - 1), 1 << 8 * sizes[dt] - 1)
+    for s, v in mapping.items():
+        if not lo <= int(v) < min(hi, 1 << 31):
+            raise ValueError(f'mapping[{s!r}]: {v} does not fit {dt}')
+    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+    plans = [string_code_table(p, column, mapping) for p in paths]
+    n_rows = sum(p[0] for p in plans)
+    pieces, table, infos, o, row = [], [], [], 0, 0
+
+    def put(b):
+        nonlocal o
+        at = o
+        pieces.append(b)
+        pad = -len(b) % 16
+        if pad:
+            pieces.append(bytes(pad))
+        o += len(b) + pad
+        return at
+    with torch.cuda.device(dev):
+        result = torch.empty(n_rows, dtype=dt, device=dev)
+        cols = [(result.data_ptr(), sizes[dt], n_rows, 4, 0)]
+        for _, groups in plans:
+            for where, c, buf, pages, dicts in groups:
+                dict_slot = -1
+                for k, p in enumerate(pages):
+                    if p.page_type == DICTIONARY_PAGE:
+                        at = put(dicts[k].tobytes())
+                        dict_slot = len(table)
+                        table.append((at, 4 * len(dicts[k]), 4 * len(dicts[k]), DICTIONARY_PAGE, 0, 0, 0, len(dicts[k]), 0, row, 0, -1))
+                    else:
+                        at = put(bytes(buf[p.src_off:p.src_off + p.comp_size]))
+                        table.append((at, p.comp_size, p.uncomp_size, p.page_type, 8, p.def_len, p.rep_len, p.num_values, p.is_compressed, row, 0,
+                                      dict_slot))
+                        row += p.num_values
+                    infos.append((where, k))
+        if o >= 1 << 31:
+            raise _lib.OttoError(f'column {column!r}: {o} bytes of index pages do not fit one call (2^31)')
+        if table:
+            d_bytes = torch.from_numpy(np.frombuffer(b''.join(pieces) or bytes(16), dtype=np.uint8).copy()).to(dev)
+            _decode(dev, d_bytes, o, table, cols, infos)
+    return result

@@ -7,6 +7,11 @@ and ``src/ranker/covisitation_candidate_generation.py:159-164``. Events are a :c
 lists are CSR pairs ``(off int64 [S+1], aid int32)``, the form ``candidates.ranker_table(labels=...)`` takes. Predictions
 are padded (``[P, k]`` int32, or ``([P, k], n int32 [P])``: what ``session_topk`` / ``predictions`` emit) or CSR
 (``(off int64 [P+1], aid int32)``: a ranker table's ``row_off`` / ``candidates``). No CPU fallback.
+
+Labels on the organisers' split come from ``DATA/splits/val_labels.parquet``: :func:`read_labels` decodes the file on the
+device and :func:`assemble_labels` (SPEC-LABELS, ``include/otto_labels.h``) aligns its rows to a session list, in place of
+the ``map`` + three ``merge(how='left')`` + ``fillna`` of ``src/covisitation/inference.py:118-123`` and
+``src/ranker/lgb_trainer.py:54-75``.
 """
 import ctypes as C
 import functools
@@ -172,3 +177,90 @@ def evaluate(top20_by_type, labels_by_type, pred_session=None, holdout=None, lab
         held['weighted'] = weighted_recall(held['clicks'], held['carts'], held['orders'])
         out['holdout'] = held
     return out
+
+
+# ---- val_labels.parquet -> label lists (SPEC-LABELS, include/otto_labels.h) ------------------------------------------------------
+TYPE_CODES = {'clicks': 0, 'carts': 1, 'orders': 2}
+LABEL_REASONS = {1: 'a session outside int32', 2: 'a type code above 2', 3: 'list offsets that descend or leave the values',
+                 4: 'the same (session, type) as an earlier row', 5: 'a value outside [0, n_aids)'}
+
+
+def assemble_labels(session, type, off, value, null, label_session, n_aids, work=None):
+    """SPEC-LABELS: the rows ``session int64 [R], type uint8 [R], off int64 [R+1], value int64 [V], null uint8 [R]`` of a label
+    file (what ``parquet.read_columns`` / ``read_string_codes`` / ``read_lists`` return) -> ``({'clicks': (off int64 [S+1],
+    aid int32), 'carts': ..., 'orders': ...}, n_dropped)`` aligned to ``label_session`` (int32 [S], ascending and distinct).
+    The list of (session, type) is the values of its one row, in file order, repeated aids kept; no row, a null list and an
+    empty list are an empty list. A row whose session is not in ``label_session`` is dropped and counted. ``OttoError``
+    naming the smallest offending row for a type code above 2, a second row of one (session, type), a value outside
+    ``[0, n_aids)`` or a session outside int32. ``work``: a uint8 scratch tensor to use instead of a fresh one."""
+    import numpy as np
+    import torch
+    dev = session.device if isinstance(session, torch.Tensor) else None
+    if dev is None or dev.type != 'cuda':
+        raise _lib.OttoError('evaluate.assemble_labels needs tensors on a ROCm device (no CPU fallback)')
+    R = int(session.numel())
+    _lib.need(session, 'session', torch.int64, 1, device=dev)
+    _lib.need(type, 'type', torch.uint8, 1, device=dev, numel=R)
+    _lib.need(off, 'off', torch.int64, 1, device=dev, numel=R + 1)
+    _lib.need(value, 'value', torch.int64, 1, device=dev)
+    _lib.need(null, 'null', torch.uint8, 1, device=dev, numel=R)
+    _lib.need(label_session, 'label_session', torch.int32, 1, device=dev)
+    S, V, n_aids = int(label_session.numel()), int(value.numel()), int(n_aids)
+    if not 0 <= n_aids < 1 << 31:
+        raise ValueError(f'n_aids must be in [0, 2^31) (got {n_aids})')
+    with torch.cuda.device(dev):
+        offs = [torch.empty(S + 1, dtype=torch.int64, device=dev) for _ in TYPES]
+        job = _lib.LabelsJob(_lib.ptr(session, dev), _lib.ptr(type, dev), _lib.ptr(off, dev), _lib.ptr(value, dev), _lib.ptr(null, dev), R, V,
+                             _lib.ptr(label_session, dev), S, n_aids, (C.c_void_p * 3)(*[o.data_ptr() for o in offs]), (C.c_void_p * 3)(),
+                             None, 0, _lib.stream(dev))
+        need = int(_lib.lib().otto_labels_workspace(C.byref(job)))
+        if need < 0:
+            _lib.check(need, 'otto_labels_workspace')
+        if work is None:
+            work = _lib.workspace(need, dev)
+        elif _lib.need(work, 'work', torch.uint8, 1, device=dev).numel() < need:
+            raise ValueError(f'work: {work.numel()} bytes, {need} are needed')
+        job.d_work, job.work_bytes = _lib.ptr(work, dev), int(work.numel())
+        counts, err = np.zeros(4, dtype=np.int64), np.full(2, -1, dtype=np.int64)
+        try:
+            _lib.call('otto_labels_count', dev, C.byref(job), counts, err, stream=False)
+        except _lib.OttoError:
+            if err[0] < 0:
+                raise
+            raise _lib.OttoError(f'assemble_labels: row {int(err[0])}: {LABEL_REASONS.get(int(err[1]), "?")}') from None
+        aids = [torch.empty(max(int(n), 1), dtype=torch.int32, device=dev) for n in counts[:3]]
+        job.d_out_aid = (C.c_void_p * 3)(*[a.data_ptr() for a in aids])
+        _lib.call('otto_labels_fill', dev, C.byref(job), stream=False)
+    return {name: (offs[t], aids[t][:int(counts[t])]) for t, name in enumerate(TYPES)}, int(counts[3])
+
+
+def read_labels(path, device, session=None, n_aids=None):
+    """``DATA/splits/val_labels.parquet`` (columns ``session``, ``type``: 'clicks' / 'carts' / 'orders', ``ground_truth``: a list
+    of aids) -> ``(label_session int32 [S], {'clicks': (off, aid), 'carts': ..., 'orders': ...}, n_dropped)``, decoded and
+    assembled on the device: ``parquet.read_columns``, ``parquet.read_string_codes``, ``parquet.read_lists``, then
+    :func:`assemble_labels`. ``session``: the session list to align to (int32, ascending and distinct; rows of other sessions
+    are dropped and counted); None: the file's distinct sessions, ascending. ``n_aids``: the bound every label must stay
+    below; None: the file's largest aid + 1. The lists go into :func:`hits`, :func:`evaluate`,
+    ``candidates.ranker_table(labels=...)`` and ``cross_validate(truth=...)`` as they are."""
+    import torch
+    from .. import parquet
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _lib.OttoError('evaluate.read_labels needs a ROCm device (no CPU fallback)')
+    sess, = parquet.read_columns(path, ['session'], dev, dtypes={'session': torch.int64})
+    typ = parquet.read_string_codes(path, 'type', TYPE_CODES, dev, dtype=torch.uint8)
+    off, value, null = parquet.read_lists(path, 'ground_truth', dev, dtype=torch.int64)
+    if not (sess.numel() == typ.numel() == null.numel()):
+        raise _lib.OttoError(f'{path}: the columns differ in length ({sess.numel()}, {typ.numel()}, {null.numel()} rows)')
+    if session is None:
+        if sess.numel() and (int(sess.min()) < -2 ** 31 or int(sess.max()) >= 2 ** 31):
+            raise _lib.OttoError(f'{path}: a session outside int32')
+        session = torch.unique(sess).to(torch.int32)
+    else:
+        session = _tensor(session, 'session', torch.int32)
+    if n_aids is None:
+        n_aids = int(value.max()) + 1 if value.numel() else 0
+        if not 0 <= n_aids < 1 << 31:
+            raise _lib.OttoError(f'{path}: a label outside [0, 2^31)')
+    labels, dropped = assemble_labels(sess, typ, off, value, null, session, n_aids)
+    return session, labels, dropped
