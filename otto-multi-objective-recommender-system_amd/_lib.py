@@ -378,6 +378,18 @@ def lib():
     return _lib
 
 
+def rocm_device(device, what):
+    """``torch.device(device)`` with its index filled in (the tensors' device carries one); ``OttoError`` in the name of
+    ``what`` unless it is a ROCm device."""
+    import torch
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise OttoError(f'{what} needs a ROCm device (no CPU fallback)')
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    return dev
+
+
 def check(rc, what):
     if rc != 0:
         msg = lib().otto_last_error()

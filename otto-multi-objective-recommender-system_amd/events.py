@@ -192,11 +192,7 @@ def jsonl_to_events_device(paths, device='cuda:0', n_aids=None, ts_unit='auto', 
     (``src/utilities/dataset_writer_pickle.py:11-65``) builds from the same files; no frame and no pickle is made."""
     import torch
     from . import _lib, jsonl
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise _lib.OttoError('jsonl_to_events_device needs a ROCm device (no CPU fallback)')
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _lib.rocm_device(device, 'jsonl_to_events_device')
     with torch.cuda.device(dev):
         d_sess, d_aid, d_ts, d_type = jsonl.read_columns(paths, dev, chunk_bytes)
         n = int(d_ts.numel())
@@ -218,11 +214,7 @@ def parquet_to_events_device(paths, device='cuda:0', n_aids=None, ts_unit='auto'
     import os
     import torch
     from . import _lib, parquet
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise _lib.OttoError('parquet_to_events_device needs a ROCm device (no CPU fallback)')
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _lib.rocm_device(device, 'parquet_to_events_device')
     paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
     with torch.cuda.device(dev):
         d_sess, d_aid, d_ts, d_type = parquet.read_columns(

@@ -141,11 +141,7 @@ class SkipGramEngine:
 
     def __init__(self, n_aids, d, ws, neg, keep_q, weight, seed=0, device='cuda:0', n_buckets=None, hs=None):
         import torch
-        self.dev = torch.device(device)
-        if self.dev.type != 'cuda':
-            raise _lib.OttoError('SkipGramEngine needs a ROCm device (no CPU fallback)')
-        if self.dev.index is None:
-            self.dev = torch.device('cuda', torch.cuda.current_device())     # the tensors' device carries its index
+        self.dev = _lib.rocm_device(device, 'SkipGramEngine')
         self.n_aids, self.d, self.ws, self.neg, self.seed = int(n_aids), int(d), int(ws), int(neg), int(seed)
         if self.d % 4 or not 4 <= self.d <= MAX_DIM or (self.d // 4) & (self.d // 4 - 1):
             raise ValueError(f'd must be a multiple of 4 in [4, {MAX_DIM}] with d/4 a power of two (got {d})')

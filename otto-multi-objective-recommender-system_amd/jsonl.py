@@ -7,6 +7,8 @@ that brings a file of any size across in chunks of whole lines.
 """
 import numpy as np
 
+from .parquet import _read_full
+
 TILE_BYTES = 4096            # OTTO_JSONL_TILE
 MAX_PIECE = 256              # OTTO_JSONL_MAX_PIECE
 COLUMNS = ('session', 'aid', 'ts', 'type', 'sess_off', 'sess_id')
@@ -69,16 +71,6 @@ def cut_chunk(buf, n, eof=False):
             return lo + int(hit[-1]) + 1
         hi, step = lo, step * 4
     raise ValueError(f'a line longer than chunk_bytes ({n} bytes without a newline)')
-
-
-def _read_full(f, view):
-    got = 0
-    while got < len(view):
-        k = f.readinto(view[got:])
-        if not k:
-            break
-        got += k
-    return got
 
 
 def read_columns(paths, device, chunk_bytes=256 << 20):

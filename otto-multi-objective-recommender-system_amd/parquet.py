@@ -11,6 +11,9 @@ Reference code replaced: the pyarrow / pandas host decode in front of every cons
 Thrift compact-protocol reader for the footer and the page headers (:func:`read_metadata`, :func:`walk_pages`), and
 :func:`read_columns`, which reads the byte ranges of the requested column chunks into page-locked staging buffers and
 sends them across as they lie in the file.
+
+Every reader is built from the same host pieces: ``_parse_footer``, :func:`walk_pages` for flat and
+list leaves, ``_plan_batches``, the staging pipeline ``_stage_batches``, ``_chunk_records`` and ``_refusal``.
 """
 import os
 import struct
@@ -22,13 +25,17 @@ TILE = 1024                  # OTTO_PQ_TILE
 FIELDS = ('src_off', 'comp_size', 'uncomp_size', 'page_type', 'encoding', 'def_len', 'rep_len', 'num_values', 'is_compressed',
           'out_row', 'col_slot', 'dict_slot')                                            # OTTO_PQ_* of a page record
 F = {k: i for i, k in enumerate(FIELDS)}
+PL_FIELDS = ('body_off', 'body_len', 'page_type', 'rep_len', 'def_len', 'num_values', 'flags', 'chunk_rows', 'chunk_pages')   # OTTO_PL_*
+PL_OUTER_OPTIONAL, PL_ELEM_OPTIONAL, PL_CHUNK_FIRST = 1, 2, 4
 PHYSICAL = ('BOOLEAN', 'INT32', 'INT64', 'INT96', 'FLOAT', 'DOUBLE', 'BYTE_ARRAY', 'FIXED_LEN_BYTE_ARRAY')
+FLOAT, DOUBLE, BYTE_ARRAY = 4, 5, 6
 CODECS = ('UNCOMPRESSED', 'SNAPPY', 'GZIP', 'LZO', 'BROTLI', 'LZ4', 'ZSTD', 'LZ4_RAW')
 ENCODINGS = {0: 'PLAIN', 2: 'PLAIN_DICTIONARY', 3: 'RLE', 4: 'BIT_PACKED', 5: 'DELTA_BINARY_PACKED', 6: 'DELTA_LENGTH_BYTE_ARRAY',
              7: 'DELTA_BYTE_ARRAY', 8: 'RLE_DICTIONARY', 9: 'BYTE_STREAM_SPLIT'}
 DATA_PAGE, INDEX_PAGE, DICTIONARY_PAGE, DATA_PAGE_V2 = 0, 1, 2, 3
 REQUIRED, OPTIONAL, REPEATED = 0, 1, 2
 TICKS_PER_SECOND = {'MILLIS': 10 ** 3, 'MICROS': 10 ** 6, 'NANOS': 10 ** 9}
+MAX_STRING_DICTIONARY = 64 << 10
 
 Leaf = namedtuple('Leaf', 'name physical repetition logical nested')
 # logical: None | ('INT', bits, signed) | ('TIMESTAMP', unit) | ('OTHER', name);  nested: a group, not a leaf
@@ -36,11 +43,19 @@ Chunk = namedtuple('Chunk', 'name physical codec num_values start length data_pa
 RowGroup = namedtuple('RowGroup', 'num_rows chunks')              # chunks: {top-level name: Chunk}
 Metadata = namedtuple('Metadata', 'path num_rows leaves row_groups')
 Page = namedtuple('Page', 'header_off ' + ' '.join(FIELDS[:9]))   # offsets relative to the chunk's first byte
+ListLeaf = namedtuple('ListLeaf', 'name path physical logical outer_optional elem_optional')
+ListMetadata = namedtuple('ListMetadata', 'path num_rows leaf row_groups')       # row_groups: [(num_rows, Chunk or None)]
 
 
 def _error(msg):
     from . import _lib
     return _lib.OttoError(msg)
+
+
+def _sizes():
+    """{torch dtype: bytes} of the integer dtypes a decode can store into"""
+    import torch
+    return {torch.uint8: 1, torch.int8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -158,59 +173,75 @@ def _footer(path):
     return path, foot
 
 
+def _top_level(schema):
+    """``(index, element)`` of the top-level schema elements, one at a time; the subtree of a group is stepped over by its
+    ``num_children`` only after the caller has looked at the element."""
+    def skip(j):                              # the element at j and its subtree -> the index behind it
+        kids = schema[j].get(5, 0) or 0
+        j += 1
+        for _ in range(kids):
+            j = skip(j)
+        return j
+    i = 1
+    for _ in range(schema[0].get(5, 0) or 0):
+        yield i, schema[i]
+        i = skip(i)
+
+
+def _parse_footer(path, consume):
+    """The one footer pass: ``consume(path, Thrift dict of the footer, its schema list)`` -> the reader's metadata. Raises
+    ``OttoError`` on a wrong magic, an encrypted, truncated or malformed footer."""
+    path, foot = _footer(path)
+    try:
+        md = _Thrift(foot).struct()
+        return consume(path, md, md[2])
+    except (ValueError, KeyError, IndexError) as e:
+        raise _error(f'{path}: malformed footer ({e})') from None
+
+
+def _chunk(name, cm):
+    """The column-chunk metadata struct ``cm`` -> :class:`Chunk`; the chunk starts at its dictionary page where it has one"""
+    dpo, dico = cm[9], cm.get(11)
+    start = dico if dico is not None and 0 < dico < dpo else dpo
+    return Chunk(name, cm[1], cm[4], cm[5], start, cm[7], dpo, dico, cm[6], tuple(cm[2]))
+
+
 def read_metadata(path):
     """The footer of a Parquet file -> :class:`Metadata`: the top-level schema leaves (nested groups marked), the row groups
     and, per top-level primitive column, the chunk's byte range, codec, ``num_values`` and sizes. Raises ``OttoError`` on a
     wrong magic, an encrypted or truncated footer."""
-    path, foot = _footer(path)
-    try:
-        md = _Thrift(foot).struct()
-        schema = md[2]
-        leaves, i = [], 1
-
-        def skip(j):                          # the element at j and its subtree -> the index behind it
-            kids = schema[j].get(5, 0) or 0
-            j += 1
-            for _ in range(kids):
-                j = skip(j)
-            return j
-        for _ in range(schema[0].get(5, 0) or 0):
-            el = schema[i]
-            nested = bool(el.get(5, 0))
-            leaves.append(Leaf(el[4].decode(), el.get(1), el.get(3, REQUIRED), _logical(el), nested))
-            i = skip(i)
+    def consume(path, md, schema):
+        leaves = [Leaf(el[4].decode(), el.get(1), el.get(3, REQUIRED), _logical(el), bool(el.get(5, 0))) for _, el in _top_level(schema)]
         groups = []
         for rg in md.get(4, []):
             chunks = {}
             for cc in rg[1]:
-                cm = cc[3]
-                pathn = [p.decode() for p in cm[3]]
-                if len(pathn) != 1:
-                    continue
-                dpo, dico = cm[9], cm.get(11)
-                start = dico if dico is not None and 0 < dico < dpo else dpo
-                chunks[pathn[0]] = Chunk(pathn[0], cm[1], cm[4], cm[5], start, cm[7], dpo, dico, cm[6], tuple(cm[2]))
+                pathn = [p.decode() for p in cc[3][3]]
+                if len(pathn) == 1:
+                    chunks[pathn[0]] = _chunk(pathn[0], cc[3])
             groups.append(RowGroup(rg[3], chunks))
         return Metadata(path, md[3], leaves, groups)
-    except (ValueError, KeyError, IndexError) as e:
-        raise _error(f'{path}: malformed footer ({e})') from None
+    return _parse_footer(path, consume)
 
 
 def _name(table, k):
     return table[k] if isinstance(table, tuple) and 0 <= k < len(table) else table.get(k, f'#{k}') if isinstance(table, dict) else f'#{k}'
 
 
-FLOAT, DOUBLE = 4, 5           # PHYSICAL
-
-
-def check_column(meta, name, floats=False):
-    """The leaf ``name`` of the file, or the ``OttoError`` SPEC-PARQUET names for a column that cannot be read.
-    ``floats``: FLOAT / DOUBLE columns are accepted too."""
+def _flat_leaf(meta, name):
+    """The top-level leaf ``name`` of the file; ``OttoError`` where there is none or it is repeated or a group"""
     leaf = next((l for l in meta.leaves if l.name == name), None)
     if leaf is None:
         raise _error(f'{meta.path}: column {name!r}: not in the file (top-level columns: {[l.name for l in meta.leaves]})')
     if leaf.nested or leaf.repetition == REPEATED:
         raise _error(f'{meta.path}: column {name!r}: a repeated or nested column is not supported')
+    return leaf
+
+
+def check_column(meta, name, floats=False):
+    """The leaf ``name`` of the file, or the ``OttoError`` SPEC-PARQUET names for a column that cannot be read.
+    ``floats``: FLOAT / DOUBLE columns are accepted too."""
+    leaf = _flat_leaf(meta, name)
     if leaf.physical not in (1, 2) and not (floats and leaf.physical in (FLOAT, DOUBLE)):
         raise _error(f'{meta.path}: column {name!r}: physical type {_name(PHYSICAL, leaf.physical)} is not supported (INT32, INT64)')
     return leaf
@@ -227,7 +258,13 @@ def _data_encoding(enc, leaf, where, k):
 
 def walk_pages(buf, chunk, leaf, where):
     """The page headers of one column chunk -> a list of :class:`Page`. ``buf`` holds the chunk's bytes (``chunk.length``
-    of them, from ``chunk.start``); only header bytes are touched. ``where``: the text that opens an error message."""
+    of them, from ``chunk.start``); only header bytes are touched. ``where``: the text that opens an error message.
+    ``leaf``: a :class:`Leaf` or a :class:`ListLeaf`. For a list column ``num_values`` counts level entries, so nulls are no
+    refusal; a V1 page must declare RLE for both level streams (BIT_PACKED is refused by name), a V2 page level lengths that
+    fit its body. For a flat column only an OPTIONAL one has definition levels to check, and a V2 page with nulls is refused."""
+    is_list = isinstance(leaf, ListLeaf)
+    optional = not is_list and leaf.repetition == OPTIONAL
+    level_streams = ('definition', 'repetition') if is_list else ('definition',) if optional else ()    # whose V1 encoding is checked
     pages, pos, seen, k = [], 0, 0, 0
     n = min(len(buf), chunk.length)
     while seen < chunk.num_values and pos < n:
@@ -249,25 +286,28 @@ def walk_pages(buf, chunk, leaf, where):
         elif ptype == DATA_PAGE:
             d = h.get(5, {})
             enc = _data_encoding(d.get(2, 0), leaf, where, k)
-            if leaf.repetition == OPTIONAL and d.get(3, 3) != 3:
-                raise _error(f'{where}, page {k}: definition level encoding {_name(ENCODINGS, d.get(3))} is not supported')
-            pages.append(Page(pos, body, comp, uncomp, ptype, enc, -1 if leaf.repetition == OPTIONAL else 0, 0, d.get(1, 0),
-                              int(snappy)))
+            for what, e in zip(level_streams, (d.get(3, 3), d.get(4, 3))):
+                if e != 3:
+                    raise _error(f'{where}, page {k}: {what} level encoding {_name(ENCODINGS, e)} is not supported{" (RLE)" if is_list else ""}')
+            pages.append(Page(pos, body, comp, uncomp, ptype, enc, -1 if optional else 0, 0, d.get(1, 0), int(snappy)))
             seen += d.get(1, 0)
         elif ptype == DATA_PAGE_V2:
             d = h.get(8, {})
             enc = _data_encoding(d.get(4, 0), leaf, where, k)
-            if d.get(2, 0) != 0:
+            dl, rl = d.get(5, 0), d.get(6, 0)
+            if is_list:
+                if dl < 0 or rl < 0 or dl + rl > comp or dl + rl > uncomp:
+                    raise _error(f'{where}, page {k}: level lengths run past the page body')
+            elif d.get(2, 0) != 0:
                 raise _error(f'{where}, page {k}: {d.get(2)} null(s): nulls are not supported')
-            pages.append(Page(pos, body, comp, uncomp, ptype, enc, d.get(5, 0), d.get(6, 0), d.get(1, 0),
-                              int(snappy and d.get(7, True))))
+            pages.append(Page(pos, body, comp, uncomp, ptype, enc, dl, rl, d.get(1, 0), int(snappy and d.get(7, True))))
             seen += d.get(1, 0)
         elif ptype != INDEX_PAGE:
             raise _error(f'{where}, page {k}: page type {ptype} is not supported')
         pos = body + comp
         k += 1
     if seen != chunk.num_values:
-        raise _error(f'{where}: the pages hold {seen} values, the column chunk declares {chunk.num_values}')
+        raise _error(f'{where}: the pages hold {seen} {"level entries" if is_list else "values"}, the column chunk declares {chunk.num_values}')
     return pages
 
 
@@ -275,16 +315,21 @@ def _where(meta, name, g):
     return f'{meta.path}: column {name!r}, row group {g}'
 
 
+def _check_chunk(c, where):
+    """The chunk ``c`` of a requested column, or the ``OttoError`` for a missing one or a codec that cannot be read"""
+    if c is None:
+        raise _error(f'{where}: no column chunk')
+    if c.codec not in (0, 1):
+        raise _error(f'{where}: codec {_name(CODECS, c.codec)} is not supported (UNCOMPRESSED, SNAPPY)')
+    return c
+
+
 def check_row_group(meta, g, columns):
     """The chunks of the requested columns of row group ``g``, checked: codec, agreement on ``num_rows``."""
     rg = meta.row_groups[g]
     out = []
     for name in columns:
-        c = rg.chunks.get(name)
-        if c is None:
-            raise _error(f'{_where(meta, name, g)}: no column chunk')
-        if c.codec not in (0, 1):
-            raise _error(f'{_where(meta, name, g)}: codec {_name(CODECS, c.codec)} is not supported (UNCOMPRESSED, SNAPPY)')
+        c = _check_chunk(rg.chunks.get(name), _where(meta, name, g))
         if c.num_values != rg.num_rows:
             raise _error(f'{_where(meta, name, g)}: {c.num_values} values in a row group of {rg.num_rows} rows')
         out.append(c)
@@ -320,6 +365,28 @@ def default_dtype(leaf):
     return torch.int32 if leaf.physical == 1 else torch.int64
 
 
+def _refusal(infos, i, code, reason_of, explain=None):
+    """The ``OttoError`` for a device call that came back with violation ``code`` at record ``i``: ``infos[i]`` names file,
+    column, row group and page, ``reason_of`` the library's ``*_reason`` by name; ``explain(i, reason)`` rewords the reason."""
+    from . import _lib
+    where, k = infos[i]
+    reason = getattr(_lib.lib(), reason_of)(code).decode()
+    return _error(f'{where}, page {k}: {explain(i, reason) if explain else reason}')
+
+
+def _call(name, dev, *args, infos, reason_of, explain=None, **kw):
+    """``_lib.call`` of an entry point whose last argument is the ``int64 [2]`` report (record, violation): a reported
+    violation raises the :func:`_refusal` for it, any other failure the call's own ``OttoError``."""
+    from . import _lib
+    err = np.full(2, -1, dtype=np.int64)
+    try:
+        _lib.call(name, dev, *args, err, **kw)
+    except _lib.OttoError:
+        if err[0] < 0:
+            raise
+        raise _refusal(infos, int(err[0]), int(err[1]), reason_of, explain) from None
+
+
 def _decode(dev, d_bytes, n_bytes, table, cols, infos, phases=3, work=None, explain=None):
     """One ``otto_parquet_decode`` call; a violation raises the ``OttoError`` that names file, column, row group and page.
     ``explain(record, reason)``: the text behind the page instead of the bare reason (``read_lists``)."""
@@ -332,16 +399,8 @@ def _decode(dev, d_bytes, n_bytes, table, cols, infos, phases=3, work=None, expl
         _lib.check(need, 'otto_parquet_workspace')
     if work is None:
         work = _lib.workspace(need, dev)
-    err = np.full(2, -1, dtype=np.int64)
-    try:
-        _lib.call('otto_parquet_decode', dev, d_bytes, int(n_bytes), table, len(table), cols, len(cols), int(phases), work,
-                  int(work.numel()), err)
-    except _lib.OttoError:
-        if err[0] < 0:
-            raise
-        where, k = infos[int(err[0])]
-        reason = _lib.lib().otto_parquet_reason(int(err[1])).decode()
-        raise _lib.OttoError(f'{where}, page {k}: {explain(int(err[0]), reason) if explain else reason}') from None
+    _call('otto_parquet_decode', dev, d_bytes, int(n_bytes), table, len(table), cols, len(cols), int(phases), work, int(work.numel()),
+          infos=infos, reason_of='otto_parquet_reason', explain=explain)
     return work
 
 
@@ -353,6 +412,135 @@ def _read_full(f, view):
             break
         got += k
     return got
+
+
+def _read_chunk(f, view, o, c, where):
+    """The bytes of chunk ``c`` of the open file ``f``, read to ``view[o:]`` (a NumPy uint8 array) -> that stretch of ``view``"""
+    f.seek(c.start)
+    if _read_full(f, memoryview(view)[o:o + c.length]) != c.length:
+        raise _error(f'{where}: the column chunk runs past the end of the file')
+    return view[o:o + c.length]
+
+
+def _paths(paths):
+    return [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+
+
+def _plan_batches(sizes, batch_bytes):
+    """``sizes``: ``(stored bytes, budget bytes)`` per row group, in reading order -> the batches as lists of indices: greedy
+    runs of whole row groups whose budgets add up to ``batch_bytes`` at most; a single larger row group is its own batch."""
+    batches, cur, cur_bytes = [], [], 0
+    for i, (_, budget) in enumerate(sizes):
+        if cur and cur_bytes + budget > batch_bytes:
+            batches.append(cur)
+            cur, cur_bytes = [], 0
+        cur.append(i)
+        cur_bytes += budget
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+def _largest_batch(sizes, batches):
+    """``(stored bytes, budget bytes)`` of the largest batch, each on its own: what the staging sets must hold"""
+    return tuple(max([sum(sizes[i][k] for i in b) for b in batches], default=0) for k in (0, 1))
+
+
+def _stage_batches(dev, paths, batches, stage, room, fill, decode):
+    """The staging pipeline of :func:`read_columns` and :func:`read_lists`: two page-locked host sets of ``stage`` bytes and
+    two device sets of ``room`` bytes alternate; batch i + 1 is read and sent on a copy stream before batch i decodes on the
+    caller's stream. ``fill(batch, view, file)`` reads the batch into the NumPy ``view`` of a host set (``file(i)``: ``paths[i]``,
+    opened at first use and closed here) and returns ``(bytes, payload)``; ``decode(device set, bytes, payload)`` launches the
+    batch on the caller's stream. Returns, or raises, with every file closed and the device synchronised."""
+    import torch
+    if batches:
+        host = [torch.empty(max(stage, 16), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        devb = [torch.empty(max(room, 16), dtype=torch.uint8, device=dev) for _ in range(2)]
+        copy_stream = torch.cuda.Stream(device=dev)
+        compute = torch.cuda.current_stream(dev)
+        # the device sets come from the caller's stream's allocator: a block it freed may still be read by work queued there
+        copy_stream.wait_stream(compute)
+        sent = [torch.cuda.Event(), torch.cuda.Event()]      # H2D of the set finished
+        used = [torch.cuda.Event(), torch.cuda.Event()]      # the decode no longer reads the set
+    files = {}
+
+    def file(i):
+        if i not in files:
+            files[i] = open(paths[i], 'rb', buffering=0)
+        return files[i]
+
+    def prepared():
+        """(staging set, bytes, payload) per batch, read and on its way to the device"""
+        for i, batch in enumerate(batches):
+            b = i & 1
+            if i >= 2:
+                used[b].synchronize()                        # the set is free again, host and device side
+            n, payload = fill(batch, host[b].numpy(), file)
+            with torch.cuda.stream(copy_stream):
+                devb[b][:n].copy_(host[b][:n], non_blocking=True)
+                sent[b].record(copy_stream)
+            yield b, n, payload
+
+    try:
+        it = prepared()
+        cur = next(it, None)
+        while cur is not None:
+            nxt = next(it, None)                             # read and send batch i + 1 before batch i decodes
+            b, n, payload = cur
+            compute.wait_event(sent[b])
+            decode(devb[b], n, payload)
+            used[b].record(compute)
+            cur = nxt
+    finally:
+        for f in files.values():
+            f.close()
+        torch.cuda.synchronize(dev)
+
+
+def _chunk_records(table, infos, where, pages, row, slot, place):
+    """The OTTO_PQ records of one chunk's ``pages``, appended to ``table``, and their ``(where, page number)`` to ``infos``.
+    ``place(k, page)`` says how page k lies in the device buffer: ``(src_off, comp_size, uncomp_size, page_type, def_len,
+    rep_len, num_values, is_compressed)``, or None for a page that has no value to decode. ``row``: the output row of the
+    chunk's first value, ``slot``: its column record. Returns the row behind the chunk's last value."""
+    dict_slot = -1
+    for k, p in enumerate(pages):
+        is_dict = p.page_type == DICTIONARY_PAGE
+        coded = not is_dict and p.encoding == 8
+        if is_dict:
+            dict_slot = len(table)
+        elif coded and dict_slot < 0:
+            raise _error(f'{where}, page {k}: dictionary-coded page without a dictionary page')
+        rec = place(k, p)
+        if rec is not None:
+            table.append((*rec[:4], p.encoding, *rec[4:], row, slot, dict_slot if coded else -1))
+            infos.append((where, k))
+            row += 0 if is_dict else rec[6]
+    return row
+
+
+def _as_stored(p, src, num_values=None):
+    """The ``place`` of a page that is decoded as it lies in the file, its body at ``src`` of the device buffer"""
+    return src, p.comp_size, p.uncomp_size, p.page_type, p.def_len, p.rep_len, p.num_values if num_values is None else num_values, p.is_compressed
+
+
+def _column_slot(cols, slots, j, physical, logical, out):
+    """The slot of the column record that stores values of ``physical`` / ``logical`` type into ``out``, the tensor of output
+    column ``j``: one record per (column, physical size, uint32 extension), appended to ``cols`` when it is new"""
+    key = (j, 4 if physical in (1, FLOAT) else 8, int(physical == 1 and logical == ('INT', 32, False)))
+    if key not in slots:
+        slots[key] = len(cols)
+        cols.append((out.data_ptr(), out.element_size(), out.numel(), key[1], key[2]))
+    return slots[key]
+
+
+def _fill_out(out, result, what):
+    """``result`` copied into the caller's ``out`` tensors, which must match it in number, shape, dtype and device"""
+    out = tuple(out)
+    if len(out) != len(result) or any(o.shape != r.shape or o.dtype != r.dtype or o.device != r.device for o, r in zip(out, result)):
+        raise ValueError(f'out: expected {what} with the shape, dtype and device of the result')
+    for o, r in zip(out, result):
+        o.copy_(r)
+    return out
 
 
 def read_columns(paths, columns, device, dtypes=None, batch_bytes=256 << 20, out=None, floats=False):
@@ -370,16 +558,12 @@ def read_columns(paths, columns, device, dtypes=None, batch_bytes=256 << 20, out
     back clean."""
     import torch
     from . import _lib
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise _lib.OttoError('parquet.read_columns needs a ROCm device (no CPU fallback)')
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _lib.rocm_device(device, 'parquet.read_columns')
     _lib.lib()
-    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
+    paths = _paths(paths)
     columns = list(columns)
     dtypes = dict(dtypes or {})
-    sizes = {torch.uint8: 1, torch.int8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
+    sizes = _sizes()
     metas = [read_metadata(p) for p in paths]
     leaves = [[check_column(m, c, floats) for c in columns] for m in metas]
     col_dt = []
@@ -393,106 +577,42 @@ def read_columns(paths, columns, device, dtypes=None, batch_bytes=256 << 20, out
         if dt not in sizes and not dt.is_floating_point:
             raise ValueError(f'dtypes[{c!r}]: {dt} is not one of {sorted(map(str, sizes))}')
         col_dt.append(dt)
-    sizes = {**sizes, torch.float32: 4, torch.float64: 8}
     # the batches: runs of whole row groups, over all files
-    groups = []                                               # (file, row group, chunks, first row, compressed bytes, both)
-    row = 0
+    groups, extents, row = [], [], 0                          # (file, row group, chunks, first row); (compressed bytes, both)
     for fi, m in enumerate(metas):
         for g in range(len(m.row_groups)):
             chunks = check_row_group(m, g, columns)
             comp = sum((c.length + 15) & ~15 for c in chunks)
-            groups.append((fi, g, chunks, row, comp, comp + sum(c.uncompressed for c in chunks)))
+            groups.append((fi, g, chunks, row))
+            extents.append((comp, comp + sum(c.uncompressed for c in chunks)))
             row += m.row_groups[g].num_rows
     n_rows = row
-    batches, cur, cur_bytes = [], [], 0
-    for gr in groups:
-        if cur and cur_bytes + gr[5] > batch_bytes:
-            batches.append(cur)
-            cur, cur_bytes = [], 0
-        cur.append(gr)
-        cur_bytes += gr[5]
-    if cur:
-        batches.append(cur)
-    stage = max([sum(gr[4] for gr in b) for b in batches], default=0)
+    batches = _plan_batches(extents, batch_bytes)
+    stage, _ = _largest_batch(extents, batches)
     if stage >= 1 << 31:
         raise _lib.OttoError(f'a row group of {stage} compressed bytes does not fit one call (2^31)')
     with torch.cuda.device(dev):
         result = [torch.empty(n_rows, dtype=dt, device=dev) for dt in col_dt]
-        if batches:
-            host = [torch.empty(max(stage, 16), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-            devb = [torch.empty(max(stage, 16), dtype=torch.uint8, device=dev) for _ in range(2)]
-            copy_stream = torch.cuda.Stream(device=dev)
-            compute = torch.cuda.current_stream(dev)
-            # the device sets come from the caller's stream's allocator: a block it freed may still be read by work queued there
-            copy_stream.wait_stream(compute)
-            sent = [torch.cuda.Event(), torch.cuda.Event()]      # H2D of the set finished
-            used = [torch.cuda.Event(), torch.cuda.Event()]      # the decode no longer reads the set
-        files = {}
 
-        def prepared():
-            """(staging set, bytes, page table, column records, page infos) per batch, read and on its way to the device"""
-            for i, batch in enumerate(batches):
-                b = i & 1
-                if i >= 2:
-                    used[b].synchronize()                        # the set is free again, host and device side
-                view = host[b].numpy()
-                table, infos, o = [], [], 0
-                cols, slots = [], {}                             # one record per (column, physical size, extension) of the batch
-                for fi, g, chunks, row0, _, _ in batch:
-                    m = metas[fi]
-                    if fi not in files:
-                        files[fi] = open(m.path, 'rb', buffering=0)
-                    f = files[fi]
-                    for j, c in enumerate(chunks):
-                        where = _where(m, c.name, g)
-                        f.seek(c.start)
-                        if _read_full(f, memoryview(view)[o:o + c.length]) != c.length:
-                            raise _lib.OttoError(f'{where}: the column chunk runs past the end of the file')
-                        leaf = leaves[fi][j]
-                        key = (j, 4 if leaf.physical in (1, FLOAT) else 8, int(leaf.physical == 1 and leaf.logical == ('INT', 32, False)))
-                        if key not in slots:
-                            slots[key] = len(cols)
-                            cols.append((result[j].data_ptr(), sizes[col_dt[j]], n_rows, key[1], key[2]))
-                        dict_slot, r = -1, row0
-                        for k, p in enumerate(walk_pages(view[o:o + c.length], c, leaf, where)):
-                            if p.page_type == DICTIONARY_PAGE:
-                                dict_slot = len(table)
-                            elif p.encoding == 8 and dict_slot < 0:
-                                raise _lib.OttoError(f'{where}, page {k}: dictionary-coded page without a dictionary page')
-                            table.append((o + p.src_off, p.comp_size, p.uncomp_size, p.page_type, p.encoding, p.def_len, p.rep_len,
-                                          p.num_values, p.is_compressed, r, slots[key],
-                                          dict_slot if p.page_type != DICTIONARY_PAGE and p.encoding == 8 else -1))
-                            infos.append((where, k))
-                            if p.page_type != DICTIONARY_PAGE:
-                                r += p.num_values
-                        o += (c.length + 15) & ~15
-                with torch.cuda.stream(copy_stream):
-                    devb[b][:o].copy_(host[b][:o], non_blocking=True)
-                    sent[b].record(copy_stream)
-                yield b, o, table, cols, infos
+        def fill(batch, view, file):
+            table, infos, o = [], [], 0
+            cols, slots = [], {}                             # one record per (column, physical size, extension) of the batch
+            for fi, g, chunks, row0 in (groups[i] for i in batch):
+                f = file(fi)
+                for j, c in enumerate(chunks):
+                    where, leaf = _where(metas[fi], c.name, g), leaves[fi][j]
+                    pages = walk_pages(_read_chunk(f, view, o, c, where), c, leaf, where)
+                    slot = _column_slot(cols, slots, j, leaf.physical, leaf.logical, result[j])
+                    _chunk_records(table, infos, where, pages, row0, slot, lambda k, p: _as_stored(p, o + p.src_off))
+                    o += (c.length + 15) & ~15
+            return o, (table, cols, infos)
 
-        try:
-            it = prepared()
-            cur = next(it, None)
-            while cur is not None:
-                nxt = next(it, None)                             # read and send batch i + 1 before batch i decodes
-                b, n, table, cols, infos = cur
-                compute.wait_event(sent[b])
-                if table:
-                    _decode(dev, devb[b], n, table, cols, infos)
-                used[b].record(compute)
-                cur = nxt
-        finally:
-            for f in files.values():
-                f.close()
-            torch.cuda.synchronize(dev)
+        def decode(d_bytes, n, payload):
+            if payload[0]:
+                _decode(dev, d_bytes, n, *payload)
+        _stage_batches(dev, [m.path for m in metas], batches, stage, stage, fill, decode)
         if out is not None:
-            out = tuple(out)
-            if len(out) != len(result) or any(o.shape != r.shape or o.dtype != r.dtype or o.device != r.device for o, r in zip(out, result)):
-                raise ValueError('out: expected one tensor per column with the shape, dtype and device of the result')
-            for o, r in zip(out, result):
-                o.copy_(r)
-            return out
+            return _fill_out(out, result, 'one tensor per column')
     return tuple(result)
 
 
@@ -533,35 +653,15 @@ def snappy_decompress(d_bytes, src_off, src_len, dst_len, out=None, dst_off=None
 # ---------------------------------------------------------------------------------------------------------------------
 # list columns (include/otto_pqlist.h, SPEC-PQLIST) and dictionary-coded string columns: val_labels.parquet
 # ---------------------------------------------------------------------------------------------------------------------
-PL_FIELDS = ('body_off', 'body_len', 'page_type', 'rep_len', 'def_len', 'num_values', 'flags', 'chunk_rows', 'chunk_pages')   # OTTO_PL_*
-PL_OUTER_OPTIONAL, PL_ELEM_OPTIONAL, PL_CHUNK_FIRST = 1, 2, 4
-BYTE_ARRAY = 6
-MAX_STRING_DICTIONARY = 64 << 10
-
-ListLeaf = namedtuple('ListLeaf', 'name path physical logical outer_optional elem_optional')
-ListMetadata = namedtuple('ListMetadata', 'path num_rows leaf row_groups')       # row_groups: [(num_rows, Chunk or None)]
-
-
 def read_list_metadata(path, column):
     """The footer of ``path`` for the list column ``column`` -> :class:`ListMetadata`. Accepted is the three-level LIST form
     of SPEC-PQLIST under any field names; every other nested form raises the ``OttoError`` that names it."""
-    path, foot = _footer(path)
-    try:
-        md = _Thrift(foot).struct()
-        schema = md[2]
-
-        def skip(j):
-            kids = schema[j].get(5, 0) or 0
-            j += 1
-            for _ in range(kids):
-                j = skip(j)
-            return j
-        i, at, names = 1, None, []
-        for _ in range(schema[0].get(5, 0) or 0):
-            names.append(schema[i][4].decode())
+    def consume(path, md, schema):
+        at, names = None, []
+        for i, el in _top_level(schema):
+            names.append(el[4].decode())
             if names[-1] == column and at is None:
                 at = i
-            i = skip(i)
         pre = f'{path}: column {column!r}'
         if at is None:
             raise _error(f'{pre}: not in the file (top-level columns: {names})')
@@ -600,73 +700,19 @@ def read_list_metadata(path, column):
         for rg in md.get(4, []):
             chunk = None
             for cc in rg[1]:
-                cm = cc[3]
-                if [p.decode() for p in cm[3]] == pathn:
-                    dpo, dico = cm[9], cm.get(11)
-                    start = dico if dico is not None and 0 < dico < dpo else dpo
-                    chunk = Chunk(column, cm[1], cm[4], cm[5], start, cm[7], dpo, dico, cm[6], tuple(cm[2]))
+                if [p.decode() for p in cc[3][3]] == pathn:
+                    chunk = _chunk(column, cc[3])
             groups.append((rg[3], chunk))
         return ListMetadata(path, md[3], leaf, groups)
-    except (ValueError, KeyError, IndexError) as e:
-        raise _error(f'{path}: malformed footer ({e})') from None
+    return _parse_footer(path, consume)
 
 
 def _list_chunk(meta, g):
     n_rows, c = meta.row_groups[g]
     where = _where(meta, meta.leaf.name, g)
-    if c is None:
-        raise _error(f'{where}: no column chunk')
-    if c.codec not in (0, 1):
-        raise _error(f'{where}: codec {_name(CODECS, c.codec)} is not supported (UNCOMPRESSED, SNAPPY)')
-    if c.physical != meta.leaf.physical:
+    if _check_chunk(c, where).physical != meta.leaf.physical:
         raise _error(f'{where}: the chunk holds {_name(PHYSICAL, c.physical)}, the schema declares {_name(PHYSICAL, meta.leaf.physical)}')
     return n_rows, c, where
-
-
-def walk_list_pages(buf, chunk, leaf, where):
-    """:func:`walk_pages` for the chunk of a list column: ``num_values`` counts level entries, a V1 page declares both
-    level encodings (RLE; BIT_PACKED is refused by name), a V2 page both level lengths."""
-    pages, pos, seen, k = [], 0, 0, 0
-    n = min(len(buf), chunk.length)
-    snappy = chunk.codec == 1
-    while seen < chunk.num_values and pos < n:
-        t = _Thrift(buf, pos)
-        try:
-            h = t.struct()
-            ptype, uncomp, comp = h[1], h[2], h[3]
-        except (ValueError, KeyError) as e:
-            raise _error(f'{where}, page {k}: malformed page header ({e})') from None
-        body = t.i
-        if comp < 0 or uncomp < 0 or body + comp > n:
-            raise _error(f'{where}, page {k}: the page runs past its column chunk')
-        if ptype == DICTIONARY_PAGE:
-            d = h.get(7, {})
-            if d.get(2, 0) not in (0, 2):
-                raise _error(f'{where}, page {k}: dictionary page encoding {_name(ENCODINGS, d.get(2))} is not supported')
-            pages.append(Page(pos, body, comp, uncomp, ptype, 0, 0, 0, d.get(1, 0), int(snappy)))
-        elif ptype == DATA_PAGE:
-            d = h.get(5, {})
-            enc = _data_encoding(d.get(2, 0), leaf, where, k)
-            for what, e in (('definition', d.get(3, 3)), ('repetition', d.get(4, 3))):
-                if e != 3:
-                    raise _error(f'{where}, page {k}: {what} level encoding {_name(ENCODINGS, e)} is not supported (RLE)')
-            pages.append(Page(pos, body, comp, uncomp, ptype, enc, 0, 0, d.get(1, 0), int(snappy)))
-            seen += d.get(1, 0)
-        elif ptype == DATA_PAGE_V2:
-            d = h.get(8, {})
-            enc = _data_encoding(d.get(4, 0), leaf, where, k)
-            dl, rl = d.get(5, 0), d.get(6, 0)
-            if dl < 0 or rl < 0 or dl + rl > comp or dl + rl > uncomp:
-                raise _error(f'{where}, page {k}: level lengths run past the page body')
-            pages.append(Page(pos, body, comp, uncomp, ptype, enc, dl, rl, d.get(1, 0), int(snappy and d.get(7, True))))
-            seen += d.get(1, 0)
-        elif ptype != INDEX_PAGE:
-            raise _error(f'{where}, page {k}: page type {ptype} is not supported')
-        pos = body + comp
-        k += 1
-    if seen != chunk.num_values:
-        raise _error(f'{where}: the pages hold {seen} level entries, the column chunk declares {chunk.num_values}')
-    return pages
 
 
 def list_page_table(path, column):
@@ -678,7 +724,7 @@ def list_page_table(path, column):
         for g in range(len(meta.row_groups)):
             _, c, where = _list_chunk(meta, g)
             f.seek(c.start)
-            out[g] = walk_list_pages(f.read(c.length), c, meta.leaf, where)
+            out[g] = walk_pages(f.read(c.length), c, meta.leaf, where)
     return meta, out
 
 
@@ -700,15 +746,7 @@ def _list_levels(dev, buf, n_bytes, table, infos, d_off, d_null, n_rows, value_b
     elif _lib.need(work, 'work', torch.uint8, 1, device=dev).numel() < need:
         raise ValueError(f'work: {work.numel()} bytes, {need} are needed')
     job.d_work, job.work_bytes = _lib.ptr(work, dev), int(work.numel())
-    err = np.full(2, -1, dtype=np.int64)
-    try:
-        _lib.call('otto_pqlist_levels', dev, C.byref(job), err, stream=False)
-    except _lib.OttoError:
-        if err[0] < 0:
-            raise
-        where, k = infos[int(err[0])]
-        reason = _lib.lib().otto_pqlist_reason(int(err[1])).decode()
-        raise _lib.OttoError(f'{where}, page {k}: {reason}') from None
+    _call('otto_pqlist_levels', dev, C.byref(job), infos=infos, reason_of='otto_pqlist_reason', stream=False)
     return report
 
 
@@ -753,7 +791,6 @@ def _decode_list_batch(dev, buf, o, items, d_off, d_null, n_rows, value_base, dt
     rows' offsets and null flags go to ``d_off`` / ``d_null``. ``buf`` has room behind ``o`` for the decoded V1 bodies."""
     import torch
     from . import _lib
-    sizes = {torch.uint8: 1, torch.int8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
     pl, pl_infos, bodies, streams, at = _list_plan(items, o)
     if at > buf.numel() or at >= 1 << 31:
         raise _lib.OttoError(f'{items[0][0]}: the pages decode to more bytes than the column chunks declare')
@@ -764,44 +801,27 @@ def _decode_list_batch(dev, buf, o, items, d_off, d_null, n_rows, value_base, dt
         _lib.call('otto_parquet_snappy', dev, buf, at, a(0), a(1), a(2), a(3), len(streams), buf, at, status, sw, int(sw.numel()))
         bad = np.flatnonzero(status)
         if len(bad):
-            s = streams[int(bad[0])]
-            raise _lib.OttoError(f'{s[4]}, page {s[5]}: {_lib.lib().otto_parquet_reason(int(status[bad[0]])).decode()}')
+            raise _refusal([s[4:] for s in streams], int(bad[0]), int(status[bad[0]]), 'otto_parquet_reason')
     report = _list_levels(dev, buf, at, pl, pl_infos, d_off, d_null, n_rows, value_base, work)
     n_values = int(report[:, 1].sum()) if len(report) else 0
     values = torch.empty(n_values, dtype=dt, device=dev)
     table, infos, cols, slots, announced = [], [], [], {}, []
-    row, r = 0, 0
-    for it, (where, leaf, rows, base, pages) in enumerate(items):
-        key = (4 if leaf.physical == 1 else 8, int(leaf.physical == 1 and leaf.logical == ('INT', 32, False)))
-        if key not in slots:
-            slots[key] = len(cols)
-            cols.append((values.data_ptr(), sizes[dt], n_values, key[0], key[1]))
-        dict_slot = -1
-        for k, p in enumerate(pages):
+    data_pages = iter(zip(bodies, report.tolist()))           # in the order of _list_plan's records
+    row = 0
+    for where, leaf, rows, base, pages in items:
+        def place(k, p):
+            """a dictionary page as it lies in the file, a V2 data page too, a V1 data page as the level-free rest of its body"""
             if p.page_type == DICTIONARY_PAGE:
-                dict_slot = len(table)
-                table.append((base + p.src_off, p.comp_size, p.uncomp_size, p.page_type, 0, 0, 0, p.num_values, p.is_compressed, row, slots[key], -1))
-                infos.append((where, k))
                 announced.append(None)
-                continue
-            body, blen = bodies[r]
-            lev, nv = int(report[r, 0]), int(report[r, 1])
-            r += 1
-            if p.encoding == 8 and dict_slot < 0:
-                raise _lib.OttoError(f'{where}, page {k}: dictionary-coded page without a dictionary page')
-            ds = dict_slot if p.encoding == 8 else -1
-            if p.page_type == DATA_PAGE_V2:
-                if nv == 0 and p.comp_size == lev:
-                    continue
-                table.append((base + p.src_off, p.comp_size, p.uncomp_size, p.page_type, p.encoding, p.def_len, p.rep_len, nv, p.is_compressed,
-                              row, slots[key], ds))
-            else:
-                if nv == 0 and blen == lev:
-                    continue
-                table.append((body + lev, blen - lev, blen - lev, DATA_PAGE, p.encoding, 0, 0, nv, 0, row, slots[key], ds))
-            infos.append((where, k))
+                return _as_stored(p, base + p.src_off)
+            (body, blen), (lev, nv, _) = next(data_pages)
+            if nv == 0 and (p.comp_size if p.page_type == DATA_PAGE_V2 else blen) == lev:
+                return None
             announced.append(nv)
-            row += nv
+            if p.page_type == DATA_PAGE_V2:
+                return _as_stored(p, base + p.src_off, nv)
+            return body + lev, blen - lev, blen - lev, DATA_PAGE, 0, 0, nv, 0
+        row = _chunk_records(table, infos, where, pages, row, _column_slot(cols, slots, 0, leaf.physical, leaf.logical, values), place)
     if table:
         _decode(dev, buf, at, table, cols, infos,
                 explain=lambda i, reason: reason if announced[i] is None else
@@ -823,98 +843,47 @@ def read_lists(paths, column, device, dtype=None, batch_bytes=256 << 20, out=Non
     every batch came back clean."""
     import torch
     from . import _lib
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise _lib.OttoError('parquet.read_lists needs a ROCm device (no CPU fallback)')
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _lib.rocm_device(device, 'parquet.read_lists')
     _lib.lib()
-    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
-    metas = [read_list_metadata(p, column) for p in paths]
+    metas = [read_list_metadata(p, column) for p in _paths(paths)]
     dt = dtype or (default_dtype(metas[0].leaf) if metas else torch.int64)
-    if dt not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+    if dt not in _sizes():
         raise ValueError(f'dtype: {dt} is not an integer dtype of 1, 2, 4 or 8 bytes')
-    groups, row = [], 0                                       # (file, row group, chunk, where, rows, first row, stored bytes, with bodies)
+    groups, extents, row = [], [], 0                          # (file, chunk, where, rows, first row); (stored bytes, with bodies)
     for fi, m in enumerate(metas):
         for g in range(len(m.row_groups)):
             n, c, where = _list_chunk(m, g)
             comp = (c.length + 15) & ~15
-            groups.append((fi, g, c, where, n, row, comp, comp + (c.uncompressed if c.codec == 1 else 0)))
+            groups.append((fi, c, where, n, row))
+            extents.append((comp, comp + (c.uncompressed if c.codec == 1 else 0)))
             row += n
     n_rows = row
-    batches, cur, cur_bytes = [], [], 0
-    for gr in groups:
-        if cur and cur_bytes + gr[7] > batch_bytes:
-            batches.append(cur)
-            cur, cur_bytes = [], 0
-        cur.append(gr)
-        cur_bytes += gr[7]
-    if cur:
-        batches.append(cur)
-    stage = max([sum(gr[6] for gr in b) for b in batches], default=0)
-    room = max([sum(gr[7] for gr in b) for b in batches], default=0)
+    batches = _plan_batches(extents, batch_bytes)
+    stage, room = _largest_batch(extents, batches)
     if room >= 1 << 31:
         raise _lib.OttoError(f'a row group of {room} stored plus decoded bytes does not fit one call (2^31)')
     with torch.cuda.device(dev):
         off = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
         null = torch.zeros(n_rows, dtype=torch.uint8, device=dev)
         parts, n_values = [], 0
-        if batches:
-            host = [torch.empty(max(stage, 16), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-            devb = [torch.empty(max(room, 16), dtype=torch.uint8, device=dev) for _ in range(2)]
-            copy_stream = torch.cuda.Stream(device=dev)
-            compute = torch.cuda.current_stream(dev)
-            copy_stream.wait_stream(compute)                     # as read_columns: the sets come from the caller's stream's allocator
-            sent = [torch.cuda.Event(), torch.cuda.Event()]
-            used = [torch.cuda.Event(), torch.cuda.Event()]
-        files = {}
 
-        def prepared():
-            for i, batch in enumerate(batches):
-                b = i & 1
-                if i >= 2:
-                    used[b].synchronize()
-                view = host[b].numpy()
-                items, o = [], 0
-                for fi, g, c, where, n, row0, _, _ in batch:
-                    m = metas[fi]
-                    if fi not in files:
-                        files[fi] = open(m.path, 'rb', buffering=0)
-                    f = files[fi]
-                    f.seek(c.start)
-                    if _read_full(f, memoryview(view)[o:o + c.length]) != c.length:
-                        raise _lib.OttoError(f'{where}: the column chunk runs past the end of the file')
-                    items.append((where, m.leaf, n, o, walk_list_pages(view[o:o + c.length], c, m.leaf, where)))
-                    o += (c.length + 15) & ~15
-                with torch.cuda.stream(copy_stream):
-                    devb[b][:o].copy_(host[b][:o], non_blocking=True)
-                    sent[b].record(copy_stream)
-                yield b, o, items, batch[0][5], sum(gr[4] for gr in batch)
+        def fill(batch, view, file):
+            items, o = [], 0
+            for fi, c, where, n, _ in (groups[i] for i in batch):
+                leaf = metas[fi].leaf
+                items.append((where, leaf, n, o, walk_pages(_read_chunk(file(fi), view, o, c, where), c, leaf, where)))
+                o += (c.length + 15) & ~15
+            return o, (items, groups[batch[0]][4], sum(groups[i][3] for i in batch))
 
-        try:
-            it = prepared()
-            cur = next(it, None)
-            while cur is not None:
-                nxt = next(it, None)                             # read and send batch i + 1 before batch i decodes
-                b, o, items, row0, rows = cur
-                compute.wait_event(sent[b])
-                v = _decode_list_batch(dev, devb[b], o, items, off[row0:], null[row0:], rows, n_values, dt)
-                used[b].record(compute)
-                parts.append(v)
-                n_values += int(v.numel())
-                cur = nxt
-        finally:
-            for f in files.values():
-                f.close()
-            torch.cuda.synchronize(dev)
+        def decode(d_bytes, o, payload):
+            nonlocal n_values
+            items, row0, rows = payload
+            parts.append(_decode_list_batch(dev, d_bytes, o, items, off[row0:], null[row0:], rows, n_values, dt))
+            n_values += int(parts[-1].numel())
+        _stage_batches(dev, [m.path for m in metas], batches, stage, room, fill, decode)
         values = parts[0] if len(parts) == 1 else torch.cat(parts) if parts else torch.empty(0, dtype=dt, device=dev)
         if out is not None:
-            out, result = tuple(out), (off, values, null)
-            if len(out) != 3 or any(o.shape != r.shape or o.dtype != r.dtype or o.device != r.device for o, r in zip(out, result)):
-                raise ValueError('out: expected (off, values, null) with the shape, dtype and device of the result')
-            for o, r in zip(out, result):
-                o.copy_(r)
-            return out
+            return _fill_out(out, (off, values, null), '(off, values, null)')
     return off, values, null
 
 
@@ -992,11 +961,7 @@ def string_code_table(path, column, mapping):
     """Host only: the plan of :func:`read_string_codes` for one file, with every refusal the host can make ->
     ``(num_rows, [(where, chunk, [Page], {page number: int32 codes of that dictionary page})] per row group)``."""
     meta = read_metadata(path)
-    leaf = next((l for l in meta.leaves if l.name == column), None)
-    if leaf is None:
-        raise _error(f'{meta.path}: column {column!r}: not in the file (top-level columns: {[l.name for l in meta.leaves]})')
-    if leaf.nested or leaf.repetition == REPEATED:
-        raise _error(f'{meta.path}: column {column!r}: a repeated or nested column is not supported')
+    leaf = _flat_leaf(meta, column)
     if leaf.physical != BYTE_ARRAY:
         raise _error(f'{meta.path}: column {column!r}: physical type {_name(PHYSICAL, leaf.physical)} is no string column (BYTE_ARRAY)')
     codes = {(k.encode() if isinstance(k, str) else bytes(k)): int(v) for k, v in mapping.items()}
@@ -1035,24 +1000,19 @@ def read_string_codes(paths, column, mapping, device, dtype=None):
     piece (a string column of three values is a few bytes per thousand rows)."""
     import torch
     from . import _lib
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise _lib.OttoError('parquet.read_string_codes needs a ROCm device (no CPU fallback)')
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = _lib.rocm_device(device, 'parquet.read_string_codes')
     _lib.lib()
     dt = dtype or torch.uint8
-    sizes = {torch.uint8: 1, torch.int8: 1, torch.int16: 2, torch.int32: 4, torch.int64: 8}
+    sizes = _sizes()
     if dt not in sizes:
         raise ValueError(f'dtype: {dt} is not one of {sorted(map(str, sizes))}')
     lo, hi = (0, 1 << 8 * sizes[dt]) if dt == torch.uint8 else (-(1 << 8 * sizes[dt] - 1), 1 << 8 * sizes[dt] - 1)
     for s, v in mapping.items():
         if not lo <= int(v) < min(hi, 1 << 31):
             raise ValueError(f'mapping[{s!r}]: {v} does not fit {dt}')
-    paths = [paths] if isinstance(paths, (str, bytes, os.PathLike)) else list(paths)
-    plans = [string_code_table(p, column, mapping) for p in paths]
+    plans = [string_code_table(p, column, mapping) for p in _paths(paths)]
     n_rows = sum(p[0] for p in plans)
-    pieces, table, infos, o, row = [], [], [], 0, 0
+    pieces, table, infos, cols, o, row = [], [], [], [], 0, 0
 
     def put(b):
         nonlocal o
@@ -1065,21 +1025,16 @@ def read_string_codes(paths, column, mapping, device, dtype=None):
         return at
     with torch.cuda.device(dev):
         result = torch.empty(n_rows, dtype=dt, device=dev)
-        cols = [(result.data_ptr(), sizes[dt], n_rows, 4, 0)]
+        slot = _column_slot(cols, {}, 0, 1, None, result)      # the device sees an INT32 dictionary
         for _, groups in plans:
             for where, c, buf, pages, dicts in groups:
-                dict_slot = -1
-                for k, p in enumerate(pages):
+                def place(k, p):
+                    """the host-built INT32 dictionary in place of the string one, an index page as it lies in the file"""
                     if p.page_type == DICTIONARY_PAGE:
-                        at = put(dicts[k].tobytes())
-                        dict_slot = len(table)
-                        table.append((at, 4 * len(dicts[k]), 4 * len(dicts[k]), DICTIONARY_PAGE, 0, 0, 0, len(dicts[k]), 0, row, 0, -1))
-                    else:
-                        at = put(bytes(buf[p.src_off:p.src_off + p.comp_size]))
-                        table.append((at, p.comp_size, p.uncomp_size, p.page_type, 8, p.def_len, p.rep_len, p.num_values, p.is_compressed, row, 0,
-                                      dict_slot))
-                        row += p.num_values
-                    infos.append((where, k))
+                        n = len(dicts[k])
+                        return put(dicts[k].tobytes()), 4 * n, 4 * n, DICTIONARY_PAGE, 0, 0, n, 0
+                    return _as_stored(p, put(bytes(buf[p.src_off:p.src_off + p.comp_size])))
+                row = _chunk_records(table, infos, where, pages, row, slot, place)
         if o >= 1 << 31:
             raise _lib.OttoError(f'column {column!r}: {o} bytes of index pages do not fit one call (2^31)')
         if table:
