@@ -54,29 +54,31 @@ def _path(hs, ctx):
     return [int(n) for n in hs['path_node'][lo:hi]], [1.0 - ((code >> j) & 1) for j in range(hi - lo)]
 
 
-def step_sequential_hs(p, cum, In, Out, Syn1, hs, seed, epoch, neg, lr, t0, t1):
+def step_sequential_hs(p, cum, In, Out, Syn1, hs, seed, epoch, neg, lr, t0, t1, dtype=np.float64):
     """Hogwild without races: centres in order, in place; per pair the path of the context on Syn1, then the 1 + neg
-    targets on Out, then h += grad. Returns the loss sum; In / Out / Syn1 (float32) are updated."""
+    targets on Out, then h += grad. Returns the loss sum; In / Out / Syn1 (float32) are updated. dtype: as in
+    sgns_restatement.step_sequential."""
     n_aids = In.shape[0]
     ctx_all, neg_all = sr.negatives(p, cum, seed, epoch, neg, t0, t1, n_aids)
-    lr = float(np.float32(lr))
+    f = float if np.dtype(dtype) == np.float64 else np.dtype(dtype).type
+    lr = f(np.float32(lr))
     loss, q = 0.0, 0
     for c in range(t0, t1):
         ca = int(p['tok_aid'][c])
         npair = int(p['pair_off'][c + 1] - p['pair_off'][c])
         if npair == 0:
             continue
-        h = In[ca].astype(np.float64)
+        h = In[ca].astype(dtype)
         for _ in range(npair):
             grad = np.zeros_like(h)
             nodes, labels = _path(hs, int(ctx_all[q]))
             targets = [(Syn1, n, lab) for n, lab in zip(nodes, labels)]
             targets += [(Out, int(t), 1.0 if m == 0 else 0.0) for m, t in enumerate([ctx_all[q], *neg_all[q]])]
             for tab, t, label in targets:
-                o = tab[t].astype(np.float64)
-                x = float(h @ o)
-                g = lr * (label - sr._sigmoid(x))
-                loss += sr._softplus(-x if label else x)
+                o = tab[t].astype(dtype)
+                x = f(h @ o)
+                g = lr * (f(label) - sr._sigmoid(x))
+                loss += float(sr._softplus(-x if label else x))
                 grad += g * o
                 tab[t] = (o + g * h).astype(np.float32)
             h = h + grad

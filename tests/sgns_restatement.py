@@ -98,33 +98,37 @@ def negatives(p, cum, seed, epoch, neg, t0, t1, n_aids):
 
 
 def _sigmoid(x):
-    return 1.0 / (1.0 + np.exp(-x)) if x >= 0 else np.exp(x) / (1.0 + np.exp(x))
+    one = type(x)(1)                    # the arithmetic stays in the type of x (a Python float, np.float64 or np.float32)
+    return one / (one + np.exp(-x)) if x >= 0 else np.exp(x) / (one + np.exp(x))
 
 
 def _softplus(z):
-    return max(z, 0.0) + np.log1p(np.exp(-abs(z)))
+    return max(z, type(z)(0)) + np.log1p(np.exp(-abs(z)))
 
 
-def step_sequential(p, cum, In, Out, seed, epoch, neg, lr, t0, t1):
-    """Hogwild without races: centres in order, in place. Returns the loss sum; In / Out (float32) are updated."""
+def step_sequential(p, cum, In, Out, seed, epoch, neg, lr, t0, t1, dtype=np.float64):
+    """Hogwild without races: centres in order, in place. Returns the loss sum; In / Out (float32) are updated.
+    dtype: the type of h, o, x, g and grad (np.float32 states what a float32 run of this loop gives: the noise floor of
+    tests/test_sgns_hogwild_cpu.py); the loss is summed in float64 either way."""
     n_aids = In.shape[0]
     ctx_all, neg_all = negatives(p, cum, seed, epoch, neg, t0, t1, n_aids)
-    lr = float(np.float32(lr))
+    f = float if np.dtype(dtype) == np.float64 else np.dtype(dtype).type
+    lr = f(np.float32(lr))
     loss, q = 0.0, 0
     for c in range(t0, t1):
         ca = int(p['tok_aid'][c])
         npair = int(p['pair_off'][c + 1] - p['pair_off'][c])
         if npair == 0:
             continue
-        h = In[ca].astype(np.float64)
+        h = In[ca].astype(dtype)
         for _ in range(npair):
             grad = np.zeros_like(h)
             for m, t in enumerate([int(ctx_all[q])] + [int(x) for x in neg_all[q]]):
-                o = Out[t].astype(np.float64)
-                x = float(h @ o)
-                label = 1.0 if m == 0 else 0.0
+                o = Out[t].astype(dtype)
+                x = f(h @ o)
+                label = f(1.0 if m == 0 else 0.0)
                 g = lr * (label - _sigmoid(x))
-                loss += _softplus(-x if m == 0 else x)
+                loss += float(_softplus(-x if m == 0 else x))
                 grad += g * o
                 Out[t] = (o + g * h).astype(np.float32)
             h = h + grad
