@@ -120,6 +120,12 @@ class PqwJob(C.Structure):
                 ('d_work', C.c_void_p), ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
 
 
+class SnappyJob(C.Structure):
+    # mirrors otto_snappy_job (include/otto_snappy.h)
+    _fields_ = [('d_in', C.c_void_p), ('n_bytes', C.c_int64), ('src_off', C.c_void_p), ('src_len', C.c_void_p), ('n_streams', C.c_int64),
+                ('d_work', C.c_void_p), ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
+
+
 class RowsJob(C.Structure):
     # mirrors otto_rows_job (include/otto_rows.h)
     _fields_ = [('d_aid_x', C.c_void_p), ('d_aid_y', C.c_void_p), ('d_wgt', C.c_void_p), ('n_rows', C.c_int64), ('d_y', C.c_void_p),
@@ -322,6 +328,11 @@ SIGNATURES = {
     'otto_deflate_workspace': (_i64, [_i64, _i32]),
     'otto_deflate_plan': (_i32, [_vp, _i64, _i32, _p_i64, _vp, _i64, _vp]),
     'otto_deflate_emit': (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
+    # include/otto_snappy.h
+    'otto_snappy_bound': (_i64, [_i64]),
+    'otto_snappy_workspace': (_i64, [C.POINTER(SnappyJob)]),
+    'otto_snappy_plan': (_i32, [C.POINTER(SnappyJob), _vp]),
+    'otto_snappy_emit': (_i32, [C.POINTER(SnappyJob), _vp, _vp, _i64]),
     # include/otto_pqwrite.h
     'otto_pqw_workspace': (_i64, [C.POINTER(PqwJob)]),
     'otto_pqw_plan': (_i32, [C.POINTER(PqwJob), _vp]),

@@ -10,6 +10,9 @@ Usage (same convention as every reference script, ``src/covisitation/inference.p
                                       encode the part files on the device (``parquet_write.encode_tables``: aid_x and aid_y
                                       as DELTA_BINARY_PACKED pages, wgt PLAIN, no compressor) instead of copying the rows
                                       to the host for pyarrow; same names, part counts, rows and dtypes
+    python builder.py <mode> --device-write --compression snappy
+                                      the wgt pages are Snappy streams made on the device (``otto_amd.snappy``); aid_x and
+                                      aid_y stay uncompressed delta pages, whose bit-packed bytes Snappy cannot shrink
 
 Reads the event frames the reference reads (validation: ``DATA/splits/{train,val}.parquet``;
 submission: ``DATA/{train,test}.pkl`` -- ``src/ranker/aid_feature_engineering.py:21-36``), builds the
@@ -113,14 +116,15 @@ def write_parts(directory, prefix, kind, rows, n_parts, n_aids):
     write_jobs(part_jobs(directory, prefix, kind, rows, n_parts, n_aids))
 
 
-def write_device_parts(directory, prefix, kind, rows, n_parts, n_aids):
+def write_device_parts(directory, prefix, kind, rows, n_parts, n_aids, compression=None):
     """The parts of :func:`part_jobs` from device rows ``(aid_x, aid_y, wgt)`` (``engine.topk_to_device_rows``): one encode
-    on the device for all parts of the row set, one ``write`` per file."""
+    on the device for all parts of the row set, one ``write`` per file. ``compression='snappy'`` compresses the PLAIN
+    ``wgt`` pages; the delta pages stay as they are."""
     from .. import parquet_write
     aid_x, aid_y, wgt = rows
     parquet_write.write_tables([directory / f'{prefix}_{kind}_{i}.pqt' for i in range(n_parts)],
                                {'aid_x': aid_x, 'aid_y': aid_y, 'wgt': wgt}, split_parts_device(aid_x, n_parts, n_aids),
-                               {'aid_x': 'delta', 'aid_y': 'delta'})
+                               {'aid_x': 'delta', 'aid_y': 'delta'}, compression={'wgt': compression} if compression else None)
 
 
 def build_matrices(ev, kinds=REFERENCE_KINDS, ks=(15, 20), device='cuda:0', window=30, max_gap=86400,
@@ -176,7 +180,11 @@ def main(argv=None):
                         help='validation: decode DATA/splits/{train,val}.parquet on the device, not with pyarrow')
     parser.add_argument('--device-write', action='store_true',
                         help='encode the part files on the device (delta pages for aid_x and aid_y), not with pyarrow')
+    parser.add_argument('--compression', choices=('snappy',), default=None,
+                        help='with --device-write: compress the wgt pages on the device (the delta columns stay uncompressed)')
     args = parser.parse_args(argv)
+    if args.compression and not args.device_write:
+        raise ValueError('--compression applies to --device-write (pyarrow compresses its own files)')
     if args.mode not in ('validation', 'submission'):
         raise ValueError('Invalid mode')
     if args.device_parquet and args.mode != 'validation':
@@ -191,7 +199,7 @@ def main(argv=None):
     res = build_matrices(ev, device_rows=args.device_write)
     if args.device_write:
         for prefix, kind, rows, n_parts in part_sets(args.mode, res):
-            write_device_parts(directory, prefix, kind, rows, n_parts, ev.n_aids)
+            write_device_parts(directory, prefix, kind, rows, n_parts, ev.n_aids, args.compression)
     else:
         write_jobs(all_part_jobs(directory, args.mode, res, ev.n_aids))
     logging.info(f'Saved covisitation parquet parts to {directory}')

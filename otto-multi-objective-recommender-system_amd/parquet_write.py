@@ -1,7 +1,8 @@
 """Device-side Parquet encode (SPEC-PQWRITE, ``include/otto_pqwrite.h``): named device columns -> the
 bytes of Parquet files whose data pages are sized and bit-packed by HIP kernels (``csrc/otto_pqwrite.hip``). Only the encoded
 bytes cross PCIe; the host adds the Thrift-compact page headers and the footer. ``pyarrow.parquet.read_table`` and
-``pandas.read_parquet`` read the files with the dtypes of the input columns.
+``pandas.read_parquet`` read the files with the dtypes of the input columns. With ``compression='snappy'`` the page bodies
+of the chosen columns are Snappy streams made on the device as well (SPEC-SNAPPY, ``include/otto_snappy.h``, section 2h).
 
 Reference code replaced: the pyarrow encode behind ``DataFrame.to_parquet`` of ``src/covisitation/covisitation.py`` (the
 matrix part files) and of ``src/utilities/split_dataset_writer_parquet.py`` (the 100,000-session chunks).
@@ -25,6 +26,7 @@ MAGIC = b'PAR1'
 CREATED_BY = b'otto_amd SPEC-PQWRITE'
 PAGE_DTYPE = np.dtype([('first_row', '<i8'), ('n_values', '<i4'), ('column', '<i4')])        # otto_pqw_page
 INT32, INT64, FLOAT32, DOUBLE = 1, 2, 4, 5   # parquet.PHYSICAL
+UNCOMPRESSED, SNAPPY = 0, 1                  # the Parquet CompressionCodec codes
 ENCODING_NAMES = {'plain': PLAIN, 'delta': DELTA, 'PLAIN': PLAIN, 'DELTA_BINARY_PACKED': DELTA, PLAIN: PLAIN, DELTA: DELTA}
 
 # element type name -> (bytes, kind, physical type, converted_type or None)
@@ -108,9 +110,9 @@ def thrift_bytes(fields):
     return bytes(ThriftWriter().struct(fields).b)
 
 
-def page_header(n_values, encoding, body_bytes):
-    """The PageHeader of a V1 data page of a REQUIRED column."""
-    return thrift_bytes([(1, T_I32, 0), (2, T_I32, body_bytes), (3, T_I32, body_bytes),
+def page_header(n_values, encoding, body_bytes, compressed_bytes=None):
+    """The PageHeader of a V1 data page of a REQUIRED column; ``compressed_bytes``: the bytes present, where a codec made them."""
+    return thrift_bytes([(1, T_I32, 0), (2, T_I32, body_bytes), (3, T_I32, body_bytes if compressed_bytes is None else compressed_bytes),
                          (5, T_STRUCT, [(1, T_I32, n_values), (2, T_I32, encoding), (3, T_I32, RLE), (4, T_I32, RLE)])])
 
 
@@ -158,10 +160,14 @@ class Layout:
         self.pages = np.array(pages, dtype=PAGE_DTYPE)
         self.cuts = cuts
 
-    def place(self, names, elements, encodings, page_bytes):
+    def place(self, names, elements, encodings, page_bytes, codecs=None, stored_bytes=None):
         """Given the body size of every page: the headers and footers, where each body goes. Returns ``(total, page_dst,
         spans, fills)``: the bytes of all images back to back, the offset of every page body, the ``(first, end)`` of each
-        image, and the ``(offset, bytes)`` pieces the host writes (everything but the bodies)."""
+        image, and the ``(offset, bytes)`` pieces the host writes (everything but the bodies). ``codecs``: the
+        CompressionCodec of each column (default UNCOMPRESSED); ``stored_bytes``: the bytes of every page as it is stored,
+        which for a page of a compressed column is its compressed size (default ``page_bytes``)."""
+        codecs = [UNCOMPRESSED] * len(names) if codecs is None else codecs
+        stored_bytes = page_bytes if stored_bytes is None else stored_bytes
         page_dst = np.zeros(len(self.pages), dtype=np.int64)
         fills, spans, at = [], [], 0
         for fi, groups in enumerate(self.files):
@@ -170,18 +176,21 @@ class Layout:
             at += 4
             rgs = []
             for rows, per_column in groups:
-                chunks, rg_first = [], at
+                chunks, rg_plain = [], 0
                 for j, idx in enumerate(per_column):
-                    first = at
+                    first, plain = at, 0                     # plain: the chunk's bytes before the codec, page headers included
                     for p in idx:
-                        h = page_header(int(self.pages['n_values'][p]), encodings[j], int(page_bytes[p]))
+                        stored = int(stored_bytes[p]) if codecs[j] else int(page_bytes[p])
+                        h = page_header(int(self.pages['n_values'][p]), encodings[j], int(page_bytes[p]), stored)
                         fills.append((at, h))
                         page_dst[p] = at + len(h)
-                        at += len(h) + int(page_bytes[p])
+                        at += len(h) + stored
+                        plain += len(h) + int(page_bytes[p])
                     meta = [(1, T_I32, elements[j][2]), (2, T_LIST, (T_I32, [encodings[j], RLE])), (3, T_LIST, (T_BINARY, [names[j]])),
-                            (4, T_I32, 0), (5, T_I64, rows), (6, T_I64, at - first), (7, T_I64, at - first), (9, T_I64, first - start)]
+                            (4, T_I32, codecs[j]), (5, T_I64, rows), (6, T_I64, plain), (7, T_I64, at - first), (9, T_I64, first - start)]
                     chunks.append([(2, T_I64, first - start), (3, T_STRUCT, meta)])
-                rgs.append([(1, T_LIST, (T_STRUCT, chunks)), (2, T_I64, at - rg_first), (3, T_I64, rows)])
+                    rg_plain += plain
+                rgs.append([(1, T_LIST, (T_STRUCT, chunks)), (2, T_I64, rg_plain), (3, T_I64, rows)])
             schema = [[(4, T_BINARY, 'schema'), (5, T_I32, len(names))]]
             for name, el in zip(names, elements):
                 leaf = [(1, T_I32, el[2]), (3, T_I32, 0), (4, T_BINARY, name)]
@@ -213,6 +222,24 @@ def _normalise(columns, encodings):
     return names, enc
 
 
+def _codecs(names, compression):
+    """``compression``: None, 'snappy' or ``{column: None | 'snappy'}`` -> the CompressionCodec of each column."""
+    if compression is None or isinstance(compression, str):
+        compression = {n: compression for n in names}
+    elif not isinstance(compression, dict):
+        raise ValueError(f"compression: None, 'snappy' or a dict of them by column (got {compression!r})")
+    unknown = set(compression) - set(names)
+    if unknown:
+        raise ValueError(f'compression names columns that are not there: {sorted(unknown)}')
+    codecs = []
+    for n in names:
+        c = compression.get(n)
+        if c not in (None, 'snappy'):
+            raise ValueError(f"compression[{n!r}]: {c!r} is not None or 'snappy'")
+        codecs.append(SNAPPY if c else UNCOMPRESSED)
+    return codecs
+
+
 def _check_columns(names, cols, elements, enc, cuts):
     n = len(cols[0])
     for name, c, el, e in zip(names, cols, elements, enc):
@@ -224,16 +251,24 @@ def _check_columns(names, cols, elements, enc, cuts):
         raise ValueError(f'cuts end at row {cuts[-1]}, the columns have {n}')
 
 
-def encode_tables_host(columns, cuts, encodings=None, page_rows=PAGE_ROWS, row_group_rows=ROW_GROUP_ROWS, body=None):
-    """:func:`encode_tables` with a host function in the device's place (tests): ``columns`` are NumPy arrays and
-    ``body(array, encoding)`` returns the bytes of one page body. Everything else is the code the product runs."""
+def encode_tables_host(columns, cuts, encodings=None, page_rows=PAGE_ROWS, row_group_rows=ROW_GROUP_ROWS, body=None, compression=None,
+                       compress=None):
+    """:func:`encode_tables` with host functions in the device's place (tests): ``columns`` are NumPy arrays,
+    ``body(array, encoding)`` returns the bytes of one page body and ``compress(bytes)`` the Snappy stream of one (default:
+    ``snappy.stored_stream``, literal elements alone). Everything else is the code the product runs."""
     names, enc = _normalise(columns, encodings)
+    codecs = _codecs(names, compression)
     cols = [np.ascontiguousarray(columns[n]) for n in names]
     elements = [element(c.dtype) for c in cols]
     lay = Layout(len(names), cuts, page_rows, row_group_rows)
     _check_columns(names, cols, elements, enc, lay.cuts)
     bodies = [body(cols[j][r:r + k], enc[j]) for r, k, j in lay.pages.tolist()]
-    total, page_dst, spans, fills = lay.place(names, elements, enc, [len(b) for b in bodies])
+    page_bytes = [len(b) for b in bodies]
+    if any(codecs):
+        if compress is None:
+            from .snappy import stored_stream as compress
+        bodies = [compress(bytes(b)) if codecs[j] else b for b, (_, _, j) in zip(bodies, lay.pages.tolist())]
+    total, page_dst, spans, fills = lay.place(names, elements, enc, page_bytes, codecs, [len(b) for b in bodies])
     buf = bytearray(total)
     for at, b in fills + list(zip(page_dst.tolist(), bodies)):
         buf[at:at + len(b)] = b
@@ -290,17 +325,64 @@ class DeviceJob:
                   int(d_out.numel()), stream=False)
 
 
-def encode_tables(columns, cuts, encodings=None, page_rows=PAGE_ROWS, row_group_rows=ROW_GROUP_ROWS, work=None):
+def _plan(job, names):
+    """``job.plan()``; a value outside the delta domain is reported under the column's name."""
+    from . import _lib
+    try:
+        return job.plan()
+    except _lib.OttoError as e:
+        m = re.search(r'column (\d+), row (\d+): (.*)', str(e))
+        if m:
+            raise _lib.OttoError(f'column {names[int(m.group(1))]!r}, row {m.group(2)}: {m.group(3)}') from None
+        raise
+
+
+def _encode_compressed(names, cols, elements, enc, codecs, lay, work):
+    """The device side of :func:`encode_tables` when a column has a codec: the pages of the compressed columns are planned
+    and emitted back to back into a staging buffer, ``otto_snappy_plan`` sizes their streams, and with those sizes placed
+    ``otto_snappy_emit`` writes the streams and ``otto_pqw_emit`` the pages of the other columns into the one image.
+    Returns ``(d_out, spans, fills)``."""
+    import torch
+    from . import snappy
+    dev = cols[0].device
+    packed = np.array([bool(codecs[j]) for j in lay.pages['column'].tolist()], dtype=bool)
+    page_bytes = np.zeros(len(lay.pages), dtype=np.int64)
+    stored = np.zeros(len(lay.pages), dtype=np.int64)
+    with torch.cuda.device(dev):
+        inner = DeviceJob(cols, enc, lay.pages[packed])
+        page_bytes[packed] = _plan(inner, names)
+        stage_off = np.r_[0, np.cumsum(page_bytes[packed])]
+        stage = torch.empty(int(stage_off[-1]), dtype=torch.uint8, device=dev)
+        inner.emit(stage_off[:-1], stage)
+        codec = snappy.DeviceJob(stage, stage_off[:-1], page_bytes[packed])
+        stored[packed] = codec.plan()
+        outer = DeviceJob(cols, enc, lay.pages[~packed], work) if not packed.all() else None
+        if outer is not None:
+            page_bytes[~packed] = _plan(outer, names)
+        total, page_dst, spans, fills = lay.place(names, elements, enc, page_bytes, codecs, stored)
+        d_out = torch.empty(total, dtype=torch.uint8, device=dev)
+        codec.emit(page_dst[packed], d_out)
+        if outer is not None:
+            outer.emit(page_dst[~packed], d_out)
+    return d_out, spans, fills
+
+
+def encode_tables(columns, cuts, encodings=None, page_rows=PAGE_ROWS, row_group_rows=ROW_GROUP_ROWS, work=None, compression=None):
     """``columns``: ``{name: 1-d tensor}`` of one length on one ROCm device; ``cuts``: ascending row numbers, rows
     ``[cuts[i], cuts[i + 1])`` become file image i. ``encodings``: ``{name: 'plain' | 'delta'}`` (default plain; delta for
     integer columns whose values lie in the domain SPEC-PQWRITE states, else ``OttoError`` naming column and row).
 
     One plan and one emit for all segments, one device-to-host copy into a page-locked buffer with the gaps for headers
     and footers in place, which the host then fills. Returns one ``memoryview`` per file (views of that one buffer).
-    ``work``: a uint8 scratch tensor to use instead of a fresh one."""
+    ``work``: a uint8 scratch tensor to use instead of a fresh one.
+
+    ``compression``: None (the default: the bytes are what they always were), ``'snappy'`` for every column, or
+    ``{name: None | 'snappy'}``. The pages of a Snappy column are compressed on the device (SPEC-SNAPPY) after their
+    value encoding; the column's metadata names the codec, and pyarrow, pandas and ``otto_amd.parquet`` read the file."""
     import torch
     from . import _lib
     names, enc = _normalise(columns, encodings)
+    codecs = _codecs(names, compression)
     cols = [columns[n] for n in names]
     if not all(isinstance(c, torch.Tensor) and c.dim() == 1 for c in cols):
         raise ValueError('columns: expected 1-d tensors')
@@ -309,19 +391,18 @@ def encode_tables(columns, cuts, encodings=None, page_rows=PAGE_ROWS, row_group_
     elements = [element(c.dtype) for c in cols]
     lay = Layout(len(names), cuts, page_rows, row_group_rows)
     _check_columns(names, cols, elements, enc, lay.cuts)
-    job = DeviceJob(cols, enc, lay.pages, work)
-    dev = job.dev
-    try:
-        page_bytes = job.plan()
-    except _lib.OttoError as e:
-        m = re.search(r'column (\d+), row (\d+): (.*)', str(e))
-        if m:
-            raise _lib.OttoError(f'column {names[int(m.group(1))]!r}, row {m.group(2)}: {m.group(3)}') from None
-        raise
-    total, page_dst, spans, fills = lay.place(names, elements, enc, page_bytes)
+    dev = cols[0].device
+    if any(codecs):
+        d_out, spans, fills = _encode_compressed(names, cols, elements, enc, codecs, lay, work)
+        total = int(d_out.numel())
+    else:
+        job = DeviceJob(cols, enc, lay.pages, work)
+        page_bytes = _plan(job, names)
+        total, page_dst, spans, fills = lay.place(names, elements, enc, page_bytes)
+        with torch.cuda.device(dev):
+            d_out = torch.empty(total, dtype=torch.uint8, device=dev)
+            job.emit(page_dst, d_out)
     with torch.cuda.device(dev):
-        d_out = torch.empty(total, dtype=torch.uint8, device=dev)
-        job.emit(page_dst, d_out)
         host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
         host.copy_(d_out, non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()
@@ -331,19 +412,19 @@ def encode_tables(columns, cuts, encodings=None, page_rows=PAGE_ROWS, row_group_
     return [buf[a:b] for a, b in spans]
 
 
-def write_tables(paths, columns, cuts, encodings=None, page_rows=PAGE_ROWS, row_group_rows=ROW_GROUP_ROWS, work=None):
+def write_tables(paths, columns, cuts, encodings=None, page_rows=PAGE_ROWS, row_group_rows=ROW_GROUP_ROWS, work=None, compression=None):
     """:func:`encode_tables`, image i written to ``paths[i]`` with one ``write``. Returns the bytes of each file."""
     paths = [os.fspath(p) for p in paths]
     if len(paths) != len(cuts) - 1:
         raise ValueError(f'{len(paths)} paths for {len(cuts) - 1} segments')
-    images = encode_tables(columns, cuts, encodings, page_rows, row_group_rows, work)
+    images = encode_tables(columns, cuts, encodings, page_rows, row_group_rows, work, compression)
     for path, image in zip(paths, images):
         with open(path, 'wb', buffering=0) as f:
             f.write(image)
     return [len(i) for i in images]
 
 
-def write_table(path, columns, encodings=None, page_rows=PAGE_ROWS, row_group_rows=ROW_GROUP_ROWS, work=None):
+def write_table(path, columns, encodings=None, page_rows=PAGE_ROWS, row_group_rows=ROW_GROUP_ROWS, work=None, compression=None):
     """One file of all rows of ``columns``."""
     n = len(columns[next(iter(columns))]) if columns else 0
-    return write_tables([path], columns, [0, n], encodings, page_rows, row_group_rows, work)[0]
+    return write_tables([path], columns, [0, n], encodings, page_rows, row_group_rows, work, compression)[0]

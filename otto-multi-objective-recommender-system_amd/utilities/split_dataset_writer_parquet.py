@@ -2,7 +2,7 @@
 reference's ``src/utilities/split_dataset_writer_parquet.py`` with decode, sort and encode on the device. Same ``settings``
 shim, same files::
 
-    OTTO_ROOT=/path/to/project python -m otto_amd.utilities.split_dataset_writer_parquet [--encoding plain|delta]
+    OTTO_ROOT=/path/to/project python -m otto_amd.utilities.split_dataset_writer_parquet [--encoding plain|delta] [--compression snappy]
 
 The two split files are decoded by ``otto_amd.parquet`` (SPEC-PARQUET), their columns raw, with no unit change; the rows are
 sorted by (session, ts), stable, with torch (plumbing); chunk i holds the sessions whose *value* lies in
@@ -16,6 +16,10 @@ the same frame; the pandas index metadata is not written, so ``pd.read_parquet``
 (``parquet.read_columns``, ``builder.py validation --device-parquet``); ``--encoding delta`` writes DELTA_BINARY_PACKED
 pages for the four integer columns, for size: pyarrow and pandas read them, and so does the device decoder
 (``events.parquet_to_events_device`` gives the same events from either encoding). The default stays PLAIN.
+
+``--compression snappy`` compresses every page on the device after its value encoding (``otto_amd.snappy``, SPEC-SNAPPY):
+the codec of the reference's own files, read by pyarrow, pandas and the device decoder. Without it the files are
+uncompressed, as before.
 """
 import argparse
 import logging
@@ -65,7 +69,8 @@ def sort_and_cut(columns, chunk=SESSION_CHUNK_SIZE):
 
 
 def write_chunks(paths, directory, device='cuda:0', encoding='plain', chunk=SESSION_CHUNK_SIZE, **kw):
-    """The chunk files of the split files ``paths`` into ``directory``; returns their paths."""
+    """The chunk files of the split files ``paths`` into ``directory``; returns their paths. ``compression='snappy'`` and the
+    other keywords of ``parquet_write.write_tables`` pass through."""
     directory = pathlib.Path(directory)
     directory.mkdir(parents=True, exist_ok=True)
     columns, cuts = sort_and_cut(read_split_columns(paths, device), chunk)
@@ -77,9 +82,11 @@ def write_chunks(paths, directory, device='cuda:0', encoding='plain', chunk=SESS
 def main(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('--encoding', choices=('plain', 'delta'), default='plain')
+    parser.add_argument('--compression', choices=('snappy',), default=None)
     args = parser.parse_args(argv)
     directory = settings.DATA / 'parquet_files' / 'train_truncated_parquet'
-    out = write_chunks([settings.DATA / 'splits' / f'{name}.parquet' for name in ('train', 'val')], directory, encoding=args.encoding)
+    out = write_chunks([settings.DATA / 'splits' / f'{name}.parquet' for name in ('train', 'val')], directory, encoding=args.encoding,
+                       compression=args.compression)
     logging.info(f'{len(out)} train_truncated_<chunk_idx>.parquet files are saved to {directory}')
 
 
