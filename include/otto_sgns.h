@@ -1,7 +1,9 @@
 /*
  * otto_sgns.h -- C-ABI of the skip-gram negative-sampling (SGNS) aid embedding trainer (SPEC-SGNS):
  * the negative-sampling table, the per-epoch plan (subsampling, compaction, shrunken windows), the SGD step, and the
- * hierarchical-softmax half of gensim's hs: 1 (SPEC-SGNS-HS below: Huffman tree, path tables, a third table Syn1).
+ * hierarchical-softmax half of gensim's hs: 1 (SPEC-SGNS-HS below: Huffman tree, path tables, a third table Syn1), and the
+ * other two architectures of a word2vec trainer on the same plan and sampler: CBOW and Doc2Vec (SPEC-CBOW and SPEC-DOC2VEC
+ * below, otto_sgns_cbow_step; PV-DM and PV-DBOW train a table of session vectors).
  *
  * What this replaces in the reference: src/gensim_fasttext/trainer.py, i.e. fasttext.train_unsupervised with
  * models/fasttext/config.yaml (skipgram, loss ns, dim 32, ws 10, neg 40, epoch 5, t 1e-4, minn = maxn = 0: no sub-words,
@@ -96,6 +98,49 @@
  * the pair.
  * Modes. HOGWILD and BATCH as above; in BATCH every x and g comes from the pre-launch In / Out / Syn1, and a third dense
  * float64 workspace gsyn1 [max(V-1, 1), d] is summed by atomics and applied once: zero on entry, zero again on return.
+ *
+ * SPEC-CBOW: the continuous bag of words (fastText model: cbow, gensim Word2Vec(sg=0); otto_sgns_cbow_step with arch
+ * OTTO_SGNS_ARCH_CBOW). Build-defined and parity-unpinned like SPEC-SGNS; tests/sgns_cbow_restatement.py is the checker.
+ * Everything not named here is SPEC-SGNS's: inputs, vocabulary tables, mix64 keys, the plan, draw, the loss terms, exact
+ * expf / log1pf.
+ * A centre token c of a plan: e = tok_src[c], a = tok_aid[c], s the session with tok_off[s] <= c < tok_off[s+1]; its np
+ * context tokens are those of SPEC-SGNS step 4 in pair order k = 0..np-1, with aids x_k.
+ * Inputs. The rows In[x_0] .. In[x_{np-1}], n = np of them. n == 0: the centre is skipped, nothing is written, no loss.
+ * Hidden vector. h = the float32 sum of the inputs in that order, component-wise: ((x_0 + x_1) + x_2) ...; with the mean
+ * flag h = h / (float)n in IEEE float32 division. h stays fixed over the centre's targets.
+ * Targets, in this order. With HS tables: the Huffman path of a (the CENTRE's aid) on Syn1 with label 1 - bit, exactly as
+ * SPEC-SGNS-HS walks a context's path. Then a on Out with label 1. Then neg negatives on Out with label 0: negative j is
+ * draw(key(ev(e), 4, (j << 4) | att)) for the first att in 0..15 whose draw differs from a, else (a + 1) % n_aids. Stream
+ * 4 is used by nothing else, so no draw aliases a skip-gram draw. x, g, the grad accumulation (grad = 0 before the first
+ * target), the target-row update and the loss are exactly SPEC-SGNS's.
+ * Input update. u = grad, or u = grad / (float)n, by the variant; for each input in input order row += u. An aid that
+ * occurs m times among the contexts receives m sequential read-modify-writes.
+ *     variant                    h      u          mirrors
+ *     OTTO_SGNS_CBOW_SUM         sum    grad       gensim cbow_mean: 0
+ *     OTTO_SGNS_CBOW_MEAN        mean   grad / n   gensim cbow_mean: 1
+ *     OTTO_SGNS_CBOW_FASTTEXT    mean   grad       fastText's unnormalised gradient
+ *
+ * SPEC-DOC2VEC: gensim Doc2Vec with one tag per document, the tag being the session (arch OTTO_SGNS_ARCH_PVDM and
+ * OTTO_SGNS_ARCH_DBOW). Doc float32 [S, d], one row per session of the plan. Build decision: a config without dm_mean (or
+ * with a null one) means the mean, as this build cannot ask gensim for its default.
+ * PV-DM (dm: 1) is SPEC-CBOW with one more input: the rows In[x_0] .. In[x_{np-1}], then Doc[s] last, n = np + 1. A centre
+ * without context trains on its doc row alone. The doc row is updated last, by the same u.
+ * PV-DBOW (dm: 0). For a session s take its tokens inside the launch's range [t0, t1) in order. h = Doc[s] lives in
+ * registers across those tokens. For each token: the targets of SPEC-CBOW with a and e of that token (no context row is
+ * read), then h += grad. Doc[s] is written once, after the session's last token in the range. In is never touched; the
+ * variant is ignored.
+ *
+ * Modes of both. HOGWILD: inside one centre (DBOW: one session) the order above holds exactly; centres race by design, and
+ * in PV-DM the doc row is shared by the session's centres and races with them. Every row update that another lane group of
+ * the launch may share is a float32 atomic add per component, issued in the order above: g * h on the target rows of Syn1
+ * and Out, u on the input rows (DBOW's doc row, which one lane group owns, is a plain store). This is the one departure from
+ * SPEC-SGNS's plain stores: the centres of a session name the same context rows, the same doc row and, for a repeated aid,
+ * the same target row at the same time, and a plain read-modify-write keeps one of their concurrent updates and loses the
+ * others. No update is lost; what a centre READ of a shared row still
+ * depends on the schedule. Without shared rows the launch equals the sequential loop. BATCH: every x and g comes from the
+ * pre-launch tables (DBOW: h = Doc[s] stays fixed over the session's tokens); the contributions go by float64 atomics into
+ * the dense workspaces gin [n_aids, d], gout [n_aids, d], gsyn1 [n_inner, d] and gdoc [S, d] and are applied once. The
+ * workspaces are zero on entry and zero again on return.
  */
 #ifndef OTTO_SGNS_H
 #define OTTO_SGNS_H
@@ -181,6 +226,61 @@ int otto_sgns_step_hs(const int32_t* d_tok_aid, const int64_t* d_tok_src, const 
                       int32_t* d_ctx_out, int32_t* d_neg_out, int64_t out_pairs, double* d_gin, double* d_gout,
                       const int64_t* d_path_off, const int32_t* d_path_node, const uint64_t* d_code, float* d_Syn1,
                       int64_t n_inner, double* d_gsyn1, void* stream);
+
+/* SPEC-CBOW and SPEC-DOC2VEC */
+#define OTTO_SGNS_ARCH_CBOW 0
+#define OTTO_SGNS_ARCH_PVDM 1
+#define OTTO_SGNS_ARCH_DBOW 2
+#define OTTO_SGNS_CBOW_SUM 0
+#define OTTO_SGNS_CBOW_MEAN 1
+#define OTTO_SGNS_CBOW_FASTTEXT 2
+
+/* One launch of otto_sgns_cbow_step over the centres [t0, t1) of a plan. All device work goes to `stream`. */
+typedef struct otto_sgns_cbow_job {
+    /* the plan of otto_sgns_plan: T tokens in S sessions; d_tok_off int64 [S+1] is read by PV-DM and DBOW alone */
+    const int32_t* d_tok_aid;
+    const int64_t* d_tok_src;
+    const uint8_t* d_tok_left;
+    const int64_t* d_pair_off;
+    const int64_t* d_tok_off;
+    int64_t T, S;
+    int64_t t0, t1;                 /* 0 <= t0 <= t1 <= T; t0 == t1 only writes the loss 0 */
+    /* tables: d_In, d_Out float32 [n_aids, d]; d_Syn1 float32 [n_inner, d]; d_Doc float32 [S, d]. d_In may be null for
+     * DBOW, d_Doc for CBOW, d_Syn1 without the Huffman tables. */
+    float* d_In;
+    float* d_Out;
+    float* d_Syn1;
+    float* d_Doc;
+    int64_t n_aids, n_inner;
+    int32_t d, neg;                 /* d by otto_sgns_step's rule; 0 <= neg <= OTTO_SGNS_MAX_NEG */
+    float lr;
+    int32_t arch, variant, mode;    /* OTTO_SGNS_ARCH_*, OTTO_SGNS_CBOW_* (ignored by DBOW), OTTO_SGNS_HOGWILD / _BATCH */
+    uint64_t seed, epoch;
+    /* the sampler (read when neg > 0: total > 0, table.n_aids == n_aids >= 2) and the tables of otto_sgns_hs_tree on the
+     * device: all three present is the HS switch, all three null is no HS */
+    otto_sgns_table table;
+    const int64_t* d_path_off;
+    const int32_t* d_path_node;
+    const uint64_t* d_code;
+    double* d_loss_sum;             /* device double: the loss sum of the launch */
+    int32_t* d_neg_out;             /* nullable, int32 [t1 - t0, neg]: the negatives of centre c in row c - t0 (the tests'
+                                       window into the sampler); the row of a skipped centre is not written */
+    /* BATCH workspaces (ignored in HOGWILD): gin [n_aids, d] (CBOW, PV-DM), gout [n_aids, d], gsyn1 [n_inner, d] (with
+     * HS), gdoc [S, d] (PV-DM, DBOW) */
+    double* d_gin;
+    double* d_gout;
+    double* d_gsyn1;
+    double* d_gdoc;
+    void* stream;
+} otto_sgns_cbow_job;
+
+/* One training launch of SPEC-CBOW / SPEC-DOC2VEC. OTTO_EINVAL, with nothing launched and every table unwritten, for: an
+ * unknown arch, variant (CBOW, PV-DM) or mode; d outside otto_sgns_step's rule; neg outside [0, OTTO_SGNS_MAX_NEG];
+ * neg > 0 with table.total == 0 or n_aids < 2; PV-DM or DBOW without d_Doc or d_tok_off; CBOW or PV-DM without d_In;
+ * only some of the three Huffman tables, or tables without d_Syn1 or with n_inner < 1; BATCH without a workspace its arch
+ * needs; t0 > t1 or a range outside [0, T]. neg == 0 without Huffman tables is accepted, as otto_sgns_step accepts it
+ * (the centre's own aid with label 1 is then the only target); the Python trainers refuse it. */
+int otto_sgns_cbow_step(const otto_sgns_cbow_job* job);
 
 #ifdef __cplusplus
 }

@@ -95,6 +95,18 @@ class SgnsTable(C.Structure):
     ]
 
 
+class SgnsCbowJob(C.Structure):
+    # mirrors otto_sgns_cbow_job (include/otto_sgns.h)
+    _fields_ = [('d_tok_aid', C.c_void_p), ('d_tok_src', C.c_void_p), ('d_tok_left', C.c_void_p), ('d_pair_off', C.c_void_p),
+                ('d_tok_off', C.c_void_p), ('T', C.c_int64), ('S', C.c_int64), ('t0', C.c_int64), ('t1', C.c_int64),
+                ('d_In', C.c_void_p), ('d_Out', C.c_void_p), ('d_Syn1', C.c_void_p), ('d_Doc', C.c_void_p),
+                ('n_aids', C.c_int64), ('n_inner', C.c_int64), ('d', C.c_int32), ('neg', C.c_int32), ('lr', C.c_float),
+                ('arch', C.c_int32), ('variant', C.c_int32), ('mode', C.c_int32), ('seed', C.c_uint64), ('epoch', C.c_uint64),
+                ('table', SgnsTable), ('d_path_off', C.c_void_p), ('d_path_node', C.c_void_p), ('d_code', C.c_void_p),
+                ('d_loss_sum', C.c_void_p), ('d_neg_out', C.c_void_p), ('d_gin', C.c_void_p), ('d_gout', C.c_void_p),
+                ('d_gsyn1', C.c_void_p), ('d_gdoc', C.c_void_p), ('stream', C.c_void_p)]
+
+
 class XgbTree(C.Structure):
     # mirrors otto_xgb_tree (include/otto_xgb.h): 16 host arrays, then what the call writes
     _fields_ = [(name, C.c_void_p) for name in (
@@ -315,6 +327,7 @@ SIGNATURES = {
                                  _vp]),
     'otto_sgns_hs_tree_sizes': (_i32, [_vp, _i64, _i64, _p_i64]),
     'otto_sgns_hs_tree': (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    'otto_sgns_cbow_step': (_i32, [C.POINTER(SgnsCbowJob)]),
     # include/otto_submit.h
     'otto_submit_workspace': (_i64, [_i64, _i32]),
     'otto_submit_measure': (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int32), _vp, _i64, _i32, _i64, _i32, _p_i64,

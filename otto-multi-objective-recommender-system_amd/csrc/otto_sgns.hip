@@ -15,6 +15,13 @@
 //                   atomics into the dense workspaces, no table is written. HS (SPEC-SGNS-HS): the Syn1 rows on the Huffman
 //                   path of the context go through sg_targets first; their ids are read from path_node (the same address in
 //                   every lane of the group), the pair's code word is one uint64.
+//   k_sgns_cbow<BATCH, HS, DOC>  SPEC-CBOW and PV-DM: one lane group per centre. The context rows of In (PV-DM: and the
+//                   session's Doc row, found by binary search of tok_off) are gathered as float4, four loads in flight, and
+//                   summed into h; the centre's own path and its 1 + neg targets go through sg_targets; the gradient is then
+//                   added to every input row in input order. HOGWILD: the target and the input rows take their updates by
+//                   float32 atomic adds in place (the centres of a session share these rows, plain read-modify-writes
+//                   would lose all but one of their concurrent updates); BATCH: float64 atomic adds into the workspaces.
+//   k_sgns_dbow<BATCH, HS>  PV-DBOW: one lane group per session that meets the launch's range; h = Doc[s] in registers.
 //   k_sgns_apply         BATCH: table += workspace, workspace = 0 (dense sweep).
 //   k_sgns_loss_final    sums the per-workgroup loss partials in a fixed order.
 // Host: otto_sgns_hs_tree_sizes / otto_sgns_hs_tree build the Huffman tree and the path tables of SPEC-SGNS-HS (no HIP call).
@@ -225,8 +232,12 @@ static __device__ __forceinline__ int32_t sgns_negative(const SgTable& t, uint64
 
 // The rows idf(0) .. idf(n - 1) of `tab` against h, four at a time: the loads of a four go out before its first update.
 // idf(m) < 0: no row. labf(m): the label. DUP: a row named twice in a four sees its own earlier update (HOGWILD over drawn
-// targets; a Huffman path never repeats a node).
-template <bool BATCH, bool DUP, class IdFn, class LabelFn>
+// targets; a Huffman path never repeats a node). ATOM (HOGWILD of SPEC-CBOW / SPEC-DOC2VEC): the row takes g * h by float32
+// atomic adds, so that lane groups which hold the same row at the same time lose none of their updates.
+static __device__ __forceinline__ void atomic_add4(float* p, const float4& v) {
+    atomicAdd(p + 0, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
+}
+template <bool BATCH, bool DUP, bool ATOM = false, class IdFn, class LabelFn>
 static __device__ __forceinline__ void sg_targets(float* tab, double* gtab, int d, int G, int gl, int n, float lr, const float4& h,
                                                   float4& grad, double& lsum, IdFn idf, LabelFn labf) {
     for (int m0 = 0; m0 < n; m0 += 4) {
@@ -257,6 +268,8 @@ static __device__ __forceinline__ void sg_targets(float* tab, double* gtab, int 
                 double* go = gtab + (int64_t)id[q] * d + 4 * gl;
                 atomicAdd(go + 0, (double)(g * h.x)); atomicAdd(go + 1, (double)(g * h.y));
                 atomicAdd(go + 2, (double)(g * h.z)); atomicAdd(go + 3, (double)(g * h.w));
+            } else if (ATOM) {
+                atomic_add4(po_, make_float4(g * h.x, g * h.y, g * h.z, g * h.w));
             } else {
                 st4(po_, make_float4(o.x + g * h.x, o.y + g * h.y, o.z + g * h.z, o.w + g * h.w));
             }
@@ -341,6 +354,205 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgns_step(SgStepArgs a) {
         for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_red[w];
         a.partial[blockIdx.x] = t;
     }
+}
+
+// ---------------------------------------------------------------------------
+// SPEC-CBOW, SPEC-DOC2VEC
+// ---------------------------------------------------------------------------
+struct SgCbowArgs {
+    const int32_t* tok_aid;
+    const int64_t* tok_src;
+    const uint8_t* tok_left;
+    const int64_t* pair_off;
+    const int64_t* tok_off;
+    int64_t T, S, t0, t1;
+    float* In;
+    float* Out;
+    float* Syn1;
+    float* Doc;
+    int d, G, neg, variant;
+    float lr;
+    uint64_t base;
+    SgTable tab;              // tab.n = n_aids also when nothing is drawn
+    double* partial;          // [SG_GRID]
+    int32_t* neg_out;
+    double* gin;
+    double* gout;
+    double* gsyn1;
+    double* gdoc;
+    const int64_t* path_off;
+    const int32_t* path_node;
+    const uint64_t* code;
+    uint32_t n_inner;
+};
+
+// negative j of the centre whose event key is ev: stream 4, redrawn while equal to the centre's aid
+static __device__ __forceinline__ int32_t cbow_negative(const SgTable& t, uint64_t ev, int j, int32_t ca) {
+    for (int att = 0; att < 16; ++att) {
+        const int32_t n = sgns_draw(t, sg_key(ev, 4, ((uint64_t)j << 4) | (uint64_t)att));
+        if (n != ca) return n;
+    }
+    return (int32_t)(((int64_t)ca + 1) % t.n);
+}
+
+// the last s in [0, S) with tok_off[s] <= c: the session of token c (empty sessions share an offset; the last one holds c)
+static __device__ __forceinline__ int64_t sg_session_of(const int64_t* tok_off, int64_t S, int64_t c) {
+    int64_t lo = 0, hi = S - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (tok_off[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+static __device__ __forceinline__ void add4(float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+static __device__ __forceinline__ void atomic_add4(double* p, const float4& v) {
+    atomicAdd(p + 0, (double)v.x); atomicAdd(p + 1, (double)v.y); atomicAdd(p + 2, (double)v.z); atomicAdd(p + 3, (double)v.w);
+}
+
+// The targets of centre c (aid ca, in range) against h: the ids are drawn into LDS before any row is loaded; the path of ca
+// on Syn1, then ca and the negatives on Out. grad accumulates.
+template <bool BATCH, bool HS>
+static __device__ __forceinline__ void cbow_targets(const SgCbowArgs& a, int G, int gl, int32_t* ids, int64_t c, int32_t ca,
+                                                    const float4& h, float4& grad, double& lsum) {
+    const uint64_t ev = sg_ev(a.base, (uint64_t)a.tok_src[c]);
+    const int nt = 1 + a.neg;
+    wave_lds_sync();
+    for (int m = gl; m < nt; m += G) ids[m] = m == 0 ? ca : cbow_negative(a.tab, ev, m - 1, ca);
+    wave_lds_sync();
+    if (a.neg_out)
+        for (int m = 1 + gl; m < nt; m += G) a.neg_out[(c - a.t0) * a.neg + (m - 1)] = ids[m];
+    if (HS) {
+        const int64_t off = a.path_off[ca];
+        const int64_t len = a.path_off[ca + 1] - off;
+        const int L = off < 0 || len < 0 ? 0 : (int)(len > 64 ? 64 : len);
+        const uint64_t code = a.code[ca];
+        const int32_t* pn = a.path_node + off;
+        const uint32_t n_inner = a.n_inner;
+        sg_targets<BATCH, false, !BATCH>(a.Syn1, a.gsyn1, a.d, G, gl, L, a.lr, h, grad, lsum,
+                                         [&](int m) { const uint32_t n = (uint32_t)pn[m]; return n < n_inner ? (int32_t)n : -1; },
+                                         [&](int m) { return ((code >> m) & 1ull) == 0; });
+    }
+    sg_targets<BATCH, true, !BATCH>(a.Out, a.gout, a.d, G, gl, nt, a.lr, h, grad, lsum, [&](int m) { return ids[m]; },
+                                    [](int m) { return m == 0; });
+}
+
+// per-workgroup loss partial, fixed order inside the workgroup
+static __device__ __forceinline__ void sg_loss_partial(double lsum, double* s_red, double* partial) {
+    lsum = wave_reduce<Sum>(lsum);
+    if (lane_id() == 0) s_red[threadIdx.x >> 6] = lsum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_red[w];
+        partial[blockIdx.x] = t;
+    }
+}
+
+// CBOW (DOC = false) and PV-DM (DOC = true): one lane group per centre, grid-stride. The context rows are gathered as float4,
+// four loads in flight, and summed in pair order; after the targets the same rows take u in that order (HOGWILD: float32
+// atomic adds, BATCH: float64 atomic adds into the workspaces).
+template <bool BATCH, bool HS, bool DOC>
+__global__ __launch_bounds__(SG_THREADS) void k_sgns_cbow(SgCbowArgs a) {
+    __shared__ int32_t s_ids[SG_MAX_GROUPS * SG_MAX_TARGETS];
+    __shared__ double s_red[SG_THREADS / 64];
+    const int G = a.G;
+    const int gl = threadIdx.x & (G - 1);
+    const int grp = threadIdx.x / G;
+    const int64_t gpb = blockDim.x / G;
+    int32_t* ids = s_ids + grp * SG_MAX_TARGETS;
+    const uint64_t n_aids = (uint64_t)a.tab.n;
+    double lsum = 0.0;
+    for (int64_t c = a.t0 + (int64_t)blockIdx.x * gpb + grp; c < a.t1; c += (int64_t)gridDim.x * gpb) {
+        const int32_t ca = a.tok_aid[c];
+        const int np = (int)(a.pair_off[c + 1] - a.pair_off[c]);
+        const int left = a.tok_left[c];
+        const int n = np + (DOC ? 1 : 0);
+        if ((uint64_t)(uint32_t)ca >= n_aids || np < 0 || np > 2 * OTTO_SGNS_MAX_WS || left > np || n == 0) continue;
+        if (c - left < 0 || c + (np - left) >= a.T) continue;         // cannot happen for a plan of T tokens
+        // context k is token cb + k + (k >= left): the centre itself is stepped over
+        const int32_t* cb = a.tok_aid + (c - left);
+        float* pdoc = nullptr;
+        double* gdoc = nullptr;
+        float4 h = make_float4(0.f, 0.f, 0.f, 0.f), dr = h;
+        if (DOC) {
+            const int64_t s = sg_session_of(a.tok_off, a.S, c);
+            pdoc = a.Doc + s * a.d + 4 * gl;
+            if (BATCH) gdoc = a.gdoc + s * a.d + 4 * gl;
+            dr = ld4(pdoc);
+        }
+        for (int k0 = 0; k0 < np; k0 += 4) {
+            float4 row[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int k = k0 + q;
+                row[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (k < np) {
+                    const uint32_t x = (uint32_t)cb[k + (k >= left)];
+                    if ((uint64_t)x < n_aids) row[q] = ld4(a.In + (int64_t)x * a.d + 4 * gl);      // the plan checked every aid
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (k0 + q < np) add4(h, row[q]);
+        }
+        if (DOC) add4(h, dr);
+        const float fn = (float)n;
+        if (a.variant != OTTO_SGNS_CBOW_SUM) { h.x = h.x / fn; h.y = h.y / fn; h.z = h.z / fn; h.w = h.w / fn; }
+        float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
+        cbow_targets<BATCH, HS>(a, G, gl, ids, c, ca, h, u, lsum);
+        if (a.variant == OTTO_SGNS_CBOW_MEAN) { u.x = u.x / fn; u.y = u.y / fn; u.z = u.z / fn; u.w = u.w / fn; }
+        if (BATCH) {
+            for (int k = 0; k < np; ++k) {
+                const uint32_t x = (uint32_t)cb[k + (k >= left)];
+                if ((uint64_t)x < n_aids) atomic_add4(a.gin + (int64_t)x * a.d + 4 * gl, u);
+            }
+            if (DOC) atomic_add4(gdoc, u);
+        } else {
+            // row += u as float32 atomic adds, in input order (one lane's adds to one address keep their order, so an aid
+            // named m times takes m sequential read-modify-writes). The centres of a session share their context rows, and
+            // in PV-DM the doc row: a plain read-modify-write would keep one of their concurrent updates and lose the rest.
+            for (int k = 0; k < np; ++k) {
+                const uint32_t x = (uint32_t)cb[k + (k >= left)];
+                if ((uint64_t)x < n_aids) atomic_add4(a.In + (int64_t)x * a.d + 4 * gl, u);
+            }
+            if (DOC) atomic_add4(pdoc, u);
+        }
+    }
+    sg_loss_partial(lsum, s_red, a.partial);
+}
+
+// PV-DBOW: one lane group per session whose token range meets [t0, t1), grid-stride over the sessions from the one of token
+// t0 to the one of token t1 - 1. h = Doc[s] stays in registers over the session's tokens.
+template <bool BATCH, bool HS>
+__global__ __launch_bounds__(SG_THREADS) void k_sgns_dbow(SgCbowArgs a) {
+    __shared__ int32_t s_ids[SG_MAX_GROUPS * SG_MAX_TARGETS];
+    __shared__ double s_red[SG_THREADS / 64];
+    const int G = a.G;
+    const int gl = threadIdx.x & (G - 1);
+    const int grp = threadIdx.x / G;
+    const int64_t gpb = blockDim.x / G;
+    int32_t* ids = s_ids + grp * SG_MAX_TARGETS;
+    const uint64_t n_aids = (uint64_t)a.tab.n;
+    double lsum = 0.0;
+    const int64_t s0 = sg_session_of(a.tok_off, a.S, a.t0), s1 = sg_session_of(a.tok_off, a.S, a.t1 - 1);
+    for (int64_t s = s0 + (int64_t)blockIdx.x * gpb + grp; s <= s1; s += (int64_t)gridDim.x * gpb) {
+        const int64_t lo = max(a.tok_off[s], a.t0), hi = min(a.tok_off[s + 1], a.t1);
+        if (lo >= hi) continue;                                       // an empty session
+        float* pdoc = a.Doc + s * a.d + 4 * gl;
+        float4 h = ld4(pdoc);
+        float4 gsum = make_float4(0.f, 0.f, 0.f, 0.f);                // BATCH: the session's whole gradient
+        for (int64_t c = lo; c < hi; ++c) {
+            const int32_t ca = a.tok_aid[c];
+            if ((uint64_t)(uint32_t)ca >= n_aids) continue;           // the plan checked every aid
+            float4 grad = make_float4(0.f, 0.f, 0.f, 0.f);
+            cbow_targets<BATCH, HS>(a, G, gl, ids, c, ca, h, grad, lsum);
+            if (BATCH) add4(gsum, grad); else add4(h, grad);
+        }
+        if (BATCH) atomic_add4(a.gdoc + s * a.d + 4 * gl, gsum);
+        else st4(pdoc, h);
+    }
+    sg_loss_partial(lsum, s_red, a.partial);
 }
 
 __global__ __launch_bounds__(256) void k_sgns_loss_final(const double* partial, int n, double* out) {
@@ -618,6 +830,89 @@ extern "C" int otto_sgns_step_hs(const int32_t* d_tok_aid, const int64_t* d_tok_
     const SgHsTables hs = {d_path_off, d_path_node, d_code, d_Syn1, n_inner, d_gsyn1};
     return sgns_step(d_tok_aid, d_tok_src, d_tok_left, d_pair_off, T, t0, t1, d_In, d_Out, d, neg, lr, mode, seed, epoch, table,
                      d_loss_sum, d_ctx_out, d_neg_out, out_pairs, d_gin, d_gout, &hs, stream);
+}
+
+namespace otto {
+
+template <bool BATCH, bool HS>
+static void launch_cbow(int arch, int grid, int threads, hipStream_t s, const SgCbowArgs& a) {
+    if (arch == OTTO_SGNS_ARCH_CBOW) k_sgns_cbow<BATCH, HS, false><<<grid, threads, 0, s>>>(a);
+    else if (arch == OTTO_SGNS_ARCH_PVDM) k_sgns_cbow<BATCH, HS, true><<<grid, threads, 0, s>>>(a);
+    else k_sgns_dbow<BATCH, HS><<<grid, threads, 0, s>>>(a);
+}
+
+}  // namespace otto
+
+extern "C" int otto_sgns_cbow_step(const otto_sgns_cbow_job* job) {
+    OTTO_REQUIRE(job, "null job");
+    const otto_sgns_cbow_job& j = *job;
+    const int arch = j.arch, d = j.d, neg = j.neg;
+    OTTO_REQUIRE(arch == OTTO_SGNS_ARCH_CBOW || arch == OTTO_SGNS_ARCH_PVDM || arch == OTTO_SGNS_ARCH_DBOW, "unknown arch %d", arch);
+    const bool dbow = arch == OTTO_SGNS_ARCH_DBOW, doc = arch != OTTO_SGNS_ARCH_CBOW, batch = j.mode == OTTO_SGNS_BATCH;
+    OTTO_REQUIRE(dbow || j.variant == OTTO_SGNS_CBOW_SUM || j.variant == OTTO_SGNS_CBOW_MEAN || j.variant == OTTO_SGNS_CBOW_FASTTEXT,
+                 "unknown variant %d", j.variant);
+    OTTO_REQUIRE(j.mode == OTTO_SGNS_HOGWILD || batch, "unknown SGNS mode %d", j.mode);
+    OTTO_REQUIRE(d >= 4 && d <= OTTO_SGNS_MAX_DIM && d % 4 == 0 && ((d / 4) & (d / 4 - 1)) == 0,
+                 "d = %d: need a multiple of 4 in [4, %d] with d/4 a power of two", d, OTTO_SGNS_MAX_DIM);
+    OTTO_REQUIRE(neg >= 0 && neg <= OTTO_SGNS_MAX_NEG, "neg = %d outside [0, %d]", neg, OTTO_SGNS_MAX_NEG);
+    OTTO_REQUIRE(j.n_aids >= 1 && j.n_aids < (1ll << 31), "n_aids = %lld outside [1, 2^31)", (long long)j.n_aids);
+    OTTO_REQUIRE(j.T >= 0 && j.T < (1ll << 31) && 0 <= j.t0 && j.t0 <= j.t1 && j.t1 <= j.T,
+                 "token range [%lld, %lld) outside the plan's %lld", (long long)j.t0, (long long)j.t1, (long long)j.T);
+    OTTO_REQUIRE(j.S >= 0 && j.S < (1ll << 31) && (j.T == 0 || j.S >= 1), "S = %lld sessions for %lld tokens", (long long)j.S,
+                 (long long)j.T);
+    OTTO_REQUIRE(j.d_pair_off && j.d_Out && j.d_loss_sum, "null argument");
+    OTTO_REQUIRE(j.T == 0 || (j.d_tok_aid && j.d_tok_src && j.d_tok_left), "null plan array");
+    OTTO_REQUIRE(dbow || j.d_In, "CBOW and PV-DM need In");
+    OTTO_REQUIRE(!doc || (j.d_Doc && j.d_tok_off), "PV-DM and DBOW need Doc and tok_off");
+    const bool hs = j.d_path_off || j.d_path_node || j.d_code;
+    if (hs) {
+        OTTO_REQUIRE(j.d_path_off && j.d_path_node && j.d_code && j.d_Syn1, "null hierarchical-softmax table");
+        OTTO_REQUIRE(j.n_inner >= 1 && j.n_inner < (1ll << 31), "n_inner = %lld outside [1, 2^31)", (long long)j.n_inner);
+    }
+    if (batch) {
+        OTTO_REQUIRE(j.d_gout && (dbow || j.d_gin) && (!doc || j.d_gdoc) && (!hs || j.d_gsyn1),
+                     "BATCH mode needs the gradient workspaces of its arch");
+    }
+    SgCbowArgs a;
+    memset(&a, 0, sizeof a);
+    if (neg > 0) {
+        OTTO_REQUIRE(j.table.total > 0, "negative table: total weight is 0, nothing can be drawn");
+        OTTO_TRY(table_from(&j.table, &a.tab));
+        OTTO_REQUIRE(j.table.n_aids == j.n_aids && j.n_aids >= 2, "negative sampling needs at least 2 aids and a table over n_aids");
+    }
+    a.tab.n = j.n_aids;
+    hipStream_t s = (hipStream_t)j.stream;
+    if (j.t0 == j.t1) {
+        OTTO_HIP(hipMemsetAsync(j.d_loss_sum, 0, sizeof(double), s));
+        return 0;
+    }
+    void* scratch = nullptr;
+    OTTO_TRY(device_scratch(SCRATCH_SGNS_STEP, (size_t)SG_GRID * sizeof(double), &scratch, s));
+    a.tok_aid = j.d_tok_aid; a.tok_src = j.d_tok_src; a.tok_left = j.d_tok_left; a.pair_off = j.d_pair_off; a.tok_off = j.d_tok_off;
+    a.T = j.T; a.S = j.S; a.t0 = j.t0; a.t1 = j.t1; a.In = j.d_In; a.Out = j.d_Out; a.Syn1 = j.d_Syn1; a.Doc = j.d_Doc;
+    a.d = d; a.G = d / 4; a.neg = neg; a.variant = j.variant; a.lr = j.lr; a.base = sg_base(j.seed, j.epoch);
+    a.partial = reinterpret_cast<double*>(scratch); a.neg_out = neg > 0 ? j.d_neg_out : nullptr;
+    a.gin = j.d_gin; a.gout = j.d_gout; a.gsyn1 = j.d_gsyn1; a.gdoc = j.d_gdoc;
+    if (hs) { a.path_off = j.d_path_off; a.path_node = j.d_path_node; a.code = j.d_code; a.n_inner = (uint32_t)j.n_inner; }
+    const int threads = a.G >= 4 ? SG_THREADS : 64 * a.G;
+    // DBOW: at most one session per token of the range meets it
+    const int64_t items = dbow ? (j.S < j.t1 - j.t0 ? j.S : j.t1 - j.t0) : j.t1 - j.t0;
+    const int grid = grid_for(items, threads / a.G);
+    if (!batch) {
+        if (hs) launch_cbow<false, true>(arch, grid, threads, s, a);
+        else launch_cbow<false, false>(arch, grid, threads, s, a);
+    } else {
+        if (hs) launch_cbow<true, true>(arch, grid, threads, s, a);
+        else launch_cbow<true, false>(arch, grid, threads, s, a);
+        const int64_t n = j.n_aids * (int64_t)d;
+        if (!dbow) k_sgns_apply<<<grid_for(n, 256), 256, 0, s>>>(j.d_In, j.d_gin, n);
+        k_sgns_apply<<<grid_for(n, 256), 256, 0, s>>>(j.d_Out, j.d_gout, n);
+        if (hs) k_sgns_apply<<<grid_for(j.n_inner * (int64_t)d, 256), 256, 0, s>>>(j.d_Syn1, j.d_gsyn1, j.n_inner * (int64_t)d);
+        if (doc) k_sgns_apply<<<grid_for(j.S * (int64_t)d, 256), 256, 0, s>>>(j.d_Doc, j.d_gdoc, j.S * (int64_t)d);
+    }
+    k_sgns_loss_final<<<1, 256, 0, s>>>(a.partial, grid, j.d_loss_sum);
+    OTTO_HIP(hipGetLastError());
+    return 0;
 }
 
 extern "C" int otto_sgns_hs_tree_sizes(const int64_t* count, int64_t n_aids, int64_t min_count, int64_t* sizes) {

@@ -9,6 +9,10 @@ SGD step run in HIP kernels. There is no CPU fallback.
 gensim's ``hs: 1`` next to ``negative > 0`` (SPEC-SGNS-HS) adds the Huffman path of every pair's context in front of its
 negative-sampling targets: :func:`huffman_tables` builds the tree and the path tables in the library (host C++), the
 engine takes them as ``hs=`` and trains a third table ``Syn1``.
+
+CBOW (fastText ``model: cbow``, gensim ``sg: 0``) and Doc2Vec (PV-DM, PV-DBOW; SPEC-CBOW and SPEC-DOC2VEC) run on the same
+plan, sampler and tables through :meth:`SkipGramEngine.step_cbow`, :func:`train_cbow` and :func:`train_doc2vec`; the two
+Doc2Vec archs train ``Doc``, one row per session.
 """
 import ctypes as C
 
@@ -17,6 +21,8 @@ import numpy as np
 from .. import _lib
 
 HOGWILD, BATCH = 0, 1               # OTTO_SGNS_HOGWILD, OTTO_SGNS_BATCH
+ARCH_CBOW, ARCH_PVDM, ARCH_DBOW = 0, 1, 2               # OTTO_SGNS_ARCH_*
+CBOW_SUM, CBOW_MEAN, CBOW_FASTTEXT = 0, 1, 2            # OTTO_SGNS_CBOW_*
 MAX_DIM, MAX_NEG, MAX_WS = 128, 64, 32
 NS_EXPONENTS = (0.0, 0.5, 0.75, 1.0)
 _U32_MAX = (1 << 32) - 1
@@ -174,6 +180,8 @@ class SkipGramEngine:
         self._work = None
         self._bufs = None
         self._grads = None
+        self._gsyn1 = None
+        self._gdoc = None
         self.hs = None
         self.Syn1 = None                 # the table of the last HS step (train(hs=True) leaves its own here)
         if hs is not None:
@@ -314,6 +322,150 @@ class SkipGramEngine:
                        self.d, self.neg, float(lr), int(mode), self.seed, plan.epoch, C.byref(self.table), loss, ctx_out, neg_out,
                        out_pairs, gin, gout)
         return loss
+
+    # ---- SPEC-CBOW, SPEC-DOC2VEC
+    def cbow_targets(self, plan, arch, t0=0, t1=None):
+        """The number of targets the centres ``[t0, t1)`` train under ``arch`` (an int, computed on the device): ``1 + neg``
+        plus the path length of the centre's aid, for every centre that is not skipped (CBOW skips a centre without
+        context)."""
+        import torch
+        t1 = plan.T if t1 is None else int(t1)
+        if t1 <= t0:
+            return 0
+        aid = plan.tok_aid[t0:t1].to(torch.int64)
+        per = torch.full_like(aid, 1 + self.neg)
+        if self.hs is not None:
+            per = per + self._path_len[aid]
+        if arch == ARCH_CBOW:
+            per = per * (plan.pair_off[t0 + 1:t1 + 1] > plan.pair_off[t0:t1])
+        return int(per.sum().item())
+
+    def _cbow_job(self, plan, t0, t1, In, Out, lr, arch, variant, mode, Syn1, Doc, neg_out, loss, grads):
+        """The ``otto_sgns_cbow_job`` of one launch on the current stream; ``grads`` = (gin, gout, gsyn1, gdoc)."""
+        p = lambda t, what: _lib.ptr(t, self.dev, what)
+        hs = self.hs is not None
+        S = int(plan.tok_off.numel()) - 1
+        gin, gout, gsyn1, gdoc = grads
+        return _lib.SgnsCbowJob(
+            p(plan.tok_aid, 'tok_aid'), p(plan.tok_src, 'tok_src'), p(plan.tok_left, 'tok_left'), p(plan.pair_off, 'pair_off'),
+            p(plan.tok_off, 'tok_off'), int(plan.T), S, int(t0), int(t1), p(In, 'In'), p(Out, 'Out'), p(Syn1, 'Syn1'), p(Doc, 'Doc'),
+            self.n_aids, self.n_inner if hs else 0, self.d, self.neg, float(lr), int(arch), int(variant), int(mode), self.seed,
+            int(plan.epoch), self.table, p(self._path_off, 'path_off') if hs else None, p(self._path_node, 'path_node') if hs else None,
+            p(self._code, 'code') if hs else None, p(loss, 'loss'), p(neg_out, 'neg_out'), p(gin, 'gin'), p(gout, 'gout'),
+            p(gsyn1, 'gsyn1'), p(gdoc, 'gdoc'), _lib.stream(self.dev))
+
+    def step_cbow(self, plan, t0, t1, In, Out, lr, arch, variant=CBOW_MEAN, mode=HOGWILD, Syn1=None, Doc=None, neg_out=None,
+                  loss=None):
+        """One launch of SPEC-CBOW / SPEC-DOC2VEC over the centres ``[t0, t1)`` of ``plan``; returns the device float64 [1]
+        loss sum. ``arch``: ``ARCH_CBOW`` (updates ``In`` and ``Out``), ``ARCH_PVDM`` (``In``, ``Out`` and ``Doc`` float32
+        [S, d], one row per session of the plan) or ``ARCH_DBOW`` (``Out`` and ``Doc``; ``In`` may be None and is never
+        touched). ``variant``: ``CBOW_SUM``, ``CBOW_MEAN`` or ``CBOW_FASTTEXT`` (ignored by DBOW). An engine built with
+        ``hs=`` walks the centre's own Huffman path on ``Syn1`` first. ``neg_out`` int32 [t1 - t0, neg]: the sampler's
+        choices per centre (tests)."""
+        import torch
+        if arch not in (ARCH_CBOW, ARCH_PVDM, ARCH_DBOW):
+            raise ValueError(f'unknown arch {arch}')
+        if arch != ARCH_DBOW and variant not in (CBOW_SUM, CBOW_MEAN, CBOW_FASTTEXT):
+            raise ValueError(f'unknown variant {variant}')
+        if mode not in (HOGWILD, BATCH):
+            raise ValueError(f'unknown mode {mode}')
+        S = int(plan.tok_off.numel()) - 1
+        shapes = [('Out', Out, self.n_aids, True), ('In', In, self.n_aids, arch != ARCH_DBOW), ('Doc', Doc, S, arch != ARCH_CBOW),
+                  ('Syn1', Syn1, self.n_inner if self.hs is not None else 0, self.hs is not None)]
+        for name, M, rows, wanted in shapes:
+            if M is None and not wanted:
+                continue
+            if name == 'Syn1' and self.hs is None:
+                raise ValueError('Syn1 given to an engine without hierarchical-softmax tables')
+            if M is None or M.dtype != torch.float32 or tuple(M.shape) != (rows, self.d) or not M.is_contiguous() or M.device != self.dev:
+                raise ValueError(f'{name}: expected contiguous float32 [{rows}, {self.d}] on {self.dev}')
+        if neg_out is not None:
+            _lib.need(neg_out, 'neg_out', torch.int32, device=self.dev)
+            if neg_out.numel() < (int(t1) - int(t0)) * self.neg:
+                raise ValueError('neg_out: room for [t1 - t0, neg] entries needed')
+        loss = self._loss if loss is None else loss
+        with torch.cuda.device(self.dev):
+            grads = (None, None, None, None)
+            if mode == BATCH:
+                z = lambda rows: torch.zeros(rows, self.d, dtype=torch.float64, device=self.dev)
+                if self._grads is None:
+                    self._grads = (z(self.n_aids), z(self.n_aids))
+                if self.hs is not None and self._gsyn1 is None:
+                    self._gsyn1 = z(self.n_inner)
+                if arch != ARCH_CBOW and (self._gdoc is None or self._gdoc.shape[0] != S):
+                    self._gdoc = z(S)
+                grads = (self._grads[0], self._grads[1], self._gsyn1 if self.hs is not None else None,
+                         self._gdoc if arch != ARCH_CBOW else None)
+            job = self._cbow_job(plan, t0, t1, In if arch != ARCH_DBOW else None, Out, lr, arch, variant, mode, Syn1,
+                                 Doc if arch != ARCH_CBOW else None, neg_out, loss, grads)
+            _lib.call('otto_sgns_cbow_step', self.dev, C.byref(job), stream=False)
+        if self.hs is not None:
+            self.Syn1 = Syn1
+        return loss
+
+
+def init_doc(n_sessions, d, seed=0):
+    """``Doc`` float32 NumPy [n_sessions, d], uniform(-1/d, 1/d) from ``default_rng([seed, 1])``: a stream of its own, so
+    that ``In`` is the same table with and without it."""
+    rng = np.random.default_rng([int(seed), 1])
+    return rng.uniform(-1.0 / d, 1.0 / d, size=(int(n_sessions), int(d))).astype(np.float32)
+
+
+def _train_arch(arch, variant, aid, sess_off, n_aids, dim, ws, neg, epochs, lr, t, min_count, ns_exponent, seed, mode,
+                tokens_per_launch, device, hs):
+    """The loop of :func:`train` over ``step_cbow``: ``(Doc or None, In, Out, losses, Syn1 or None)``."""
+    import torch
+    dev = aid.device if device is None else torch.device(device)
+    tokens_per_launch = int(tokens_per_launch)
+    if tokens_per_launch < 1:
+        raise ValueError('tokens_per_launch must be positive')
+    if int(neg) == 0 and not hs:
+        raise ValueError('neg = 0 without hierarchical softmax leaves nothing to train against')
+    count, keep_q, weight = vocab_tables(aid, n_aids, min_count, t, ns_exponent)
+    tables = huffman_tables(count, min_count) if hs else None
+    eng = SkipGramEngine(n_aids, dim, ws, neg, keep_q, weight, seed=seed, device=dev, hs=tables)
+    In_h, Out_h = init_tables(n_aids, dim, seed)
+    In, Out = torch.from_numpy(In_h).to(eng.dev), torch.from_numpy(Out_h).to(eng.dev)
+    Syn1 = torch.zeros(tables.n_inner, int(dim), dtype=torch.float32, device=eng.dev) if hs else None
+    S = int(sess_off.numel()) - 1
+    Doc = torch.from_numpy(init_doc(S, dim, seed)).to(eng.dev) if arch != ARCH_CBOW else None
+    E = int(aid.numel())
+    losses = []
+    for ep in range(int(epochs)):
+        plan = eng.plan(aid, sess_off, ep)
+        starts = list(range(0, plan.T, tokens_per_launch))
+        first_src = plan.tok_src[torch.tensor(starts, dtype=torch.int64, device=eng.dev)].cpu().tolist() if starts else []
+        total = torch.zeros(1, dtype=torch.float64, device=eng.dev)
+        for t0, src in zip(starts, first_src):
+            rate = learning_rate(lr, ep * E + int(src), int(epochs) * E)
+            total += eng.step_cbow(plan, t0, min(t0 + tokens_per_launch, plan.T), In, Out, rate, arch, variant, mode, Syn1=Syn1,
+                                   Doc=Doc)
+        losses.append(float(total.item()) / max(eng.cbow_targets(plan, arch), 1))
+    return Doc, In, Out, losses, Syn1
+
+
+def train_cbow(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, t=1e-4, min_count=1, ns_exponent=0.5, seed=0,
+               mode=HOGWILD, tokens_per_launch=1 << 24, device=None, hs=False, variant=CBOW_MEAN):
+    """Train CBOW aid embeddings (SPEC-CBOW): the arguments, the loop, the launch cut and the rate of :func:`train`.
+    ``variant``: ``CBOW_SUM`` (gensim ``cbow_mean: 0``), ``CBOW_MEAN`` (``cbow_mean: 1``) or ``CBOW_FASTTEXT`` (fastText
+    ``model: cbow``). Returns ``(In, Out, losses)``, or ``(In, Out, losses, Syn1)`` with ``hs=True``; the mean loss divides
+    by the number of targets actually trained (a centre without context trains none). ``neg = 0`` needs ``hs=True``."""
+    _, In, Out, losses, Syn1 = _train_arch(ARCH_CBOW, variant, aid, sess_off, n_aids, dim, ws, neg, epochs, lr, t, min_count,
+                                           ns_exponent, seed, mode, tokens_per_launch, device, hs)
+    return (In, Out, losses, Syn1) if hs else (In, Out, losses)
+
+
+def train_doc2vec(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, t=1e-4, min_count=1, ns_exponent=0.5, seed=0,
+                  mode=HOGWILD, tokens_per_launch=1 << 24, device=None, hs=False, dm=1, dm_mean=1):
+    """Train session vectors (SPEC-DOC2VEC): ``dm=1`` is PV-DM (the mean of the context rows and the session's row with
+    ``dm_mean=1``, their sum with ``dm_mean=0``), ``dm=0`` is PV-DBOW (``In`` is returned as initialised). ``Doc`` float32
+    [S, dim] starts uniform(-1/dim, 1/dim) from ``default_rng([seed, 1])``. Returns ``(Doc, In, Out, losses)``, or
+    ``(Doc, In, Out, losses, Syn1)`` with ``hs=True``."""
+    arch = ARCH_PVDM if int(dm) else ARCH_DBOW
+    variant = CBOW_MEAN if int(dm_mean) else CBOW_SUM
+    Doc, In, Out, losses, Syn1 = _train_arch(arch, variant, aid, sess_off, n_aids, dim, ws, neg, epochs, lr, t, min_count,
+                                             ns_exponent, seed, mode, tokens_per_launch, device, hs)
+    return (Doc, In, Out, losses, Syn1) if hs else (Doc, In, Out, losses)
 
 
 def train(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, t=1e-4, min_count=1, ns_exponent=0.5, seed=0,

@@ -8,10 +8,17 @@ section 3i). Sessions come from ``settings.DATA / 'train.pkl'`` and ``'test.pkl'
 text format, in-vocabulary aids by count descending then aid ascending). ``fasttext.bin`` / ``word2vec.model`` are not
 written.
 
-Refused with ``ValueError``: ``model: cbow``, ``loss`` other than ``ns``, ``minn`` / ``maxn`` above 0 (fastText);
-``sg: 0`` or ``negative: 0`` (Word2Vec, with or without ``hs: 1``: hierarchical softmax alone is not built);
-``Doc2Vec``. ``hs: 1`` with ``negative > 0`` (the reference's own Word2Vec file) trains hierarchical softmax next to the
-negative-sampling part (SPEC-SGNS-HS), over the word2vec.c tree rather than gensim's heap; that departure is logged once.
+:func:`resolve` maps a config to one of three trainers. ``fasttext_args``, ``word2vec_args`` and ``train_args`` are the
+skip-gram mapping and refuse everything else with ``ValueError``: ``model: cbow``, ``loss`` other than ``ns``, ``minn`` /
+``maxn`` above 0 (fastText); ``sg: 0`` or ``negative: 0`` (Word2Vec, with or without ``hs: 1``: hierarchical softmax alone
+is not built for skip-gram); ``Doc2Vec``. ``hs: 1`` with ``negative > 0`` (the reference's own Word2Vec file) trains
+hierarchical softmax next to the negative-sampling part (SPEC-SGNS-HS), over the word2vec.c tree rather than gensim's
+heap; that departure is logged once.
+
+:func:`resolve` additionally takes fastText ``model: cbow`` and gensim ``sg: 0`` (SPEC-CBOW) and ``Doc2Vec`` (SPEC-DOC2VEC:
+``dm: 1`` PV-DM, ``dm: 0`` PV-DBOW), where ``hs: 1`` may also stand alone (``negative: 0``). Doc2Vec is the one model that
+yields a session vector: ``doc_embeddings.npy`` (float32 [S, dim]) and ``doc_sessions.npy`` (the session id of each row).
+Still refused: ``dm_concat``, ``dbow_words``, ``dm_tag_count`` other than 1, sub-words, ``loss`` other than ``ns``.
 """
 import argparse
 import logging
@@ -72,14 +79,61 @@ def train_args(config):
     if name == 'Word2Vec':
         return word2vec_args(config['model']['model_args'])
     if name == 'Doc2Vec':
-        raise ValueError('Doc2Vec is not built')
+        raise ValueError('Doc2Vec is not built as skip-gram (resolve maps it to train_doc2vec)')
     raise ValueError('Invalid model_name')
 
 
+def _objective(hs, neg):
+    if not hs and neg <= 0:
+        raise ValueError('negative: 0 without hs: 1 leaves nothing to train against')
+    return dict(neg=max(neg, 0), hs=hs)
+
+
+def _gensim_common(a):
+    """What Word2Vec(sg=0) and Doc2Vec share: gensim's defaults where absent."""
+    hs, neg = bool(int(a.get('hs', 0))), int(a['negative'] if 'negative' in a else 5)
+    return dict(dim=int(a.get('vector_size', 100)), ws=int(a.get('window', 5)), epochs=int(a.get('epochs', 5)),
+                lr=float(a.get('alpha', 0.025)), t=float(a.get('sample', 1e-3)), min_count=int(a.get('min_count', 5)),
+                ns_exponent=float(a.get('ns_exponent', 0.75)), seed=int(a.get('seed', 1)), **_objective(hs, neg))
+
+
+def resolve(config):
+    """``config`` (the whole YAML mapping) -> ``(arch, kwargs)``: ``'skipgram'`` with the :func:`skipgram.train` keywords
+    (the skip-gram mapping above, its refusals included), ``'cbow'`` with :func:`skipgram.train_cbow`'s, or ``'doc2vec'``
+    with :func:`skipgram.train_doc2vec`'s. ``hs`` is among the keywords.
+
+    fastText ``model: cbow`` is the FASTTEXT variant; gensim ``sg: 0`` takes ``cbow_mean`` (default 1); ``Doc2Vec`` takes
+    ``dm`` (default 1) and ``dm_mean``, where an absent or null ``dm_mean`` means the mean (SPEC-DOC2VEC's build
+    decision). ``hs: 1`` with ``negative: 0`` is accepted by the two new archs. Refused: ``dm_concat``, ``dbow_words``,
+    ``dm_tag_count`` other than 1, sub-words, ``loss`` other than ``ns``, and no objective at all."""
+    model = config['model']
+    name, a = model['model_name'], dict(model.get('model_args') or {})
+    if name == 'FastText' and a.get('model', 'skipgram') == 'cbow':
+        kw = fasttext_args({**a, 'model': 'skipgram'})      # the same keywords and the same refusals (loss, sub-words)
+        kw.update(_objective(False, kw['neg']), variant=skipgram.CBOW_FASTTEXT)
+        return 'cbow', kw
+    if name == 'Word2Vec' and int(a.get('sg', 0)) == 0:
+        variant = skipgram.CBOW_MEAN if int(a.get('cbow_mean', 1)) else skipgram.CBOW_SUM
+        return 'cbow', dict(_gensim_common(a), variant=variant)
+    if name == 'Doc2Vec':
+        if int(a.get('dm_concat', 0)):
+            raise ValueError('dm_concat: 1 is not built')
+        if int(a.get('dbow_words', 0)):
+            raise ValueError('dbow_words: 1 is not built')
+        if int(a.get('dm_tag_count', 1)) != 1:
+            raise ValueError('dm_tag_count other than 1 is not built (one tag, the session, per document)')
+        dm_mean = a.get('dm_mean')
+        return 'doc2vec', dict(_gensim_common(a), dm=int(a.get('dm', 1)), dm_mean=1 if dm_mean is None else int(dm_mean))
+    return 'skipgram', dict(train_args(config), hs=hs_requested(config))
+
+
 def run(config, df=None, device='cuda:0', n_aids=None, tokens_per_launch=1 << 24):
-    """Train and write both files; returns ``(In, losses, model_root_directory)``. ``df``: a frame or a list of frames
-    with ``session``, ``aid``, ``ts``, ``type`` (default: ``train.pkl`` + ``test.pkl`` under ``settings.DATA``)."""
-    kw = train_args(config)                               # refusals come before any file or device is touched
+    """Train and write the files; returns ``(In, losses, model_root_directory)``. ``df``: a frame or a list of frames
+    with ``session``, ``aid``, ``ts``, ``type`` (default: ``train.pkl`` + ``test.pkl`` under ``settings.DATA``).
+    Doc2Vec also writes ``doc_embeddings.npy`` (float32 [S, dim]) and ``doc_sessions.npy`` (the session id of each row);
+    the first entry of the result is then that session table, and PV-DBOW, which trains no aid vectors, writes no aid
+    files."""
+    arch, kw = resolve(config)                            # refusals come before any file or device is touched
     from ..events import frame_to_events_device
     model_root_directory = pathlib.Path(settings.MODELS / config['persistence']['model_directory'])
     model_root_directory.mkdir(parents=True, exist_ok=True)
@@ -88,17 +142,27 @@ def run(config, df=None, device='cuda:0', n_aids=None, tokens_per_launch=1 << 24
         df = [pd.read_pickle(settings.DATA / 'train.pkl'), pd.read_pickle(settings.DATA / 'test.pkl')]
     ev = frame_to_events_device(df, device=device, n_aids=n_aids)
     logging.info(f'Sentences Dataset - sentences: {ev.n_sessions} - tokens: {ev.n_events}')
-    In, _, losses = skipgram.train(ev.aid, ev.sess_off, ev.n_aids, tokens_per_launch=tokens_per_launch,
-                                   hs=hs_requested(config), **kw)[:3]
+    Doc = None
+    if arch == 'doc2vec':
+        Doc, In, _, losses = skipgram.train_doc2vec(ev.aid, ev.sess_off, ev.n_aids, tokens_per_launch=tokens_per_launch, **kw)[:4]
+    else:
+        fn = skipgram.train_cbow if arch == 'cbow' else skipgram.train
+        In, _, losses = fn(ev.aid, ev.sess_off, ev.n_aids, tokens_per_launch=tokens_per_launch, **kw)[:3]
     for ep, ls in enumerate(losses):
         logging.info(f'epoch {ep}: mean loss {ls:.6f}')
     In = In.cpu().numpy()
-    count, _, _ = skipgram.vocab_tables(ev.aid, ev.n_aids, kw['min_count'], kw['t'], kw['ns_exponent'])
-    count[count < max(kw['min_count'], 1)] = 0
-    np.save(model_root_directory / 'aid_embeddings.npy', In)
-    skipgram.save_vec(model_root_directory / 'aid_embeddings.vec', In, count)
-    logging.info(f"{config['model']['model_name']} aid embeddings finished training and saved to {model_root_directory}")
-    return In, losses, model_root_directory
+    if Doc is not None:
+        Doc = Doc.cpu().numpy()
+        np.save(model_root_directory / 'doc_embeddings.npy', Doc)
+        ids = ev.session_ids
+        np.save(model_root_directory / 'doc_sessions.npy', ids.cpu().numpy() if hasattr(ids, 'cpu') else np.asarray(ids))
+    if Doc is None or kw['dm']:
+        count, _, _ = skipgram.vocab_tables(ev.aid, ev.n_aids, kw['min_count'], kw['t'], kw['ns_exponent'])
+        count[count < max(kw['min_count'], 1)] = 0
+        np.save(model_root_directory / 'aid_embeddings.npy', In)
+        skipgram.save_vec(model_root_directory / 'aid_embeddings.vec', In, count)
+    logging.info(f"{config['model']['model_name']} embeddings finished training and saved to {model_root_directory}")
+    return (In if Doc is None else Doc), losses, model_root_directory
 
 
 if __name__ == '__main__':

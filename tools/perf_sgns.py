@@ -14,11 +14,18 @@ Sessions from ``synth.generate_sessions`` (n_aids = 1,855,603), d = 32, ws = 10,
 node id per path node per pair. Compare it with a run without ``--hs`` by alternating the two in one job, several processes
 each; ``--skip-host`` leaves the host baseline out of such runs.
 
+``--arch cbow | pvdm | dbow`` times one launch of ``otto_sgns_cbow_step`` (SPEC-CBOW, SPEC-DOC2VEC) on the same plan instead,
+with ``--variant sum | mean | fasttext``. Its targets are 1 + neg (plus the centre's own path with ``--hs``) per trained
+centre, not per pair; to the algorithmic bytes each input row (a context row of In, PV-DM's doc row) adds 2 * 4d bytes, read
+and written once, and each context 4 bytes of token id. DBOW reads and writes one Doc row per session of the launch.
+``--append`` adds the JSON line to ``--out`` instead of replacing the file, so that alternating runs collect in one .jsonl.
+
 Host baseline, same run: vectorised NumPy batch steps of 4,096 centres over 2^16 tokens (the restatement's sequential loop is far too
 slow to time). No fastText or gensim figure exists: neither library is installed where this project is built.
 Needs a GPU; there is no fallback.
 
-    python tools/perf_sgns.py [--sessions 2000000] [--tokens 16777216] [--hs] [--skip-host] [--out profiles/sgns/perf_sgns.json]
+    python tools/perf_sgns.py [--sessions 2000000] [--tokens 16777216] [--hs] [--arch skipgram] [--variant mean] [--skip-host]
+                              [--out profiles/sgns/perf_sgns.json] [--append]
 """
 import argparse
 import json
@@ -80,7 +87,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--hs', action='store_true', help='time otto_sgns_step_hs: the Huffman path half next to the negatives')
+    ap.add_argument('--arch', choices=('skipgram', 'cbow', 'pvdm', 'dbow'), default='skipgram',
+                    help='cbow, pvdm, dbow: time otto_sgns_cbow_step on the same plan')
+    ap.add_argument('--variant', choices=('sum', 'mean', 'fasttext'), default='mean')
     ap.add_argument('--skip-host', action='store_true', help='leave the NumPy host baseline out')
+    ap.add_argument('--append', action='store_true', help='append the line to --out')
     ap.add_argument('--out', default='')
     args = ap.parse_args()
     import torch
@@ -108,7 +119,7 @@ def main():
         step_kw['Syn1'] = torch.from_numpy(sg.init_tables(tables.n_inner, d, 2)[0]).to(dev)
     out = {'tool': 'perf_sgns', 'device': torch.cuda.get_device_name(0), 'sessions': args.sessions, 'events': E, 'n_aids': n_aids,
            'd': d, 'ws': args.ws, 'neg': args.neg, 't': args.t, 'warmup': args.warmup, 'repeats': args.repeats,
-           'table_bytes_each': n_aids * d * 4, 'hs': bool(args.hs)}
+           'table_bytes_each': n_aids * d * 4, 'hs': bool(args.hs), 'arch': args.arch}
     if args.hs:
         out['huffman'] = {'V': tables.V, 'n_inner': tables.n_inner, 'max_len': tables.max_len, 'path_nodes': int(tables.path_node.size),
                           'host_tree_seconds': round(tree_s, 3)}
@@ -117,6 +128,11 @@ def main():
     n_tok = min(args.tokens, plan.T)
     pairs = int(plan.pair_off[n_tok] - plan.pair_off[0])
     out.update(kept_tokens=plan.T, pairs=plan.P, launch_tokens=n_tok, launch_pairs=pairs)
+    if args.arch != 'skipgram':
+        out['variant'] = args.variant
+        out['hogwild'] = _time_cbow(args, sg, eng, plan, n_tok, pairs, In, Out, step_kw, d)
+        _emit(out, args.out, args.append)
+        return
     hw = _time(lambda: eng.step(plan, 0, n_tok, In, Out, 0.05, sg.HOGWILD, **step_kw), args.warmup, args.repeats)
     sec = hw['median_ms'] * 1e-3
     path_rows = eng.path_targets(plan, 0, n_tok)
@@ -128,7 +144,7 @@ def main():
               bytes_per_s=round(n_bytes / sec), share_of_hbm_peak=round(n_bytes / sec / HBM_PEAK, 4))
     out['hogwild'] = hw
     if args.skip_host:
-        _emit(out, args.out)
+        _emit(out, args.out, args.append)
         return
     m = min(args.host_tokens, plan.T)
     tok_aid, left = plan.tok_aid[:m + 64].cpu().numpy().astype(np.int64), plan.tok_left[:m + 64].cpu().numpy()
@@ -146,15 +162,40 @@ def main():
     out['host_numpy_batch_step'] = {'tokens': valid, 'pairs': host_pairs, 'seconds': round(hs, 3), 'tokens_per_s': round(valid / hs),
                                     'what': 'one run, one process, vectorised NumPy batch step on the host of the GPU machine; '
                                             'no fastText or gensim figure exists (neither is installed)'}
-    _emit(out, args.out)
+    _emit(out, args.out, args.append)
 
 
-def _emit(out, path):
+def _time_cbow(args, sg, eng, plan, n_tok, pairs, In, Out, step_kw, d):
+    """one hogwild launch of otto_sgns_cbow_step over the first n_tok centres: the timing and the byte model of the docstring"""
+    import torch
+    arch = {'cbow': sg.ARCH_CBOW, 'pvdm': sg.ARCH_PVDM, 'dbow': sg.ARCH_DBOW}[args.arch]
+    variant = {'sum': sg.CBOW_SUM, 'mean': sg.CBOW_MEAN, 'fasttext': sg.CBOW_FASTTEXT}[args.variant]
+    S = int(plan.tok_off.numel()) - 1
+    kw = dict(step_kw)
+    if arch != sg.ARCH_CBOW:
+        kw['Doc'] = torch.from_numpy(sg.init_doc(S, d, 1)).to(In.device)
+    hw = _time(lambda: eng.step_cbow(plan, 0, n_tok, In, Out, 0.05, arch, variant, sg.HOGWILD, **kw), args.warmup, args.repeats)
+    sec = hw['median_ms'] * 1e-3
+    targets = eng.cbow_targets(plan, arch, 0, n_tok)
+    sessions = int(((plan.tok_off[:-1] < n_tok) & (plan.tok_off[1:] > plan.tok_off[:-1])).sum().item())      # with a token in the launch
+    if arch == sg.ARCH_DBOW:
+        input_rows, id_bytes = sessions, n_tok * 4
+    else:
+        input_rows = pairs + (n_tok if arch == sg.ARCH_PVDM else 0)
+        id_bytes = n_tok * 5 + pairs * 4
+    n_bytes = targets * 2 * 4 * d + input_rows * 2 * 4 * d + id_bytes
+    hw.update(targets=targets, input_rows=input_rows, sessions_in_launch=sessions, tokens_per_s=round(n_tok / sec),
+              target_rows_per_s=round(targets / sec), algorithmic_bytes=n_bytes, bytes_per_s=round(n_bytes / sec),
+              share_of_hbm_peak=round(n_bytes / sec / HBM_PEAK, 4))
+    return hw
+
+
+def _emit(out, path, append=False):
     line = json.dumps(out)
     print(line)
     if path:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, 'w') as fh:
+        with open(path, 'a' if append else 'w') as fh:
             fh.write(line + '\n')
 
 
