@@ -98,7 +98,12 @@ int otto_covis_reset(otto_covis_ctx* ctx);
 /*
  * K1 pair-expand over one chunk of sessions.  Events of session s are
  * d_aid/d_ts/d_type[d_sess_off[s] .. d_sess_off[s+1]) with ts NON-DECREASING inside a session (SPEC-COVIS 1;
- * the gap-free window test relies on it).  May be called
+ * the gap-free window test relies on it).  A window whose stamps are NOT sorted still has a defined result:
+ * the ordered pairs (i, j) of window positions with aid_i != aid_j and |ts_i - ts_j| <= max_gap, deduplicated
+ * by the first valid (i, j) in lexicographic order, exactly as for a sorted window (the component-list kernel
+ * detects the descending step and expands the window with its general row loop; the class kernels test every
+ * pair anyway).  Stamps lie in [0, 2^31 - 1], so the difference of two stamps always fits an int32; the
+ * kernels' int / uint32 differences rely on it, and a negative stamp is outside the contract.  May be called
  * several times (session chunks); records accumulate in the context.
  * Synchronises the stream once (to size the record buffers).
  */

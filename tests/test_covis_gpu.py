@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import covis_oracle as co
+import expand_check
 from otto_amd.synth import generate_sessions, Events
 from otto_amd.covisitation import spec as cs
 
@@ -76,48 +77,17 @@ def test_pair_expand_records_match_oracle(gpu_device, kinds, options):
     (x, y, type_y, filter bits, time extra): each ordered pair at most once, whatever runs it is spread over."""
     ev = generate_sessions(1500, n_aids=400, seed=3)
     b, _ = _build(ev, gpu_device, kinds=kinds, options=options)
-    rec, tw, run_x, run_desc = b.copy_records()
     sp = co.CovisSpec()
     t0, t1 = int(ev.ts.min()), int(ev.ts.max())
-    fk = b.filter_kinds
     L = np.diff(ev.sess_off)
     nwin = np.where(np.minimum(L, 30) >= 2, np.minimum(L, 30), 0)
     ev_base = np.r_[0, np.cumsum(nwin)]
     pair_base = np.r_[0, np.cumsum(nwin * (nwin - 1))]
-    lists = len(rec) == pair_base[-1] + ev_base[-1]          # component lists: n list slots per window behind the pair slots
+    lists, reports = expand_check.check_records(ev, b, sp, t0, t1)   # per window: geometry of the runs, records as a set vs the oracle
+    assert lists == (b.stats()['pair_slots'] == pair_base[-1] + ev_base[-1])   # component lists: n list slots per window behind the pair slots
     assert b.stats()['tail_events'] == ev_base[-1] and b.stats()['pair_slots'] == pair_base[-1] + (ev_base[-1] if lists else 0)
-    total = shared_runs = 0
-    for s in range(ev.n_sessions):
-        want = co.expand_window_python(ev.aid, ev.ts, ev.type, int(ev.sess_off[s]), int(ev.sess_off[s + 1]), sp, fk, t0, t1)
-        got = []
-        used = set()
-        for r in range(int(ev_base[s]), int(ev_base[s + 1])):
-            d = int(run_desc[r])
-            ln, off, spos = d & 0x3F, (d >> 8) & ((1 << 40) - 1), (d >> 48) & 63
-            if not ln:
-                assert d == 0 and run_x[r] == 0xFFFFFFFF
-                continue
-            x = int(run_x[r])
-            if spos != 63:
-                assert lists and pair_base[-1] + ev_base[s] <= off and off + ln <= pair_base[-1] + ev_base[s + 1]
-                assert spos < ln and int(rec[off + spos]) & 0x3FFFFFF == x
-                shared_runs += 1
-            else:
-                assert pair_base[s] <= off and off + ln <= pair_base[s + 1]
-            for t in range(ln):
-                if t == spos:
-                    continue
-                rc = int(rec[off + t])
-                if spos == 63:
-                    assert off + t not in used
-                    used.add(off + t)
-                e = 0 if tw is None else int(tw[off + (spos if spos != 63 else t)])
-                got.append((x, rc & 0x3FFFFFF, (rc >> 26) & 3, rc >> 28, e))
-        if tw is None:
-            want = [w[:4] + (0,) for w in want]
-        assert len(set(g[:2] for g in got)) == len(got), f'session {s}: a pair occurs twice'
-        assert sorted(got) == sorted(want), f'session {s}'
-        total += len(want)
+    total = sum(r.pairs for r in reports)
+    shared_runs = sum(r.shared_runs for r in reports)
     assert b.stats()['pairs'] == total
     assert (shared_runs > 0) == lists
 
