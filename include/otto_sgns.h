@@ -3,7 +3,8 @@
  * the negative-sampling table, the per-epoch plan (subsampling, compaction, shrunken windows), the SGD step, and the
  * hierarchical-softmax half of gensim's hs: 1 (SPEC-SGNS-HS below: Huffman tree, path tables, a third table Syn1), and the
  * other two architectures of a word2vec trainer on the same plan and sampler: CBOW and Doc2Vec (SPEC-CBOW and SPEC-DOC2VEC
- * below, otto_sgns_cbow_step; PV-DM and PV-DBOW train a table of session vectors).
+ * below, otto_sgns_cbow_step; PV-DM and PV-DBOW train a table of session vectors), and the inference of such a vector for a
+ * session that took no part in training (SPEC-DOC2VEC-INFER below, otto_sgns_infer).
  *
  * What this replaces in the reference: src/gensim_fasttext/trainer.py, i.e. fasttext.train_unsupervised with
  * models/fasttext/config.yaml (skipgram, loss ns, dim 32, ws 10, neg 40, epoch 5, t 1e-4, minn = maxn = 0: no sub-words,
@@ -141,6 +142,41 @@
  * pre-launch tables (DBOW: h = Doc[s] stays fixed over the session's tokens); the contributions go by float64 atomics into
  * the dense workspaces gin [n_aids, d], gout [n_aids, d], gsyn1 [n_inner, d] and gdoc [S, d] and are applied once. The
  * workspaces are zero on entry and zero again on return.
+ *
+ * SPEC-DOC2VEC-INFER: session vectors for sessions that took no part in training (gensim's Doc2Vec.infer_vector;
+ * otto_sgns_infer). Build-defined and parity-unpinned like SPEC-SGNS; tests/sgns_infer_restatement.py is the checker.
+ * Everything not named here is SPEC-SGNS, SPEC-CBOW or SPEC-DOC2VEC as they stand: mix64, base / ev / key, draw, the Huffman
+ * tables, exact expf / log1pf, the label and loss terms.
+ * Model, frozen: Out float32 [n_aids, d]; In float32 [n_aids, d] (PV-DM alone); Syn1 and the three Huffman tables (with
+ * hs); the negative table of the training corpus; the training corpus's keep_q, of which only zero / non-zero is read (zero:
+ * out of the vocabulary). No model table is written: there is no race in the launch.
+ * Tokens. A new session's tokens are its events with keep_q[aid] != 0, in order. Departure from gensim: there is no
+ * sub-sampling at inference. The caller gets tok_aid and tok_off from otto_sgns_plan with a keep table that is 2^32 - 1
+ * where keep_q != 0 and 0 elsewhere (an aid outside [0, n_aids) is therefore the plan's OTTO_EINVAL). i is a token's index
+ * among the tokens of its session.
+ * Keys. sess_key uint64 [S]: the session id (a null pointer: the row index s). For pass p:
+ *     sb(p, s)    = ev-mix of base(seed, p) with sess_key[s]:  mix64(base(seed, p) ^ (sess_key[s] * 0xA0761D6478BD642F))
+ *     ev(p, s, i) = mix64(sb(p, s) ^ (i * 0xA0761D6478BD642F))
+ *     radius      = 1 + ((hi32(key(ev, 2, 0)) * ws) >> 32)
+ *     negative j  = SPEC-CBOW's rule on ev and the token's aid: stream 4, redrawn up to 16 times while equal to the aid
+ * Nothing depends on the batch, the grid, the lane-group size or the order in which sessions are taken: a session's vector
+ * is the same bytes whatever batch it arrives in.
+ * Initial row. Component j of session s: k = key(sb(0, s), 5, j), r = k >> 41 (23 bits),
+ *     v = ((float)(2r + 1) * 2^-24 - 0.5f) * (2.0f / d)
+ * an odd multiple of 2^-24 * 2/d inside (-1/d, 1/d). Every step is exact in float32 (d is a power of two). Stream 5 is used
+ * by nothing else.
+ * Passes. P passes, 1 <= P <= OTTO_SGNS_MAX_INFER_PASSES, with the rates lr[p] float32 made by the caller
+ * (otto_amd.gensim_fasttext.skipgram.infer_rates: alpha - (alpha - min_alpha) * p / max(P - 1, 1) in float64, then rounded).
+ * The doc row h_doc is held from the initial row to one store after the last pass; a session's passes run in order.
+ * PV-DBOW. Per pass, per token i in order: the targets of SPEC-CBOW for the token's aid a and ev(p, s, i) (the path of a on
+ * Syn1 with label 1 - bit, a on Out with label 1, neg negatives with label 0); x = <h_doc, row>, g = lr[p] * (label -
+ * sigmoid(x)), grad += g * row; no target row is written; then h_doc += grad.
+ * PV-DM. Per pass, per token c in order: the contexts are the session's tokens at offsets -r..-1, +1..+r clipped to the
+ * session, in that order; h = the float32 sum of In[x_k] in order, then h_doc last; n = np + 1; with the mean variants
+ * h / (float)n. The targets are evaluated against h as above. u = grad or grad / (float)n by the SUM / MEAN / FASTTEXT table
+ * of SPEC-CBOW; h_doc += u; In is not written. Centre c + 1 sees the doc row that centre c left: the exact sequential loop.
+ * Outputs. Doc' float32 [S, d]; optionally loss float64 [S, 2]: the session's loss sum in pass 0 and in pass P - 1. A session
+ * without tokens keeps its initial row and has loss 0. Nothing is reduced across sessions: no scratch, no synchronisation.
  */
 #ifndef OTTO_SGNS_H
 #define OTTO_SGNS_H
@@ -281,6 +317,49 @@ typedef struct otto_sgns_cbow_job {
  * needs; t0 > t1 or a range outside [0, T]. neg == 0 without Huffman tables is accepted, as otto_sgns_step accepts it
  * (the centre's own aid with label 1 is then the only target); the Python trainers refuse it. */
 int otto_sgns_cbow_step(const otto_sgns_cbow_job* job);
+
+/* SPEC-DOC2VEC-INFER */
+#define OTTO_SGNS_MAX_INFER_PASSES 64
+
+/* One launch of otto_sgns_infer over S new sessions. All device work goes to `stream`. */
+typedef struct otto_sgns_infer_job {
+    /* the tokens (otto_sgns_plan over the 0 / 2^32 - 1 keep table): d_tok_aid int32 [T], d_tok_off int64 [S+1] */
+    const int32_t* d_tok_aid;
+    const int64_t* d_tok_off;
+    int64_t T, S;
+    const uint64_t* d_sess_key;     /* nullable, uint64 [S]: the session ids that key every draw; null: the row index */
+    const int64_t* d_order;         /* nullable, int64 [S]: a permutation of the rows, the order in which lane groups take
+                                       them (longest first evens out a wave); null: identity. An entry outside [0, S) is
+                                       skipped. The result does not depend on it. */
+    /* the frozen model: d_In (PV-DM alone), d_Out float32 [n_aids, d]; d_Syn1 float32 [n_inner, d] with the Huffman tables */
+    const float* d_In;
+    const float* d_Out;
+    const float* d_Syn1;
+    int64_t n_aids, n_inner;
+    int32_t d, neg, ws;             /* d by otto_sgns_step's rule; 0 <= neg <= OTTO_SGNS_MAX_NEG; 1 <= ws <= OTTO_SGNS_MAX_WS */
+    int32_t arch, variant, passes;  /* OTTO_SGNS_ARCH_PVDM / _DBOW; OTTO_SGNS_CBOW_* (read by PV-DM alone, but checked);
+                                       1 <= passes <= OTTO_SGNS_MAX_INFER_PASSES */
+    float lr[OTTO_SGNS_MAX_INFER_PASSES];   /* lr[p], p < passes */
+    uint64_t seed;
+    /* the sampler of the training corpus (read when neg > 0) and its Huffman tables: all three present is the HS switch */
+    otto_sgns_table table;
+    const int64_t* d_path_off;
+    const int32_t* d_path_node;
+    const uint64_t* d_code;
+    float* d_Doc;                   /* out, float32 [S, d] */
+    double* d_loss;                 /* nullable, float64 [S, 2]: the session's loss sum in pass 0 and in pass passes - 1 */
+    int32_t* d_neg_out;             /* nullable, int32 [passes, T, neg]: the negatives of token c in pass p (the tests' window) */
+    uint8_t* d_radius_out;          /* nullable, uint8 [passes, T]: the radius of centre c in pass p (PV-DM alone writes it) */
+    void* stream;
+} otto_sgns_infer_job;
+
+/* SPEC-DOC2VEC-INFER in one launch: one lane group per session, every pass inside the kernel. No model table is written, no
+ * scratch is used and the stream is not synchronised. OTTO_EINVAL, with nothing launched and d_Doc unwritten, for: arch CBOW
+ * or unknown, an unknown variant; d outside otto_sgns_step's rule; neg outside [0, OTTO_SGNS_MAX_NEG], or neg > 0 without a
+ * usable table over n_aids >= 2 aids; ws outside [1, OTTO_SGNS_MAX_WS]; passes outside [1, OTTO_SGNS_MAX_INFER_PASSES]; PV-DM
+ * without d_In; only some of the three Huffman tables, or tables without d_Syn1 or with n_inner < 1; neg == 0 without
+ * Huffman tables (nothing would train); a null d_tok_off, d_Out or d_Doc. S == 0 launches nothing. */
+int otto_sgns_infer(const otto_sgns_infer_job* job);
 
 #ifdef __cplusplus
 }

@@ -107,6 +107,20 @@ class SgnsCbowJob(C.Structure):
                 ('d_gsyn1', C.c_void_p), ('d_gdoc', C.c_void_p), ('stream', C.c_void_p)]
 
 
+SGNS_MAX_INFER_PASSES = 64          # OTTO_SGNS_MAX_INFER_PASSES
+
+
+class SgnsInferJob(C.Structure):
+    # mirrors otto_sgns_infer_job (include/otto_sgns.h)
+    _fields_ = [('d_tok_aid', C.c_void_p), ('d_tok_off', C.c_void_p), ('T', C.c_int64), ('S', C.c_int64),
+                ('d_sess_key', C.c_void_p), ('d_order', C.c_void_p), ('d_In', C.c_void_p), ('d_Out', C.c_void_p),
+                ('d_Syn1', C.c_void_p), ('n_aids', C.c_int64), ('n_inner', C.c_int64), ('d', C.c_int32), ('neg', C.c_int32),
+                ('ws', C.c_int32), ('arch', C.c_int32), ('variant', C.c_int32), ('passes', C.c_int32),
+                ('lr', C.c_float * SGNS_MAX_INFER_PASSES), ('seed', C.c_uint64), ('table', SgnsTable), ('d_path_off', C.c_void_p),
+                ('d_path_node', C.c_void_p), ('d_code', C.c_void_p), ('d_Doc', C.c_void_p), ('d_loss', C.c_void_p),
+                ('d_neg_out', C.c_void_p), ('d_radius_out', C.c_void_p), ('stream', C.c_void_p)]
+
+
 class XgbTree(C.Structure):
     # mirrors otto_xgb_tree (include/otto_xgb.h): 16 host arrays, then what the call writes
     _fields_ = [(name, C.c_void_p) for name in (
@@ -328,6 +342,7 @@ SIGNATURES = {
     'otto_sgns_hs_tree_sizes': (_i32, [_vp, _i64, _i64, _p_i64]),
     'otto_sgns_hs_tree': (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     'otto_sgns_cbow_step': (_i32, [C.POINTER(SgnsCbowJob)]),
+    'otto_sgns_infer': (_i32, [C.POINTER(SgnsInferJob)]),
     # include/otto_submit.h
     'otto_submit_workspace': (_i64, [_i64, _i32]),
     'otto_submit_measure': (_i32, [_i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int32), _vp, _i64, _i32, _i64, _i32, _p_i64,

@@ -22,6 +22,10 @@
 //                   float32 atomic adds in place (the centres of a session share these rows, plain read-modify-writes
 //                   would lose all but one of their concurrent updates); BATCH: float64 atomic adds into the workspaces.
 //   k_sgns_dbow<BATCH, HS>  PV-DBOW: one lane group per session that meets the launch's range; h = Doc[s] in registers.
+//   k_sgns_infer<HS, DM> SPEC-DOC2VEC-INFER: one lane group per new session, taken through an order array; every pass and every
+//                   token of the session inside the launch, the doc row in registers from its keyed initial value to one store.
+//                   The model is frozen: the targets go through sg_targets' FROZEN path (no store, no atomic). No loss partial,
+//                   no scratch: the loss is per session.
 //   k_sgns_apply         BATCH: table += workspace, workspace = 0 (dense sweep).
 //   k_sgns_loss_final    sums the per-workgroup loss partials in a fixed order.
 // Host: otto_sgns_hs_tree_sizes / otto_sgns_hs_tree build the Huffman tree and the path tables of SPEC-SGNS-HS (no HIP call).
@@ -233,11 +237,12 @@ static __device__ __forceinline__ int32_t sgns_negative(const SgTable& t, uint64
 // The rows idf(0) .. idf(n - 1) of `tab` against h, four at a time: the loads of a four go out before its first update.
 // idf(m) < 0: no row. labf(m): the label. DUP: a row named twice in a four sees its own earlier update (HOGWILD over drawn
 // targets; a Huffman path never repeats a node). ATOM (HOGWILD of SPEC-CBOW / SPEC-DOC2VEC): the row takes g * h by float32
-// atomic adds, so that lane groups which hold the same row at the same time lose none of their updates.
+// atomic adds, so that lane groups which hold the same row at the same time lose none of their updates. FROZEN
+// (SPEC-DOC2VEC-INFER): the table is read-only, the row takes nothing: no store and no atomic.
 static __device__ __forceinline__ void atomic_add4(float* p, const float4& v) {
     atomicAdd(p + 0, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
 }
-template <bool BATCH, bool DUP, bool ATOM = false, class IdFn, class LabelFn>
+template <bool BATCH, bool DUP, bool ATOM = false, bool FROZEN = false, class IdFn, class LabelFn>
 static __device__ __forceinline__ void sg_targets(float* tab, double* gtab, int d, int G, int gl, int n, float lr, const float4& h,
                                                   float4& grad, double& lsum, IdFn idf, LabelFn labf) {
     for (int m0 = 0; m0 < n; m0 += 4) {
@@ -264,7 +269,9 @@ static __device__ __forceinline__ void sg_targets(float* tab, double* gtab, int 
             const float g = lr * ((pos ? 1.0f : 0.0f) - sigmoidf_exact(x));
             if (gl == 0) lsum += (double)softplusf_exact(pos ? -x : x);
             grad.x += g * o.x; grad.y += g * o.y; grad.z += g * o.z; grad.w += g * o.w;
-            if (BATCH) {
+            if (FROZEN) {
+                // nothing is written
+            } else if (BATCH) {
                 double* go = gtab + (int64_t)id[q] * d + 4 * gl;
                 atomicAdd(go + 0, (double)(g * h.x)); atomicAdd(go + 1, (double)(g * h.y));
                 atomicAdd(go + 2, (double)(g * h.z)); atomicAdd(go + 3, (double)(g * h.w));
@@ -553,6 +560,147 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgns_dbow(SgCbowArgs a) {
         else st4(pdoc, h);
     }
     sg_loss_partial(lsum, s_red, a.partial);
+}
+
+// ---------------------------------------------------------------------------
+// SPEC-DOC2VEC-INFER
+// ---------------------------------------------------------------------------
+struct SgInferArgs {
+    const int32_t* tok_aid;
+    const int64_t* tok_off;
+    const uint64_t* sess_key;     // null: the row index
+    const int64_t* order;         // null: identity
+    int64_t T, S;
+    const float* In;
+    const float* Out;
+    const float* Syn1;
+    float* Doc;
+    double* loss;                 // [S, 2], nullable
+    int32_t* neg_out;             // [P, T, neg], nullable
+    uint8_t* radius_out;          // [P, T], nullable
+    int d, G, neg, ws, variant, passes;
+    SgTable tab;                  // tab.n = n_aids also when nothing is drawn
+    const int64_t* path_off;
+    const int32_t* path_node;
+    const uint64_t* code;
+    uint32_t n_inner;
+    float lr[OTTO_SGNS_MAX_INFER_PASSES];
+    uint64_t base[OTTO_SGNS_MAX_INFER_PASSES];     // sg_base(seed, p)
+};
+
+// component j of the initial row of the session whose pass-0 key is sb0: an odd multiple of 2^-24 * 2/d inside (-1/d, 1/d)
+static __device__ __forceinline__ float infer_init(uint64_t sb0, int j, float two_over_d) {
+    const uint32_t r = (uint32_t)(sg_key(sb0, 5, (uint64_t)j) >> 41);                   // 23 bits
+    return ((float)(2u * r + 1u) * 5.9604644775390625e-8f - 0.5f) * two_over_d;         // 2^-24; every step is exact
+}
+
+// The targets of token c (aid ca, in range, event key ev) against h on the frozen tables: cbow_targets without a write.
+template <bool HS, bool WIN>
+static __device__ __forceinline__ void infer_targets(const SgInferArgs& a, int G, int gl, int32_t* ids, int64_t slot, int32_t ca,
+                                                     uint64_t ev, float lr, const float4& h, float4& grad, double& lsum) {
+    const int nt = 1 + a.neg;
+    wave_lds_sync();
+    for (int m = gl; m < nt; m += G) ids[m] = m == 0 ? ca : cbow_negative(a.tab, ev, m - 1, ca);
+    wave_lds_sync();
+    if (WIN && a.neg_out)
+        for (int m = 1 + gl; m < nt; m += G) a.neg_out[slot * a.neg + (m - 1)] = ids[m];
+    // FROZEN never writes through these pointers
+    if (HS) {
+        const int64_t off = a.path_off[ca];
+        const int64_t len = a.path_off[ca + 1] - off;
+        const int L = off < 0 || len < 0 ? 0 : (int)(len > 64 ? 64 : len);
+        const uint64_t code = a.code[ca];
+        const int32_t* pn = a.path_node + off;
+        const uint32_t n_inner = a.n_inner;
+        sg_targets<false, false, false, true>(const_cast<float*>(a.Syn1), nullptr, a.d, G, gl, L, lr, h, grad, lsum,
+                                              [&](int m) { const uint32_t n = (uint32_t)pn[m]; return n < n_inner ? (int32_t)n : -1; },
+                                              [&](int m) { return ((code >> m) & 1ull) == 0; });
+    }
+    sg_targets<false, false, false, true>(const_cast<float*>(a.Out), nullptr, a.d, G, gl, nt, lr, h, grad, lsum,
+                                          [&](int m) { return ids[m]; }, [](int m) { return m == 0; });
+}
+
+// One lane group per session, taken through `order`, grid-stride. The doc row lives in registers from its keyed initial value
+// over all passes and tokens to the one store; the model tables are only read. DM: PV-DM, else PV-DBOW. WIN: the tests' window
+// (neg_out, radius_out) is compiled in; a call without either pointer runs the kernels without it.
+template <bool HS, bool DM, bool WIN>
+__global__ __launch_bounds__(SG_THREADS) void k_sgns_infer(SgInferArgs a) {
+    __shared__ int32_t s_ids[SG_MAX_GROUPS * SG_MAX_TARGETS];
+    const int G = a.G;
+    const int gl = threadIdx.x & (G - 1);
+    const int grp = threadIdx.x / G;
+    const int64_t gpb = blockDim.x / G;
+    int32_t* ids = s_ids + grp * SG_MAX_TARGETS;
+    const uint64_t n_aids = (uint64_t)a.tab.n;
+    const float two_over_d = 2.0f / (float)a.d;
+    const bool mean_h = a.variant != OTTO_SGNS_CBOW_SUM, mean_u = a.variant == OTTO_SGNS_CBOW_MEAN;
+    for (int64_t it = (int64_t)blockIdx.x * gpb + grp; it < a.S; it += (int64_t)gridDim.x * gpb) {
+        const int64_t s = a.order ? a.order[it] : it;
+        if (s < 0 || s >= a.S) continue;                              // not a permutation: the row is left alone
+        const int64_t lo64 = a.tok_off[s], hi64 = a.tok_off[s + 1];
+        const bool plan_ok = lo64 >= 0 && lo64 <= hi64 && hi64 <= a.T;      // always, for a plan of T tokens (T < 2^31)
+        const int lo = plan_ok ? (int)lo64 : 0, hi = plan_ok ? (int)hi64 : 0;
+        const uint64_t skey = a.sess_key ? a.sess_key[s] : (uint64_t)s;
+        const uint64_t sb0 = sg_ev(a.base[0], skey);
+        float4 hd = make_float4(infer_init(sb0, 4 * gl + 0, two_over_d), infer_init(sb0, 4 * gl + 1, two_over_d),
+                                infer_init(sb0, 4 * gl + 2, two_over_d), infer_init(sb0, 4 * gl + 3, two_over_d));
+        // one loop over (pass, token): the passes of a session run in order, each over its tokens in order
+        double l_first = 0.0, lsum = 0.0;
+        int p = 0;
+        int c = lo;
+        uint64_t sb = sb0;
+        float lr = a.lr[0];
+        while (c < hi) {
+            const int32_t ca = a.tok_aid[c];
+            if ((uint64_t)(uint32_t)ca < n_aids) {                    // the plan checked every aid
+                const uint64_t ev = sg_ev(sb, (uint64_t)(c - lo));
+                const int64_t slot = (int64_t)p * a.T + c;
+                float4 grad = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!DM) {
+                    infer_targets<HS, WIN>(a, G, gl, ids, slot, ca, ev, lr, hd, grad, lsum);
+                } else {
+                    const int r = 1 + (int)(((sg_key(ev, 2, 0) >> 32) * (uint64_t)a.ws) >> 32);
+                    if (WIN && a.radius_out && gl == 0) a.radius_out[slot] = (uint8_t)r;
+                    const int left = min(r, c - lo), np = left + min(r, hi - 1 - c);
+                    // context k is token cb + k + (k >= left): the centre itself is stepped over
+                    const int32_t* cb = a.tok_aid + (c - left);
+                    float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+                    for (int k0 = 0; k0 < np; k0 += 4) {
+                        float4 row[4];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const int k = k0 + q;
+                            row[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+                            if (k < np) {
+                                const uint32_t x = (uint32_t)cb[k + (k >= left)];
+                                if ((uint64_t)x < n_aids) row[q] = ld4(a.In + (int64_t)x * a.d + 4 * gl);
+                            }
+                        }
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            if (k0 + q < np) add4(h, row[q]);
+                    }
+                    add4(h, hd);
+                    const float fn = (float)(np + 1);
+                    if (mean_h) { h.x = h.x / fn; h.y = h.y / fn; h.z = h.z / fn; h.w = h.w / fn; }
+                    infer_targets<HS, WIN>(a, G, gl, ids, slot, ca, ev, lr, h, grad, lsum);
+                    if (mean_u) { grad.x = grad.x / fn; grad.y = grad.y / fn; grad.z = grad.z / fn; grad.w = grad.w / fn; }
+                }
+                add4(hd, grad);                                       // centre c + 1 sees the doc row that centre c left
+            }
+            if (++c == hi) {                                          // the pass ends
+                if (p == 0) l_first = lsum;
+                if (++p == a.passes) break;
+                c = lo;
+                sb = sg_ev(a.base[p], skey);
+                lr = a.lr[p];
+                lsum = 0.0;
+            }
+        }
+        const double l_last = lsum;                                   // the sum of the last pass (0 without tokens)
+        st4(a.Doc + s * a.d + 4 * gl, hd);
+        if (a.loss && gl == 0) { a.loss[2 * s] = l_first; a.loss[2 * s + 1] = l_last; }
+    }
 }
 
 __global__ __launch_bounds__(256) void k_sgns_loss_final(const double* partial, int n, double* out) {
@@ -911,6 +1059,73 @@ extern "C" int otto_sgns_cbow_step(const otto_sgns_cbow_job* job) {
         if (doc) k_sgns_apply<<<grid_for(j.S * (int64_t)d, 256), 256, 0, s>>>(j.d_Doc, j.d_gdoc, j.S * (int64_t)d);
     }
     k_sgns_loss_final<<<1, 256, 0, s>>>(a.partial, grid, j.d_loss_sum);
+    OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
+namespace otto {
+
+template <bool WIN>
+static void launch_infer(bool hs, bool dm, int grid, int threads, hipStream_t s, const SgInferArgs& a) {
+    if (dm) {
+        if (hs) k_sgns_infer<true, true, WIN><<<grid, threads, 0, s>>>(a);
+        else k_sgns_infer<false, true, WIN><<<grid, threads, 0, s>>>(a);
+    } else {
+        if (hs) k_sgns_infer<true, false, WIN><<<grid, threads, 0, s>>>(a);
+        else k_sgns_infer<false, false, WIN><<<grid, threads, 0, s>>>(a);
+    }
+}
+
+}  // namespace otto
+
+extern "C" int otto_sgns_infer(const otto_sgns_infer_job* job) {
+    OTTO_REQUIRE(job, "null job");
+    const otto_sgns_infer_job& j = *job;
+    const int arch = j.arch, d = j.d, neg = j.neg;
+    OTTO_REQUIRE(arch == OTTO_SGNS_ARCH_PVDM || arch == OTTO_SGNS_ARCH_DBOW, "arch %d: inference is PV-DM or PV-DBOW", arch);
+    const bool dm = arch == OTTO_SGNS_ARCH_PVDM;
+    OTTO_REQUIRE(j.variant == OTTO_SGNS_CBOW_SUM || j.variant == OTTO_SGNS_CBOW_MEAN || j.variant == OTTO_SGNS_CBOW_FASTTEXT,
+                 "unknown variant %d", j.variant);
+    OTTO_REQUIRE(d >= 4 && d <= OTTO_SGNS_MAX_DIM && d % 4 == 0 && ((d / 4) & (d / 4 - 1)) == 0,
+                 "d = %d: need a multiple of 4 in [4, %d] with d/4 a power of two", d, OTTO_SGNS_MAX_DIM);
+    OTTO_REQUIRE(neg >= 0 && neg <= OTTO_SGNS_MAX_NEG, "neg = %d outside [0, %d]", neg, OTTO_SGNS_MAX_NEG);
+    OTTO_REQUIRE(j.ws >= 1 && j.ws <= OTTO_SGNS_MAX_WS, "ws = %d outside [1, %d]", j.ws, OTTO_SGNS_MAX_WS);
+    OTTO_REQUIRE(j.passes >= 1 && j.passes <= OTTO_SGNS_MAX_INFER_PASSES, "passes = %d outside [1, %d]", j.passes,
+                 OTTO_SGNS_MAX_INFER_PASSES);
+    OTTO_REQUIRE(j.n_aids >= 1 && j.n_aids < (1ll << 31), "n_aids = %lld outside [1, 2^31)", (long long)j.n_aids);
+    OTTO_REQUIRE(j.T >= 0 && j.T < (1ll << 31) && j.S >= 0 && j.S < (1ll << 31) && (j.T == 0 || j.S >= 1),
+                 "S = %lld sessions for %lld tokens", (long long)j.S, (long long)j.T);
+    OTTO_REQUIRE(j.d_tok_off && j.d_Out && j.d_Doc && (j.T == 0 || j.d_tok_aid), "null argument");
+    OTTO_REQUIRE(!dm || j.d_In, "PV-DM needs In");
+    const bool hs = j.d_path_off || j.d_path_node || j.d_code;
+    if (hs) {
+        OTTO_REQUIRE(j.d_path_off && j.d_path_node && j.d_code && j.d_Syn1, "null hierarchical-softmax table");
+        OTTO_REQUIRE(j.n_inner >= 1 && j.n_inner < (1ll << 31), "n_inner = %lld outside [1, 2^31)", (long long)j.n_inner);
+    }
+    OTTO_REQUIRE(neg > 0 || hs, "neg = 0 without hierarchical-softmax tables leaves nothing to infer against");
+    SgInferArgs a;
+    memset(&a, 0, sizeof a);
+    if (neg > 0) {
+        OTTO_REQUIRE(j.table.total > 0, "negative table: total weight is 0, nothing can be drawn");
+        OTTO_TRY(table_from(&j.table, &a.tab));
+        OTTO_REQUIRE(j.table.n_aids == j.n_aids && j.n_aids >= 2, "negative sampling needs at least 2 aids and a table over n_aids");
+    }
+    a.tab.n = j.n_aids;
+    if (j.S == 0) return 0;
+    a.tok_aid = j.d_tok_aid; a.tok_off = j.d_tok_off; a.sess_key = j.d_sess_key; a.order = j.d_order; a.T = j.T; a.S = j.S;
+    a.In = j.d_In; a.Out = j.d_Out; a.Syn1 = j.d_Syn1; a.Doc = j.d_Doc; a.loss = j.d_loss;
+    a.neg_out = neg > 0 ? j.d_neg_out : nullptr; a.radius_out = dm ? j.d_radius_out : nullptr;
+    a.d = d; a.G = d / 4; a.neg = neg; a.ws = j.ws; a.variant = j.variant; a.passes = j.passes;
+    if (hs) { a.path_off = j.d_path_off; a.path_node = j.d_path_node; a.code = j.d_code; a.n_inner = (uint32_t)j.n_inner; }
+    for (int p = 0; p < j.passes; ++p) {
+        a.lr[p] = j.lr[p];
+        a.base[p] = sg_base(j.seed, (uint64_t)p);
+    }
+    hipStream_t s = (hipStream_t)j.stream;
+    const int threads = a.G >= 4 ? SG_THREADS : 64 * a.G;
+    const int grid = grid_for(j.S, threads / a.G);
+    if (a.neg_out || a.radius_out) launch_infer<true>(hs, dm, grid, threads, s, a);
+    else launch_infer<false>(hs, dm, grid, threads, s, a);
     OTTO_HIP(hipGetLastError());
     return 0;
 }

@@ -13,6 +13,10 @@ engine takes them as ``hs=`` and trains a third table ``Syn1``.
 CBOW (fastText ``model: cbow``, gensim ``sg: 0``) and Doc2Vec (PV-DM, PV-DBOW; SPEC-CBOW and SPEC-DOC2VEC) run on the same
 plan, sampler and tables through :meth:`SkipGramEngine.step_cbow`, :func:`train_cbow` and :func:`train_doc2vec`; the two
 Doc2Vec archs train ``Doc``, one row per session.
+
+A session that took no part in training gets its vector from :func:`infer_doc2vec` (SPEC-DOC2VEC-INFER, gensim's
+``infer_vector``): one launch over all passes against a frozen :class:`Doc2VecModel`, which :func:`train_doc2vec` returns
+with ``return_model=True`` and :func:`doc2vec_model` builds from arrays.
 """
 import ctypes as C
 
@@ -24,6 +28,7 @@ HOGWILD, BATCH = 0, 1               # OTTO_SGNS_HOGWILD, OTTO_SGNS_BATCH
 ARCH_CBOW, ARCH_PVDM, ARCH_DBOW = 0, 1, 2               # OTTO_SGNS_ARCH_*
 CBOW_SUM, CBOW_MEAN, CBOW_FASTTEXT = 0, 1, 2            # OTTO_SGNS_CBOW_*
 MAX_DIM, MAX_NEG, MAX_WS = 128, 64, 32
+MAX_INFER_PASSES = 64               # OTTO_SGNS_MAX_INFER_PASSES
 NS_EXPONENTS = (0.0, 0.5, 0.75, 1.0)
 _U32_MAX = (1 << 32) - 1
 _MAX_BUCKETS = 1 << 21
@@ -53,7 +58,12 @@ def vocab_tables(aid, n_aids, min_count=1, t=1e-4, ns_exponent=0.5):
         raise ValueError('t must be >= 0')
     if e not in NS_EXPONENTS:
         raise ValueError(f'ns_exponent must be one of {NS_EXPONENTS} (got {ns_exponent})')
-    count = _host_counts(aid, n_aids)
+    return _tables_of_counts(_host_counts(aid, n_aids), min_count, t, e)
+
+
+def _tables_of_counts(count, min_count, t, e):
+    """:func:`vocab_tables` from the counts on: what training and inference both derive from ``count``."""
+    n_aids = len(count)
     E = int(count.sum())
     in_vocab = count >= max(min_count, 1)
     c = count.astype(np.float64)
@@ -456,16 +466,190 @@ def train_cbow(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, 
 
 
 def train_doc2vec(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, t=1e-4, min_count=1, ns_exponent=0.5, seed=0,
-                  mode=HOGWILD, tokens_per_launch=1 << 24, device=None, hs=False, dm=1, dm_mean=1):
+                  mode=HOGWILD, tokens_per_launch=1 << 24, device=None, hs=False, dm=1, dm_mean=1, return_model=False):
     """Train session vectors (SPEC-DOC2VEC): ``dm=1`` is PV-DM (the mean of the context rows and the session's row with
     ``dm_mean=1``, their sum with ``dm_mean=0``), ``dm=0`` is PV-DBOW (``In`` is returned as initialised). ``Doc`` float32
     [S, dim] starts uniform(-1/dim, 1/dim) from ``default_rng([seed, 1])``. Returns ``(Doc, In, Out, losses)``, or
-    ``(Doc, In, Out, losses, Syn1)`` with ``hs=True``."""
+    ``(Doc, In, Out, losses, Syn1)`` with ``hs=True``. ``return_model=True`` appends the :class:`Doc2VecModel` of the run
+    (the trained tables as they are on the device, the counts and the hyper-parameters): what :func:`infer_doc2vec`
+    needs to embed a session that was not trained on."""
     arch = ARCH_PVDM if int(dm) else ARCH_DBOW
     variant = CBOW_MEAN if int(dm_mean) else CBOW_SUM
     Doc, In, Out, losses, Syn1 = _train_arch(arch, variant, aid, sess_off, n_aids, dim, ws, neg, epochs, lr, t, min_count,
                                              ns_exponent, seed, mode, tokens_per_launch, device, hs)
-    return (Doc, In, Out, losses, Syn1) if hs else (Doc, In, Out, losses)
+    out = (Doc, In, Out, losses, Syn1) if hs else (Doc, In, Out, losses)
+    if return_model:
+        out += (Doc2VecModel(In if int(dm) else None, Out, Syn1, _host_counts(aid, int(n_aids)), dim=dim, ws=ws, neg=neg, t=t,
+                             min_count=min_count, ns_exponent=ns_exponent, seed=seed, dm=dm, dm_mean=dm_mean, hs=hs, lr=lr,
+                             epochs=epochs),)
+    return out
+
+
+# ---- SPEC-DOC2VEC-INFER
+class Doc2VecModel:
+    """What training knew, frozen: ``In`` (PV-DM; None for PV-DBOW), ``Out`` float32 [n_aids, dim], ``Syn1`` float32
+    [n_inner, dim] (with ``hs``, else None), ``count`` int64 [n_aids] of the training corpus, and the hyper-parameters
+    ``dim, ws, neg, t, min_count, ns_exponent, seed, dm, dm_mean, hs, lr, epochs``. The tables are NumPy arrays or tensors on
+    any device. ``ValueError`` for shapes and values no training run could have produced; nothing here touches a device."""
+    HYPER = ('dim', 'ws', 'neg', 't', 'min_count', 'ns_exponent', 'seed', 'dm', 'dm_mean', 'hs', 'lr', 'epochs')
+
+    def __init__(self, In, Out, Syn1, count, dim, ws, neg, t, min_count, ns_exponent, seed, dm, dm_mean, hs, lr, epochs):
+        self.dim, self.ws, self.neg, self.min_count, self.seed = int(dim), int(ws), int(neg), int(min_count), int(seed)
+        self.t, self.ns_exponent, self.lr, self.epochs = float(t), float(ns_exponent), float(lr), int(epochs)
+        self.dm, self.dm_mean, self.hs = int(bool(int(dm))), int(bool(int(dm_mean))), bool(hs)
+        if self.dim % 4 or not 4 <= self.dim <= MAX_DIM or (self.dim // 4) & (self.dim // 4 - 1):
+            raise ValueError(f'dim must be a multiple of 4 in [4, {MAX_DIM}] with dim/4 a power of two (got {dim})')
+        if not 0 <= self.neg <= MAX_NEG:
+            raise ValueError(f'neg must be in [0, {MAX_NEG}] (got {neg})')
+        if self.neg == 0 and not self.hs:
+            raise ValueError('neg = 0 without hierarchical softmax leaves nothing to infer against')
+        if not 1 <= self.ws <= MAX_WS:
+            raise ValueError(f'ws must be in [1, {MAX_WS}] (got {ws})')
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError('seed: expected a uint64')
+        if self.t < 0 or self.ns_exponent not in NS_EXPONENTS:
+            raise ValueError(f't must be >= 0 and ns_exponent one of {NS_EXPONENTS}')
+        self.count = np.ascontiguousarray(np.asarray(count, dtype=np.int64))
+        if self.count.ndim != 1 or self.count.size < 1 or (self.count < 0).any():
+            raise ValueError('count: expected non-negative int64 [n_aids], n_aids >= 1')
+        self.n_aids = int(self.count.size)
+        self.huffman = None                  # the HuffmanTables, built at the first inference
+        for name, M, wanted in (('Out', Out, True), ('In', In, bool(self.dm)), ('Syn1', Syn1, self.hs)):
+            if M is None:
+                if wanted:
+                    raise ValueError(f'{name}: this model (dm = {self.dm}, hs = {self.hs}) needs it')
+                continue
+            rows = None if name == 'Syn1' else self.n_aids
+            if len(M.shape) != 2 or M.shape[1] != self.dim or (rows is not None and M.shape[0] != rows) or 'float32' not in str(M.dtype):
+                raise ValueError(f'{name}: expected float32 [{"n_inner" if rows is None else rows}, {self.dim}]')
+        self.In, self.Out, self.Syn1 = (In if self.dm else None), Out, (Syn1 if self.hs else None)
+        self._engines = {}                   # device -> (engine, device tables)
+
+    @property
+    def variant(self):
+        return CBOW_MEAN if self.dm_mean else CBOW_SUM
+
+    def hyper(self):
+        """the hyper-parameters as a plain dict (what ``model.json`` holds)"""
+        return {k: getattr(self, k) for k in self.HYPER}
+
+    def host(self, name):
+        """table ``name`` as a NumPy array (None when the model has none)"""
+        M = getattr(self, name)
+        return None if M is None else (M.detach().cpu().numpy() if hasattr(M, 'detach') else np.asarray(M))
+
+    def engine(self, dev):
+        """``(SkipGramEngine, {name: device tensor})`` of this model on ``dev``, built once per device: the 0 / 2^32 - 1 keep
+        table, the training corpus's negative table and Huffman tables, and the model tables as contiguous device tensors."""
+        import torch
+        if dev not in self._engines:
+            _, keep_q, weight = _tables_of_counts(self.count, self.min_count, self.t, self.ns_exponent)
+            keep = np.where(keep_q != 0, _U32_MAX, 0).astype(np.uint32)
+            if self.hs and self.huffman is None:
+                self.huffman = huffman_tables(self.count, self.min_count)
+            if self.hs and tuple(self.Syn1.shape) != (self.huffman.n_inner, self.dim):
+                raise ValueError(f'Syn1: expected float32 [{self.huffman.n_inner}, {self.dim}] for these counts')
+            eng = SkipGramEngine(self.n_aids, self.dim, self.ws, self.neg, keep, weight, seed=self.seed, device=dev,
+                                 hs=self.huffman if self.hs else None)
+            tabs = {}
+            for name in ('In', 'Out', 'Syn1'):
+                M = getattr(self, name)
+                if M is not None:
+                    M = M if hasattr(M, 'detach') else torch.from_numpy(np.ascontiguousarray(M))
+                    tabs[name] = M.detach().to(eng.dev).contiguous()
+            self._engines[dev] = (eng, tabs)
+        return self._engines[dev]
+
+
+def doc2vec_model(In, Out, Syn1, count, **hyper):
+    """The :class:`Doc2VecModel` of arrays saved earlier: ``hyper`` holds every name of ``Doc2VecModel.HYPER``."""
+    missing = [k for k in Doc2VecModel.HYPER if k not in hyper]
+    if missing or len(hyper) != len(Doc2VecModel.HYPER):
+        raise ValueError(f'hyper-parameters: expected exactly {Doc2VecModel.HYPER}, missing {missing}')
+    return Doc2VecModel(In, Out, Syn1, count, **hyper)
+
+
+def infer_rates(alpha, min_alpha, passes):
+    """float32 [passes]: ``alpha - (alpha - min_alpha) * p / max(passes - 1, 1)`` in float64, then rounded: the linear decay
+    of gensim's ``infer_vector`` from ``alpha`` in pass 0 to ``min_alpha`` in the last pass (one pass runs at ``alpha``)."""
+    passes, alpha, min_alpha = int(passes), float(alpha), float(min_alpha)
+    if not 1 <= passes <= MAX_INFER_PASSES:
+        raise ValueError(f'passes must be in [1, {MAX_INFER_PASSES}] (got {passes})')
+    if not (np.isfinite(alpha) and np.isfinite(min_alpha)) or alpha <= 0 or min_alpha < 0 or min_alpha > alpha:
+        raise ValueError(f'expected 0 <= min_alpha <= alpha, alpha > 0 (got alpha {alpha}, min_alpha {min_alpha})')
+    return np.array([alpha - (alpha - min_alpha) * p / max(passes - 1, 1) for p in range(passes)], dtype=np.float64).astype(np.float32)
+
+
+def infer_job(model, dev, tok_aid, tok_off, rates, Doc, loss=None, sess_key=None, order=None, neg_out=None, radius_out=None,
+              variant=None):
+    """The ``otto_sgns_infer_job`` of one launch on ``dev``'s current stream: ``tok_aid`` int32 [T] / ``tok_off`` int64 [S+1] as
+    the plan left them, ``rates`` float32 [passes], ``Doc`` float32 [S, dim] out; every tensor contiguous on ``dev``."""
+    eng, tabs = model.engine(dev)
+    p = lambda t, what: _lib.ptr(t, dev, what)
+    hs = eng.hs is not None
+    return _lib.SgnsInferJob(
+        p(tok_aid, 'tok_aid'), p(tok_off, 'tok_off'), int(tok_aid.numel()), int(tok_off.numel()) - 1, p(sess_key, 'sess_key'),
+        p(order, 'order'), p(tabs.get('In'), 'In'), p(tabs['Out'], 'Out'), p(tabs.get('Syn1'), 'Syn1'), model.n_aids,
+        eng.n_inner if hs else 0, model.dim, model.neg, model.ws, ARCH_PVDM if model.dm else ARCH_DBOW,
+        model.variant if variant is None else int(variant), len(rates), (C.c_float * MAX_INFER_PASSES)(*[float(r) for r in rates]),
+        model.seed, eng.table, p(eng._path_off, 'path_off') if hs else None, p(eng._path_node, 'path_node') if hs else None,
+        p(eng._code, 'code') if hs else None, p(Doc, 'Doc'), p(loss, 'loss'), p(neg_out, 'neg_out'), p(radius_out, 'radius_out'),
+        _lib.stream(dev))
+
+
+def infer_doc2vec(aid, sess_off, model, passes=None, alpha=None, min_alpha=1e-4, sess_key=None, length_order=True, neg_out=None,
+                  radius_out=None, variant=None):
+    """Session vectors for sessions the model was not trained on (SPEC-DOC2VEC-INFER): ``aid`` int32 [E] sorted by
+    (session, ts) and ``sess_off`` int64 [S+1], device tensors as :func:`train_doc2vec` takes them; ``model`` a
+    :class:`Doc2VecModel`, which stays as it is. ``passes`` defaults to the model's ``epochs``, ``alpha`` to its ``lr``;
+    the rates are :func:`infer_rates`. ``sess_key``: int64 / uint64 [S], the session ids that key the initial row and every
+    draw (default: the row index); with it a session's vector is the same bytes in whatever batch it arrives. Events whose
+    aid the model does not know are dropped; nothing is sub-sampled. Returns ``(Doc', loss)``: float32 [S, dim] and
+    float64 [S, 2] (the session's loss sum in the first and in the last pass) on the device; the call does not synchronise.
+
+    ``length_order``: sessions are handed to the lane groups longest first (sorted on the device); the result does not
+    depend on it. ``variant``: ``CBOW_SUM`` / ``CBOW_MEAN`` / ``CBOW_FASTTEXT`` for PV-DM in place of the model's ``dm_mean``.
+    ``neg_out`` int32 [passes, T, neg] / ``radius_out`` uint8 [passes, T]: the sampler's choices (tests).
+    ``ValueError`` for bad arguments, raised before the device is touched."""
+    import torch
+    if not isinstance(model, Doc2VecModel):
+        raise ValueError('model: expected a Doc2VecModel (train_doc2vec(..., return_model=True) or doc2vec_model(...))')
+    rates = infer_rates(model.lr if alpha is None else alpha, min_alpha, model.epochs if passes is None else passes)
+    P = len(rates)
+    if variant is not None and variant not in (CBOW_SUM, CBOW_MEAN, CBOW_FASTTEXT):
+        raise ValueError(f'unknown variant {variant}')
+    for name, t in (('aid', aid), ('sess_off', sess_off)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError(f'{name}: expected a 1-d tensor')
+    S = int(sess_off.numel()) - 1
+    if S < 0:
+        raise ValueError('sess_off: expected int64 [S+1]')
+    if sess_key is not None:
+        if not isinstance(sess_key, torch.Tensor):
+            k = np.asarray(sess_key)
+            if k.dtype.kind not in 'iu':
+                raise ValueError('sess_key: expected integers')
+            sess_key = torch.from_numpy(np.ascontiguousarray(k.astype(np.uint64)).view(np.int64))
+        if sess_key.dtype != torch.int64 or tuple(sess_key.shape) != (S,):
+            raise ValueError(f'sess_key: expected int64 (or uint64 viewed as int64) [{S}]')
+    dev = _lib.rocm_device(aid.device, 'infer_doc2vec')
+    eng, tabs = model.engine(dev)
+    plan = eng.plan(aid, sess_off, 0)                      # the keep table holds 0 and 2^32 - 1: in-vocabulary events, in order
+    T = plan.T
+    for name, w, n in (('neg_out', neg_out, P * T * model.neg), ('radius_out', radius_out, P * T)):
+        if w is not None and (w.dtype != (torch.int32 if name == 'neg_out' else torch.uint8) or w.numel() < n):
+            raise ValueError(f'{name}: room for {n} entries of its type needed')
+    with torch.cuda.device(dev):
+        Doc = torch.empty(S, model.dim, dtype=torch.float32, device=dev)
+        loss = torch.empty(S, 2, dtype=torch.float64, device=dev)
+        order = None
+        if length_order and S > 1:
+            order = torch.argsort(plan.tok_off[1:] - plan.tok_off[:-1], descending=True, stable=True)
+        if sess_key is not None:
+            sess_key = sess_key.to(dev).contiguous()
+        job = infer_job(model, dev, plan.tok_aid, plan.tok_off, rates, Doc, loss, sess_key, order, neg_out, radius_out, variant)
+        _lib.call('otto_sgns_infer', dev, C.byref(job), stream=False)
+    return Doc, loss
 
 
 def train(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, t=1e-4, min_count=1, ns_exponent=0.5, seed=0,

@@ -19,8 +19,14 @@ heap; that departure is logged once.
 ``dm: 1`` PV-DM, ``dm: 0`` PV-DBOW), where ``hs: 1`` may also stand alone (``negative: 0``). Doc2Vec is the one model that
 yields a session vector: ``doc_embeddings.npy`` (float32 [S, dim]) and ``doc_sessions.npy`` (the session id of each row).
 Still refused: ``dm_concat``, ``dbow_words``, ``dm_tag_count`` other than 1, sub-words, ``loss`` other than ``ns``.
+
+``--save-model`` (``run(save_model=True)``) makes a Doc2Vec run also write what inference needs: ``out_embeddings.npy``,
+``syn1.npy`` (with ``hs: 1``), ``aid_counts.npy`` and ``model.json`` (the hyper-parameters). ``--infer <frame.pkl|.parquet>``
+(:func:`infer`) reads those files and embeds the frame's sessions, none of which the model has to have seen
+(SPEC-DOC2VEC-INFER), into ``doc_embeddings_inferred.npy`` and ``doc_sessions_inferred.npy``.
 """
 import argparse
+import json
 import logging
 import pathlib
 
@@ -127,13 +133,72 @@ def resolve(config):
     return 'skipgram', dict(train_args(config), hs=hs_requested(config))
 
 
-def run(config, df=None, device='cuda:0', n_aids=None, tokens_per_launch=1 << 24):
+MODEL_FILES = dict(In='aid_embeddings.npy', Out='out_embeddings.npy', Syn1='syn1.npy', count='aid_counts.npy', hyper='model.json')
+
+
+def write_model(model, directory):
+    """Write the files of ``--save-model`` (``aid_embeddings.npy`` is the run's own file and is not written again)."""
+    directory = pathlib.Path(directory)
+    np.save(directory / MODEL_FILES['Out'], model.host('Out'))
+    if model.hs:
+        np.save(directory / MODEL_FILES['Syn1'], model.host('Syn1'))
+    np.save(directory / MODEL_FILES['count'], model.count)
+    with open(directory / MODEL_FILES['hyper'], 'w') as fh:
+        json.dump(model.hyper(), fh, indent=1, sort_keys=True)
+
+
+def read_model(directory):
+    """The :class:`skipgram.Doc2VecModel` of a directory that a ``--save-model`` run wrote."""
+    directory = pathlib.Path(directory)
+    with open(directory / MODEL_FILES['hyper']) as fh:
+        hyper = json.load(fh)
+    In = np.load(directory / MODEL_FILES['In']) if int(hyper['dm']) else None
+    Syn1 = np.load(directory / MODEL_FILES['Syn1']) if hyper['hs'] else None
+    return skipgram.doc2vec_model(In, np.load(directory / MODEL_FILES['Out']), Syn1, np.load(directory / MODEL_FILES['count']), **hyper)
+
+
+def infer(config, df, device='cuda:0', passes=None, alpha=None, min_alpha=1e-4):
+    """Embed the sessions of ``df`` (a frame, a list of frames, or the path of a ``.pkl`` / ``.parquet`` frame) with the
+    Doc2Vec model that ``run(config, save_model=True)`` saved; returns ``(Doc', session ids, model_root_directory)`` and
+    writes ``doc_embeddings_inferred.npy`` (float32 [S, dim]) and ``doc_sessions_inferred.npy``. The session id keys every
+    draw, so a session's row does not depend on the frame it arrives in. Events whose aid the model does not know (never
+    seen in training, below ``min_count``, or past its id space) are dropped."""
+    if resolve(config)[0] != 'doc2vec':
+        raise ValueError('infer needs a Doc2Vec config: no other model yields a session vector')
+    from ..events import frame_to_events_device
+    model_root_directory = pathlib.Path(settings.MODELS / config['persistence']['model_directory'])
+    model = read_model(model_root_directory)
+    if isinstance(df, (str, pathlib.Path)):
+        import pandas as pd
+        df = pd.read_parquet(df) if str(df).endswith('.parquet') else pd.read_pickle(df)
+    ev = frame_to_events_device(df, device=device)
+    aid = ev.aid
+    if ev.n_aids > model.n_aids:                          # an aid past the model's id space is out of its vocabulary
+        import torch
+        known = aid < model.n_aids
+        pos = torch.zeros(aid.numel() + 1, dtype=torch.int64, device=aid.device)
+        pos[1:] = torch.cumsum(known, 0)
+        aid, sess_off = aid[known].contiguous(), pos[ev.sess_off]
+    else:
+        sess_off = ev.sess_off
+    ids = ev.session_ids
+    Doc, _ = skipgram.infer_doc2vec(aid, sess_off, model, passes=passes, alpha=alpha, min_alpha=min_alpha, sess_key=ids)
+    Doc, ids = Doc.cpu().numpy(), (ids.cpu().numpy() if hasattr(ids, 'cpu') else np.asarray(ids))
+    np.save(model_root_directory / 'doc_embeddings_inferred.npy', Doc)
+    np.save(model_root_directory / 'doc_sessions_inferred.npy', ids)
+    logging.info(f'{len(ids)} session vectors inferred and saved to {model_root_directory}')
+    return Doc, ids, model_root_directory
+
+
+def run(config, df=None, device='cuda:0', n_aids=None, tokens_per_launch=1 << 24, save_model=False):
     """Train and write the files; returns ``(In, losses, model_root_directory)``. ``df``: a frame or a list of frames
     with ``session``, ``aid``, ``ts``, ``type`` (default: ``train.pkl`` + ``test.pkl`` under ``settings.DATA``).
     Doc2Vec also writes ``doc_embeddings.npy`` (float32 [S, dim]) and ``doc_sessions.npy`` (the session id of each row);
     the first entry of the result is then that session table, and PV-DBOW, which trains no aid vectors, writes no aid
-    files."""
+    files. ``save_model=True`` (Doc2Vec alone; ``ValueError`` otherwise) also writes the files :func:`infer` reads."""
     arch, kw = resolve(config)                            # refusals come before any file or device is touched
+    if save_model and arch != 'doc2vec':
+        raise ValueError('save_model: only a Doc2Vec model is saved for inference')
     from ..events import frame_to_events_device
     model_root_directory = pathlib.Path(settings.MODELS / config['persistence']['model_directory'])
     model_root_directory.mkdir(parents=True, exist_ok=True)
@@ -142,9 +207,11 @@ def run(config, df=None, device='cuda:0', n_aids=None, tokens_per_launch=1 << 24
         df = [pd.read_pickle(settings.DATA / 'train.pkl'), pd.read_pickle(settings.DATA / 'test.pkl')]
     ev = frame_to_events_device(df, device=device, n_aids=n_aids)
     logging.info(f'Sentences Dataset - sentences: {ev.n_sessions} - tokens: {ev.n_events}')
-    Doc = None
+    Doc = model = None
     if arch == 'doc2vec':
-        Doc, In, _, losses = skipgram.train_doc2vec(ev.aid, ev.sess_off, ev.n_aids, tokens_per_launch=tokens_per_launch, **kw)[:4]
+        out = skipgram.train_doc2vec(ev.aid, ev.sess_off, ev.n_aids, tokens_per_launch=tokens_per_launch, return_model=save_model, **kw)
+        Doc, In, _, losses = out[:4]
+        model = out[-1] if save_model else None
     else:
         fn = skipgram.train_cbow if arch == 'cbow' else skipgram.train
         In, _, losses = fn(ev.aid, ev.sess_off, ev.n_aids, tokens_per_launch=tokens_per_launch, **kw)[:3]
@@ -161,6 +228,8 @@ def run(config, df=None, device='cuda:0', n_aids=None, tokens_per_launch=1 << 24
         count[count < max(kw['min_count'], 1)] = 0
         np.save(model_root_directory / 'aid_embeddings.npy', In)
         skipgram.save_vec(model_root_directory / 'aid_embeddings.vec', In, count)
+    if model is not None:
+        write_model(model, model_root_directory)
     logging.info(f"{config['model']['model_name']} embeddings finished training and saved to {model_root_directory}")
     return (In if Doc is None else Doc), losses, model_root_directory
 
@@ -168,6 +237,12 @@ def run(config, df=None, device='cuda:0', n_aids=None, tokens_per_launch=1 << 24
 if __name__ == '__main__':
     parser = argparse.ArgumentParser()
     parser.add_argument('config_path', type=str)
+    parser.add_argument('--save-model', action='store_true', help='Doc2Vec: also write the files --infer reads')
+    parser.add_argument('--infer', type=str, default=None, metavar='FRAME', help='a .pkl or .parquet frame of sessions to embed '
+                        'with the saved Doc2Vec model, instead of training')
     args = parser.parse_args()
     config = yaml.load(open(settings.MODELS / args.config_path, 'r'), Loader=yaml.FullLoader)
-    run(config)
+    if args.infer is not None:
+        infer(config, args.infer)
+    else:
+        run(config, save_model=args.save_model)
