@@ -28,6 +28,12 @@
 //                   no scratch: the loss is per session.
 //   k_sgns_apply         BATCH: table += workspace, workspace = 0 (dense sweep).
 //   k_sgns_loss_final    sums the per-workgroup loss partials in a fixed order.
+// Device helpers the step kernels share, each defined once above k_sgns_step: sg_targets (four rows at a time against h),
+//   sg_path_targets (the Huffman path of an aid through sg_targets), sg_draw_ids (1 + neg ids into LDS between two syncs),
+//   sg_gather (the summed context rows), sg_loss_partial, sg_session_of (session of an event or a token), add4 / atomic_add4.
+// Host helpers the entry points over those kernels share: check_shape (d, neg), check_n_aids, check_range, check_sessions,
+//   check_paths (the Huffman tables), table_or_size (a job's negative table, or only n_aids), launch_dims,
+//   apply_and_sum (BATCH apply, then k_sgns_loss_final). otto_sgns_step and otto_sgns_step_hs fill one SgStepCall.
 // Host: otto_sgns_hs_tree_sizes / otto_sgns_hs_tree build the Huffman tree and the path tables of SPEC-SGNS-HS (no HIP call).
 #include "common.h"
 #include "wave.h"
@@ -76,6 +82,17 @@ static __device__ __forceinline__ int32_t sgns_draw(const SgTable& t, uint64_t k
     const uint64_t u = __umul64hi(key, t.total);          // < total
     const uint64_t b = u >> t.shift;
     return (int32_t)sg_upper(t.cum, t.bucket[b], t.bucket[b + 1], u);
+}
+
+// the last s in [0, S) with off[s] <= i: the session of event (sess_off) or token (tok_off) i. Empty sessions share an
+// offset; the last one holds i.
+static __device__ __forceinline__ int64_t sg_session_of(const int64_t* off, int64_t S, int64_t i) {
+    int64_t lo = 0, hi = S - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
 }
 
 __global__ __launch_bounds__(256) void k_sgns_bucket(const uint64_t* cum, int64_t n, uint64_t total, int shift, int64_t n_buckets,
@@ -160,12 +177,7 @@ __global__ __launch_bounds__(256) void k_sgns_plan_tokens(SgPlanArgs a) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < a.E; e += (int64_t)gridDim.x * 256) {
         const int64_t t = (int64_t)a.pos[e];
         if ((int64_t)a.pos[e + 1] == t) continue;          // not kept
-        // session of e: the last s with sess_off[s] <= e (empty sessions share an offset; the last one holds e)
-        int64_t lo = 0, hi = a.S - 1;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi + 1) >> 1;
-            if (a.sess_off[mid] <= e) lo = mid; else hi = mid - 1;
-        }
+        const int64_t lo = sg_session_of(a.sess_off, a.S, e);
         const int64_t tlo = (int64_t)a.pos[a.sess_off[lo]], thi = (int64_t)a.pos[a.sess_off[lo + 1]];
         const uint64_t ev = sg_ev(a.base, (uint64_t)(a.event0 + e));
         const int64_t r = 1 + (int64_t)(((sg_key(ev, 2, 0) >> 32) * (uint64_t)a.ws) >> 32);
@@ -224,6 +236,13 @@ static __device__ __forceinline__ float sigmoidf_exact(float x) {
 static __device__ __forceinline__ float softplusf_exact(float z) {    // log(1 + exp(z))
     return fmaxf(z, 0.0f) + log1pf(expf(-fabsf(z)));
 }
+static __device__ __forceinline__ void add4(float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+static __device__ __forceinline__ void atomic_add4(float* p, const float4& v) {
+    atomicAdd(p + 0, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
+}
+static __device__ __forceinline__ void atomic_add4(double* p, const float4& v) {
+    atomicAdd(p + 0, (double)v.x); atomicAdd(p + 1, (double)v.y); atomicAdd(p + 2, (double)v.z); atomicAdd(p + 3, (double)v.w);
+}
 
 // negative j of pair k of the centre whose event key is ev: redrawn while equal to the context aid
 static __device__ __forceinline__ int32_t sgns_negative(const SgTable& t, uint64_t ev, int k, int j, int32_t ctx) {
@@ -239,9 +258,6 @@ static __device__ __forceinline__ int32_t sgns_negative(const SgTable& t, uint64
 // targets; a Huffman path never repeats a node). ATOM (HOGWILD of SPEC-CBOW / SPEC-DOC2VEC): the row takes g * h by float32
 // atomic adds, so that lane groups which hold the same row at the same time lose none of their updates. FROZEN
 // (SPEC-DOC2VEC-INFER): the table is read-only, the row takes nothing: no store and no atomic.
-static __device__ __forceinline__ void atomic_add4(float* p, const float4& v) {
-    atomicAdd(p + 0, v.x); atomicAdd(p + 1, v.y); atomicAdd(p + 2, v.z); atomicAdd(p + 3, v.w);
-}
 template <bool BATCH, bool DUP, bool ATOM = false, bool FROZEN = false, class IdFn, class LabelFn>
 static __device__ __forceinline__ void sg_targets(float* tab, double* gtab, int d, int G, int gl, int n, float lr, const float4& h,
                                                   float4& grad, double& lsum, IdFn idf, LabelFn labf) {
@@ -272,15 +288,74 @@ static __device__ __forceinline__ void sg_targets(float* tab, double* gtab, int 
             if (FROZEN) {
                 // nothing is written
             } else if (BATCH) {
-                double* go = gtab + (int64_t)id[q] * d + 4 * gl;
-                atomicAdd(go + 0, (double)(g * h.x)); atomicAdd(go + 1, (double)(g * h.y));
-                atomicAdd(go + 2, (double)(g * h.z)); atomicAdd(go + 3, (double)(g * h.w));
+                atomic_add4(gtab + (int64_t)id[q] * d + 4 * gl, make_float4(g * h.x, g * h.y, g * h.z, g * h.w));
             } else if (ATOM) {
                 atomic_add4(po_, make_float4(g * h.x, g * h.y, g * h.z, g * h.w));
             } else {
                 st4(po_, make_float4(o.x + g * h.x, o.y + g * h.y, o.z + g * h.z, o.w + g * h.w));
             }
         }
+    }
+}
+
+// The Syn1 rows on the Huffman path of `aid` from the root, through sg_targets: label 1 - bit; a row outside [0, n_inner) is
+// skipped, never touched. The ids are read from the table (the same address in every lane of the group). a: the kernel's
+// argument record, for path_off, path_node, code, n_inner and d.
+template <bool BATCH, bool ATOM, bool FROZEN, class Args>
+static __device__ __forceinline__ void sg_path_targets(const Args& a, float* Syn1, double* gsyn1, int32_t aid, int G, int gl,
+                                                       float lr, const float4& h, float4& grad, double& lsum) {
+    const int64_t off = a.path_off[aid];
+    const int64_t len = a.path_off[aid + 1] - off;
+    const int L = off < 0 || len < 0 ? 0 : (int)(len > 64 ? 64 : len);
+    const uint64_t code = a.code[aid];
+    const int32_t* pn = a.path_node + off;
+    const uint32_t n_inner = a.n_inner;
+    sg_targets<BATCH, false, ATOM, FROZEN>(Syn1, gsyn1, a.d, G, gl, L, lr, h, grad, lsum,
+                                           [&](int m) { const uint32_t n = (uint32_t)pn[m]; return n < n_inner ? (int32_t)n : -1; },
+                                           [&](int m) { return ((code >> m) & 1ull) == 0; });
+}
+
+// The nt target ids of a lane group into its LDS row before any row is loaded: `first`, then negf(0) .. negf(nt - 2), drawn
+// by the group's lanes. The first sync keeps the draw behind the group's reads of its previous ids.
+template <class NegFn>
+static __device__ __forceinline__ void sg_draw_ids(int32_t* ids, int G, int gl, int nt, int32_t first, const NegFn& negf) {
+    wave_lds_sync();
+    for (int m = gl; m < nt; m += G) ids[m] = m == 0 ? first : negf(m - 1);
+    wave_lds_sync();
+}
+
+// The sum of the In rows of the np contexts of a centre, in pair order, four loads in flight. Context k is token
+// cb + k + (k >= left): the centre itself is stepped over. An aid outside the table adds nothing (the plan checked every aid).
+static __device__ __forceinline__ float4 sg_gather(const float* In, const int32_t* cb, int np, int left, uint64_t n_aids, int d,
+                                                   int gl) {
+    float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k0 = 0; k0 < np; k0 += 4) {
+        float4 row[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = k0 + q;
+            row[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (k < np) {
+                const uint32_t x = (uint32_t)cb[k + (k >= left)];
+                if ((uint64_t)x < n_aids) row[q] = ld4(In + (int64_t)x * d + 4 * gl);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (k0 + q < np) add4(h, row[q]);
+    }
+    return h;
+}
+
+// per-workgroup loss partial, fixed order inside the workgroup
+static __device__ __forceinline__ void sg_loss_partial(double lsum, double* s_red, double* partial) {
+    lsum = wave_reduce<Sum>(lsum);
+    if (lane_id() == 0) s_red[threadIdx.x >> 6] = lsum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_red[w];
+        partial[blockIdx.x] = t;
     }
 }
 
@@ -313,10 +388,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgns_step(SgStepArgs a) {
             if (ct < 0 || ct >= a.T) continue;               // cannot happen for a plan of T tokens
             const int32_t ctx = a.tok_aid[ct];
             if ((uint64_t)(uint32_t)ctx >= (uint64_t)a.tab.n) continue;
-            // draw every target id of the pair before the first row load
-            wave_lds_sync();
-            for (int m = gl; m < nt; m += G) ids[m] = m == 0 ? ctx : sgns_negative(a.tab, ev, k, m - 1, ctx);
-            wave_lds_sync();
+            sg_draw_ids(ids, G, gl, nt, ctx, [&](int j) { return sgns_negative(a.tab, ev, k, j, ctx); });
             const int64_t po = pb + k - p0;
             if (po < a.out_pairs) {
                 if (a.ctx_out && gl == 0) a.ctx_out[po] = ctx;
@@ -324,43 +396,15 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgns_step(SgStepArgs a) {
                     for (int m = 1 + gl; m < nt; m += G) a.neg_out[po * a.neg + (m - 1)] = ids[m];
             }
             float4 grad = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (HS) {
-                // the path of ctx from the root: label 1 - bit; a row outside [0, n_inner) is skipped, never touched
-                const int64_t off = a.path_off[ctx];
-                const int64_t len = a.path_off[ctx + 1] - off;
-                const int L = off < 0 || len < 0 ? 0 : (int)(len > 64 ? 64 : len);
-                const uint64_t code = a.code[ctx];
-                const int32_t* pn = a.path_node + off;
-                const uint32_t n_inner = a.n_inner;
-                sg_targets<BATCH, false>(a.Syn1, a.gsyn1, a.d, G, gl, L, lr, h, grad, lsum,
-                                         [&](int m) { const uint32_t n = (uint32_t)pn[m]; return n < n_inner ? (int32_t)n : -1; },
-                                         [&](int m) { return ((code >> m) & 1ull) == 0; });
-            }
+            if (HS) sg_path_targets<BATCH, false, false>(a, a.Syn1, a.gsyn1, ctx, G, gl, lr, h, grad, lsum);
             sg_targets<BATCH, true>(a.Out, a.gout, a.d, G, gl, nt, lr, h, grad, lsum, [&](int m) { return ids[m]; },
                                     [](int m) { return m == 0; });
-            if (BATCH) {
-                gsum.x += grad.x; gsum.y += grad.y; gsum.z += grad.z; gsum.w += grad.w;
-            } else {
-                h.x += grad.x; h.y += grad.y; h.z += grad.z; h.w += grad.w;
-            }
+            if (BATCH) add4(gsum, grad); else add4(h, grad);
         }
-        if (BATCH) {
-            double* gi = a.gin + (int64_t)ca * a.d + 4 * gl;
-            atomicAdd(gi + 0, (double)gsum.x); atomicAdd(gi + 1, (double)gsum.y);
-            atomicAdd(gi + 2, (double)gsum.z); atomicAdd(gi + 3, (double)gsum.w);
-        } else {
-            st4(pin, h);
-        }
+        if (BATCH) atomic_add4(a.gin + (int64_t)ca * a.d + 4 * gl, gsum);
+        else st4(pin, h);
     }
-    // per-workgroup loss partial, fixed order inside the workgroup
-    lsum = wave_reduce<Sum>(lsum);
-    if (lane_id() == 0) s_red[threadIdx.x >> 6] = lsum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_red[w];
-        a.partial[blockIdx.x] = t;
-    }
+    sg_loss_partial(lsum, s_red, a.partial);
 }
 
 // ---------------------------------------------------------------------------
@@ -402,21 +446,6 @@ static __device__ __forceinline__ int32_t cbow_negative(const SgTable& t, uint64
     return (int32_t)(((int64_t)ca + 1) % t.n);
 }
 
-// the last s in [0, S) with tok_off[s] <= c: the session of token c (empty sessions share an offset; the last one holds c)
-static __device__ __forceinline__ int64_t sg_session_of(const int64_t* tok_off, int64_t S, int64_t c) {
-    int64_t lo = 0, hi = S - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (tok_off[mid] <= c) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-static __device__ __forceinline__ void add4(float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
-static __device__ __forceinline__ void atomic_add4(double* p, const float4& v) {
-    atomicAdd(p + 0, (double)v.x); atomicAdd(p + 1, (double)v.y); atomicAdd(p + 2, (double)v.z); atomicAdd(p + 3, (double)v.w);
-}
-
 // The targets of centre c (aid ca, in range) against h: the ids are drawn into LDS before any row is loaded; the path of ca
 // on Syn1, then ca and the negatives on Out. grad accumulates.
 template <bool BATCH, bool HS>
@@ -424,36 +453,12 @@ static __device__ __forceinline__ void cbow_targets(const SgCbowArgs& a, int G, 
                                                     const float4& h, float4& grad, double& lsum) {
     const uint64_t ev = sg_ev(a.base, (uint64_t)a.tok_src[c]);
     const int nt = 1 + a.neg;
-    wave_lds_sync();
-    for (int m = gl; m < nt; m += G) ids[m] = m == 0 ? ca : cbow_negative(a.tab, ev, m - 1, ca);
-    wave_lds_sync();
+    sg_draw_ids(ids, G, gl, nt, ca, [&](int j) { return cbow_negative(a.tab, ev, j, ca); });
     if (a.neg_out)
         for (int m = 1 + gl; m < nt; m += G) a.neg_out[(c - a.t0) * a.neg + (m - 1)] = ids[m];
-    if (HS) {
-        const int64_t off = a.path_off[ca];
-        const int64_t len = a.path_off[ca + 1] - off;
-        const int L = off < 0 || len < 0 ? 0 : (int)(len > 64 ? 64 : len);
-        const uint64_t code = a.code[ca];
-        const int32_t* pn = a.path_node + off;
-        const uint32_t n_inner = a.n_inner;
-        sg_targets<BATCH, false, !BATCH>(a.Syn1, a.gsyn1, a.d, G, gl, L, a.lr, h, grad, lsum,
-                                         [&](int m) { const uint32_t n = (uint32_t)pn[m]; return n < n_inner ? (int32_t)n : -1; },
-                                         [&](int m) { return ((code >> m) & 1ull) == 0; });
-    }
+    if (HS) sg_path_targets<BATCH, !BATCH, false>(a, a.Syn1, a.gsyn1, ca, G, gl, a.lr, h, grad, lsum);
     sg_targets<BATCH, true, !BATCH>(a.Out, a.gout, a.d, G, gl, nt, a.lr, h, grad, lsum, [&](int m) { return ids[m]; },
                                     [](int m) { return m == 0; });
-}
-
-// per-workgroup loss partial, fixed order inside the workgroup
-static __device__ __forceinline__ void sg_loss_partial(double lsum, double* s_red, double* partial) {
-    lsum = wave_reduce<Sum>(lsum);
-    if (lane_id() == 0) s_red[threadIdx.x >> 6] = lsum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_red[w];
-        partial[blockIdx.x] = t;
-    }
 }
 
 // CBOW (DOC = false) and PV-DM (DOC = true): one lane group per centre, grid-stride. The context rows are gathered as float4,
@@ -481,28 +486,14 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgns_cbow(SgCbowArgs a) {
         const int32_t* cb = a.tok_aid + (c - left);
         float* pdoc = nullptr;
         double* gdoc = nullptr;
-        float4 h = make_float4(0.f, 0.f, 0.f, 0.f), dr = h;
+        float4 dr = make_float4(0.f, 0.f, 0.f, 0.f);
         if (DOC) {
             const int64_t s = sg_session_of(a.tok_off, a.S, c);
             pdoc = a.Doc + s * a.d + 4 * gl;
             if (BATCH) gdoc = a.gdoc + s * a.d + 4 * gl;
             dr = ld4(pdoc);
         }
-        for (int k0 = 0; k0 < np; k0 += 4) {
-            float4 row[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int k = k0 + q;
-                row[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (k < np) {
-                    const uint32_t x = (uint32_t)cb[k + (k >= left)];
-                    if ((uint64_t)x < n_aids) row[q] = ld4(a.In + (int64_t)x * a.d + 4 * gl);      // the plan checked every aid
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (k0 + q < np) add4(h, row[q]);
-        }
+        float4 h = sg_gather(a.In, cb, np, left, n_aids, a.d, gl);
         if (DOC) add4(h, dr);
         const float fn = (float)n;
         if (a.variant != OTTO_SGNS_CBOW_SUM) { h.x = h.x / fn; h.y = h.y / fn; h.z = h.z / fn; h.w = h.w / fn; }
@@ -599,23 +590,11 @@ template <bool HS, bool WIN>
 static __device__ __forceinline__ void infer_targets(const SgInferArgs& a, int G, int gl, int32_t* ids, int64_t slot, int32_t ca,
                                                      uint64_t ev, float lr, const float4& h, float4& grad, double& lsum) {
     const int nt = 1 + a.neg;
-    wave_lds_sync();
-    for (int m = gl; m < nt; m += G) ids[m] = m == 0 ? ca : cbow_negative(a.tab, ev, m - 1, ca);
-    wave_lds_sync();
+    sg_draw_ids(ids, G, gl, nt, ca, [&](int j) { return cbow_negative(a.tab, ev, j, ca); });
     if (WIN && a.neg_out)
         for (int m = 1 + gl; m < nt; m += G) a.neg_out[slot * a.neg + (m - 1)] = ids[m];
     // FROZEN never writes through these pointers
-    if (HS) {
-        const int64_t off = a.path_off[ca];
-        const int64_t len = a.path_off[ca + 1] - off;
-        const int L = off < 0 || len < 0 ? 0 : (int)(len > 64 ? 64 : len);
-        const uint64_t code = a.code[ca];
-        const int32_t* pn = a.path_node + off;
-        const uint32_t n_inner = a.n_inner;
-        sg_targets<false, false, false, true>(const_cast<float*>(a.Syn1), nullptr, a.d, G, gl, L, lr, h, grad, lsum,
-                                              [&](int m) { const uint32_t n = (uint32_t)pn[m]; return n < n_inner ? (int32_t)n : -1; },
-                                              [&](int m) { return ((code >> m) & 1ull) == 0; });
-    }
+    if (HS) sg_path_targets<false, false, true>(a, const_cast<float*>(a.Syn1), nullptr, ca, G, gl, lr, h, grad, lsum);
     sg_targets<false, false, false, true>(const_cast<float*>(a.Out), nullptr, a.d, G, gl, nt, lr, h, grad, lsum,
                                           [&](int m) { return ids[m]; }, [](int m) { return m == 0; });
 }
@@ -664,22 +643,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_sgns_infer(SgInferArgs a) {
                     const int left = min(r, c - lo), np = left + min(r, hi - 1 - c);
                     // context k is token cb + k + (k >= left): the centre itself is stepped over
                     const int32_t* cb = a.tok_aid + (c - left);
-                    float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
-                    for (int k0 = 0; k0 < np; k0 += 4) {
-                        float4 row[4];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            const int k = k0 + q;
-                            row[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-                            if (k < np) {
-                                const uint32_t x = (uint32_t)cb[k + (k >= left)];
-                                if ((uint64_t)x < n_aids) row[q] = ld4(a.In + (int64_t)x * a.d + 4 * gl);
-                            }
-                        }
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            if (k0 + q < np) add4(h, row[q]);
-                    }
+                    float4 h = sg_gather(a.In, cb, np, left, n_aids, a.d, gl);
                     add4(h, hd);
                     const float fn = (float)(np + 1);
                     if (mean_h) { h.x = h.x / fn; h.y = h.y / fn; h.z = h.z / fn; h.w = h.w / fn; }
@@ -743,6 +707,78 @@ static int table_from(const otto_sgns_table* t, SgTable* out) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// what the three entry points over the step kernels (otto_sgns_step[_hs], otto_sgns_cbow_step, otto_sgns_infer) share
+// ---------------------------------------------------------------------------
+static int check_shape(int d, int neg) {
+    OTTO_REQUIRE(d >= 4 && d <= OTTO_SGNS_MAX_DIM && d % 4 == 0 && ((d / 4) & (d / 4 - 1)) == 0,
+                 "d = %d: need a multiple of 4 in [4, %d] with d/4 a power of two", d, OTTO_SGNS_MAX_DIM);
+    OTTO_REQUIRE(neg >= 0 && neg <= OTTO_SGNS_MAX_NEG, "neg = %d outside [0, %d]", neg, OTTO_SGNS_MAX_NEG);
+    return 0;
+}
+
+static int check_n_aids(int64_t n_aids) {
+    OTTO_REQUIRE(n_aids >= 1 && n_aids < (1ll << 31), "n_aids = %lld outside [1, 2^31)", (long long)n_aids);
+    return 0;
+}
+
+static int check_range(int64_t T, int64_t t0, int64_t t1) {
+    OTTO_REQUIRE(T >= 0 && T < (1ll << 31) && 0 <= t0 && t0 <= t1 && t1 <= T, "token range [%lld, %lld) outside the plan's %lld",
+                 (long long)t0, (long long)t1, (long long)T);
+    return 0;
+}
+
+static int check_sessions(int64_t S, int64_t T) {
+    OTTO_REQUIRE(T >= 0 && T < (1ll << 31) && S >= 0 && S < (1ll << 31) && (T == 0 || S >= 1), "S = %lld sessions for %lld tokens",
+                 (long long)S, (long long)T);
+    return 0;
+}
+
+// the Huffman tables of a caller that gave any of them
+static int check_paths(const int64_t* path_off, const int32_t* path_node, const uint64_t* code, const float* Syn1, int64_t n_inner) {
+    OTTO_REQUIRE(path_off && path_node && code && Syn1, "null hierarchical-softmax table");
+    OTTO_REQUIRE(n_inner >= 1 && n_inner < (1ll << 31), "n_inner = %lld outside [1, 2^31)", (long long)n_inner);
+    return 0;
+}
+
+// The negative table of a job record when something is drawn (an unset one reads as "total weight is 0"), else only its
+// size: tab.n = n_aids either way.
+static int table_or_size(const otto_sgns_table& t, int neg, int64_t n_aids, SgTable* out) {
+    if (neg > 0) {
+        OTTO_REQUIRE(t.total > 0, "negative table: total weight is 0, nothing can be drawn");
+        OTTO_TRY(table_from(&t, out));
+        OTTO_REQUIRE(t.n_aids == n_aids && n_aids >= 2, "negative sampling needs at least 2 aids and a table over n_aids");
+    }
+    out->n = n_aids;
+    return 0;
+}
+
+// one lane group of G = d/4 lanes per item: the workgroup is min(256, 64 * G) threads; returns the grid
+static int launch_dims(int G, int64_t items, int* threads) {
+    *threads = G >= 4 ? SG_THREADS : 64 * G;
+    return grid_for(items, *threads / G);
+}
+
+// a table a training launch may have written and its BATCH workspace; tab = null: this launch's arch has no such table
+struct SgDense {
+    float* tab;
+    double* g;
+    int64_t rows;
+};
+
+// the tail of a training launch: BATCH applies every workspace to its table, in the order given; then the loss sum
+static int apply_and_sum(bool batch, std::initializer_list<SgDense> tabs, int d, const double* partial, int grid,
+                         double* d_loss_sum, hipStream_t s) {
+    for (const SgDense& t : tabs) {
+        if (!batch || !t.tab) continue;
+        const int64_t n = t.rows * (int64_t)d;
+        k_sgns_apply<<<grid_for(n, 256), 256, 0, s>>>(t.tab, t.g, n);
+    }
+    k_sgns_loss_final<<<1, 256, 0, s>>>(partial, grid, d_loss_sum);
+    OTTO_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace otto
 
 using namespace otto;
@@ -755,7 +791,7 @@ extern "C" int64_t otto_sgns_neg_table_workspace(int64_t n_aids) {
 extern "C" int otto_sgns_neg_table(const uint32_t* d_weight, int64_t n_aids, int64_t n_buckets, uint64_t* d_cum,
                                    uint32_t* d_bucket, otto_sgns_table* table, void* d_work, int64_t work_bytes, void* stream) {
     OTTO_REQUIRE(d_weight && d_cum && d_bucket && table && d_work, "null argument");
-    OTTO_REQUIRE(n_aids >= 1 && n_aids < (1ll << 31), "n_aids = %lld outside [1, 2^31)", (long long)n_aids);
+    OTTO_TRY(check_n_aids(n_aids));
     OTTO_REQUIRE(n_buckets >= 1 && n_buckets < (1ll << 31), "n_buckets = %lld outside [1, 2^31)", (long long)n_buckets);
     OTTO_REQUIRE(work_bytes >= otto_sgns_neg_table_workspace(n_aids), "workspace too small");
     hipStream_t s = (hipStream_t)stream;
@@ -798,7 +834,7 @@ extern "C" int otto_sgns_plan(const int32_t* d_aid, int64_t E, const int64_t* d_
                               void* stream) {
     OTTO_REQUIRE(E >= 0 && E < (1ll << 31), "E = %lld outside [0, 2^31)", (long long)E);
     OTTO_REQUIRE(S >= 0 && S < (1ll << 31), "S = %lld outside [0, 2^31)", (long long)S);
-    OTTO_REQUIRE(n_aids >= 1 && n_aids < (1ll << 31), "n_aids = %lld outside [1, 2^31)", (long long)n_aids);
+    OTTO_TRY(check_n_aids(n_aids));
     OTTO_REQUIRE(ws >= 1 && ws <= OTTO_SGNS_MAX_WS, "ws = %d outside [1, %d]", ws, OTTO_SGNS_MAX_WS);
     OTTO_REQUIRE(event0 >= 0 && cap_tokens >= 0, "negative event0 or cap_tokens");
     OTTO_REQUIRE(d_sess_off && d_keep_q && d_tok_off && d_pair_off && h_counts && d_work && (E == 0 || d_aid), "null argument");
@@ -842,75 +878,96 @@ extern "C" int otto_sgns_plan(const int32_t* d_aid, int64_t E, const int64_t* d_
 
 namespace otto {
 
-// what otto_sgns_step_hs adds to otto_sgns_step
-struct SgHsTables {
-    const int64_t* path_off;
-    const int32_t* path_node;
-    const uint64_t* code;
-    float* Syn1;
-    int64_t n_inner;
-    double* gsyn1;
+// The arguments of otto_sgns_step, in the order of the header, and what otto_sgns_step_hs adds to them.
+struct SgStepCall {
+    const int32_t* tok_aid;
+    const int64_t* tok_src;
+    const uint8_t* tok_left;
+    const int64_t* pair_off;
+    int64_t T, t0, t1;
+    float* In;
+    float* Out;
+    int32_t d, neg;
+    float lr;
+    int32_t mode;
+    uint64_t seed, epoch;
+    const otto_sgns_table* table;
+    double* loss_sum;
+    int32_t* ctx_out;
+    int32_t* neg_out;
+    int64_t out_pairs;
+    double* gin;
+    double* gout;
+    void* stream;
+    // what otto_sgns_step_hs adds, assigned by name
+    bool hs = false;
+    const int64_t* path_off = nullptr;
+    const int32_t* path_node = nullptr;
+    const uint64_t* code = nullptr;
+    float* Syn1 = nullptr;
+    int64_t n_inner = 0;
+    double* gsyn1 = nullptr;
 };
 
-static int sgns_step(const int32_t* d_tok_aid, const int64_t* d_tok_src, const uint8_t* d_tok_left, const int64_t* d_pair_off,
-                     int64_t T, int64_t t0, int64_t t1, float* d_In, float* d_Out, int32_t d, int32_t neg, float lr, int32_t mode,
-                     uint64_t seed, uint64_t epoch, const otto_sgns_table* table, double* d_loss_sum, int32_t* d_ctx_out,
-                     int32_t* d_neg_out, int64_t out_pairs, double* d_gin, double* d_gout, const SgHsTables* hs, void* stream) {
-    OTTO_REQUIRE(d >= 4 && d <= OTTO_SGNS_MAX_DIM && d % 4 == 0 && ((d / 4) & (d / 4 - 1)) == 0,
-                 "d = %d: need a multiple of 4 in [4, %d] with d/4 a power of two", d, OTTO_SGNS_MAX_DIM);
-    OTTO_REQUIRE(neg >= 0 && neg <= OTTO_SGNS_MAX_NEG, "neg = %d outside [0, %d]", neg, OTTO_SGNS_MAX_NEG);
-    OTTO_REQUIRE(mode == OTTO_SGNS_HOGWILD || mode == OTTO_SGNS_BATCH, "unknown SGNS mode %d", mode);
-    OTTO_REQUIRE(T >= 0 && T < (1ll << 31) && 0 <= t0 && t0 <= t1 && t1 <= T, "token range [%lld, %lld) outside the plan's %lld",
-                 (long long)t0, (long long)t1, (long long)T);
-    OTTO_REQUIRE(d_pair_off && d_In && d_Out && d_loss_sum && table, "null argument");
-    OTTO_REQUIRE(T == 0 || (d_tok_aid && d_tok_src && d_tok_left), "null plan array");
-    OTTO_REQUIRE(mode == OTTO_SGNS_HOGWILD || (d_gin && d_gout), "BATCH mode needs both gradient workspaces");
-    OTTO_REQUIRE(out_pairs >= 0 && (out_pairs > 0 || (!d_ctx_out && !d_neg_out)), "ctx_out / neg_out without out_pairs");
+static int sgns_step(const SgStepCall& c) {
+    const bool hs = c.hs, batch = c.mode == OTTO_SGNS_BATCH;
+    OTTO_TRY(check_shape(c.d, c.neg));
+    OTTO_REQUIRE(c.mode == OTTO_SGNS_HOGWILD || batch, "unknown SGNS mode %d", c.mode);
+    OTTO_TRY(check_range(c.T, c.t0, c.t1));
+    OTTO_REQUIRE(c.pair_off && c.In && c.Out && c.loss_sum && c.table, "null argument");
+    OTTO_REQUIRE(c.T == 0 || (c.tok_aid && c.tok_src && c.tok_left), "null plan array");
+    OTTO_REQUIRE(!batch || (c.gin && c.gout), "BATCH mode needs both gradient workspaces");
+    OTTO_REQUIRE(c.out_pairs >= 0 && (c.out_pairs > 0 || (!c.ctx_out && !c.neg_out)), "ctx_out / neg_out without out_pairs");
     if (hs) {
-        OTTO_REQUIRE(hs->path_off && hs->path_node && hs->code && hs->Syn1, "null hierarchical-softmax table");
-        OTTO_REQUIRE(hs->n_inner >= 1 && hs->n_inner < (1ll << 31), "n_inner = %lld outside [1, 2^31)", (long long)hs->n_inner);
-        OTTO_REQUIRE(mode == OTTO_SGNS_HOGWILD || hs->gsyn1, "BATCH mode needs the Syn1 gradient workspace");
+        OTTO_TRY(check_paths(c.path_off, c.path_node, c.code, c.Syn1, c.n_inner));
+        OTTO_REQUIRE(!batch || c.gsyn1, "BATCH mode needs the Syn1 gradient workspace");
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (t0 == t1) {
-        OTTO_HIP(hipMemsetAsync(d_loss_sum, 0, sizeof(double), s));
+    hipStream_t s = (hipStream_t)c.stream;
+    if (c.t0 == c.t1) {
+        OTTO_HIP(hipMemsetAsync(c.loss_sum, 0, sizeof(double), s));
         return 0;
     }
     SgStepArgs a;
     memset(&a, 0, sizeof a);
-    if (neg > 0) {
-        OTTO_TRY(table_from(table, &a.tab));
-        OTTO_REQUIRE(table->n_aids >= 2, "negative sampling needs at least 2 aids");
+    // the table is this entry point's only source of n_aids
+    if (c.neg > 0) {
+        OTTO_TRY(table_from(c.table, &a.tab));
+        OTTO_REQUIRE(c.table->n_aids >= 2, "negative sampling needs at least 2 aids");
     } else {
-        OTTO_REQUIRE(table->n_aids >= 1 && table->n_aids < (1ll << 31), "negative table: bad sizes");
-        a.tab.n = table->n_aids;
+        OTTO_REQUIRE(c.table->n_aids >= 1 && c.table->n_aids < (1ll << 31), "negative table: bad sizes");
+        a.tab.n = c.table->n_aids;
     }
     void* scratch = nullptr;
     OTTO_TRY(device_scratch(SCRATCH_SGNS_STEP, (size_t)SG_GRID * sizeof(double), &scratch, s));
-    a.tok_aid = d_tok_aid; a.tok_src = d_tok_src; a.tok_left = d_tok_left; a.pair_off = d_pair_off;
-    a.T = T; a.t0 = t0; a.t1 = t1; a.In = d_In; a.Out = d_Out; a.d = d; a.G = d / 4; a.neg = neg; a.lr = lr;
-    a.base = sg_base(seed, epoch); a.partial = reinterpret_cast<double*>(scratch);
-    a.ctx_out = d_ctx_out; a.neg_out = neg > 0 ? d_neg_out : nullptr; a.out_pairs = out_pairs; a.gin = d_gin; a.gout = d_gout;
-    if (hs) {
-        a.path_off = hs->path_off; a.path_node = hs->path_node; a.code = hs->code; a.Syn1 = hs->Syn1; a.gsyn1 = hs->gsyn1;
-        a.n_inner = (uint32_t)hs->n_inner;
-    }
-    const int threads = a.G >= 4 ? SG_THREADS : 64 * a.G;
-    const int grid = grid_for(t1 - t0, threads / a.G);
-    if (mode == OTTO_SGNS_HOGWILD) {
-        if (hs) k_sgns_step<false, true><<<grid, threads, 0, s>>>(a);
-        else k_sgns_step<false, false><<<grid, threads, 0, s>>>(a);
-    } else {
-        if (hs) k_sgns_step<true, true><<<grid, threads, 0, s>>>(a);
-        else k_sgns_step<true, false><<<grid, threads, 0, s>>>(a);
-        const int64_t n = table->n_aids * (int64_t)d;
-        k_sgns_apply<<<grid_for(n, 256), 256, 0, s>>>(d_In, d_gin, n);
-        k_sgns_apply<<<grid_for(n, 256), 256, 0, s>>>(d_Out, d_gout, n);
-        if (hs) k_sgns_apply<<<grid_for(hs->n_inner * (int64_t)d, 256), 256, 0, s>>>(hs->Syn1, hs->gsyn1, hs->n_inner * (int64_t)d);
-    }
-    k_sgns_loss_final<<<1, 256, 0, s>>>(a.partial, grid, d_loss_sum);
-    OTTO_HIP(hipGetLastError());
-    return 0;
+    a.tok_aid = c.tok_aid; a.tok_src = c.tok_src; a.tok_left = c.tok_left; a.pair_off = c.pair_off;
+    a.T = c.T; a.t0 = c.t0; a.t1 = c.t1; a.In = c.In; a.Out = c.Out; a.d = c.d; a.G = c.d / 4; a.neg = c.neg; a.lr = c.lr;
+    a.base = sg_base(c.seed, c.epoch); a.partial = reinterpret_cast<double*>(scratch);
+    a.ctx_out = c.ctx_out; a.neg_out = c.neg > 0 ? c.neg_out : nullptr; a.out_pairs = c.out_pairs; a.gin = c.gin; a.gout = c.gout;
+    a.path_off = c.path_off; a.path_node = c.path_node; a.code = c.code; a.Syn1 = c.Syn1; a.gsyn1 = c.gsyn1;
+    a.n_inner = (uint32_t)c.n_inner;                          // null and 0 from otto_sgns_step
+    int threads;
+    const int grid = launch_dims(a.G, c.t1 - c.t0, &threads);
+    if (!batch && hs) k_sgns_step<false, true><<<grid, threads, 0, s>>>(a);
+    else if (!batch) k_sgns_step<false, false><<<grid, threads, 0, s>>>(a);
+    else if (hs) k_sgns_step<true, true><<<grid, threads, 0, s>>>(a);
+    else k_sgns_step<true, false><<<grid, threads, 0, s>>>(a);
+    return apply_and_sum(batch, {{c.In, c.gin, a.tab.n}, {c.Out, c.gout, a.tab.n}, {a.Syn1, c.gsyn1, c.n_inner}}, c.d, a.partial, grid,
+                         c.loss_sum, s);
+}
+
+template <bool BATCH, bool HS>
+static void launch_cbow(int arch, int grid, int threads, hipStream_t s, const SgCbowArgs& a) {
+    if (arch == OTTO_SGNS_ARCH_CBOW) k_sgns_cbow<BATCH, HS, false><<<grid, threads, 0, s>>>(a);
+    else if (arch == OTTO_SGNS_ARCH_PVDM) k_sgns_cbow<BATCH, HS, true><<<grid, threads, 0, s>>>(a);
+    else k_sgns_dbow<BATCH, HS><<<grid, threads, 0, s>>>(a);
+}
+
+template <bool WIN>
+static void launch_infer(bool hs, bool dm, int grid, int threads, hipStream_t s, const SgInferArgs& a) {
+    if (dm && hs) k_sgns_infer<true, true, WIN><<<grid, threads, 0, s>>>(a);
+    else if (dm) k_sgns_infer<false, true, WIN><<<grid, threads, 0, s>>>(a);
+    else if (hs) k_sgns_infer<true, false, WIN><<<grid, threads, 0, s>>>(a);
+    else k_sgns_infer<false, false, WIN><<<grid, threads, 0, s>>>(a);
 }
 
 // The tree of SPEC-SGNS-HS over the in-vocabulary aids: leaves 0..V-1 in (count desc, aid asc) order, inner nodes V..2V-2.
@@ -924,7 +981,7 @@ struct SgTree {
 
 static int sgns_hs_build(const int64_t* count, int64_t n_aids, int64_t min_count, SgTree* t) {
     OTTO_REQUIRE(count, "null argument");
-    OTTO_REQUIRE(n_aids >= 1 && n_aids < (1ll << 31), "n_aids = %lld outside [1, 2^31)", (long long)n_aids);
+    OTTO_TRY(check_n_aids(n_aids));
     const int64_t floor_count = min_count > 1 ? min_count : 1;
     int64_t total = 0;
     for (int64_t a = 0; a < n_aids; ++a) {
@@ -965,8 +1022,8 @@ extern "C" int otto_sgns_step(const int32_t* d_tok_aid, const int64_t* d_tok_src
                               int32_t neg, float lr, int32_t mode, uint64_t seed, uint64_t epoch, const otto_sgns_table* table,
                               double* d_loss_sum, int32_t* d_ctx_out, int32_t* d_neg_out, int64_t out_pairs, double* d_gin,
                               double* d_gout, void* stream) {
-    return sgns_step(d_tok_aid, d_tok_src, d_tok_left, d_pair_off, T, t0, t1, d_In, d_Out, d, neg, lr, mode, seed, epoch, table,
-                     d_loss_sum, d_ctx_out, d_neg_out, out_pairs, d_gin, d_gout, nullptr, stream);
+    return sgns_step({d_tok_aid, d_tok_src, d_tok_left, d_pair_off, T, t0, t1, d_In, d_Out, d, neg, lr, mode, seed, epoch, table,
+                      d_loss_sum, d_ctx_out, d_neg_out, out_pairs, d_gin, d_gout, stream});
 }
 
 extern "C" int otto_sgns_step_hs(const int32_t* d_tok_aid, const int64_t* d_tok_src, const uint8_t* d_tok_left,
@@ -975,21 +1032,12 @@ extern "C" int otto_sgns_step_hs(const int32_t* d_tok_aid, const int64_t* d_tok_
                                  double* d_loss_sum, int32_t* d_ctx_out, int32_t* d_neg_out, int64_t out_pairs, double* d_gin,
                                  double* d_gout, const int64_t* d_path_off, const int32_t* d_path_node, const uint64_t* d_code,
                                  float* d_Syn1, int64_t n_inner, double* d_gsyn1, void* stream) {
-    const SgHsTables hs = {d_path_off, d_path_node, d_code, d_Syn1, n_inner, d_gsyn1};
-    return sgns_step(d_tok_aid, d_tok_src, d_tok_left, d_pair_off, T, t0, t1, d_In, d_Out, d, neg, lr, mode, seed, epoch, table,
-                     d_loss_sum, d_ctx_out, d_neg_out, out_pairs, d_gin, d_gout, &hs, stream);
+    SgStepCall c = {d_tok_aid, d_tok_src, d_tok_left, d_pair_off, T, t0, t1, d_In, d_Out, d, neg, lr, mode, seed, epoch, table,
+                    d_loss_sum, d_ctx_out, d_neg_out, out_pairs, d_gin, d_gout, stream};
+    c.hs = true; c.path_off = d_path_off; c.path_node = d_path_node; c.code = d_code; c.Syn1 = d_Syn1; c.n_inner = n_inner;
+    c.gsyn1 = d_gsyn1;
+    return sgns_step(c);
 }
-
-namespace otto {
-
-template <bool BATCH, bool HS>
-static void launch_cbow(int arch, int grid, int threads, hipStream_t s, const SgCbowArgs& a) {
-    if (arch == OTTO_SGNS_ARCH_CBOW) k_sgns_cbow<BATCH, HS, false><<<grid, threads, 0, s>>>(a);
-    else if (arch == OTTO_SGNS_ARCH_PVDM) k_sgns_cbow<BATCH, HS, true><<<grid, threads, 0, s>>>(a);
-    else k_sgns_dbow<BATCH, HS><<<grid, threads, 0, s>>>(a);
-}
-
-}  // namespace otto
 
 extern "C" int otto_sgns_cbow_step(const otto_sgns_cbow_job* job) {
     OTTO_REQUIRE(job, "null job");
@@ -1000,35 +1048,21 @@ extern "C" int otto_sgns_cbow_step(const otto_sgns_cbow_job* job) {
     OTTO_REQUIRE(dbow || j.variant == OTTO_SGNS_CBOW_SUM || j.variant == OTTO_SGNS_CBOW_MEAN || j.variant == OTTO_SGNS_CBOW_FASTTEXT,
                  "unknown variant %d", j.variant);
     OTTO_REQUIRE(j.mode == OTTO_SGNS_HOGWILD || batch, "unknown SGNS mode %d", j.mode);
-    OTTO_REQUIRE(d >= 4 && d <= OTTO_SGNS_MAX_DIM && d % 4 == 0 && ((d / 4) & (d / 4 - 1)) == 0,
-                 "d = %d: need a multiple of 4 in [4, %d] with d/4 a power of two", d, OTTO_SGNS_MAX_DIM);
-    OTTO_REQUIRE(neg >= 0 && neg <= OTTO_SGNS_MAX_NEG, "neg = %d outside [0, %d]", neg, OTTO_SGNS_MAX_NEG);
-    OTTO_REQUIRE(j.n_aids >= 1 && j.n_aids < (1ll << 31), "n_aids = %lld outside [1, 2^31)", (long long)j.n_aids);
-    OTTO_REQUIRE(j.T >= 0 && j.T < (1ll << 31) && 0 <= j.t0 && j.t0 <= j.t1 && j.t1 <= j.T,
-                 "token range [%lld, %lld) outside the plan's %lld", (long long)j.t0, (long long)j.t1, (long long)j.T);
-    OTTO_REQUIRE(j.S >= 0 && j.S < (1ll << 31) && (j.T == 0 || j.S >= 1), "S = %lld sessions for %lld tokens", (long long)j.S,
-                 (long long)j.T);
+    OTTO_TRY(check_shape(d, neg));
+    OTTO_TRY(check_n_aids(j.n_aids));
+    OTTO_TRY(check_range(j.T, j.t0, j.t1));
+    OTTO_TRY(check_sessions(j.S, j.T));
     OTTO_REQUIRE(j.d_pair_off && j.d_Out && j.d_loss_sum, "null argument");
     OTTO_REQUIRE(j.T == 0 || (j.d_tok_aid && j.d_tok_src && j.d_tok_left), "null plan array");
     OTTO_REQUIRE(dbow || j.d_In, "CBOW and PV-DM need In");
     OTTO_REQUIRE(!doc || (j.d_Doc && j.d_tok_off), "PV-DM and DBOW need Doc and tok_off");
     const bool hs = j.d_path_off || j.d_path_node || j.d_code;
-    if (hs) {
-        OTTO_REQUIRE(j.d_path_off && j.d_path_node && j.d_code && j.d_Syn1, "null hierarchical-softmax table");
-        OTTO_REQUIRE(j.n_inner >= 1 && j.n_inner < (1ll << 31), "n_inner = %lld outside [1, 2^31)", (long long)j.n_inner);
-    }
-    if (batch) {
-        OTTO_REQUIRE(j.d_gout && (dbow || j.d_gin) && (!doc || j.d_gdoc) && (!hs || j.d_gsyn1),
-                     "BATCH mode needs the gradient workspaces of its arch");
-    }
+    if (hs) OTTO_TRY(check_paths(j.d_path_off, j.d_path_node, j.d_code, j.d_Syn1, j.n_inner));
+    OTTO_REQUIRE(!batch || (j.d_gout && (dbow || j.d_gin) && (!doc || j.d_gdoc) && (!hs || j.d_gsyn1)),
+                 "BATCH mode needs the gradient workspaces of its arch");
     SgCbowArgs a;
     memset(&a, 0, sizeof a);
-    if (neg > 0) {
-        OTTO_REQUIRE(j.table.total > 0, "negative table: total weight is 0, nothing can be drawn");
-        OTTO_TRY(table_from(&j.table, &a.tab));
-        OTTO_REQUIRE(j.table.n_aids == j.n_aids && j.n_aids >= 2, "negative sampling needs at least 2 aids and a table over n_aids");
-    }
-    a.tab.n = j.n_aids;
+    OTTO_TRY(table_or_size(j.table, neg, j.n_aids, &a.tab));
     hipStream_t s = (hipStream_t)j.stream;
     if (j.t0 == j.t1) {
         OTTO_HIP(hipMemsetAsync(j.d_loss_sum, 0, sizeof(double), s));
@@ -1042,41 +1076,17 @@ extern "C" int otto_sgns_cbow_step(const otto_sgns_cbow_job* job) {
     a.partial = reinterpret_cast<double*>(scratch); a.neg_out = neg > 0 ? j.d_neg_out : nullptr;
     a.gin = j.d_gin; a.gout = j.d_gout; a.gsyn1 = j.d_gsyn1; a.gdoc = j.d_gdoc;
     if (hs) { a.path_off = j.d_path_off; a.path_node = j.d_path_node; a.code = j.d_code; a.n_inner = (uint32_t)j.n_inner; }
-    const int threads = a.G >= 4 ? SG_THREADS : 64 * a.G;
     // DBOW: at most one session per token of the range meets it
-    const int64_t items = dbow ? (j.S < j.t1 - j.t0 ? j.S : j.t1 - j.t0) : j.t1 - j.t0;
-    const int grid = grid_for(items, threads / a.G);
-    if (!batch) {
-        if (hs) launch_cbow<false, true>(arch, grid, threads, s, a);
-        else launch_cbow<false, false>(arch, grid, threads, s, a);
-    } else {
-        if (hs) launch_cbow<true, true>(arch, grid, threads, s, a);
-        else launch_cbow<true, false>(arch, grid, threads, s, a);
-        const int64_t n = j.n_aids * (int64_t)d;
-        if (!dbow) k_sgns_apply<<<grid_for(n, 256), 256, 0, s>>>(j.d_In, j.d_gin, n);
-        k_sgns_apply<<<grid_for(n, 256), 256, 0, s>>>(j.d_Out, j.d_gout, n);
-        if (hs) k_sgns_apply<<<grid_for(j.n_inner * (int64_t)d, 256), 256, 0, s>>>(j.d_Syn1, j.d_gsyn1, j.n_inner * (int64_t)d);
-        if (doc) k_sgns_apply<<<grid_for(j.S * (int64_t)d, 256), 256, 0, s>>>(j.d_Doc, j.d_gdoc, j.S * (int64_t)d);
-    }
-    k_sgns_loss_final<<<1, 256, 0, s>>>(a.partial, grid, j.d_loss_sum);
-    OTTO_HIP(hipGetLastError());
-    return 0;
+    int threads;
+    const int grid = launch_dims(a.G, dbow ? (j.S < j.t1 - j.t0 ? j.S : j.t1 - j.t0) : j.t1 - j.t0, &threads);
+    if (!batch && hs) launch_cbow<false, true>(arch, grid, threads, s, a);
+    else if (!batch) launch_cbow<false, false>(arch, grid, threads, s, a);
+    else if (hs) launch_cbow<true, true>(arch, grid, threads, s, a);
+    else launch_cbow<true, false>(arch, grid, threads, s, a);
+    return apply_and_sum(batch, {{dbow ? nullptr : j.d_In, j.d_gin, j.n_aids}, {j.d_Out, j.d_gout, j.n_aids},
+                                 {hs ? j.d_Syn1 : nullptr, j.d_gsyn1, j.n_inner}, {doc ? j.d_Doc : nullptr, j.d_gdoc, j.S}},
+                         d, a.partial, grid, j.d_loss_sum, s);
 }
-
-namespace otto {
-
-template <bool WIN>
-static void launch_infer(bool hs, bool dm, int grid, int threads, hipStream_t s, const SgInferArgs& a) {
-    if (dm) {
-        if (hs) k_sgns_infer<true, true, WIN><<<grid, threads, 0, s>>>(a);
-        else k_sgns_infer<false, true, WIN><<<grid, threads, 0, s>>>(a);
-    } else {
-        if (hs) k_sgns_infer<true, false, WIN><<<grid, threads, 0, s>>>(a);
-        else k_sgns_infer<false, false, WIN><<<grid, threads, 0, s>>>(a);
-    }
-}
-
-}  // namespace otto
 
 extern "C" int otto_sgns_infer(const otto_sgns_infer_job* job) {
     OTTO_REQUIRE(job, "null job");
@@ -1086,31 +1096,20 @@ extern "C" int otto_sgns_infer(const otto_sgns_infer_job* job) {
     const bool dm = arch == OTTO_SGNS_ARCH_PVDM;
     OTTO_REQUIRE(j.variant == OTTO_SGNS_CBOW_SUM || j.variant == OTTO_SGNS_CBOW_MEAN || j.variant == OTTO_SGNS_CBOW_FASTTEXT,
                  "unknown variant %d", j.variant);
-    OTTO_REQUIRE(d >= 4 && d <= OTTO_SGNS_MAX_DIM && d % 4 == 0 && ((d / 4) & (d / 4 - 1)) == 0,
-                 "d = %d: need a multiple of 4 in [4, %d] with d/4 a power of two", d, OTTO_SGNS_MAX_DIM);
-    OTTO_REQUIRE(neg >= 0 && neg <= OTTO_SGNS_MAX_NEG, "neg = %d outside [0, %d]", neg, OTTO_SGNS_MAX_NEG);
+    OTTO_TRY(check_shape(d, neg));
     OTTO_REQUIRE(j.ws >= 1 && j.ws <= OTTO_SGNS_MAX_WS, "ws = %d outside [1, %d]", j.ws, OTTO_SGNS_MAX_WS);
     OTTO_REQUIRE(j.passes >= 1 && j.passes <= OTTO_SGNS_MAX_INFER_PASSES, "passes = %d outside [1, %d]", j.passes,
                  OTTO_SGNS_MAX_INFER_PASSES);
-    OTTO_REQUIRE(j.n_aids >= 1 && j.n_aids < (1ll << 31), "n_aids = %lld outside [1, 2^31)", (long long)j.n_aids);
-    OTTO_REQUIRE(j.T >= 0 && j.T < (1ll << 31) && j.S >= 0 && j.S < (1ll << 31) && (j.T == 0 || j.S >= 1),
-                 "S = %lld sessions for %lld tokens", (long long)j.S, (long long)j.T);
+    OTTO_TRY(check_n_aids(j.n_aids));
+    OTTO_TRY(check_sessions(j.S, j.T));
     OTTO_REQUIRE(j.d_tok_off && j.d_Out && j.d_Doc && (j.T == 0 || j.d_tok_aid), "null argument");
     OTTO_REQUIRE(!dm || j.d_In, "PV-DM needs In");
     const bool hs = j.d_path_off || j.d_path_node || j.d_code;
-    if (hs) {
-        OTTO_REQUIRE(j.d_path_off && j.d_path_node && j.d_code && j.d_Syn1, "null hierarchical-softmax table");
-        OTTO_REQUIRE(j.n_inner >= 1 && j.n_inner < (1ll << 31), "n_inner = %lld outside [1, 2^31)", (long long)j.n_inner);
-    }
+    if (hs) OTTO_TRY(check_paths(j.d_path_off, j.d_path_node, j.d_code, j.d_Syn1, j.n_inner));
     OTTO_REQUIRE(neg > 0 || hs, "neg = 0 without hierarchical-softmax tables leaves nothing to infer against");
     SgInferArgs a;
     memset(&a, 0, sizeof a);
-    if (neg > 0) {
-        OTTO_REQUIRE(j.table.total > 0, "negative table: total weight is 0, nothing can be drawn");
-        OTTO_TRY(table_from(&j.table, &a.tab));
-        OTTO_REQUIRE(j.table.n_aids == j.n_aids && j.n_aids >= 2, "negative sampling needs at least 2 aids and a table over n_aids");
-    }
-    a.tab.n = j.n_aids;
+    OTTO_TRY(table_or_size(j.table, neg, j.n_aids, &a.tab));
     if (j.S == 0) return 0;
     a.tok_aid = j.d_tok_aid; a.tok_off = j.d_tok_off; a.sess_key = j.d_sess_key; a.order = j.d_order; a.T = j.T; a.S = j.S;
     a.In = j.d_In; a.Out = j.d_Out; a.Syn1 = j.d_Syn1; a.Doc = j.d_Doc; a.loss = j.d_loss;
@@ -1122,8 +1121,8 @@ extern "C" int otto_sgns_infer(const otto_sgns_infer_job* job) {
         a.base[p] = sg_base(j.seed, (uint64_t)p);
     }
     hipStream_t s = (hipStream_t)j.stream;
-    const int threads = a.G >= 4 ? SG_THREADS : 64 * a.G;
-    const int grid = grid_for(j.S, threads / a.G);
+    int threads;
+    const int grid = launch_dims(a.G, j.S, &threads);
     if (a.neg_out || a.radius_out) launch_infer<true>(hs, dm, grid, threads, s, a);
     else launch_infer<false>(hs, dm, grid, threads, s, a);
     OTTO_HIP(hipGetLastError());

@@ -150,6 +150,23 @@ def _as_u32_tensor(a, dev):
     return torch.from_numpy(a.view(np.int32)).to(dev)
 
 
+def _check_hyper(d, neg, ws, seed, name='d', hs=True):
+    """``(d, neg, ws, seed)`` as ints, ``ValueError`` (naming the argument as given, ``d`` as ``name``) unless they are in
+    SPEC-SGNS's ranges; ``hs=False``: ``neg = 0`` leaves a frozen model without targets."""
+    di, negi, wsi, seedi = int(d), int(neg), int(ws), int(seed)
+    if di % 4 or not 4 <= di <= MAX_DIM or (di // 4) & (di // 4 - 1):
+        raise ValueError(f'{name} must be a multiple of 4 in [4, {MAX_DIM}] with {name}/4 a power of two (got {d})')
+    if not 0 <= negi <= MAX_NEG:
+        raise ValueError(f'neg must be in [0, {MAX_NEG}] (got {neg})')
+    if negi == 0 and not hs:
+        raise ValueError('neg = 0 without hierarchical softmax leaves nothing to infer against')
+    if not 1 <= wsi <= MAX_WS:
+        raise ValueError(f'ws must be in [1, {MAX_WS}] (got {ws})')
+    if not 0 <= seedi < 1 << 64:
+        raise ValueError('seed: expected a uint64')
+    return di, negi, wsi, seedi
+
+
 class SkipGramEngine:
     """Plan / step with persistent workspaces. ``keep_q`` / ``weight``: the uint32 tables of :func:`vocab_tables`.
     ``hs``: the :class:`HuffmanTables` of :func:`huffman_tables` (or any object with its fields); they are uploaded, and
@@ -158,15 +175,8 @@ class SkipGramEngine:
     def __init__(self, n_aids, d, ws, neg, keep_q, weight, seed=0, device='cuda:0', n_buckets=None, hs=None):
         import torch
         self.dev = _lib.rocm_device(device, 'SkipGramEngine')
-        self.n_aids, self.d, self.ws, self.neg, self.seed = int(n_aids), int(d), int(ws), int(neg), int(seed)
-        if self.d % 4 or not 4 <= self.d <= MAX_DIM or (self.d // 4) & (self.d // 4 - 1):
-            raise ValueError(f'd must be a multiple of 4 in [4, {MAX_DIM}] with d/4 a power of two (got {d})')
-        if not 0 <= self.neg <= MAX_NEG:
-            raise ValueError(f'neg must be in [0, {MAX_NEG}] (got {neg})')
-        if not 1 <= self.ws <= MAX_WS:
-            raise ValueError(f'ws must be in [1, {MAX_WS}] (got {ws})')
-        if not 0 <= self.seed < 1 << 64:
-            raise ValueError('seed: expected a uint64')
+        self.n_aids = int(n_aids)
+        self.d, self.neg, self.ws, self.seed = _check_hyper(d, neg, ws, seed)
         if len(keep_q) != self.n_aids or len(weight) != self.n_aids:
             raise ValueError('keep_q and weight must have n_aids entries')
         self.lib = _lib.lib()
@@ -200,6 +210,28 @@ class SkipGramEngine:
 
     def _call(self, name, *args):
         _lib.call(name, self.dev, *args)
+
+    def _need_table(self, name, M, rows):
+        """``ValueError`` unless ``M`` is a table a step can train: contiguous float32 [rows, d] on the engine's device"""
+        import torch
+        if M is None or M.dtype != torch.float32 or tuple(M.shape) != (rows, self.d) or not M.is_contiguous() or M.device != self.dev:
+            raise ValueError(f'{name}: expected contiguous float32 [{rows}, {self.d}] on {self.dev}')
+
+    def _workspaces(self, mode, doc_rows=None):
+        """``(gin, gout, gsyn1, gdoc)`` of a launch: None in HOGWILD; in BATCH the float64 workspaces, made zero at their
+        first use (a launch leaves them zero), ``gsyn1`` with Huffman tables only and ``gdoc`` [doc_rows, d] for the Doc2Vec
+        archs only."""
+        import torch
+        if mode != BATCH:
+            return None, None, None, None
+        z = lambda rows: torch.zeros(rows, self.d, dtype=torch.float64, device=self.dev)
+        if self._grads is None:
+            self._grads = (z(self.n_aids), z(self.n_aids))
+        if self.hs is not None and self._gsyn1 is None:
+            self._gsyn1 = z(self.n_inner)
+        if doc_rows is not None and (self._gdoc is None or self._gdoc.shape[0] != doc_rows):
+            self._gdoc = z(doc_rows)
+        return (*self._grads, self._gsyn1 if self.hs is not None else None, self._gdoc if doc_rows is not None else None)
 
     def _upload_hs(self, hs):
         import torch
@@ -293,14 +325,12 @@ class SkipGramEngine:
         SPEC-SGNS-HS entry point and needs ``Syn1`` float32 [hs.n_inner, d], updated in place as well; without tables
         ``Syn1`` must stay None."""
         import torch
-        for name, M in (('In', In), ('Out', Out)):
-            if M.dtype != torch.float32 or tuple(M.shape) != (self.n_aids, self.d) or not M.is_contiguous() or M.device != self.dev:
-                raise ValueError(f'{name}: expected contiguous float32 [{self.n_aids}, {self.d}] on {self.dev}')
+        self._need_table('In', In, self.n_aids)
+        self._need_table('Out', Out, self.n_aids)
         if self.hs is None and Syn1 is not None:
             raise ValueError('Syn1 given to an engine without hierarchical-softmax tables')
-        if Syn1 is not None and (Syn1.dtype != torch.float32 or tuple(Syn1.shape) != (self.n_inner, self.d)
-                                 or not Syn1.is_contiguous() or Syn1.device != self.dev):
-            raise ValueError(f'Syn1: expected contiguous float32 [{self.n_inner}, {self.d}] on {self.dev}')
+        if Syn1 is not None:
+            self._need_table('Syn1', Syn1, self.n_inner)
         if mode not in (HOGWILD, BATCH):
             raise ValueError(f'unknown mode {mode}')
         out_pairs = 0
@@ -310,18 +340,8 @@ class SkipGramEngine:
             out_pairs = neg_out.numel() // max(self.neg, 1) if ctx_out is None else min(out_pairs, neg_out.numel() // max(self.neg, 1))
         loss = self._loss if loss is None else loss
         with torch.cuda.device(self.dev):
-            gin = gout = None
-            if mode == BATCH:
-                if self._grads is None:
-                    self._grads = (torch.zeros(self.n_aids, self.d, dtype=torch.float64, device=self.dev),
-                                   torch.zeros(self.n_aids, self.d, dtype=torch.float64, device=self.dev))
-                gin, gout = self._grads
+            gin, gout, gsyn1, _ = self._workspaces(mode)
             if self.hs is not None:
-                gsyn1 = None
-                if mode == BATCH:
-                    if self._gsyn1 is None:
-                        self._gsyn1 = torch.zeros(self.n_inner, self.d, dtype=torch.float64, device=self.dev)
-                    gsyn1 = self._gsyn1
                 self._call('otto_sgns_step_hs', plan.tok_aid, plan.tok_src, plan.tok_left, plan.pair_off, plan.T, int(t0), int(t1),
                            In, Out, self.d, self.neg, float(lr), int(mode), self.seed, plan.epoch, C.byref(self.table), loss,
                            ctx_out, neg_out, out_pairs, gin, gout, self._path_off, self._path_node, self._code, Syn1,
@@ -387,25 +407,14 @@ class SkipGramEngine:
                 continue
             if name == 'Syn1' and self.hs is None:
                 raise ValueError('Syn1 given to an engine without hierarchical-softmax tables')
-            if M is None or M.dtype != torch.float32 or tuple(M.shape) != (rows, self.d) or not M.is_contiguous() or M.device != self.dev:
-                raise ValueError(f'{name}: expected contiguous float32 [{rows}, {self.d}] on {self.dev}')
+            self._need_table(name, M, rows)
         if neg_out is not None:
             _lib.need(neg_out, 'neg_out', torch.int32, device=self.dev)
             if neg_out.numel() < (int(t1) - int(t0)) * self.neg:
                 raise ValueError('neg_out: room for [t1 - t0, neg] entries needed')
         loss = self._loss if loss is None else loss
         with torch.cuda.device(self.dev):
-            grads = (None, None, None, None)
-            if mode == BATCH:
-                z = lambda rows: torch.zeros(rows, self.d, dtype=torch.float64, device=self.dev)
-                if self._grads is None:
-                    self._grads = (z(self.n_aids), z(self.n_aids))
-                if self.hs is not None and self._gsyn1 is None:
-                    self._gsyn1 = z(self.n_inner)
-                if arch != ARCH_CBOW and (self._gdoc is None or self._gdoc.shape[0] != S):
-                    self._gdoc = z(S)
-                grads = (self._grads[0], self._grads[1], self._gsyn1 if self.hs is not None else None,
-                         self._gdoc if arch != ARCH_CBOW else None)
+            grads = self._workspaces(mode, S if arch != ARCH_CBOW else None)
             job = self._cbow_job(plan, t0, t1, In if arch != ARCH_DBOW else None, Out, lr, arch, variant, mode, Syn1,
                                  Doc if arch != ARCH_CBOW else None, neg_out, loss, grads)
             _lib.call('otto_sgns_cbow_step', self.dev, C.byref(job), stream=False)
@@ -421,24 +430,24 @@ def init_doc(n_sessions, d, seed=0):
     return rng.uniform(-1.0 / d, 1.0 / d, size=(int(n_sessions), int(d))).astype(np.float32)
 
 
-def _train_arch(arch, variant, aid, sess_off, n_aids, dim, ws, neg, epochs, lr, t, min_count, ns_exponent, seed, mode,
+def _train_loop(step, targets, doc, aid, sess_off, n_aids, dim, ws, neg, epochs, lr, t, min_count, ns_exponent, seed,
                 tokens_per_launch, device, hs):
-    """The loop of :func:`train` over ``step_cbow``: ``(Doc or None, In, Out, losses, Syn1 or None)``."""
+    """The tables, the engine, the initial rows and the epoch / launch loop of :func:`train`, :func:`train_cbow` and
+    :func:`train_doc2vec`. What differs comes in as two callables: ``step(eng, plan, t0, t1, In, Out, rate, Syn1, Doc)`` is one
+    launch and returns its device loss sum, ``targets(eng, plan)`` is the denominator of the epoch's mean loss. ``doc``: a
+    ``Doc`` table is trained. Returns ``(Doc or None, In, Out, losses, Syn1 or None)``."""
     import torch
     dev = aid.device if device is None else torch.device(device)
     tokens_per_launch = int(tokens_per_launch)
     if tokens_per_launch < 1:
         raise ValueError('tokens_per_launch must be positive')
-    if int(neg) == 0 and not hs:
-        raise ValueError('neg = 0 without hierarchical softmax leaves nothing to train against')
     count, keep_q, weight = vocab_tables(aid, n_aids, min_count, t, ns_exponent)
     tables = huffman_tables(count, min_count) if hs else None
     eng = SkipGramEngine(n_aids, dim, ws, neg, keep_q, weight, seed=seed, device=dev, hs=tables)
     In_h, Out_h = init_tables(n_aids, dim, seed)
     In, Out = torch.from_numpy(In_h).to(eng.dev), torch.from_numpy(Out_h).to(eng.dev)
     Syn1 = torch.zeros(tables.n_inner, int(dim), dtype=torch.float32, device=eng.dev) if hs else None
-    S = int(sess_off.numel()) - 1
-    Doc = torch.from_numpy(init_doc(S, dim, seed)).to(eng.dev) if arch != ARCH_CBOW else None
+    Doc = torch.from_numpy(init_doc(int(sess_off.numel()) - 1, dim, seed)).to(eng.dev) if doc else None
     E = int(aid.numel())
     losses = []
     for ep in range(int(epochs)):
@@ -448,10 +457,18 @@ def _train_arch(arch, variant, aid, sess_off, n_aids, dim, ws, neg, epochs, lr, 
         total = torch.zeros(1, dtype=torch.float64, device=eng.dev)
         for t0, src in zip(starts, first_src):
             rate = learning_rate(lr, ep * E + int(src), int(epochs) * E)
-            total += eng.step_cbow(plan, t0, min(t0 + tokens_per_launch, plan.T), In, Out, rate, arch, variant, mode, Syn1=Syn1,
-                                   Doc=Doc)
-        losses.append(float(total.item()) / max(eng.cbow_targets(plan, arch), 1))
+            total += step(eng, plan, t0, min(t0 + tokens_per_launch, plan.T), In, Out, rate, Syn1, Doc)
+        losses.append(float(total.item()) / max(targets(eng, plan), 1))
     return Doc, In, Out, losses, Syn1
+
+
+def _train_arch(arch, variant, mode, neg, hs, *args):
+    """:func:`_train_loop` over ``step_cbow``; ``args``: its arguments from ``aid`` on."""
+    if int(neg) == 0 and not hs:
+        raise ValueError('neg = 0 without hierarchical softmax leaves nothing to train against')
+    return _train_loop(lambda eng, plan, t0, t1, In, Out, rate, Syn1, Doc:
+                       eng.step_cbow(plan, t0, t1, In, Out, rate, arch, variant, mode, Syn1=Syn1, Doc=Doc),
+                       lambda eng, plan: eng.cbow_targets(plan, arch), arch != ARCH_CBOW, *args)
 
 
 def train_cbow(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, t=1e-4, min_count=1, ns_exponent=0.5, seed=0,
@@ -460,8 +477,8 @@ def train_cbow(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, 
     ``variant``: ``CBOW_SUM`` (gensim ``cbow_mean: 0``), ``CBOW_MEAN`` (``cbow_mean: 1``) or ``CBOW_FASTTEXT`` (fastText
     ``model: cbow``). Returns ``(In, Out, losses)``, or ``(In, Out, losses, Syn1)`` with ``hs=True``; the mean loss divides
     by the number of targets actually trained (a centre without context trains none). ``neg = 0`` needs ``hs=True``."""
-    _, In, Out, losses, Syn1 = _train_arch(ARCH_CBOW, variant, aid, sess_off, n_aids, dim, ws, neg, epochs, lr, t, min_count,
-                                           ns_exponent, seed, mode, tokens_per_launch, device, hs)
+    _, In, Out, losses, Syn1 = _train_arch(ARCH_CBOW, variant, mode, neg, hs, aid, sess_off, n_aids, dim, ws, neg, epochs, lr, t,
+                                           min_count, ns_exponent, seed, tokens_per_launch, device, hs)
     return (In, Out, losses, Syn1) if hs else (In, Out, losses)
 
 
@@ -475,8 +492,8 @@ def train_doc2vec(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.0
     needs to embed a session that was not trained on."""
     arch = ARCH_PVDM if int(dm) else ARCH_DBOW
     variant = CBOW_MEAN if int(dm_mean) else CBOW_SUM
-    Doc, In, Out, losses, Syn1 = _train_arch(arch, variant, aid, sess_off, n_aids, dim, ws, neg, epochs, lr, t, min_count,
-                                             ns_exponent, seed, mode, tokens_per_launch, device, hs)
+    Doc, In, Out, losses, Syn1 = _train_arch(arch, variant, mode, neg, hs, aid, sess_off, n_aids, dim, ws, neg, epochs, lr, t,
+                                             min_count, ns_exponent, seed, tokens_per_launch, device, hs)
     out = (Doc, In, Out, losses, Syn1) if hs else (Doc, In, Out, losses)
     if return_model:
         out += (Doc2VecModel(In if int(dm) else None, Out, Syn1, _host_counts(aid, int(n_aids)), dim=dim, ws=ws, neg=neg, t=t,
@@ -494,19 +511,9 @@ class Doc2VecModel:
     HYPER = ('dim', 'ws', 'neg', 't', 'min_count', 'ns_exponent', 'seed', 'dm', 'dm_mean', 'hs', 'lr', 'epochs')
 
     def __init__(self, In, Out, Syn1, count, dim, ws, neg, t, min_count, ns_exponent, seed, dm, dm_mean, hs, lr, epochs):
-        self.dim, self.ws, self.neg, self.min_count, self.seed = int(dim), int(ws), int(neg), int(min_count), int(seed)
-        self.t, self.ns_exponent, self.lr, self.epochs = float(t), float(ns_exponent), float(lr), int(epochs)
+        self.min_count, self.t, self.ns_exponent, self.lr, self.epochs = int(min_count), float(t), float(ns_exponent), float(lr), int(epochs)
         self.dm, self.dm_mean, self.hs = int(bool(int(dm))), int(bool(int(dm_mean))), bool(hs)
-        if self.dim % 4 or not 4 <= self.dim <= MAX_DIM or (self.dim // 4) & (self.dim // 4 - 1):
-            raise ValueError(f'dim must be a multiple of 4 in [4, {MAX_DIM}] with dim/4 a power of two (got {dim})')
-        if not 0 <= self.neg <= MAX_NEG:
-            raise ValueError(f'neg must be in [0, {MAX_NEG}] (got {neg})')
-        if self.neg == 0 and not self.hs:
-            raise ValueError('neg = 0 without hierarchical softmax leaves nothing to infer against')
-        if not 1 <= self.ws <= MAX_WS:
-            raise ValueError(f'ws must be in [1, {MAX_WS}] (got {ws})')
-        if not 0 <= self.seed < 1 << 64:
-            raise ValueError('seed: expected a uint64')
+        self.dim, self.neg, self.ws, self.seed = _check_hyper(dim, neg, ws, seed, 'dim', self.hs)
         if self.t < 0 or self.ns_exponent not in NS_EXPONENTS:
             raise ValueError(f't must be >= 0 and ns_exponent one of {NS_EXPONENTS}')
         self.count = np.ascontiguousarray(np.asarray(count, dtype=np.int64))
@@ -663,28 +670,10 @@ def train(aid, sess_off, n_aids, dim=32, ws=10, neg=40, epochs=5, lr=0.05, t=1e-
     float32 [max(V - 1, 1), dim], zero-initialised. The mean loss then divides by ``pairs * (1 + neg)`` plus the sum of
     the path lengths of the pairs' contexts (computed on the device from the plan), so it stays a mean per target.
     The return value becomes ``(In, Out, losses, Syn1)``: the fourth entry exists only with ``hs=True``."""
-    import torch
-    dev = aid.device if device is None else torch.device(device)
-    tokens_per_launch = int(tokens_per_launch)
-    if tokens_per_launch < 1:
-        raise ValueError('tokens_per_launch must be positive')
-    count, keep_q, weight = vocab_tables(aid, n_aids, min_count, t, ns_exponent)
-    tables = huffman_tables(count, min_count) if hs else None
-    eng = SkipGramEngine(n_aids, dim, ws, neg, keep_q, weight, seed=seed, device=dev, hs=tables)
-    In_h, Out_h = init_tables(n_aids, dim, seed)
-    In, Out = torch.from_numpy(In_h).to(dev), torch.from_numpy(Out_h).to(dev)
-    Syn1 = torch.zeros(tables.n_inner, int(dim), dtype=torch.float32, device=eng.dev) if hs else None
-    E = int(aid.numel())
-    losses = []
-    for ep in range(int(epochs)):
-        plan = eng.plan(aid, sess_off, ep)
-        starts = list(range(0, plan.T, tokens_per_launch))
-        first_src = plan.tok_src[torch.tensor(starts, dtype=torch.int64, device=dev)].cpu().tolist() if starts else []
-        total = torch.zeros(1, dtype=torch.float64, device=dev)
-        for t0, src in zip(starts, first_src):
-            rate = learning_rate(lr, ep * E + int(src), int(epochs) * E)
-            total += eng.step(plan, t0, min(t0 + tokens_per_launch, plan.T), In, Out, rate, mode, Syn1=Syn1)
-        losses.append(float(total.item()) / max(plan.P * (1 + int(neg)) + eng.path_targets(plan), 1))
+    _, In, Out, losses, Syn1 = _train_loop(
+        lambda eng, plan, t0, t1, In, Out, rate, Syn1, Doc: eng.step(plan, t0, t1, In, Out, rate, mode, Syn1=Syn1),
+        lambda eng, plan: plan.P * (1 + int(neg)) + eng.path_targets(plan), False,
+        aid, sess_off, n_aids, dim, ws, neg, epochs, lr, t, min_count, ns_exponent, seed, tokens_per_launch, device, hs)
     return (In, Out, losses, Syn1) if hs else (In, Out, losses)
 
 
