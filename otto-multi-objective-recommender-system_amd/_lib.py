@@ -174,6 +174,34 @@ class LabelsJob(C.Structure):
                 ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
 
 
+class TfidfFitJob(C.Structure):
+    # mirrors otto_tfidf_fit_job (include/otto_tfidf.h)
+    _fields_ = [('d_tok_aid', C.c_void_p), ('d_doc_off', C.c_void_p), ('n_tokens', C.c_int64), ('n_docs', C.c_int64), ('n_aids', C.c_int64),
+                ('min_aid', C.c_int32), ('reserved', C.c_int32), ('d_row_off', C.c_void_p), ('d_df', C.c_void_p), ('d_col', C.c_void_p),
+                ('d_tf', C.c_void_p), ('nnz', C.c_int64), ('d_work', C.c_void_p), ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
+
+
+class TfidfWeightsJob(C.Structure):
+    # mirrors otto_tfidf_weights_job (include/otto_tfidf.h)
+    _fields_ = [('d_row_off', C.c_void_p), ('d_col', C.c_void_p), ('d_tf', C.c_void_p), ('d_idf', C.c_void_p), ('d_val', C.c_void_p),
+                ('n_rows', C.c_int64), ('n_cols', C.c_int64), ('stream', C.c_void_p)]
+
+
+class TfidfTransposeJob(C.Structure):
+    # mirrors otto_tfidf_transpose_job (include/otto_tfidf.h)
+    _fields_ = [('d_off', C.c_void_p), ('d_idx', C.c_void_p), ('d_val', C.c_void_p), ('n_rows', C.c_int64), ('n_cols', C.c_int64),
+                ('nnz', C.c_int64), ('d_t_off', C.c_void_p), ('d_t_idx', C.c_void_p), ('d_t_val', C.c_void_p), ('d_work', C.c_void_p),
+                ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
+
+
+class TfidfCosineJob(C.Structure):
+    # mirrors otto_tfidf_cosine_job (include/otto_tfidf.h)
+    _fields_ = [('d_a_off', C.c_void_p), ('d_a_idx', C.c_void_p), ('d_a_val', C.c_void_p), ('d_t_off', C.c_void_p), ('d_t_idx', C.c_void_p),
+                ('d_t_val', C.c_void_p), ('n_rows', C.c_int64), ('n_cols', C.c_int64), ('d_queries', C.c_void_p), ('n_queries', C.c_int64),
+                ('k', C.c_int32), ('exclude_self', C.c_int32), ('d_ids', C.c_void_p), ('d_sim', C.c_void_p), ('d_n', C.c_void_p),
+                ('d_work', C.c_void_p), ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
+
+
 _vp, _i64, _i32, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_uint32
 _p_i64 = C.POINTER(C.c_int64)
 
@@ -376,6 +404,15 @@ SIGNATURES = {
     'otto_labels_workspace': (_i64, [C.POINTER(LabelsJob)]),
     'otto_labels_count': (_i32, [C.POINTER(LabelsJob), _vp, _vp]),
     'otto_labels_fill': (_i32, [C.POINTER(LabelsJob)]),
+    # include/otto_tfidf.h
+    'otto_tfidf_fit_workspace': (_i64, [C.POINTER(TfidfFitJob)]),
+    'otto_tfidf_count': (_i32, [C.POINTER(TfidfFitJob), _vp, _vp]),
+    'otto_tfidf_fill': (_i32, [C.POINTER(TfidfFitJob)]),
+    'otto_tfidf_weights': (_i32, [C.POINTER(TfidfWeightsJob)]),
+    'otto_tfidf_transpose_workspace': (_i64, [C.POINTER(TfidfTransposeJob)]),
+    'otto_tfidf_transpose': (_i32, [C.POINTER(TfidfTransposeJob), _vp]),
+    'otto_tfidf_cosine_workspace': (_i64, [C.POINTER(TfidfCosineJob)]),
+    'otto_tfidf_cosine_topk': (_i32, [C.POINTER(TfidfCosineJob), _vp]),
 }
 
 _lib = None
