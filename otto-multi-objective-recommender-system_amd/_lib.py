@@ -202,6 +202,32 @@ class TfidfCosineJob(C.Structure):
                 ('d_work', C.c_void_p), ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
 
 
+class GruPlanJob(C.Structure):
+    # mirrors otto_gru_plan_job (include/otto_gru.h)
+    _fields_ = [('d_aid', C.c_void_p), ('d_sess_off', C.c_void_p), ('n_events', C.c_int64), ('n_sessions', C.c_int64), ('n_aids', C.c_int64),
+                ('max_len', C.c_int32), ('reserved', C.c_int32), ('seed', C.c_uint64), ('epoch', C.c_uint64), ('d_p', C.c_void_p),
+                ('d_seq_lo', C.c_void_p), ('d_seq_len', C.c_void_p), ('d_target', C.c_void_p), ('d_neg', C.c_void_p), ('d_work', C.c_void_p),
+                ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
+
+
+class GruJob(C.Structure):
+    # mirrors otto_gru_job (include/otto_gru.h)
+    _fields_ = [('d_E', C.c_void_p), ('d_W_ih', C.c_void_p), ('d_W_hh', C.c_void_p), ('d_W_d', C.c_void_p), ('d_b_d', C.c_void_p),
+                ('n_aids', C.c_int64), ('De', C.c_int32), ('H', C.c_int32), ('d_aid', C.c_void_p), ('n_events', C.c_int64),
+                ('d_seq_lo', C.c_void_p), ('d_seq_len', C.c_void_p), ('d_target', C.c_void_p), ('d_neg', C.c_void_p), ('B', C.c_int64),
+                ('max_len', C.c_int32), ('reserved', C.c_int32), ('d_o', C.c_void_p), ('d_gW_ih', C.c_void_p), ('d_gW_hh', C.c_void_p),
+                ('d_gW_d', C.c_void_p), ('d_gb_d', C.c_void_p), ('d_ids', C.c_void_p), ('d_rows', C.c_void_p), ('cap', C.c_int64),
+                ('d_count', C.c_void_p), ('d_loss_sum', C.c_void_p), ('d_work', C.c_void_p), ('work_bytes', C.c_int64), ('stream', C.c_void_p)]
+
+
+class GruApplyJob(C.Structure):
+    # mirrors otto_gru_apply_job (include/otto_gru.h)
+    _fields_ = [('d_E', C.c_void_p), ('d_mE', C.c_void_p), ('d_vE', C.c_void_p), ('n_aids', C.c_int64), ('De', C.c_int32), ('H', C.c_int32),
+                ('d_W', C.c_void_p * 4), ('d_m', C.c_void_p * 4), ('d_v', C.c_void_p * 4), ('d_g', C.c_void_p * 4), ('d_ids', C.c_void_p),
+                ('d_rows', C.c_void_p), ('cap', C.c_int64), ('d_count', C.c_void_p), ('lr', C.c_double), ('beta1', C.c_double),
+                ('beta2', C.c_double), ('eps', C.c_double), ('t', C.c_int64), ('stream', C.c_void_p)]
+
+
 _vp, _i64, _i32, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_uint32
 _p_i64 = C.POINTER(C.c_int64)
 
@@ -413,6 +439,13 @@ SIGNATURES = {
     'otto_tfidf_transpose': (_i32, [C.POINTER(TfidfTransposeJob), _vp]),
     'otto_tfidf_cosine_workspace': (_i64, [C.POINTER(TfidfCosineJob)]),
     'otto_tfidf_cosine_topk': (_i32, [C.POINTER(TfidfCosineJob), _vp]),
+    # include/otto_gru.h
+    'otto_gru_plan_workspace': (_i64, [C.POINTER(GruPlanJob)]),
+    'otto_gru_plan': (_i32, [C.POINTER(GruPlanJob), _vp, _vp]),
+    'otto_gru_workspace': (_i64, [C.POINTER(GruJob), _i32]),
+    'otto_gru_encode': (_i32, [C.POINTER(GruJob)]),
+    'otto_gru_grad': (_i32, [C.POINTER(GruJob)]),
+    'otto_gru_apply': (_i32, [C.POINTER(GruApplyJob)]),
 }
 
 _lib = None
