@@ -108,6 +108,20 @@ __host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 
+// the BPR negative item for global row `row` (oracle/mf_oracle.py; the MF and the GRU trainers draw by this one rule):
+// uniform over [0, n_items) (multiply-high of 32 random bits), redrawn (attempt 0..15) while equal to the positive;
+// falls back to (pos + 1) % n_items
+__host__ __device__ __forceinline__ int64_t bpr_negative(uint64_t seed, uint64_t epoch, uint64_t row, int64_t pos,
+                                                         int64_t n_items) {
+    const uint64_t base = mix64(seed ^ (epoch * 0xD1342543DE82EF95ull)) ^ (row * 0xA0761D6478BD642Full);
+    for (uint64_t att = 0; att < 16; ++att) {
+        const uint64_t r = mix64(base ^ (att * 0xE7037ED1A0B428DBull));
+        const int64_t j = (int64_t)(((r >> 32) * (uint64_t)n_items) >> 32);
+        if (j != pos) return j;
+    }
+    return (pos + 1) % n_items;
+}
+
 // mix(s, i) of SPEC-GBDT and of the fold trainer
 __host__ __device__ __forceinline__ uint64_t row_key(uint64_t seed, uint64_t r) { return mix64(seed + r * 0x9E3779B97F4A7C15ull); }
 

@@ -222,11 +222,6 @@ __global__ __launch_bounds__(256) void k_join_mark(const uint64_t* key, const ui
     }
 }
 
-struct FlagAt {
-    const uint8_t* f;
-    __device__ uint64_t operator()(int64_t i) const { return f[i]; }
-};
-
 __global__ __launch_bounds__(256) void k_join_emit(JoinArgs a, const uint64_t* key, const uint32_t* val, const uint8_t* mod, int64_t n,
                                                    const uint8_t* flag, const uint64_t* pos, int32_t* out_aid, float* out_pred,
                                                    double* out_pred64, int32_t* out_sess, JoinScratch* sc) {

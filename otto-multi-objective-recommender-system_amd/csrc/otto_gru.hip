@@ -42,27 +42,6 @@ static_assert(TS == 2 * NS, "a tile is two halves of NS sequences");
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + GT - 1) / GT); }
 inline unsigned capped_blocks(int64_t n) { const int64_t b = (n + GT - 1) / GT; return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b); }
 
-// number of entries of the non-decreasing a[0, n) that are <= x
-__device__ __forceinline__ int64_t upper_bound(const int64_t* a, int64_t n, int64_t x) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// bpr_negative of otto_mf.hip (oracle/mf_oracle.py), word for word: the two trainers draw by one rule
-__device__ __forceinline__ int64_t bpr_negative(uint64_t seed, uint64_t epoch, uint64_t row, int64_t pos, int64_t n_items) {
-    const uint64_t base = mix64(seed ^ (epoch * 0xD1342543DE82EF95ull)) ^ (row * 0xA0761D6478BD642Full);
-    for (uint64_t att = 0; att < 16; ++att) {
-        const uint64_t r = mix64(base ^ (att * 0xE7037ED1A0B428DBull));
-        const int64_t j = (int64_t)(((r >> 32) * (uint64_t)n_items) >> 32);
-        if (j != pos) return j;
-    }
-    return (pos + 1) % n_items;
-}
-
 __device__ __forceinline__ uint64_t order_key(uint64_t seed, uint64_t epoch, uint64_t p) {
     return mix64(mix64(seed ^ (epoch * 0xD1342543DE82EF95ull)) ^ (p * 0xA0761D6478BD642Full)) >> 1;
 }
@@ -89,19 +68,13 @@ __global__ __launch_bounds__(GT) void k_plan_check(const int32_t* __restrict__ a
     }
 }
 
-// the session of event i: off is read inside [0, S] whatever it holds
-__device__ __forceinline__ int64_t session_of(const int64_t* off, int64_t S, int64_t i) {
-    int64_t s = upper_bound(off, S + 1, i) - 1;
-    return s < 0 ? 0 : s >= S ? S - 1 : s;
-}
-
 __global__ __launch_bounds__(GT) void k_plan_keys(const int64_t* __restrict__ off, int64_t E, int64_t S, uint64_t seed, uint64_t epoch,
                                                   uint64_t* key, uint32_t* val, PlanCtrl* ctrl) {
     const int64_t i = (int64_t)blockIdx.x * GT + threadIdx.x;
     unsigned long long vo = 0, va = ~0ull;
     bool sample = false;
     if (i < E) {
-        sample = i > off[session_of(off, S, i)];
+        sample = i > off[segment_of(off, S, i)];
         const uint64_t k = sample ? order_key(seed, epoch, (uint64_t)i) : 1ull << 63;
         key[i] = k;
         val[i] = (uint32_t)i;
@@ -120,7 +93,7 @@ __global__ __launch_bounds__(GT) void k_plan_emit(const uint32_t* __restrict__ v
     if (q >= N) return;
     const int64_t p = val[q];
     if (p >= E) return;                                          // never: the values are event indices
-    const int64_t lo = off[session_of(off, S, p)];
+    const int64_t lo = off[segment_of(off, S, p)];
     int64_t len = p - lo;
     len = len > L ? L : len < 0 ? 0 : len;
     const int32_t t = aid[p];
@@ -520,11 +493,6 @@ __global__ __launch_bounds__(GT) void k_co_heads(const uint64_t* __restrict__ ke
     if (i < n2) flag[i] = key[i] < (uint64_t)n_rows && (i == 0 || key[i - 1] != key[i]);
 }
 
-struct FlagAt {
-    const uint8_t* f;
-    __device__ uint64_t operator()(int64_t i) const { return f[i]; }
-};
-
 __global__ __launch_bounds__(GT) void k_co_start(const uint8_t* __restrict__ flag, const uint64_t* __restrict__ pos, int64_t n2, uint64_t* start,
                                                  int64_t cap, int64_t* count) {
     const int64_t i = (int64_t)blockIdx.x * GT + threadIdx.x;
@@ -785,7 +753,8 @@ __global__ __launch_bounds__(GT) void k_gru_adam_rows(AdamArgs a) {
         if (id < 1 || id > a.n_aids) continue;                   // PAD and anything that is no row
         const int64_t k = id * a.De + idx % a.De;
         const float g = a.rows[idx];
-        // torch/optim/_functional.py sparse_adam, as adam1 of otto_mf.hip
+        // torch/optim/_functional.py sparse_adam. Not shared with adam1 of otto_mf.hip: this kernel is compiled with fp
+        // contraction off and adam1 with it on, and one inline function would take one of the two states for both
         float m = a.mE[k], v = a.vE[k];
         m = m + (g - m) * a.omb1;
         v = v + (g * g - v) * a.omb2;

@@ -14,6 +14,7 @@
 //                            per-row top-k; the B x N score matrix is never materialised
 //                            (recbole/inference.py:76-80 materialises and copies it to the host)
 #include "common.h"
+#include "wave.h"
 #include "sclist.h"
 #include "../../include/otto_mf.h"
 
@@ -31,8 +32,6 @@ __device__ __forceinline__ float group_sum(float v, int G) {
     return v;
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 
 // loss and d(loss)/d(out) (without the 1/B of reduction='mean')
@@ -464,20 +463,7 @@ __global__ __launch_bounds__(256) void k_dpa_adam(DpApplyArgs a) {
 // ---------------------------------------------------------------------------
 // BPR
 // ---------------------------------------------------------------------------
-// mix64: the keyed counter hash of common.h
-// negative item for global row `row`: uniform over [0, n_items) (multiply-high of 32 random bits),
-// redrawn (attempt 0..15) while equal to the positive; falls back to (pos + 1) % n_items
-__host__ __device__ __forceinline__ int64_t bpr_negative(uint64_t seed, uint64_t epoch, uint64_t row, int64_t pos,
-                                                         int64_t n_items) {
-    const uint64_t base = mix64(seed ^ (epoch * 0xD1342543DE82EF95ull)) ^ (row * 0xA0761D6478BD642Full);
-    for (uint64_t att = 0; att < 16; ++att) {
-        const uint64_t r = mix64(base ^ (att * 0xE7037ED1A0B428DBull));
-        const int64_t j = (int64_t)(((r >> 32) * (uint64_t)n_items) >> 32);
-        if (j != pos) return j;
-    }
-    return (pos + 1) % n_items;
-}
-
+// bpr_negative: the counter-based negative sampler of common.h
 struct BprArgs {
     float* U;
     float* V;

@@ -40,15 +40,6 @@ static_assert((COS_SLOTS & (COS_SLOTS - 1)) == 0 && COS_SLOTS % WAVE == 0, "the 
 
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + TF_THREADS - 1) / TF_THREADS); }
 
-// number of entries of the non-decreasing a[0, n) that are <= x
-__device__ __forceinline__ int64_t upper_bound(const int64_t* a, int64_t n, int64_t x) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 // first position of the sorted keys whose upper half is >= d
 __device__ __forceinline__ int64_t first_of_row(const uint64_t* key, int64_t n, uint64_t d) {
     int64_t lo = 0, hi = n;
@@ -66,11 +57,6 @@ struct Ctrl {                                                    // the first 25
     unsigned int n_small, n_large, next;                         // cosine: tier sizes, the large tier's query counter
 };
 
-struct FlagAt {
-    const uint8_t* f;
-    __device__ uint64_t operator()(int64_t i) const { return f[i]; }
-};
-
 // ---------------------------------------------------------------------------------------------------------------------
 // count / fill
 // ---------------------------------------------------------------------------------------------------------------------
@@ -85,8 +71,7 @@ __global__ __launch_bounds__(TF_THREADS) void k_fit_keys(const int32_t* __restri
         if (a < 0 || a >= n_aids) {
             atomicMin(&ctrl->err, (unsigned long long)i);
         } else if (a >= min_aid) {
-            int64_t d = upper_bound(doc_off, D + 1, i) - 1;
-            d = d < 0 ? 0 : d >= D ? D - 1 : d;
+            const int64_t d = segment_of(doc_off, D, i);
             k = (uint64_t)d << 32 | (uint32_t)a;
         }
         key[i] = k;
@@ -213,8 +198,7 @@ __global__ __launch_bounds__(TF_THREADS) void k_tr_keys(const int64_t* __restric
         if (c < 0 || c >= C) {
             atomicMin(&ctrl->err, (unsigned long long)i);
         } else {
-            int64_t r = upper_bound(off, R + 1, i) - 1;
-            r = r < 0 ? 0 : r >= R ? R - 1 : r;
+            const int64_t r = segment_of(off, R, i);
             k = (uint64_t)c << 32 | (uint32_t)r;
         }
         key[i] = k;

@@ -1,4 +1,5 @@
-// Generic device-wide exclusive scan of a functor (three launches), shared by the covisitation index and the event sort.
+// Generic device-wide exclusive scan of a functor (three launches), shared by the covisitation index and the event sort,
+// and the search of such a scan's offsets for the segment of a position.
 #pragma once
 #include "common.h"
 
@@ -76,5 +77,25 @@ static int device_scan(F f, int64_t n, uint64_t* out, uint64_t* partial, hipStre
 }
 static inline size_t scan_partial_bytes(int64_t n) { return ((size_t)((n + SCAN_TILE - 1) / SCAN_TILE) + 1) * sizeof(uint64_t); }
 
+// the functor of a scan over byte flags
+struct FlagAt {
+    const uint8_t* f;
+    __device__ uint64_t operator()(int64_t i) const { return f[i]; }
+};
+
+// number of entries of the non-decreasing a[0, n) that are <= x
+__device__ __forceinline__ int64_t upper_bound(const int64_t* a, int64_t n, int64_t x) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a[mid] <= x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// the segment of position i under the offsets off[0 .. S], clamped to [0, S): off is read inside [0, S] whatever it holds
+__device__ __forceinline__ int64_t segment_of(const int64_t* off, int64_t S, int64_t i) {
+    const int64_t s = upper_bound(off, S + 1, i) - 1;
+    return s < 0 ? 0 : s >= S ? S - 1 : s;
+}
 
 }  // namespace otto

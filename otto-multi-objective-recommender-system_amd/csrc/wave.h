@@ -1,4 +1,4 @@
-// Small helpers shared by the ranker-side kernels (everything but otto_covis.hip and otto_mf.hip, which keep their own):
+// Small helpers shared by the kernels (everything but otto_covis.hip, which keeps its own):
 // 64-lane reductions, order-preserving integer images of floats, 16-byte loads and stores, workspace alignment.
 #pragma once
 #include "common.h"
